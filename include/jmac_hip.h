@@ -250,23 +250,11 @@ int jmac_rel_attn_aggregate_bwd_phases_f32(
 /* BatchNorm1d (batch statistics or running statistics) + tanh on [N,d]
  * (replaces: self.layer_act(self.bn(.)), src/jmac_model.py:52).
  * training != 0: mean/var are computed over the N rows (biased var), written to save_mean /
- * save_invstd [d], and running_mean/var (may be NULL) are updated with `momentum` (unbiased var). */
+ * save_invstd [d], and running_mean/var (may be NULL) are updated with `momentum` (unbiased var).
+ * The layer's output is an operand of two concatenations in JMAC.forward_name (src/jmac_model.py:192 cat(comp_l1, align_l1)
+ * and :203 cat(align_layers)): the forward writes the rows into both cat buffers (y2 / ldy2, may be NULL), the backward sums
+ * the two incoming gradients (gy2 / ldgy2, may be NULL) while it reads them -- no cat copy, no gradient add. */
 size_t jmac_bn_tanh_workspace_bytes(int64_t N, int64_t d);
-int jmac_bn_tanh_fwd_f32(const float* x, int64_t ldx, int64_t N, int64_t d, const float* weight,
-                         const float* bias, float* running_mean, float* running_var,
-                         int32_t training, float momentum, float eps, float* y, int64_t ldy,
-                         float* save_mean, float* save_invstd, void* ws, size_t ws_bytes,
-                         jmac_stream_t stream);
-int jmac_bn_tanh_bwd_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, const float* gy,
-                         int64_t ldgy, int64_t N, int64_t d, const float* weight,
-                         const float* save_mean, const float* save_invstd, int32_t training,
-                         float* gx, int64_t ldgx, float* gweight, float* gbias, void* ws,
-                         size_t ws_bytes, jmac_stream_t stream);
-
-/* The same with a second destination / a second gradient source: the layer's output is an operand of two concatenations in
- * JMAC.forward_name (src/jmac_model.py:192 cat(comp_l1, align_l1) and :203 cat(align_layers)): the forward writes the rows
- * into both cat buffers (y2 / ldy2, may be NULL), the backward sums the two incoming gradients (gy2 / ldgy2, may be NULL)
- * while it reads them -- no cat copy, no gradient add. */
 int jmac_bn_tanh_fwd2_f32(const float* x, int64_t ldx, int64_t N, int64_t d, const float* weight,
                           const float* bias, float* running_mean, float* running_var,
                           int32_t training, float momentum, float eps, float* y, int64_t ldy,
@@ -431,14 +419,9 @@ int jmac_softmax_entropy_f32(const float* A, int64_t lda, const float* B, int64_
                              int64_t n2, int64_t d, float scale, float* ent_rows, float* ent_cols,
                              void* ws, size_t ws_bytes, jmac_stream_t stream);
 
-/* Row softmax of scale*S with rows in `row_mask` and columns in `col_mask` (uint8, 1 = keep) left as
- * is and every other entry replaced by `fill` first (train.py:252-257: fill = -1). In place allowed. */
-int jmac_masked_row_softmax_f32(const float* S, int64_t lds, int64_t n1, int64_t n2,
-                                const uint8_t* row_mask, const uint8_t* col_mask, float fill,
-                                float scale, float* out, int64_t ldo, jmac_stream_t stream);
-
-/* Generalisations of the call above on an existing score matrix S [n1,n2] (row-major): the entries kept by the masks
- * are scaled, every other entry is `fill` * scale (NULL mask = keep all), then
+/* Softmax of an existing score matrix S [n1,n2] (row-major) with rows in `row_mask` and columns in `col_mask` (uint8, 1 = keep;
+ * NULL mask = keep all) left as they are and every other entry replaced by `fill` (train.py:252-257: fill = -1), all scaled by
+ * `scale`, then
  *   jmac_row_softmax_f32: softmax over each ROW    -> out [n1,n2] (may be NULL), ent [n1] = entropy of the row (may be NULL)
  *   jmac_col_softmax_f32: softmax over each COLUMN -> out_t [n2,n1] = the TRANSPOSED probabilities, i.e.
  *                         softmax(scale * S^T, dim=1) (may be NULL), ent [n2] (may be NULL)
@@ -517,14 +500,10 @@ int jmac_gemm_grouped_f32(const jmac_gemm_task_t* tasks, int32_t n_tasks, jmac_s
  * counters (pack only): up to JMAC_WCAT_MAX device int64 incremented by one in the same launch -- nn.BatchNorm1d's
  * num_batches_tracked of the layers a training-mode encoder call is about to run (src/jmac_model.py:52). */
 #define JMAC_WCAT_MAX 4
-int jmac_wcat_pack_f32(const float* const* w_att, const float* const* gcn, float* const* wcat,
-                       int32_t n_layers, int64_t d, const float* extra_src, float* extra_dst,
-                       int64_t extra_floats, int64_t* const* counters, int32_t n_counters,
-                       jmac_stream_t stream);
-/* The same with the step's DROPOUT SEEDS riding along (round 5): seed_state [2] = persistent device int64 words, advanced by one
+/* The step's DROPOUT SEEDS ride along in the pack (round 5): seed_state [2] = persistent device int64 words, advanced by one
  * per launch; seed_out [2] receives the advanced values -- the seeds jmac_row_normalize_dropseed_{fwd,bwd}_f32 draw from in this
  * step (completion_dropout, src/jmac_model.py:179,191).  No torch RNG op per step: a captured step that uses none is replayed
- * without the generator-state fills torch puts in front of every replay of a graph that does.  Both NULL: as above. */
+ * without the generator-state fills torch puts in front of every replay of a graph that does.  Both NULL: no seeds. */
 int jmac_wcat_pack_seed_f32(const float* const* w_att, const float* const* gcn, float* const* wcat, int32_t n_layers,
                             int64_t d, const float* extra_src, float* extra_dst, int64_t extra_floats,
                             int64_t* const* counters, int32_t n_counters, int64_t* seed_state, int64_t* seed_out,
@@ -593,67 +572,46 @@ int jmac_triple_l1_bwd_f32(const float* ent, int64_t lde, const float* rel, int6
                            const int64_t* h, const int64_t* r, const int64_t* t, int64_t T,
                            int64_t period, int64_t d, const float* gscore, float* dent, int64_t ldde, float* drel, int64_t lddr,
                            jmac_stream_t stream);
-/* The same adjoint for a score vector that fed the margin ranking loss of completion_loss directly (T = B (K + 1) triples, the
- * batch layout of train.py:347-352, src/jmac_model.py:351-378): the score gradient is derived inside the kernel from the
- * scores, gamma (device scalar) and gloss (device scalar, the loss' incoming gradient) by jmac_margin_loss_bwd_f32's rule --
- * no dscore vector, no launch for it.  dent / drel zeroed by the caller as above. */
-int jmac_triple_l1_margin_bwd_f32(const float* ent, int64_t lde, const float* rel, int64_t ldr,
-                                  const int64_t* h, const int64_t* r, const int64_t* t, int64_t B, int64_t K,
-                                  int64_t d, const float* score, const float* gamma, const float* gloss,
-                                  float* dent, int64_t ldde, float* drel, int64_t lddr, jmac_stream_t stream);
-
-/* Bitwise REPRODUCIBLE form of jmac_triple_l1_margin_bwd_f32 (same arguments + the row counts of the two gradient tables,
- * which it scales in a second pass): the gradient of the margin ranking loss is (gloss / (2 B K)) times an INTEGER matrix (the
- * weights of torch.max are 0, 1/2 or 1), so the float atomics add exact small integers -- order-independent below 2^24 -- and a
- * scaling pass finishes the tables.  dent [n_ent rows] / drel [n_rel rows] must be ZERO on entry.  4 B K >= 2^24: the plain form. */
-int jmac_triple_l1_margin_bwd_exact_f32(const float* ent, int64_t lde, const float* rel, int64_t ldr, const int64_t* h,
-                                        const int64_t* r, const int64_t* t, int64_t B, int64_t K, int64_t d,
-                                        const float* score, const float* gamma, const float* gloss, float* dent,
-                                        int64_t ldde, int64_t n_ent, float* drel, int64_t lddr, int64_t n_rel,
-                                        jmac_stream_t stream);
-
-/* Pair cosine distance with a bitwise reproducible backward: the forward also leaves stats [L,4] = (a.b, a.a, b.b, 0) per pair;
- * the backward walks the 2 L (pair, side) incidences in the order the HOST sorted them by the gradient row they touch (stable:
- * ties in pair order) and writes every touched row ONCE with a plain store (sum in sorted order); untouched rows keep the
- * caller's zero fill.  rec [2L][4] int32, one record per SORTED position: {pair x, own table row, partner table row,
- * flags | gradient row} -- own / partner rows relative to the e1 / e2 pointers passed here; flags: bit 31 = first incidence of
- * its gradient row, bit 30 = side 1 (own row in e2, partner in e1), bit 29 = the gradient row is a row of de2 (else de1);
- * bits 0-28 = the gradient row.  The index vectors of an alignment loss are constant over many steps (seed links:
- * train.py:347-352), so the host sorts once per index tensor (jmac_amd.losses._pair_index). */
+/* Pair cosine distance with a bitwise reproducible backward (src/jmac_model.py:237-249): the forward also leaves stats [L,4] =
+ * (a.b, a.a, b.b, 0) per pair.  The backward walks the 2 L (pair, side) incidences in the order the HOST sorted them by the
+ * gradient row they touch (stable: ties in pair order) and is the FIRST WRITER of its gradient tables (no zero fill by the caller):
+ * one wave per gradient ROW over [0, n1 + n2) (rows [0,n1) of de1, then n2 rows of de2; n2 = 0 when both sides share one table)
+ * sums its run in sorted order and writes the row once with a plain store; rows without incidences are written as zeros.
+ * rec [2L][4] int32, one record per SORTED position: {pair x, own table row, partner table row, flags | gradient row} -- own /
+ * partner rows relative to the e1 / e2 pointers passed here; flags: bit 31 = first incidence of its gradient row, bit 30 = side 1
+ * (own row in e2, partner in e1), bit 29 = the gradient row is a row of de2 (else de1); bits 0-28 = the gradient row.
+ * rowptr [n1+n2+1] = first sorted position (into rec) of every row's run.  The incoming gradient is gdist [L], or the scalar
+ * gscalar[0] / gscale for every pair (the .mean() over the pairs of alignment_loss_simple, :249).  The index vectors of an
+ * alignment loss are constant over many steps (seed links: train.py:347-352), so the host sorts once per index tensor
+ * (jmac_amd.losses._pair_index). */
 int jmac_pair_cosine_fwd_stats_f32(const float* e1, int64_t ld1, const float* e2, int64_t ld2, const int64_t* i1,
                                    const int64_t* i2, int64_t L, int64_t d, float* dist, float* stats,
                                    jmac_stream_t stream);
-int jmac_pair_cosine_bwd_sorted_f32(const float* e1, int64_t ld1, const float* e2, int64_t ld2, int64_t L, int64_t d,
-                                    const float* gdist, const float* stats, const int32_t* rec, float* de1, int64_t ldd1,
-                                    float* de2, int64_t ldd2, jmac_stream_t stream);
-
-/* Round 5 -- the same two adjoints as FIRST WRITERS of their gradient tables (no zero fill by the caller, no add of the step's
- * gradient contributions afterwards; src/jmac_model.py:237-249, 345-378):
- *  - jmac_pair_cosine_bwd_rows_f32: one wave per gradient ROW over [0, n1 + n2) (rows [0,n1) of de1, then n2 rows of de2; n2 = 0
- *    when both sides share one table), rowptr [n1+n2+1] = first sorted position (into rec) of every row's run; rows without
- *    incidences are written as zeros; sums in sorted order (the bits of the sorted form).  The incoming gradient is gdist [L], or
- *    the scalar gscalar[0] / gscale for every pair (the .mean() over the pairs of alignment_loss_simple, :249).
- *  - jmac_triple_l1_margin_bwd_exact2_f32: the exact-integer atomics go into PERSISTENT count tables cnt_ent [rows_ent, d] /
- *    cnt_rel [rows_rel, d] (dense, 16-byte aligned, ZERO on entry and left at zero again) at the windows [ent_off ..), [rel_off ..)
- *    the ids are local to; the scaling pass writes dent / drel (dense, all rows) = cnt * gloss / (2 B K), on top of their
- *    contents where acc_ent / acc_rel != 0 (e.g. the rows jmac_pair_cosine_bwd_rows_f32 wrote).  d % 4 == 0; 4 B K >= 2^24:
- *    JMAC_ERANGE (use jmac_triple_l1_margin_bwd_f32).
- *  - jmac_vec_mean_acc_f32: out[0] = mean(x[0..n)) + (add_to ? add_to[0] : 0), fixed summation order;
- *    jmac_margin_loss_fwd_acc_f32: jmac_margin_loss_fwd_f32 + add_to[0] -- a step's loss terms chain through add_to instead of
- *    through element-wise adds. */
 int jmac_pair_cosine_bwd_rows_f32(const float* e1, int64_t ld1, const float* e2, int64_t ld2, int64_t L, int64_t d,
                                   const float* gdist, const float* gscalar, float gscale, const float* stats,
                                   const int32_t* rec, const int32_t* rowptr, int64_t n1, int64_t n2, float* de1,
                                   int64_t ldd1, float* de2, int64_t ldd2, jmac_stream_t stream);
+
+/* Bitwise REPRODUCIBLE adjoint of the triple L1 scores for a score vector that fed the margin ranking loss of completion_loss
+ * directly (T = B (K + 1) triples, the batch layout of train.py:347-352, src/jmac_model.py:345-378): the score gradient is derived
+ * inside the kernel from the scores, gamma (device scalar) and gloss (device scalar, the loss' incoming gradient) by
+ * jmac_margin_loss_bwd_f32's rule -- no dscore vector, no launch for it.  That gradient is (gloss / (2 B K)) times an INTEGER
+ * matrix (the weights of torch.max are 0, 1/2 or 1), so the float atomics add exact small integers -- order-independent below
+ * 2^24 -- into PERSISTENT count tables cnt_ent [rows_ent, d] / cnt_rel [rows_rel, d] (dense, 16-byte aligned, ZERO on entry and
+ * left at zero again) at the windows [ent_off ..), [rel_off ..) the ids are local to; a scaling pass writes dent / drel (dense,
+ * all rows) = cnt * gloss / (2 B K) as their FIRST WRITER, or on top of their contents where acc_ent / acc_rel != 0 (e.g. the
+ * rows jmac_pair_cosine_bwd_rows_f32 wrote).  d % 4 == 0; 4 B K >= 2^24: JMAC_ERANGE (use jmac_margin_loss_bwd_f32 and
+ * jmac_triple_l1_bwd_f32). */
 int jmac_triple_l1_margin_bwd_exact2_f32(const float* ent, int64_t lde, const float* rel, int64_t ldr, const int64_t* h,
                                          const int64_t* r, const int64_t* t, int64_t B, int64_t K, int64_t d,
                                          const float* score, const float* gamma, const float* gloss, int64_t ent_off,
                                          int64_t rel_off, float* cnt_ent, float* cnt_rel, float* dent, int64_t rows_ent,
                                          int32_t acc_ent, float* drel, int64_t rows_rel, int32_t acc_rel,
                                          jmac_stream_t stream);
+
+/* out[0] = mean(x[0..n)) + (add_to ? add_to[0] : 0), fixed summation order -- a step's loss terms chain through add_to instead
+ * of through element-wise adds. */
 int jmac_vec_mean_acc_f32(const float* x, int64_t n, const float* add_to, float* out, jmac_stream_t stream);
-int jmac_margin_loss_fwd_acc_f32(const float* score, int64_t B, int64_t K, const float* gamma, const float* add_to,
-                                 float* loss, jmac_stream_t stream);
 
 /* dist[x] = 1 - <u, v>, u = e1[i1[x]] / max(||.||, 1e-12), v = e2[i2[x]] / max(||.||, 1e-12)
  * (replaces F.normalize(E[idx]) x2 + sum of alignment_loss / alignment_loss_simple,
@@ -669,11 +627,12 @@ int jmac_pair_cosine_bwd_f32(const float* e1, int64_t ld1, const float* e2, int6
 
 /* Margin ranking loss of completion_loss (src/jmac_model.py:351-378) on the [B + B*K] score vector of one batch, with the
  * reference's n-major consumption of the negative block kept (neg_{b,k} = score[B + k*B + b]):
- *   loss[0] = mean_{b<B,k<K} max(score[b] - neg_{b,k}, -gamma[0]) + gamma[0]
- * gamma: DEVICE pointer (the model's margin_completion parameter).  bwd: dscore [B + B*K] = gloss[0] * d loss / d score
- * (a tie diff == -gamma receives half the gradient, as torch.max(a, b) gives it).  One launch each way, fixed summation order. */
-int jmac_margin_loss_fwd_f32(const float* score, int64_t B, int64_t K, const float* gamma, float* loss,
-                             jmac_stream_t stream);
+ *   loss[0] = mean_{b<B,k<K} max(score[b] - neg_{b,k}, -gamma[0]) + gamma[0] + (add_to ? add_to[0] : 0)
+ * gamma: DEVICE pointer (the model's margin_completion parameter); add_to: the step's running loss (may be NULL).
+ * bwd: dscore [B + B*K] = gloss[0] * d loss / d score (a tie diff == -gamma receives half the gradient, as torch.max(a, b)
+ * gives it).  One launch each way, fixed summation order. */
+int jmac_margin_loss_fwd_acc_f32(const float* score, int64_t B, int64_t K, const float* gamma, const float* add_to,
+                                 float* loss, jmac_stream_t stream);
 int jmac_margin_loss_bwd_f32(const float* score, int64_t B, int64_t K, const float* gamma,
                              const float* gloss, float* dscore, jmac_stream_t stream);
 

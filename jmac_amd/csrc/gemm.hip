@@ -780,13 +780,6 @@ static int wcat_extra(WcatArgs& a, const float* src, float* dst, int64_t n) {
     return JMAC_OK;
 }
 
-int jmac_wcat_pack_f32(const float* const* w_att, const float* const* gcn, float* const* wcat, int32_t n_layers, int64_t d,
-                       const float* extra_src, float* extra_dst, int64_t extra_floats, int64_t* const* counters,
-                       int32_t n_counters, jmac_stream_t stream) {
-    return jmac_wcat_pack_seed_f32(w_att, gcn, wcat, n_layers, d, extra_src, extra_dst, extra_floats, counters, n_counters, nullptr,
-                                   nullptr, stream);
-}
-
 int jmac_wcat_pack_seed_f32(const float* const* w_att, const float* const* gcn, float* const* wcat, int32_t n_layers, int64_t d,
                             const float* extra_src, float* extra_dst, int64_t extra_floats, int64_t* const* counters,
                             int32_t n_counters, int64_t* seed_state, int64_t* seed_out, jmac_stream_t stream) {

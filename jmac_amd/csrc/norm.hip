@@ -912,21 +912,6 @@ int jmac_bn_tanh_fwd2_f32(const float* x, int64_t ldx, int64_t N, int64_t d, con
     return (int)hipGetLastError();
 }
 
-int jmac_bn_tanh_fwd_f32(const float* x, int64_t ldx, int64_t N, int64_t d, const float* weight, const float* bias,
-                         float* running_mean, float* running_var, int32_t training, float momentum, float eps, float* y,
-                         int64_t ldy, float* save_mean, float* save_invstd, void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    return jmac_bn_tanh_fwd2_f32(x, ldx, N, d, weight, bias, running_mean, running_var, training, momentum, eps, y, ldy, nullptr, 0,
-                                 save_mean, save_invstd, ws, ws_bytes, stream);
-}
-
-int jmac_bn_tanh_bwd_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, const float* gy, int64_t ldgy, int64_t N,
-                         int64_t d, const float* weight, const float* save_mean, const float* save_invstd, int32_t training,
-                         float* gx, int64_t ldgx, float* gweight, float* gbias, void* ws, size_t ws_bytes,
-                         jmac_stream_t stream) {
-    return jmac_bn_tanh_bwd2_f32(x, ldx, y, ldy, gy, ldgy, nullptr, 0, N, d, weight, save_mean, save_invstd, training, gx, ldgx,
-                                 gweight, gbias, ws, ws_bytes, stream);
-}
-
 int jmac_bn_tanh_bwd2_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, const float* gy, int64_t ldgy,
                           const float* gy2, int64_t ldgy2, int64_t N, int64_t d, const float* weight, const float* save_mean,
                           const float* save_invstd, int32_t training, float* gx, int64_t ldgx, float* gweight, float* gbias,

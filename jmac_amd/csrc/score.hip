@@ -4,7 +4,7 @@
 //  * jmac_filtered_rank_f32 filter + sort + np.where ranking loop        src/validate.py:50-64
 //  * jmac_sim_matrix_f32    torch.mm(ILL_vec, KG_vec.t())                modules/utils/util.py:52, train.py:239
 //  * jmac_row_topk_f32 / jmac_sim_topk_f32   sim.topk(k, dim=1)          modules/utils/util.py:53
-//  * jmac_softmax_entropy_f32, jmac_masked_row_softmax_f32               train.py:241-257
+//  * jmac_softmax_entropy_f32, jmac_row_softmax_f32                      train.py:241-257
 //
 // L1 distance is |a-b| accumulation: not a contraction, so it runs on the VALU (register-tiled through
 // LDS); the similarity matrices are contractions and run on the matrix cores with the fp32-input MFMA
@@ -1905,13 +1905,6 @@ int jmac_row_softmax_f32(const float* S, int64_t lds, int64_t n1, int64_t n2, co
     hipLaunchKernelGGL(masked_row_softmax_kernel, dim3((unsigned)n1), dim3(kBlock), 0, (hipStream_t)stream, S, lds, (int)n2,
                        row_mask, col_mask, fill, scale, out, ldo, ent);
     return (int)hipGetLastError();
-}
-
-int jmac_masked_row_softmax_f32(const float* S, int64_t lds, int64_t n1, int64_t n2, const uint8_t* row_mask,
-                                const uint8_t* col_mask, float fill, float scale, float* out, int64_t ldo,
-                                jmac_stream_t stream) {
-    if (!out) return JMAC_EINVAL;
-    return jmac_row_softmax_f32(S, lds, n1, n2, row_mask, col_mask, fill, scale, out, ldo, nullptr, stream);
 }
 
 static int col_softmax_row_splits(int64_t n1, int64_t n2) {

@@ -81,7 +81,7 @@ _PAIR_PINNED: dict = {}        # entries a stream capture used (strong reference
 
 
 def _pair_index(i1: torch.Tensor, i2: torch.Tensor, off1: int, off2: int, same: bool, n1: int = 0, n2: int = 0):
-    """(rec, rowptr).  rec int32 [2L, 4] of jmac_pair_cosine_bwd_{sorted,rows}_f32: the (pair, side) incidences sorted by the gradient row they touch,
+    """(rec, rowptr).  rec int32 [2L, 4] of jmac_pair_cosine_bwd_rows_f32: the (pair, side) incidences sorted by the gradient row they touch,
     built ONCE per pair of index tensors (identity + version, weak references) -- the seed links of a KG pair are the same
     tensors for every batch of an epoch (train.py:347-352), the mined negatives until the next refresh -- like the CSR of a
     graph.  ``off1`` / ``off2``: first row of the windows the ids are local to; ``same``: both sides share one gradient table.
@@ -258,7 +258,8 @@ class _MarginLoss(torch.autograd.Function):
         require_device(score, margin)
         score = score.contiguous()
         loss = torch.empty(1, dtype=torch.float32, device=score.device)
-        check(lib().jmac_margin_loss_fwd_f32(ptr(score), B, K, ptr(margin), ptr(loss), stream()), "jmac_margin_loss_fwd_f32")
+        check(lib().jmac_margin_loss_fwd_acc_f32(ptr(score), B, K, ptr(margin), None, ptr(loss), stream()),
+              "jmac_margin_loss_fwd_acc_f32")
         ctx.save_for_backward(score, margin)
         ctx.bk = (B, K)
         return loss
@@ -287,44 +288,6 @@ def _win(table: torch.Tensor, win):
 
 def _wptr(t: torch.Tensor, off: int) -> int:
     return t.data_ptr() + off * t.stride(0) * t.element_size()
-
-
-class _TripleL1Margin(torch.autograd.Function):
-    """score = triple L1 distances, loss = margin ranking loss of the score vector, as ONE node: the backward derives the score
-    gradient inside the L1 adjoint kernel (no dscore vector, no launch for it).  ``eoff`` / ``roff``: first row of the entity /
-    relation window the indices are local to."""
-
-    @staticmethod
-    def forward(ctx, ent, rel, h, r, t, margin, B, K, eoff, roff, en, rn):
-        require_device(ent, rel, h, r, t, margin)
-        ent, rel = _rows(ent), _rows(rel)
-        T, d = h.numel(), ent.shape[1]
-        if rel.shape[1] != d or r.numel() != T or t.numel() != T or T != B * (K + 1):
-            raise ValueError("triple_l1_margin_loss: shapes disagree")
-        score = torch.empty(T, dtype=torch.float32, device=ent.device)
-        loss = torch.empty(1, dtype=torch.float32, device=ent.device)
-        check(lib().jmac_triple_l1_fwd_f32(_wptr(ent, eoff), ent.stride(0), _wptr(rel, roff), rel.stride(0), ptr(h), ptr(r), ptr(t),
-                                           T, B, d, ptr(score), stream()), "jmac_triple_l1_fwd_f32")
-        check(lib().jmac_margin_loss_fwd_f32(ptr(score), B, K, ptr(margin), ptr(loss), stream()), "jmac_margin_loss_fwd_f32")
-        ctx.save_for_backward(ent, rel, h, r, t, score, margin)
-        ctx.bk = (B, K, eoff, roff, en, rn)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        ent, rel, h, r, t, score, margin = ctx.saved_tensors
-        B, K, eoff, roff, en, rn = ctx.bk
-        d = ent.shape[1]
-        g = g.contiguous()
-        dent = torch.zeros((ent.shape[0], d), dtype=torch.float32, device=ent.device)
-        drel = torch.zeros((rel.shape[0], d), dtype=torch.float32, device=ent.device)
-        # bitwise reproducible: the atomics add exact integers (the loss' gradient is gloss / (2 B K) times an integer matrix),
-        # a second pass scales the two windows
-        check(lib().jmac_triple_l1_margin_bwd_exact_f32(_wptr(ent, eoff), ent.stride(0), _wptr(rel, roff), rel.stride(0), ptr(h), ptr(r),
-                                                        ptr(t), B, K, d, ptr(score), ptr(margin), ptr(g), _wptr(dent, eoff), d, en,
-                                                        _wptr(drel, roff), d, rn, stream()),
-              "jmac_triple_l1_margin_bwd_exact_f32")
-        return dent, drel, None, None, None, None, None, None, None, None, None, None
 
 
 _CNT: dict = {}               # (device, rows_ent, rows_rel, d) -> persistent count tables of the exact margin adjoint (always zero between calls)
@@ -356,6 +319,8 @@ class _LayerLoss(torch.autograd.Function):
         require_device(ent, rel, h, r, t, margin)
         ent, rel = _rows(ent), _rows(rel)
         T, d = h.numel(), ent.shape[1]
+        if rel.shape[1] != d or r.numel() != T or t.numel() != T or T != B * (K + 1) or (c0 is not None and c1.numel() != c0.numel()):
+            raise ValueError("completion_layer_loss: shapes disagree")
         dev = ent.device
         score = torch.empty(T, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
@@ -401,10 +366,11 @@ class _LayerLoss(torch.autograd.Function):
 def completion_layer_loss(ent: torch.Tensor, rel: torch.Tensor, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, batch_size: int,
                           margin: torch.Tensor, ent_win=None, rel_win=None, links=None, add_to: torch.Tensor = None) -> torch.Tensor:
     """One layer's term of JMAC.completion_loss (src/jmac_model.py:331-380) -> [1]:
-    ``add_to + triple_l1_margin_loss(ent, rel, h, r, t, B, margin, ent_win, rel_win) [+ pair_cosine_distance(ent, c0, ent, c1,
+    ``add_to + margin_loss(triple_l1_score(ent, rel, h, r, t, period=B), B, margin) [+ pair_cosine_distance(ent, c0, ent, c1,
     win0, win1).mean()]`` with ``links = (c0, c1, win0, win1)`` (alignment_loss_simple on the seed links: both sides windows of
-    ``ent``), as ONE autograd node where the fused form covers the inputs (dense fp32 tables, d % 4 == 0, d <= 512, a batch of
-    B (K + 1) triples, a margin without gradient); the separate ops otherwise."""
+    ``ent``), as ONE autograd node where the fused form covers the inputs (fp32 tables, d % 4 == 0, d <= 512, a batch of
+    B (K + 1) triples with 4 B K < 2^24, a margin without gradient); the separate ops otherwise.  ``ent_win`` / ``rel_win`` =
+    (first row, rows): the ids are local to that window of the table (a KG's block of a stacked encoder output)."""
     dev = ent.device
     T, B = int(h.numel()), int(batch_size)
     eoff, en = _win(ent, ent_win)
@@ -414,7 +380,7 @@ def completion_layer_loss(ent: torch.Tensor, rel: torch.Tensor, h: torch.Tensor,
              and 4 * B * ((T - B) // B) < (1 << 24) and ent.dtype == torch.float32 and rel.dtype == torch.float32
              and (links is None or links[0].numel() > 0))
     if not fused:
-        out = triple_l1_margin_loss(ent, rel, h, r, t, B, margin, ent_win, rel_win)
+        out = margin_loss(triple_l1_score(ent[eoff:eoff + en], rel[roff:roff + rn], h, r, t, period=B), B, margin)
         if links is not None and links[0].numel() > 0:
             out = out + pair_cosine_distance(ent, links[0], ent, links[1], links[2], links[3]).mean()
         return out if add_to is None else out + add_to
@@ -432,18 +398,10 @@ def completion_layer_loss(ent: torch.Tensor, rel: torch.Tensor, h: torch.Tensor,
 
 def triple_l1_margin_loss(ent: torch.Tensor, rel: torch.Tensor, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor,
                           batch_size: int, margin: torch.Tensor, ent_win=None, rel_win=None) -> torch.Tensor:
-    """``margin_loss(triple_l1_score(ent, rel, h, r, t, period=batch_size), batch_size, margin)`` (src/jmac_model.py:345-378)
-    as one autograd node; batches that are not ``B (K + 1)`` triples long, or a margin that wants a gradient, take the two
-    ops.  ``ent_win`` / ``rel_win`` = (first row, rows): the ids are local to that window of the table (a KG's block of a
-    stacked encoder output)."""
-    dev = ent.device
-    T, B = int(h.numel()), int(batch_size)
-    eoff, en = _win(ent, ent_win)
-    roff, rn = _win(rel, rel_win)
-    if B <= 0 or T <= B or (T - B) % B != 0 or margin.numel() != 1 or margin.requires_grad:
-        return margin_loss(triple_l1_score(ent[eoff:eoff + en], rel[roff:roff + rn], h, r, t, period=B), B, margin)
-    return _TripleL1Margin.apply(ent, rel, _index(h, en, dev, "batch_h"), _index(r, rn, dev, "batch_r"),
-                                 _index(t, en, dev, "batch_t"), margin.reshape(1).to(torch.float32), B, (T - B) // B, eoff, roff, en, rn)
+    """``margin_loss(triple_l1_score(ent, rel, h, r, t, period=batch_size), batch_size, margin)`` (src/jmac_model.py:345-378):
+    ``completion_layer_loss`` without links or running loss -- one autograd node with the exact adjoint where the fused form
+    covers the inputs, the two ops otherwise."""
+    return completion_layer_loss(ent, rel, h, r, t, batch_size, margin, ent_win, rel_win)
 
 
 def margin_loss(score: torch.Tensor, batch_size: int, margin: torch.Tensor) -> torch.Tensor:

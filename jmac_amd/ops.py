@@ -340,9 +340,9 @@ class _BnTanh(torch.autograd.Function):
         save_invstd = torch.empty(d, dtype=torch.float32, device=dev)
         ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
         ws = _ws(ws_bytes, dev)
-        check(L.jmac_bn_tanh_fwd_f32(ptr(x), d, N, d, ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var),
-                                     1 if training else 0, float(momentum), float(eps), ptr(y), d, ptr(save_mean),
-                                     ptr(save_invstd), ptr(ws), ws_bytes, stream()), "jmac_bn_tanh_fwd_f32")
+        check(L.jmac_bn_tanh_fwd2_f32(ptr(x), d, N, d, ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var),
+                                      1 if training else 0, float(momentum), float(eps), ptr(y), d, None, 0, ptr(save_mean),
+                                      ptr(save_invstd), ptr(ws), ws_bytes, stream()), "jmac_bn_tanh_fwd2_f32")
         ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
         ctx.training = training
         return y
@@ -359,9 +359,9 @@ class _BnTanh(torch.autograd.Function):
         gb, gw = gbw[:d], gbw[d:]
         ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
         ws = _ws(ws_bytes, dev)
-        check(L.jmac_bn_tanh_bwd_f32(ptr(x), d, ptr(y), d, ptr(gy), d, N, d, ptr(weight), ptr(save_mean), ptr(save_invstd),
-                                     1 if ctx.training else 0, ptr(gx), d, ptr(gw), ptr(gb), ptr(ws), ws_bytes, stream()),
-              "jmac_bn_tanh_bwd_f32")
+        check(L.jmac_bn_tanh_bwd2_f32(ptr(x), d, ptr(y), d, ptr(gy), d, None, 0, N, d, ptr(weight), ptr(save_mean), ptr(save_invstd),
+                                      1 if ctx.training else 0, ptr(gx), d, ptr(gw), ptr(gb), ptr(ws), ws_bytes, stream()),
+              "jmac_bn_tanh_bwd2_f32")
         return gx, gw, gb, None, None, None, None, None
 
 

@@ -217,15 +217,7 @@ def align_entropy(e1: torch.Tensor, e2: torch.Tensor, scale: float = 20.0):
 
 def masked_row_softmax(s: torch.Tensor, row_mask: Optional[torch.Tensor], col_mask: Optional[torch.Tensor],
                        fill: float = -1.0, scale: float = 20.0) -> torch.Tensor:
-    require_device(s)
-    s = s.contiguous()
-    n1, n2 = s.shape
-    out = torch.empty_like(s)
-    rm = row_mask.to(torch.uint8).contiguous() if row_mask is not None else None
-    cm = col_mask.to(torch.uint8).contiguous() if col_mask is not None else None
-    check(lib().jmac_masked_row_softmax_f32(ptr(s), n2, n1, n2, ptr(rm), ptr(cm), float(fill), float(scale), ptr(out), n2,
-                                            stream()), "jmac_masked_row_softmax_f32")
-    return out
+    return row_softmax(s, row_mask, col_mask, fill, scale)[0]
 
 
 def _mask8(m: Optional[torch.Tensor]) -> Optional[torch.Tensor]:

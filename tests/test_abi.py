@@ -2,6 +2,7 @@
 before touching a device, and the product path refuses to run without a HIP device (no CPU fallback)."""
 import ctypes
 import os
+import re
 import subprocess
 import sys
 
@@ -22,6 +23,63 @@ def test_library_exports_every_declared_symbol():
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], stdout=subprocess.PIPE, text=True).stdout
     exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
     assert set(names) <= exported
+
+
+def _c_kind(decl: str) -> str:
+    """Kind of a C type as the header spells it: any pointer (jmac_stream_t is void*) or the scalar it names."""
+    if "*" in decl or decl == "jmac_stream_t":
+        return "pointer"
+    scalar = {"int64_t": "int64", "int32_t": "int32", "int": "int32", "float": "float", "double": "double",
+              "size_t": "size_t", "void": "void"}
+    return scalar[" ".join(w for w in decl.split() if w != "const")]
+
+
+def _ctypes_kind(t) -> str:
+    """Kind of a ctypes type in _lib's tables (None = void return)."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    scalar = {ctypes.c_int64: "int64", ctypes.c_int32: "int32", ctypes.c_float: "float", ctypes.c_double: "double",
+              ctypes.c_size_t: "size_t"}
+    return scalar[t]
+
+
+def _prototypes(path):
+    """name -> (return type, [parameter types]) of every function the header declares."""
+    text = "\n".join(l for l in _lib.header_text(path).splitlines() if not l.lstrip().startswith("#"))
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][\w\s*]*?)\b(jmac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        params = " ".join(m.group(3).split())
+        types = []
+        for p in ([] if params in ("", "void") else params.split(",")):
+            t = re.sub(r"\s*\b[A-Za-z_]\w*$", "", p.strip())       # drop the parameter's name
+            assert t, (m.group(2), p)
+            types.append(t)
+        out[m.group(2)] = (" ".join(m.group(1).split()), types)
+    return out
+
+
+@pytest.mark.parametrize("header,sigs", [("jmac_hip.h", _lib._SIGS), ("jmac_hip_testing.h", _lib._TESTING_SIGS)])
+def test_ctypes_signatures_match_the_header(header, sigs):
+    """Every ctypes signature in _lib has the header prototype's argument count, and per position and for the return value
+    the same kind of type: a wrong int32 / int64 / float would otherwise pass garbage to a kernel without any error."""
+    path = os.path.join(os.path.dirname(_lib.HEADER_PATH), header)
+    protos = _prototypes(path)
+    assert sorted(protos) == _lib.header_symbols(path)                # every declared function was parsed
+    assert set(sigs) == set(protos)
+    bad = []
+    for name, (ret, params) in sorted(protos.items()):
+        res, args = sigs[name]
+        if _ctypes_kind(res) != _c_kind(ret):
+            bad.append("%s: returns %s, ctypes says %s" % (name, ret, res))
+        if len(args) != len(params):
+            bad.append("%s: %d arguments, ctypes says %d" % (name, len(params), len(args)))
+            continue
+        for i, (p, a) in enumerate(zip(params, args)):
+            if _ctypes_kind(a) != _c_kind(p):
+                bad.append("%s: argument %d is %s, ctypes says %s" % (name, i, p, a.__name__))
+    assert not bad, "\n".join(bad)
 
 
 def test_argument_validation_needs_no_device():

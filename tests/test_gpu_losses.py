@@ -171,9 +171,10 @@ def test_margin_loss_matches_reference_expression(B, K):
 
 @pytest.mark.parametrize("B,K,d", [(64, 5, 40), (250, 25, 300), (7, 1, 12)])
 def test_triple_l1_margin_loss_is_the_two_ops_in_one_node(B, K, d):
-    """losses.triple_l1_margin_loss == margin_loss(triple_l1_score(...)): same loss (bitwise: the same two forward kernels),
-    same gradients for both tables (the score gradient is derived inside the L1 adjoint; float atomics: tolerance), on the
-    reference's batch layout (sub.repeat(K+1), rel.repeat(K+1), cat(obj, negatives); train.py:347-352)."""
+    """losses.triple_l1_margin_loss (the completion_layer_loss node) == margin_loss(triple_l1_score(...)): same loss (bitwise: the
+    same two forward kernels), same gradients for both tables (the score gradient is derived inside the exact L1 adjoint; the
+    separate ops sum with float atomics: tolerance), on the reference's batch layout (sub.repeat(K+1), rel.repeat(K+1),
+    cat(obj, negatives); train.py:347-352)."""
     from jmac_amd import losses
     gen = torch.Generator(device="cuda").manual_seed(B * K + d)
     n, nr = 5 * B, 17
@@ -204,6 +205,25 @@ def test_triple_l1_margin_loss_is_the_two_ops_in_one_node(B, K, d):
         losses.triple_l1_margin_loss(ent0, rel0, h[:-1], r[:-1], t[:-1], B, margin)
 
 
+def _exact_l1_margin_adjoint(ent, rel, h, r, t, B, K, margin, gloss):
+    """A torch restatement of the exact L1 margin adjoint (jmac_triple_l1_margin_bwd_exact2_f32) -> (d ent, d rel): the score
+    gradient in units of u = gloss / (2 B K) is an integer per triple (2 w with w = 1, 1/2 or 0 from the fp32 scores), the count
+    tables are those integers times the fp32 signs, summed in float64 (exact: integers below 2^24), and each table is one fp32
+    product with u as scale_clear_flat2_kernel forms it (u = gloss * (1 / (2 B K)), every step rounded to fp32)."""
+    from jmac_amd import losses
+    with torch.no_grad():
+        score = losses.triple_l1_score(ent, rel, h, r, t, period=B)        # the node's forward kernel: the same scores
+        diff = score[:B].unsqueeze(0) - score[B:].view(K, B)               # [K, B]: pos_b - neg_{b,k} (n-major negatives), fp32
+        gam = margin.detach().reshape(())
+        w2 = (diff > -gam).double() * 2 + (diff == -gam).double()          # 2 w: 2, 1 (tie) or 0
+        G = torch.cat((w2.sum(0), -w2.reshape(-1)))                        # [T]
+        c = G[:, None] * torch.sign((ent[h] + rel[r]) - ent[t]).double()   # the kernel's fp32 signs
+        cnt_e = torch.zeros(ent.shape, dtype=torch.float64, device=ent.device).index_add_(0, h, c).index_add_(0, t, -c)
+        cnt_r = torch.zeros(rel.shape, dtype=torch.float64, device=ent.device).index_add_(0, r, c)
+        u = np.float32(gloss) * (np.float32(1) / (np.float32(2) * np.float32(B) * np.float32(K)))
+        return cnt_e.float() * float(u), cnt_r.float() * float(u)
+
+
 def _layer_loss_case(B, K, d, seed, n=None, nr=17, L=0):
     gen = torch.Generator().manual_seed(seed)
     n = n or 5 * B
@@ -221,9 +241,10 @@ def _layer_loss_case(B, K, d, seed, n=None, nr=17, L=0):
 def test_completion_layer_loss_is_the_separate_ops_in_one_node(B, K, d, L):
     """losses.completion_layer_loss (round 5: one node per layer's term of completion_loss, src/jmac_model.py:331-380) against
     (a) the oracle's float64 restatement -- margin ranking loss of the L1 triple scores + alignment_loss_simple on the links + the
-    running loss -- forward and both table gradients, and (b) the separate ops of this library composed with torch adds: the loss
-    to rounding, the L1 term's gradients BITWISE (the same integers times the same factor), the sum with the cosine rows to the
-    last bit or two.  The persistent count tables are zero again afterwards."""
+    running loss -- forward and both table gradients, and (b) the separate ops of this library composed with torch adds for the
+    loss (to rounding) and a torch restatement of the exact L1 adjoint for the gradients: the L1 term's gradients BITWISE (the
+    same integers times the same factor), the sum with the cosine rows of the separate cosine op to the last bit or two.  The
+    persistent count tables are zero again afterwards."""
     from jmac_amd import losses
     ent, rel, h, r, t, links = _layer_loss_case(B, K, d, B * K + d, L=L)
     n = ent.shape[0]
@@ -244,16 +265,18 @@ def test_completion_layer_loss_is_the_separate_ops_in_one_node(B, K, d, L):
     lk = (links[:, 0].contiguous().to(dev), links[:, 1].contiguous().to(dev), w0, w1) if L else None
     mg, pv = margin.to(dev), prev.to(dev)
     res = []
-    for fused in (True, False):
-        eg, rg = ent.to(dev).requires_grad_(True), rel.to(dev).requires_grad_(True)
-        if fused:
-            loss = losses.completion_layer_loss(eg, rg, hd, rd, td, B, mg, links=lk, add_to=pv)
-        else:
-            loss = losses.triple_l1_margin_loss(eg, rg, hd, rd, td, B, mg) + pv
-            if L:
-                loss = loss + losses.pair_cosine_distance(eg, lk[0], eg, lk[1], w0, w1).mean()
-        (loss * 1.7).sum().backward()
-        res.append((loss.detach(), eg.grad, rg.grad))
+    eg, rg = ent.to(dev).requires_grad_(True), rel.to(dev).requires_grad_(True)
+    loss = losses.completion_layer_loss(eg, rg, hd, rd, td, B, mg, links=lk, add_to=pv)
+    (loss * 1.7).sum().backward()
+    res.append((loss.detach(), eg.grad, rg.grad))
+    eg, rg = ent.to(dev).requires_grad_(True), rel.to(dev).requires_grad_(True)
+    loss = losses.margin_loss(losses.triple_l1_score(eg.detach(), rg.detach(), hd, rd, td, period=B), B, mg) + pv
+    d_ent, d_rel = _exact_l1_margin_adjoint(eg.detach(), rg.detach(), hd, rd, td, B, K, mg, 1.7)
+    if L:
+        cos = losses.pair_cosine_distance(eg, lk[0], eg, lk[1], w0, w1).mean()
+        (cos * 1.7).sum().backward()
+        loss, d_ent = loss + cos.detach(), d_ent + eg.grad
+    res.append((loss, d_ent, d_rel))
     assert tuple(res[0][0].shape) == (1,)
     assert abs(float(res[0][0]) - float(ref)) <= 1e-5 * abs(float(ref))
     assert abs(float(res[0][0]) - float(res[1][0])) <= 1e-6 * abs(float(ref))
