@@ -217,6 +217,13 @@ def check(rc: int, what: str = "") -> None:
         raise JmacError("%s failed: %s (rc=%d)" % (what or "jmac call", msg.decode() if msg else "?", rc))
 
 
+def workspace(nbytes: int, device):
+    """Scratch buffer of a launch: ``nbytes`` bytes, at least 16 -- an empty tensor has a NULL pointer, which the entry points
+    refuse even where they need no scratch."""
+    import torch
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
 def ptr(t) -> Optional[int]:
     """Device pointer of a tensor (None -> NULL)."""
     if t is None:

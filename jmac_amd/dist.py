@@ -326,12 +326,12 @@ class _HipBN:
 
     @staticmethod
     def moments(x):
-        from ._lib import check, lib, ptr, stream
+        from ._lib import check, lib, ptr, stream, workspace
         n, d = x.shape
         mean = torch.empty(d, dtype=torch.float32, device=x.device)
         m2 = torch.empty(d, dtype=torch.float32, device=x.device)
         wsb = int(lib().jmac_bn_tanh_workspace_bytes(n, d))
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
+        ws = workspace(wsb, x.device)
         check(lib().jmac_col_moments_f32(ptr(x), x.stride(0), n, d, ptr(mean), ptr(m2), ptr(ws), wsb, stream()), "jmac_col_moments_f32")
         return mean, m2
 
@@ -346,11 +346,11 @@ class _HipBN:
 
     @staticmethod
     def bwd_sums(x, y, gy, mean, invstd):
-        from ._lib import check, lib, ptr, stream
+        from ._lib import check, lib, ptr, stream, workspace
         n, d = x.shape
         sums = torch.empty(2 * d, dtype=torch.float32, device=x.device)
         wsb = int(lib().jmac_bn_tanh_workspace_bytes(n, d))
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=x.device)
+        ws = workspace(wsb, x.device)
         check(lib().jmac_bn_tanh_bwd_sums_f32(ptr(x), x.stride(0), ptr(y), d, ptr(gy), gy.stride(0), n, d, ptr(mean), ptr(invstd),
                                               ptr(sums), ptr(ws), wsb, stream()), "jmac_bn_tanh_bwd_sums_f32")
         return sums

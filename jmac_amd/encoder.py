@@ -116,100 +116,18 @@ def _empty(dev, *shape):
     return torch.empty(shape, dtype=torch.float32, device=dev)
 
 
-def _agg_fwd(PQZ, RR, a, graph: RelGraph, slope, out_scale=0.5, compact=False):
-    """jmac_rel_attn_aggregate_fwd_{f32,bf16,bf16_padded} on the [P|Q|Z] table (fp32, or bf16 for the inference form: sums,
-    softmax and the output stay fp32; bf16 tables may carry padded halves, ops.bf16_pad); the self loop is the last relation
-    row."""
-    L = lib()
-    N, d3 = PQZ.shape
-    dh, d = d3 // 3, int(a.numel())
-    dev = PQZ.device
-    bf16 = PQZ.dtype == torch.bfloat16
-    out, smax, sden = _empty(dev, N, d), _empty(dev, max(N, 1)), _empty(dev, max(N, 1))
-    s = graph.by_dst
-    wsb = int(L.jmac_rel_attn_fwd_workspace_bytes(s.n_parts_max, d))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    etype = graph.etype_c if compact else graph.etype         # compact: RR holds the rows of graph.rel_used + the loop row
-    sview = s.view_compact(graph.col, graph.etype_c) if compact else s.view()
-    ev0 = ops._ev() if ops.PROFILE is not None else None
-    if dh != d:
-        if not bf16 or RR.shape[1] != 2 * dh:
-            raise ValueError("padded table halves exist for bf16 tables only")
-        check(L.jmac_rel_attn_aggregate_fwd_bf16_padded(
-            ptr(PQZ), d3, PQZ.data_ptr() + dh * PQZ.element_size(), d3, ptr(RR), RR.stride(0), dh, ptr(a), ptr(graph.col),
-            ptr(etype), C.byref(sview), N, d, float(slope), RR.shape[0] - 1, 0, float(out_scale), ptr(out), d, ptr(smax),
-            ptr(sden), ptr(ws), wsb, stream()), "jmac_rel_attn_aggregate_fwd_bf16_padded")
-    else:
-        fwd = L.jmac_rel_attn_aggregate_fwd_bf16 if bf16 else L.jmac_rel_attn_aggregate_fwd_f32
-        check(fwd(
-            ptr(PQZ), d3, PQZ.data_ptr() + d * PQZ.element_size(), d3, ptr(RR), RR.stride(0), ptr(a), ptr(graph.col), ptr(etype),
-            C.byref(sview), N, d, float(slope), RR.shape[0] - 1, 0, float(out_scale), ptr(out), d, ptr(smax), ptr(sden),
-            ptr(ws), wsb, stream()), "jmac_rel_attn_aggregate_fwd_%s" % ("bf16" if bf16 else "f32"))
-    if ev0 is not None:
-        ops.PROFILE.append(("rel_attn_fwd_bf16" if bf16 else "rel_attn_fwd", ev0, ops._ev()))
-    return out, smax, sden
-
-
 PAIR_LAUNCHES = True      # tests / A-B: False runs the two independent first layers' aggregations as two launches each
 
 
 def _agg_fwd_pair(specs, graph: RelGraph, out_scale=0.5, compact=False):
     """jmac_rel_attn_aggregate_fwd_jobs_f32: the forward aggregation of TWO independent layers on the same graph (fp32 tables
-    [P|Q|Z], relation tables, attention vectors, slopes = ``specs``) as one launch -> [(out, seg_max, seg_den)] * 2."""
-    L = lib()
-    s = graph.by_dst
-    etype = graph.etype_c if compact else graph.etype
-    sview = s.view_compact(graph.col, graph.etype_c) if compact else s.view()
-    jobs = (AggFwdJob * len(specs))()
-    res, keep = [], []
-    for k, (PQZ, RR, a, slope) in enumerate(specs):
-        N, d3 = PQZ.shape
-        d = d3 // 3
-        dev = PQZ.device
-        out, smax, sden = _empty(dev, N, d), _empty(dev, max(N, 1)), _empty(dev, max(N, 1))
-        wsb = int(L.jmac_rel_attn_fwd_workspace_bytes(s.n_parts_max, d))
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-        j = jobs[k]
-        j.P, j.ldp, j.QZ, j.ldqz, j.RR, j.ldrr, j.a_att = ptr(PQZ), d3, PQZ.data_ptr() + d * 4, d3, ptr(RR), RR.stride(0), ptr(a)
-        j.col, j.etype, j.by_dst, j.N, j.d, j.slope = ptr(graph.col), ptr(etype), C.pointer(sview), N, d, float(slope)
-        j.loop_rel, j.self_off, j.out_scale = RR.shape[0] - 1, 0, float(out_scale)
-        j.out, j.ldo, j.seg_max, j.seg_den, j.ws, j.ws_bytes = ptr(out), d, ptr(smax), ptr(sden), ptr(ws), wsb
-        res.append((out, smax, sden))
-        keep.append(ws)
-    ev0 = ops._ev() if ops.PROFILE is not None else None
-    check(L.jmac_rel_attn_aggregate_fwd_jobs_f32(jobs, len(specs), stream()), "jmac_rel_attn_aggregate_fwd_jobs_f32")
-    if ev0 is not None:
-        ops.PROFILE.append(("rel_attn_fwd_pair", ev0, ops._ev()))
-    return res
-
-
-def _agg_bwd(PQZ, RR, a, graph: RelGraph, slope, out, smax, sden, G, out_scale=0.5, compact=False):
-    """Deterministic backward (three launches): dPQZ [N,3d], dRR [nrel,2d], da [d]."""
-    L = lib()
-    N, d3 = PQZ.shape
-    d = d3 // 3
-    dev = PQZ.device
-    nrel = RR.shape[0]
-    if compact:
-        graph.ensure_backward_views_compact()
-    else:
-        graph.ensure_backward_views()
-    by_rel, etype = (graph.by_rel_c, graph.etype_c) if compact else (graph.by_rel, graph.etype)
-    dPQZ, dRR, da = _empty(dev, N, d3), _empty(dev, nrel, 2 * d), _empty(dev, d)
-    vd = graph.by_dst_bwd.view_compact(graph.col, graph.etype_c) if compact else graph.by_dst_bwd.view()
-    vs, vr = graph.by_src.view(), by_rel.view()
-    wsb = int(L.jmac_rel_attn_bwd_workspace_bytes(N, graph.E, nrel, d, graph.by_dst_bwd.n_parts_max, graph.by_src.n_parts_max,
-                                                  by_rel.n_parts_max, 1))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    ev0 = ops._ev() if ops.PROFILE is not None else None
-    check(L.jmac_rel_attn_aggregate_bwd_f32(
-        ptr(PQZ), d3, PQZ.data_ptr() + d * 4, d3, ptr(RR), RR.stride(0), ptr(a), ptr(graph.col), ptr(etype),
-        ptr(graph.dst_of_slot), C.byref(vd), C.byref(vs), C.byref(vr), N, N, graph.E, nrel, d, float(slope), nrel - 1, 0,
-        float(out_scale), ptr(out), d, ptr(smax), ptr(sden), ptr(G), G.stride(0), ptr(dPQZ), d3, dPQZ.data_ptr() + d * 4, d3,
-        ptr(dRR), 2 * d, ptr(da), 1, ptr(ws), wsb, stream()), "jmac_rel_attn_aggregate_bwd_f32")
-    if ev0 is not None:
-        ops.PROFILE.append(("rel_attn_bwd", ev0, ops._ev()))
-    return dPQZ, dRR, da
+    [P|Q|Z], relation tables, attention vectors, slopes = ``specs``) as one launch -> [(out, seg_max, seg_den)] * 2.  A job
+    holds the arguments of the single launch (ops.rel_attn_split_fwd_raw)."""
+    calls = [ops._fwd_call(*ops.pqz_views(PQZ), RR, a, graph, slope, out_scale, RR.shape[0] - 1, 0, compact)
+             for PQZ, RR, a, slope in specs]
+    jobs = (AggFwdJob * len(calls))(*[AggFwdJob(*args[:-1]) for _, args, _, _ in calls])      # (without the stream)
+    ops._launch(lib().jmac_rel_attn_aggregate_fwd_jobs_f32, (jobs, len(calls), stream()), "rel_attn_fwd_pair")
+    return [res for _, _, res, _ in calls]
 
 
 class RowBlocks:
@@ -237,58 +155,20 @@ def _bn_fwd(x, bn, training, y, y2=None, seg=None):
     """tanh(BatchNorm1d(x)) into y (and y2), nn.BatchNorm1d bookkeeping included (src/jmac_model.py:52).  ``seg`` (RowBlocks,
     more than one block, batch statistics): every block of rows is normalised with ITS statistics and the running estimates
     move once per block, as one forward_base call per KG leaves them (src/jmac_model.py:325-326)."""
-    L = lib()
-    N, d = x.shape
-    dev = x.device
     use_batch = bool(training or not bn.track_running_stats)
-    nb = seg.nb if (seg is not None and use_batch) else 1
-    if nb > 1 and seg.offsets[-1] != N:
-        raise ValueError("RowBlocks cover %d rows, the layer has %d" % (seg.offsets[-1], N))
     if training and bn.track_running_stats:
         if _TRACKERS is not None:
             _TRACKERS.append(bn.num_batches_tracked)           # the encoder node bumps its layers' counters in ONE launch
         else:
-            bn.num_batches_tracked.add_(nb)
-    if nb > 1:
-        mean, invstd = _empty(dev, nb, d), _empty(dev, nb, d)
-        wsb = int(L.jmac_bn_tanh_seg_workspace_bytes(nb, d))
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-        check(L.jmac_bn_tanh_seg_fwd2_f32(ptr(x), x.stride(0), d, nb, seg.c_ptr, seg.c_order, ptr(bn.weight), ptr(bn.bias),
-                                          ptr(bn.running_mean), ptr(bn.running_var), float(bn.momentum), float(bn.eps), ptr(y),
-                                          y.stride(0), ptr(y2), y2.stride(0) if y2 is not None else 0, ptr(mean), ptr(invstd),
-                                          ptr(ws), wsb, stream()), "jmac_bn_tanh_seg_fwd2_f32")
-        return mean, invstd, use_batch
-    mean, invstd = _empty(dev, d), _empty(dev, d)
-    wsb = int(L.jmac_bn_tanh_workspace_bytes(N, d))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    check(L.jmac_bn_tanh_fwd2_f32(ptr(x), x.stride(0), N, d, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                                  ptr(bn.running_var), 1 if use_batch else 0, float(bn.momentum), float(bn.eps), ptr(y),
-                                  y.stride(0), ptr(y2), y2.stride(0) if y2 is not None else 0, ptr(mean), ptr(invstd), ptr(ws),
-                                  wsb, stream()), "jmac_bn_tanh_fwd2_f32")
+            bn.num_batches_tracked.add_(seg.nb if seg is not None else 1)
+    mean, invstd = ops.bn_tanh_fwd_raw(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch, bn.momentum, bn.eps,
+                                       y, y2, seg)
     return mean, invstd, use_batch
 
 
-def _bn_bwd(x, y, gy, gy2, weight, mean, invstd, use_batch, seg=None):
-    L = lib()
-    N, d = x.shape
-    dev = x.device
-    gx, gbw = _empty(dev, N, d), _empty(dev, 2 * d)            # gbw = [grad bias | grad weight]
-    if mean.dim() == 2:                                        # per-block statistics (segmented forward)
-        nb = seg.nb
-        wsb = int(L.jmac_bn_tanh_seg_workspace_bytes(nb, d))
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-        check(L.jmac_bn_tanh_seg_bwd2_f32(ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(gy), gy.stride(0), ptr(gy2),
-                                          gy2.stride(0) if gy2 is not None else 0, d, nb, seg.c_ptr, ptr(weight), ptr(mean),
-                                          ptr(invstd), ptr(gx), d, gbw.data_ptr() + d * 4, ptr(gbw), ptr(ws), wsb, stream()),
-              "jmac_bn_tanh_seg_bwd2_f32")
-        return gx, gbw
-    wsb = int(L.jmac_bn_tanh_workspace_bytes(N, d))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    check(L.jmac_bn_tanh_bwd2_f32(ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(gy), gy.stride(0), ptr(gy2),
-                                  gy2.stride(0) if gy2 is not None else 0, N, d, ptr(weight), ptr(mean), ptr(invstd),
-                                  1 if use_batch else 0, ptr(gx), d, gbw.data_ptr() + d * 4, ptr(gbw), ptr(ws), wsb, stream()),
-          "jmac_bn_tanh_bwd2_f32")
-    return gx, gbw
+# Backward of _bn_fwd: (x, y, gy, gy2, weight, mean, invstd, use_batch, seg) -> gx, [grad bias | grad weight].  The backward
+# touches no module state, so it is the raw launch itself.
+_bn_bwd = ops.bn_tanh_bwd_raw
 
 
 def _norm_drop_fwd(x, p_drop, training, y, mask=None, seed=None):
@@ -746,7 +626,9 @@ def _layer_fwd(lay, X, wc, RR, a, graph, training, y, y2=None, table_dtype=torch
     slope = float(lay.atv_mlp.negative_slope)
     if agg is _DEFER:                                   # the caller aggregates (two layers in one launch) and finishes below
         return SimpleNamespace(X=X, wc=wc, RR=RR, a=a, PQZ=PQZ, slope=slope)
-    pre, smax, sden = agg if agg is not None else _agg_fwd(PQZ, RR, a, graph, slope, compact=compact)
+    if agg is None:                                     # the self loop is the last relation row
+        agg = ops.rel_attn_split_fwd_raw(*ops.pqz_views(PQZ), RR, a, graph, slope, 0.5, RR.shape[0] - 1, 0, compact=compact)
+    pre, smax, sden = agg
     mean, invstd, use_batch = _bn_fwd(pre, lay.bn, training, y, y2, seg)
     return SimpleNamespace(X=X, wc=wc, RR=RR, a=a, PQZ=PQZ, pre=pre, smax=smax, sden=sden, y=y, mean=mean, invstd=invstd,
                            use_batch=use_batch, slope=slope, bn_weight=lay.bn.weight, seg=seg, compact=compact, rows=rows)
@@ -765,7 +647,9 @@ def _layer_bwd(st, graph, gy, gy2, dX, dX_accumulate):
     """Backward of _layer_fwd.  dX: destination of the input gradient (None: not needed).  Returns dRR, dwc (node part),
     da, gbw."""
     gpre, gbw = _bn_bwd(st.pre, st.y, gy, gy2, st.bn_weight, st.mean, st.invstd, st.use_batch, st.seg)
-    dPQZ, dRR, da = _agg_bwd(st.PQZ, st.RR, st.a, graph, st.slope, st.pre, st.smax, st.sden, gpre, compact=st.compact)
+    dPQZ = _empty(st.PQZ.device, *st.PQZ.shape)
+    _, _, dRR, da = ops.rel_attn_split_bwd_raw(*ops.pqz_views(st.PQZ), st.RR, st.a, graph, st.slope, 0.5, st.RR.shape[0] - 1, 0,
+                                               st.pre, st.smax, st.sden, gpre, compact=st.compact, dPQZ=dPQZ)
     rows = getattr(st, "rows", None)
     if dX is not None and rows is not None:
         # class-ordered rows: dP is zero outside the destinations, dQ outside the sources -- the three terms of the input gradient

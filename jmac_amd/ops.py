@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import check, lib, ptr, require_device, stream, testing_lib
+from ._lib import check, lib, ptr, require_device, stream, testing_lib, workspace
 from .graph import RelGraph
 
 BWD_MODE_ATOMIC = 0            # testing build only (libjmac_hip_testing.so): float atomics, a second implementation for the tests
@@ -27,8 +27,14 @@ def _ev():
     return e
 
 
-def _ws(nbytes: int, device) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+def _launch(fn, args, name: str) -> None:
+    """check(fn(*args)), between two PROFILE events recorded as ``name`` while PROFILE is a list."""
+    if PROFILE is None:
+        check(fn(*args), fn.__name__)
+        return
+    ev0 = _ev()
+    check(fn(*args), fn.__name__)
+    PROFILE.append((name, ev0, _ev()))
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -68,6 +74,12 @@ def pad_table(t: torch.Tensor, d: int, parts: int) -> torch.Tensor:
     return pad_table_weight(t, d, parts)
 
 
+def pqz_views(PQZ: torch.Tensor):
+    """P and [Q|Z]: column views of a [P|Q|Z] table (half pitch PQZ.shape[1] // 3), as the raw forms below take them."""
+    dh = PQZ.shape[1] // 3
+    return PQZ[:, :dh], PQZ[:, dh:]
+
+
 class _RelAttnAggregate(torch.autograd.Function):
     """out = out_scale * ( sqrt(deg) * softmax-weighted sum over in-edges of (Z[j]-Rz[t]) + [Z[i]-Rz[loop]] ).
 
@@ -78,41 +90,8 @@ class _RelAttnAggregate(torch.autograd.Function):
     def forward(ctx, PQZ, RR, a, graph: RelGraph, slope: float, loop_rel: int, out_scale: float, bwd_mode: int):
         require_device(PQZ, RR, a)
         PQZ, RR, a = _table(PQZ).contiguous(), _table(RR).contiguous(), _f32c(a).contiguous()
-        if PQZ.dtype != RR.dtype:
-            raise TypeError("PQZ and RR must share a dtype")
-        bf16 = PQZ.dtype == torch.bfloat16
-        N, d3 = PQZ.shape
-        dh = d3 // 3                       # half pitch of the table rows; > d for padded bf16 tables (bf16_pad)
-        d = int(a.numel())
-        if dh != d and not (bf16 and dh == bf16_pad(d) and RR.shape[1] == 2 * dh):
-            raise ValueError("tables of half pitch %d do not go with a_att of %d elements" % (dh, d))
-        if graph.N != N:
-            raise ValueError("graph has %d nodes, tables have %d rows" % (graph.N, N))
-        L = lib()
-        dev = PQZ.device
-        out = torch.empty((N, d), dtype=torch.float32, device=dev)
-        seg_max = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
-        seg_den = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
-        s = graph.by_dst
-        ws_bytes = int(L.jmac_rel_attn_fwd_workspace_bytes(s.n_parts_max, d))
-        ws = _ws(ws_bytes, dev)
-        esz = PQZ.element_size()
-        ev0 = _ev() if PROFILE is not None else None
-        if dh != d:
-            check(L.jmac_rel_attn_aggregate_fwd_bf16_padded(
-                ptr(PQZ), d3, PQZ.data_ptr() + dh * esz, d3, ptr(RR), RR.shape[1], dh, ptr(a),
-                ptr(graph.col), ptr(graph.etype), C.byref(s.view()), N, d, float(slope), int(loop_rel), 0, float(out_scale),
-                ptr(out), d, ptr(seg_max), ptr(seg_den), ptr(ws), ws_bytes, stream()), "jmac_rel_attn_aggregate_fwd_bf16_padded")
-        else:
-            fwd = L.jmac_rel_attn_aggregate_fwd_bf16 if bf16 else L.jmac_rel_attn_aggregate_fwd_f32
-            check(fwd(
-                ptr(PQZ), d3, PQZ.data_ptr() + d * esz, d3, ptr(RR), RR.shape[1], ptr(a),
-                ptr(graph.col), ptr(graph.etype), C.byref(s.view()), N, d, float(slope), int(loop_rel), 0, float(out_scale),
-                ptr(out), d, ptr(seg_max), ptr(seg_den), ptr(ws), ws_bytes, stream()),
-                "jmac_rel_attn_aggregate_fwd_%s" % ("bf16" if bf16 else "f32"))
-        if ev0 is not None:
-            PROFILE.append(("rel_attn_fwd_bf16" if bf16 else "rel_attn_fwd", ev0, _ev()))
-        if bf16:
+        out, seg_max, seg_den = rel_attn_split_fwd_raw(*pqz_views(PQZ), RR, a, graph, slope, out_scale, loop_rel, 0)
+        if PQZ.dtype == torch.bfloat16:
             ctx.mark_non_differentiable(out)
             return out
         ctx.save_for_backward(PQZ, RR, a, out, seg_max, seg_den)
@@ -122,38 +101,9 @@ class _RelAttnAggregate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, G):
         PQZ, RR, a, out, seg_max, seg_den = ctx.saved_tensors
-        graph: RelGraph = ctx.graph
-        mode = int(ctx.bwd_mode)
-        L = lib() if mode == BWD_MODE_DETERMINISTIC else testing_lib()      # mode 0 exists in the testing build only
-        dev = PQZ.device
-        N, d3 = PQZ.shape
-        d = d3 // 3
-        nrel = RR.shape[0]
-        G = _f32c(G).contiguous()
-        if mode == BWD_MODE_DETERMINISTIC:
-            graph.ensure_backward_views()
         dPQZ = torch.empty_like(PQZ)
-        dRR = torch.empty_like(RR)
-        da = torch.empty_like(a)
-        vd = graph.by_dst_bwd.view()
-        vs = graph.by_src.view() if mode else None
-        vr = graph.by_rel.view() if mode else None
-        ws_bytes = int(L.jmac_rel_attn_bwd_workspace_bytes(
-            N, graph.E, nrel, d, graph.by_dst_bwd.n_parts_max,
-            graph.by_src.n_parts_max if mode else 0, graph.by_rel.n_parts_max if mode else 0, mode))
-        ws = _ws(ws_bytes, dev)
-        esz = PQZ.element_size()
-        ev0 = _ev() if PROFILE is not None else None
-        check(L.jmac_rel_attn_aggregate_bwd_f32(
-            ptr(PQZ), d3, PQZ.data_ptr() + d * esz, d3, ptr(RR), RR.shape[1], ptr(a),
-            ptr(graph.col), ptr(graph.etype), ptr(graph.dst_of_slot) if mode else None,
-            C.byref(vd), C.byref(vs) if mode else None, C.byref(vr) if mode else None,
-            N, N, graph.E, nrel, d, float(ctx.slope), int(ctx.loop_rel), 0, float(ctx.out_scale),
-            ptr(out), d, ptr(seg_max), ptr(seg_den), ptr(G), d,
-            ptr(dPQZ), d3, dPQZ.data_ptr() + d * esz, d3, ptr(dRR), dRR.shape[1], ptr(da),
-            mode, ptr(ws), ws_bytes, stream()), "jmac_rel_attn_aggregate_bwd_f32")
-        if ev0 is not None:
-            PROFILE.append(("rel_attn_bwd", ev0, _ev()))
+        _, _, dRR, da = rel_attn_split_bwd_raw(*pqz_views(PQZ), RR, a, ctx.graph, ctx.slope, ctx.out_scale, ctx.loop_rel, 0, out,
+                                               seg_max, seg_den, G, mode=int(ctx.bwd_mode), dPQZ=dPQZ)
         return dPQZ, dRR, da, None, None, None, None, None
 
 
@@ -165,11 +115,16 @@ def rel_attn_aggregate(PQZ: torch.Tensor, RR: torch.Tensor, a: torch.Tensor, gra
     return _RelAttnAggregate.apply(PQZ, RR, a, graph, float(slope), int(loop_rel), float(out_scale), int(bwd_mode))
 
 
-def rel_attn_split_fwd_raw(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int):
-    """jmac_rel_attn_aggregate_fwd_f32 with P [N_dst, d] and QZ [N_src, 2d] as separate tables (no autograd): out [N, d] and
-    the per-destination softmax (max, denominator)."""
-    N, d = P.shape
-    if graph.N != N or graph.num_src != QZ.shape[0] or QZ.shape[1] != 2 * d:
+def _fwd_call(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int, compact: bool):
+    """(entry point, arguments, (out, seg_max, seg_den), workspace) of one forward aggregation.  The arguments of the fp32 form
+    without the stream are the fields of an AggFwdJob (jmac_rel_attn_aggregate_fwd_jobs_f32)."""
+    if QZ.dtype != P.dtype or RR.dtype != P.dtype:
+        raise TypeError("P, QZ and RR must share a dtype")
+    N, dh, d = P.shape[0], P.shape[1], int(a.numel())      # dh: half pitch of the table rows; > d for padded bf16 tables
+    bf16 = P.dtype == torch.bfloat16
+    if dh != d and not (bf16 and dh == bf16_pad(d) and RR.shape[1] == 2 * dh):
+        raise ValueError("tables of half pitch %d do not go with a_att of %d elements" % (dh, d))
+    if graph.N != N or graph.num_src != QZ.shape[0] or QZ.shape[1] != 2 * dh:
         raise ValueError("graph / table shapes disagree")
     L = lib()
     dev = P.device
@@ -178,48 +133,85 @@ def rel_attn_split_fwd_raw(P, QZ, RR, a, graph: RelGraph, slope: float, out_scal
     seg_den = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
     s = graph.by_dst
     ws_bytes = int(L.jmac_rel_attn_fwd_workspace_bytes(s.n_parts_max, d))
-    ws = _ws(ws_bytes, dev)
-    ev0 = _ev() if PROFILE is not None else None
-    check(L.jmac_rel_attn_aggregate_fwd_f32(
-        ptr(P), d, ptr(QZ), 2 * d, ptr(RR), RR.shape[1], ptr(a),
-        ptr(graph.col), ptr(graph.etype), C.byref(s.view()), N, d, float(slope), int(loop_rel), int(self_off), float(out_scale),
-        ptr(out), d, ptr(seg_max), ptr(seg_den), ptr(ws), ws_bytes, stream()), "jmac_rel_attn_aggregate_fwd_f32")
-    if ev0 is not None:
-        PROFILE.append(("rel_attn_fwd", ev0, _ev()))
-    return out, seg_max, seg_den
+    ws = workspace(ws_bytes, dev)
+    # compact: RR holds the rows of graph.rel_used + the loop row (RelGraph.ensure_rel_compact)
+    etype, view = (graph.etype_c, s.view_compact(graph.col, graph.etype_c)) if compact else (graph.etype, s.view())
+    if dh != d:                                         # the padded form takes the half pitch after ldrr
+        fn, pitch = L.jmac_rel_attn_aggregate_fwd_bf16_padded, (dh,)
+    else:
+        fn, pitch = (L.jmac_rel_attn_aggregate_fwd_bf16 if bf16 else L.jmac_rel_attn_aggregate_fwd_f32), ()
+    args = (ptr(P), P.stride(0), ptr(QZ), QZ.stride(0), ptr(RR), RR.stride(0), *pitch, ptr(a), ptr(graph.col), ptr(etype),
+            C.pointer(view), N, d, float(slope), int(loop_rel), int(self_off), float(out_scale), ptr(out), d, ptr(seg_max),
+            ptr(seg_den), ptr(ws), ws_bytes, stream())
+    return fn, args, (out, seg_max, seg_den), ws
+
+
+def rel_attn_split_fwd_raw(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int, *,
+                           compact: bool = False):
+    """The forward aggregation without autograd on P [N_dst, dh] and QZ [N_src, 2dh] -- separate tables, or the column views
+    of one [P|Q|Z] table (pqz_views): out [N, d] and the per-destination softmax (max, denominator).  d = a.numel(); the half
+    pitch dh is d, or bf16_pad(d) for padded bf16 tables.  ``compact``: the edge types and RR's rows are in the compact
+    relation numbering (RelGraph.ensure_rel_compact)."""
+    fn, args, res, ws = _fwd_call(P, QZ, RR, a, graph, slope, out_scale, loop_rel, self_off, compact)
+    _launch(fn, args, "rel_attn_fwd_bf16" if P.dtype == torch.bfloat16 else "rel_attn_fwd")
+    return res
+
+
+class _AggBackward:
+    """Outputs, views and workspace of one backward aggregation, and the argument tuple that jmac_rel_attn_aggregate_bwd_f32
+    and jmac_rel_attn_aggregate_bwd_phases_f32 both take (the int before ws: ``mode`` in the first, ``phases`` in the
+    second).  ``dPQZ``: an [N, 3d] buffer whose column views receive dP and d[Q|Z] (callers that hold one [P|Q|Z] table)."""
+
+    def __init__(self, P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int, out, seg_max,
+                 seg_den, G, compact: bool = False, mode: int = BWD_MODE_DETERMINISTIC, dPQZ=None):
+        self.L = lib() if mode == BWD_MODE_DETERMINISTIC else testing_lib()      # mode 0 exists in the testing build only
+        self.P, self.QZ, self.RR, self.a, self.graph = P, QZ, RR, a, graph
+        self.slope, self.out_scale, self.loop_rel, self.self_off = float(slope), float(out_scale), int(loop_rel), int(self_off)
+        self.out, self.seg_max, self.seg_den, self.G = out, seg_max, seg_den, _f32c(G).contiguous()
+        self.N, self.d, self.nsrc, self.nrel = P.shape[0], int(a.numel()), QZ.shape[0], RR.shape[0]
+        if mode:                          # mode 0 reads the by-destination view only
+            if compact:
+                graph.ensure_backward_views_compact()
+            else:
+                graph.ensure_backward_views()
+        by_rel = graph.by_rel_c if compact else graph.by_rel
+        self.etype = graph.etype_c if compact else graph.etype
+        self.dst_of_slot = graph.dst_of_slot if mode else None
+        self.vd = graph.by_dst_bwd.view_compact(graph.col, graph.etype_c) if compact else graph.by_dst_bwd.view()
+        self.vs = graph.by_src.view() if mode else None
+        self.vr = by_rel.view() if mode else None
+        self.dP, self.dQZ = pqz_views(dPQZ) if dPQZ is not None else (torch.empty_like(P), torch.empty_like(QZ))
+        self.dRR, self.da = torch.empty_like(RR), torch.empty_like(a)
+        self.ws_bytes = int(self.L.jmac_rel_attn_bwd_workspace_bytes(
+            self.N, graph.E, self.nrel, self.d, graph.by_dst_bwd.n_parts_max, graph.by_src.n_parts_max if mode else 0,
+            by_rel.n_parts_max if mode else 0, mode))
+        self.ws = workspace(self.ws_bytes, P.device)
+
+    def args(self, flag: int, src_view, row0: int, rows: int) -> tuple:
+        """Arguments of a call whose pass B covers source rows [row0, row0 + rows) of d[Q|Z] through ``src_view``."""
+        g, dQZ = self.graph, self.dQZ
+        return (ptr(self.P), self.P.stride(0), ptr(self.QZ), self.QZ.stride(0), ptr(self.RR), self.RR.stride(0), ptr(self.a),
+                ptr(g.col), ptr(self.etype), ptr(self.dst_of_slot), C.byref(self.vd),
+                C.byref(src_view) if src_view is not None else None, C.byref(self.vr) if self.vr is not None else None,
+                self.N, rows, g.E, self.nrel, self.d, self.slope, self.loop_rel, self.self_off - row0, self.out_scale,
+                ptr(self.out), self.out.stride(0), ptr(self.seg_max), ptr(self.seg_den), ptr(self.G), self.G.stride(0),
+                ptr(self.dP), self.dP.stride(0), dQZ.data_ptr() + row0 * dQZ.stride(0) * dQZ.element_size(), dQZ.stride(0),
+                ptr(self.dRR), self.dRR.stride(0), ptr(self.da), int(flag), ptr(self.ws), self.ws_bytes, stream())
 
 
 def rel_attn_split_bwd_raw(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int,
-                           out, seg_max, seg_den, G):
-    """jmac_rel_attn_aggregate_bwd_f32 (deterministic form) for the split tables: dP, dQZ, dRR, da."""
-    L = lib()
-    dev = P.device
-    N, d = P.shape
-    nsrc, nrel = QZ.shape[0], RR.shape[0]
-    G = _f32c(G).contiguous()
-    graph.ensure_backward_views()
-    dP, dQZ, dRR, da = torch.empty_like(P), torch.empty_like(QZ), torch.empty_like(RR), torch.empty_like(a)
-    vd, vs, vr = graph.by_dst_bwd.view(), graph.by_src.view(), graph.by_rel.view()
-    ws_bytes = int(L.jmac_rel_attn_bwd_workspace_bytes(N, graph.E, nrel, d, graph.by_dst_bwd.n_parts_max,
-                                                       graph.by_src.n_parts_max, graph.by_rel.n_parts_max, 1))
-    ws = _ws(ws_bytes, dev)
-    ev0 = _ev() if PROFILE is not None else None
-    check(L.jmac_rel_attn_aggregate_bwd_f32(
-        ptr(P), d, ptr(QZ), 2 * d, ptr(RR), RR.shape[1], ptr(a),
-        ptr(graph.col), ptr(graph.etype), ptr(graph.dst_of_slot), C.byref(vd), C.byref(vs), C.byref(vr),
-        N, nsrc, graph.E, nrel, d, float(slope), int(loop_rel), int(self_off), float(out_scale),
-        ptr(out), d, ptr(seg_max), ptr(seg_den), ptr(G), d,
-        ptr(dP), d, ptr(dQZ), 2 * d, ptr(dRR), dRR.shape[1], ptr(da), 1, ptr(ws), ws_bytes, stream()),
-        "jmac_rel_attn_aggregate_bwd_f32")
-    if ev0 is not None:
-        PROFILE.append(("rel_attn_bwd", ev0, _ev()))
-    return dP, dQZ, dRR, da
+                           out, seg_max, seg_den, G, *, compact: bool = False, mode: int = BWD_MODE_DETERMINISTIC, dPQZ=None):
+    """jmac_rel_attn_aggregate_bwd_f32 on the tables of rel_attn_split_fwd_raw: dP, dQZ, dRR, da (``dPQZ``: see _AggBackward).
+    ``mode``: BWD_MODE_DETERMINISTIC, or BWD_MODE_ATOMIC (testing build)."""
+    b = _AggBackward(P, QZ, RR, a, graph, slope, out_scale, loop_rel, self_off, out, seg_max, seg_den, G, compact, mode, dPQZ)
+    _launch(b.L.jmac_rel_attn_aggregate_bwd_f32, b.args(mode, b.vs, 0, b.nsrc), "rel_attn_bwd")
+    return b.dP, b.dQZ, b.dRR, b.da
 
 
 PHASE_A, PHASE_B, PHASE_C, PHASE_M, PHASE_ALL = 1, 2, 4, 8, 15
 
 
-class SplitBackwardPhases:
+class SplitBackwardPhases(_AggBackward):
     """jmac_rel_attn_aggregate_bwd_phases_f32 on the split tables: the deterministic backward as separately launched phases --
     pass A (+ pass C and the merges that hang on them) first, then pass B over SLABS of the source rows, each slab's d[Q|Z] rows
     complete when its call returns to the stream (the caller queues that slab's reduce-scatter and goes on with the next slab).
@@ -228,37 +220,17 @@ class SplitBackwardPhases:
 
     def __init__(self, P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int, out, seg_max,
                  seg_den, G, slab_bounds):
-        self.L = lib()
-        self.P, self.QZ, self.RR, self.a, self.graph = P, QZ, RR, a, graph
-        self.slope, self.out_scale, self.loop_rel, self.self_off = float(slope), float(out_scale), int(loop_rel), int(self_off)
-        self.out, self.seg_max, self.seg_den, self.G = out, seg_max, seg_den, _f32c(G).contiguous()
-        graph.ensure_backward_views()
+        super().__init__(P, QZ, RR, a, graph, slope, out_scale, loop_rel, self_off, out, seg_max, seg_den, G)
         self.bounds = [int(b) for b in slab_bounds]
         self.slabs = graph.src_slab_views(self.bounds)
-        N, d = P.shape
-        self.N, self.d, self.nsrc, self.nrel = N, d, QZ.shape[0], RR.shape[0]
-        self.dP, self.dQZ, self.dRR, self.da = torch.empty_like(P), torch.empty_like(QZ), torch.empty_like(RR), torch.empty_like(a)
-        ws_bytes = int(self.L.jmac_rel_attn_bwd_workspace_bytes(N, graph.E, self.nrel, d, graph.by_dst_bwd.n_parts_max,
-                                                                graph.by_src.n_parts_max, graph.by_rel.n_parts_max, 1))
-        self.ws, self.ws_bytes = _ws(ws_bytes, P.device), ws_bytes
 
     def _call(self, phases: int, src_view, row0: int, rows: int) -> None:
-        g, d = self.graph, self.d
-        vd, vr = g.by_dst_bwd.view(), g.by_rel.view()
-        ev0 = _ev() if PROFILE is not None else None
-        check(self.L.jmac_rel_attn_aggregate_bwd_phases_f32(
-            ptr(self.P), d, ptr(self.QZ), 2 * d, ptr(self.RR), self.RR.shape[1], ptr(self.a),
-            ptr(g.col), ptr(g.etype), ptr(g.dst_of_slot), C.byref(vd), C.byref(src_view), C.byref(vr),
-            self.N, rows, g.E, self.nrel, d, self.slope, self.loop_rel, self.self_off - row0, self.out_scale,
-            ptr(self.out), d, ptr(self.seg_max), ptr(self.seg_den), ptr(self.G), d,
-            ptr(self.dP), d, self.dQZ.data_ptr() + row0 * 2 * d * 4, 2 * d, ptr(self.dRR), self.dRR.shape[1], ptr(self.da),
-            int(phases), ptr(self.ws), self.ws_bytes, stream()), "jmac_rel_attn_aggregate_bwd_phases_f32")
-        if ev0 is not None:
-            PROFILE.append(("rel_attn_bwd_phase%d" % phases, ev0, _ev()))
+        _launch(self.L.jmac_rel_attn_aggregate_bwd_phases_f32, self.args(phases, src_view, row0, rows),
+                "rel_attn_bwd_phase%d" % phases)
 
     def begin(self) -> None:
         """Pass A, pass C and every merge but the by-source one: dP, dRR, da are final afterwards."""
-        self._call(PHASE_A | PHASE_C | PHASE_M, self.graph.by_src.view(), 0, self.nsrc)
+        self._call(PHASE_A | PHASE_C | PHASE_M, self.vs, 0, self.nsrc)
 
     def slab(self, c: int) -> torch.Tensor:
         """Pass B on source rows [bounds[c], bounds[c+1]): returns that slice of d[Q|Z] (final once the stream reaches here)."""
@@ -325,6 +297,64 @@ def rel_attn_aggregate_split(P, QZ, RR, a, graph: RelGraph, slope: float, out_sc
     return _RelAttnAggregateSplit.apply(P, QZ, RR, a, graph, float(slope), float(out_scale), int(loop_rel), int(self_off))
 
 
+def bn_tanh_fwd_raw(x, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float, y, y2=None,
+                    seg=None):
+    """tanh(BatchNorm1d(x)) into y (and y2, may be None) with nn.BatchNorm1d's running-estimate update (src/jmac_model.py:52;
+    num_batches_tracked is the caller's): jmac_bn_tanh_fwd2_f32, or jmac_bn_tanh_seg_fwd2_f32 for batch statistics over the
+    row blocks of ``seg`` (encoder.RowBlocks, more than one block): every block is normalised with ITS statistics and the
+    running estimates move once per block.  -> (save_mean, save_invstd): [d], or [blocks, d] from the segmented form."""
+    L = lib()
+    N, d = x.shape
+    dev = x.device
+    ldy2 = y2.stride(0) if y2 is not None else 0
+    if training and seg is not None and seg.nb > 1:
+        if seg.offsets[-1] != N:
+            raise ValueError("RowBlocks cover %d rows, the layer has %d" % (seg.offsets[-1], N))
+        mean = torch.empty((seg.nb, d), dtype=torch.float32, device=dev)
+        invstd = torch.empty((seg.nb, d), dtype=torch.float32, device=dev)
+        ws_bytes = int(L.jmac_bn_tanh_seg_workspace_bytes(seg.nb, d))
+        ws = workspace(ws_bytes, dev)
+        check(L.jmac_bn_tanh_seg_fwd2_f32(ptr(x), x.stride(0), d, seg.nb, seg.c_ptr, seg.c_order, ptr(weight), ptr(bias),
+                                          ptr(running_mean), ptr(running_var), float(momentum), float(eps), ptr(y), y.stride(0),
+                                          ptr(y2), ldy2, ptr(mean), ptr(invstd), ptr(ws), ws_bytes, stream()),
+              "jmac_bn_tanh_seg_fwd2_f32")
+        return mean, invstd
+    mean = torch.empty(d, dtype=torch.float32, device=dev)
+    invstd = torch.empty(d, dtype=torch.float32, device=dev)
+    ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
+    ws = workspace(ws_bytes, dev)
+    check(L.jmac_bn_tanh_fwd2_f32(ptr(x), x.stride(0), N, d, ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var),
+                                  1 if training else 0, float(momentum), float(eps), ptr(y), y.stride(0), ptr(y2), ldy2, ptr(mean),
+                                  ptr(invstd), ptr(ws), ws_bytes, stream()), "jmac_bn_tanh_fwd2_f32")
+    return mean, invstd
+
+
+def bn_tanh_bwd_raw(x, y, gy, gy2, weight, mean, invstd, training: bool, seg=None):
+    """Backward of bn_tanh_fwd_raw, the incoming gradients gy + gy2 (gy2 may be None) summed as the kernel reads them: gx [N, d]
+    and [grad bias | grad weight] [2d] (one reduction writes both).  ``seg``: the forward's RowBlocks where its statistics are
+    per block (mean / invstd [blocks, d])."""
+    L = lib()
+    N, d = x.shape
+    dev = x.device
+    gx = torch.empty((N, d), dtype=torch.float32, device=dev)
+    gbw = torch.empty(2 * d, dtype=torch.float32, device=dev)
+    ldgy2 = gy2.stride(0) if gy2 is not None else 0
+    if mean.dim() == 2:                                        # per-block statistics (segmented forward)
+        ws_bytes = int(L.jmac_bn_tanh_seg_workspace_bytes(seg.nb, d))
+        ws = workspace(ws_bytes, dev)
+        check(L.jmac_bn_tanh_seg_bwd2_f32(ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(gy), gy.stride(0), ptr(gy2), ldgy2, d,
+                                          seg.nb, seg.c_ptr, ptr(weight), ptr(mean), ptr(invstd), ptr(gx), d,
+                                          gbw.data_ptr() + d * 4, ptr(gbw), ptr(ws), ws_bytes, stream()),
+              "jmac_bn_tanh_seg_bwd2_f32")
+        return gx, gbw
+    ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
+    ws = workspace(ws_bytes, dev)
+    check(L.jmac_bn_tanh_bwd2_f32(ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(gy), gy.stride(0), ptr(gy2), ldgy2, N, d,
+                                  ptr(weight), ptr(mean), ptr(invstd), 1 if training else 0, ptr(gx), d, gbw.data_ptr() + d * 4,
+                                  ptr(gbw), ptr(ws), ws_bytes, stream()), "jmac_bn_tanh_bwd2_f32")
+    return gx, gbw
+
+
 class _BnTanh(torch.autograd.Function):
     """tanh(BatchNorm1d(x)) with nn.BatchNorm1d semantics (src/jmac_model.py:52)."""
 
@@ -332,17 +362,8 @@ class _BnTanh(torch.autograd.Function):
     def forward(ctx, x, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float):
         require_device(x, weight, bias)
         x = _f32c(x).contiguous()
-        N, d = x.shape
-        L = lib()
-        dev = x.device
         y = torch.empty_like(x)
-        save_mean = torch.empty(d, dtype=torch.float32, device=dev)
-        save_invstd = torch.empty(d, dtype=torch.float32, device=dev)
-        ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
-        ws = _ws(ws_bytes, dev)
-        check(L.jmac_bn_tanh_fwd2_f32(ptr(x), d, N, d, ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var),
-                                      1 if training else 0, float(momentum), float(eps), ptr(y), d, None, 0, ptr(save_mean),
-                                      ptr(save_invstd), ptr(ws), ws_bytes, stream()), "jmac_bn_tanh_fwd2_f32")
+        save_mean, save_invstd = bn_tanh_fwd_raw(x, weight, bias, running_mean, running_var, training, momentum, eps, y)
         ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
         ctx.training = training
         return y
@@ -350,19 +371,9 @@ class _BnTanh(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, y, weight, save_mean, save_invstd = ctx.saved_tensors
-        N, d = x.shape
-        L = lib()
-        dev = x.device
-        gy = _f32c(gy).contiguous()
-        gx = torch.empty_like(x)
-        gbw = torch.empty(2 * d, dtype=torch.float32, device=dev)        # [grad bias | grad weight]: one reduction writes both
-        gb, gw = gbw[:d], gbw[d:]
-        ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
-        ws = _ws(ws_bytes, dev)
-        check(L.jmac_bn_tanh_bwd2_f32(ptr(x), d, ptr(y), d, ptr(gy), d, None, 0, N, d, ptr(weight), ptr(save_mean), ptr(save_invstd),
-                                      1 if ctx.training else 0, ptr(gx), d, ptr(gw), ptr(gb), ptr(ws), ws_bytes, stream()),
-              "jmac_bn_tanh_bwd2_f32")
-        return gx, gw, gb, None, None, None, None, None
+        d = x.shape[1]
+        gx, gbw = bn_tanh_bwd_raw(x, y, _f32c(gy).contiguous(), None, weight, save_mean, save_invstd, ctx.training)
+        return gx, gbw[d:], gbw[:d], None, None, None, None, None
 
 
 def bn_tanh(x, weight, bias, running_mean, running_var, training: bool, momentum: float = 0.1, eps: float = 1e-5):

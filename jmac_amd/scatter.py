@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import check, lib, ptr, require_device, stream
+from ._lib import check, lib, ptr, require_device, stream, workspace
 
 
 def _prep(src: torch.Tensor, index: torch.Tensor, dim: int):
@@ -50,7 +50,7 @@ class _ScatterSoftmax(torch.autograd.Function):
         L = lib()
         out = torch.empty_like(src2d)
         ws_bytes = int(L.jmac_scatter_softmax_workspace_bytes(n, d))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=src2d.device)
+        ws = workspace(ws_bytes, src2d.device)
         check(L.jmac_scatter_softmax_f32(ptr(src2d), ptr(index), E, d, n, ptr(out), ptr(ws), ws_bytes, stream()),
               "jmac_scatter_softmax_f32")
         ctx.save_for_backward(out, index)

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import check, check_index_range, lib, ptr, require_device, stream
+from ._lib import check, check_index_range, lib, ptr, require_device, stream, workspace
 
 
 def _rows16(t: torch.Tensor, allow_bf16: bool = False) -> torch.Tensor:
@@ -100,7 +100,7 @@ def linkpred_ranks(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequenc
     rank = torch.empty(B, dtype=torch.int32, device=dev)
     L = lib()
     ws_bytes = int(L.jmac_linkpred_rank_workspace_bytes(B, d, nl))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws = workspace(ws_bytes, dev)
     fn, name = (L.jmac_linkpred_rank_bf16, "jmac_linkpred_rank_bf16") if bf16 else (L.jmac_linkpred_rank_f32, "jmac_linkpred_rank_f32")
     check(fn(arr, nl, ptr(h), ptr(r), 1 if pred_head else 0, ptr(g), ptr(filt_ptr), ptr(filt_idx), B, N, d, ptr(rank), ptr(ws),
              ws_bytes, stream()), name)
@@ -157,7 +157,7 @@ def sim_topk(a: torch.Tensor, b: torch.Tensor, k: int, return_values: bool = Fal
     idx = torch.empty((L_, k), dtype=torch.int32, device=a.device)
     val = torch.empty((L_, k), dtype=torch.float32, device=a.device) if return_values else None
     ws_bytes = int(L.jmac_sim_topk_workspace_bytes(L_, N, int(k)))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=a.device)
+    ws = workspace(ws_bytes, a.device)
     check(L.jmac_sim_topk_f32(ptr(a), d, ptr(b), d, L_, N, d, int(k), ptr(val), ptr(idx), ptr(ws), ws_bytes, stream()),
           "jmac_sim_topk_f32")
     idx = idx.to(torch.int64)
@@ -188,7 +188,7 @@ def col_topk_values(s: torch.Tensor, k: int) -> torch.Tensor:
     val = torch.empty((n2, k), dtype=torch.float32, device=s.device)
     L = lib()
     wsb = int(L.jmac_col_topk_workspace_bytes(n1, n2, int(k)))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=s.device)
+    ws = workspace(wsb, s.device)
     check(L.jmac_col_topk_f32(ptr(s), n2, n1, n2, int(k), ptr(val), ptr(ws), wsb, stream()), "jmac_col_topk_f32")
     return val
 
@@ -209,7 +209,7 @@ def align_entropy(e1: torch.Tensor, e2: torch.Tensor, scale: float = 20.0):
     hr = torch.empty(n1, dtype=torch.float32, device=e1.device)
     hc = torch.empty(n2, dtype=torch.float32, device=e1.device)
     ws_bytes = int(L.jmac_softmax_entropy_workspace_bytes(n1, n2))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=e1.device)
+    ws = workspace(ws_bytes, e1.device)
     check(L.jmac_softmax_entropy_f32(ptr(e1), d, ptr(e2), d, n1, n2, d, float(scale), ptr(hr), ptr(hc), ptr(ws), ws_bytes,
                                      stream()), "jmac_softmax_entropy_f32")
     return hr.mean() + hc.mean(), hr, hc
@@ -252,7 +252,7 @@ def col_softmax(s: torch.Tensor, row_mask=None, col_mask=None, fill: float = -1.
     rm, cm = _mask8(row_mask), _mask8(col_mask)
     L = lib()
     wsb = int(L.jmac_col_softmax_workspace_bytes(n1, n2))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=s.device)
+    ws = workspace(wsb, s.device)
     check(L.jmac_col_softmax_f32(ptr(s), n2, n1, n2, ptr(rm), ptr(cm), float(fill), float(scale), ptr(out_t), n1, ptr(ent),
                                  ptr(ws), wsb, stream()), "jmac_col_softmax_f32")
     return out_t, ent
