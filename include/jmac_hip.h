@@ -637,6 +637,30 @@ int jmac_margin_loss_bwd_f32(const float* score, int64_t B, int64_t K, const flo
                              const float* gloss, float* dscore, jmac_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Completion batches (replaces: TrainDataset.get_neg_sample, modules/load/data_loader.py:36-47 -- K distinct entities drawn
+ * uniformly from those that are not a true tail of (h, r), the dictionary of train.py:262-285 -- its DataLoader workers, and
+ * the repeat / cat of train.py:347-352).
+ * --------------------------------------------------------------------------------------------- */
+
+/* One training batch, built on the device: row b is triple perm[(step[1] mod (T / B)) * B + b] of triples [T,3] (h, r, t), and
+ *   batch_h[j*B + b] = h_b, batch_r[j*B + b] = r_b (j = 0..K), batch_t[b] = t_b, batch_t[B + b*K + k] = neg[b, k]
+ * ([B (K+1)] each: the layout of train.py:347-352, where neg.view(-1) pairs row b's negatives with other heads; kept).
+ * neg[b, 0..K) = the first K VALID candidates of row b's stream, where candidate i = word i % 4 of
+ *   philox4x32_10(counter = (b, lo32(step[0]), i / 4, hi32(step[0])), key = (lo32(seed[0]), lo32(seed[1]))),
+ * m = word * num_ent (64-bit product), c_i = m >> 32, and c_i is invalid if lo32(m) < 2^32 mod num_ent, or c_i is in
+ * tail_idx[tail_ptr[key_of_triple[.]] .. tail_ptr[. + 1]) (the SORTED DISTINCT true tails of the row's (h, r)), or c_i equals a
+ * candidate accepted before it: a uniform draw without replacement from the allowed entities, one wave per row.
+ * seed: device, 2 words, read.  step: device, 2 words, both read and then advanced by 1 on the device ([0] launches so far,
+ * never reset by the caller; [1] batch number in the epoch, zeroed by the caller with every new perm), so a captured launch
+ * replayed N times gives the N batches of N calls.  1 <= K <= 64, B >= 1, T >= B (JMAC_EINVAL), num_ent, B, T < 2^31
+ * (JMAC_ERANGE).  Preconditions the host vouches for: perm and key_of_triple entries in range, triples' ids in [0, num_ent),
+ * and every key leaves at least K entities (a row that cannot be filled ends with copies of its gold tail). */
+int jmac_sample_completion_batch(const int64_t* triples, int64_t T, const int64_t* perm, const int32_t* key_of_triple,
+                                 const int32_t* tail_ptr, const int32_t* tail_idx, int64_t num_ent, int64_t B, int64_t K,
+                                 const int64_t* seed, int64_t* step, int64_t* batch_h, int64_t* batch_r, int64_t* batch_t,
+                                 jmac_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * torch_scatter-compatible primitives (replace the third-party calls at src/jmac_model.py:105 and
  * modules/helper/message_passing.py:24,28) so the UNMODIFIED reference layer can run on this library.
  * index need not be sorted.  out must be pre-zeroed by the caller for scatter_sum.

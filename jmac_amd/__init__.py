@@ -10,6 +10,8 @@ this package is the Python host side that mirrors the reference's operator inter
     jmac_amd.scatter                       torch_scatter-compatible scatter_add / scatter / scatter_softmax
     jmac_amd.dist                          destination-sharded multi-GPU layer (RCCL over xGMI)
     jmac_amd.optim                         Adam / AdamW: torch.optim.Adam's update (train.py:406-407) as one launch
+    jmac_amd.sampling                      CompletionSampler: the filtered negative sampler of modules/load/data_loader.py:36-47
+                                           and the batch layout of train.py:347-352 as one launch per batch
 """
 from ._lib import JmacError, lib  # noqa: F401
 

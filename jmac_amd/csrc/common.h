@@ -79,6 +79,20 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[U]) {
     for (int u = 0; u < U; ++u) v[u] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[u]), 63));
 }
 
+// ---- Philox4x32-10 (Salmon et al., SC'11): the counter-based generator of the in-kernel dropout draws (norm.hip) and of the
+// negative sampler (sample.hip); the same function as curand's / torch's, so a host restatement needs nothing but the counter
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
+        k.x += 0x9E3779B9u;
+        k.y += 0xBB67AE85u;
+    }
+    return c;
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // non-temporal (streaming) 16-byte load: for rows that are read once, so they do not evict the relation table
 typedef float jmac_f32x4 __attribute__((ext_vector_type(4)));

@@ -629,18 +629,7 @@ __global__ __launch_bounds__(kBlock) void row_normalize_bwd_kernel(const float* 
 // one wave per row, 16 bytes per lane (d % 4 == 0, leading dimensions % 4 == 0).
 // Dropout draws made in the kernel (SEED form): Philox4x32-10 keyed by the caller's device-resident seed, counter = index of
 // the float4 (row * d/4 + column quad): its four words decide the four elements.  The backward regenerates the same draws, so
-// no mask tensor is written or read (28 MB each way at DBP-5L size, plus the launch that drew it).
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u;
-        k.y += 0xBB67AE85u;
-    }
-    return c;
-}
+// no mask tensor is written or read (28 MB each way at DBP-5L size, plus the launch that drew it).  (philox4x32_10: common.h)
 struct DropSrc {
     const float* mask;       // {0,1} draws of the caller, or NULL
     int64_t ldm;

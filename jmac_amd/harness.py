@@ -9,9 +9,21 @@ embeddings are out of scope): just enough host code t
     one epoch over the KG pairs  train.py:423-512    get_emb -> EnTr -> completion -> alignment
 
 end to end, so the integration of data.py / graph.py / model.py / losses.py / scoring.py / entr.py is tested as a
-whole (tests/test_gpu_harness.py).  Negatives are drawn uniformly on the device and tails that are true for (h, r)
-are redrawn once -- the reference's per-triple numpy mask (modules/load/data_loader.py:35-46) runs in DataLoader
-workers and is not part of the hot path.
+whole (tests/test_gpu_harness.py).
+
+Where the completion batches come from is ``args.neg_sampler``:
+
+    "uniform" (default)   ``completion_batches``: a few torch calls per batch -- negatives drawn uniformly WITH replacement, a clash
+                          with the gold tail redrawn once (it can clash again; the other true tails of (h, r) are not looked at).
+                          An approximation of the reference's sampler, kept as it was.
+    "filtered"            ``sampling.CompletionSampler``: the reference's sampler (modules/load/data_loader.py:36-47: distinct
+                          negatives, uniform over the entities that are not a true tail of (h, r)) as one launch per batch into
+                          persistent buffers, one sampler per KG of the pair, rebuilt at every refresh.
+    ``args.capture_completion`` (with "filtered" only): after three eager steps the step zero_grad -> next_batch ->
+                          completion_loss -> backward -> step is captured in a hipGraph once per (pair, side, refresh) and replayed
+                          for the remaining batches of every epoch until the next refresh; the per-step losses land in a device
+                          vector that is read once per epoch.  Needs an optimizer whose step captures (``jmac_amd.optim.Adam``,
+                          or ``torch.optim.Adam(capturable=True)``).
 """
 from __future__ import annotations
 
@@ -22,6 +34,7 @@ import numpy as np
 import torch
 
 from . import entr, scoring
+from .sampling import CompletionSampler
 from .data import KnowledgeGraph
 from .model import JMAC
 
@@ -29,7 +42,8 @@ from .model import JMAC
 def make_args(dim=300, batch_size=1000, num_negative=25, device="cuda", **kw):
     a = dict(dim=dim, dropout=0.4, leaky_relu_w=0.05, comp_op="sub", num_gcn_layer=2, num_negative=num_negative,
              margin_align=1.0, margin_completion=5.0, batch_size=batch_size, no_name_info=False, device=device,
-             pair_sample_weight=0.2, lr=1e-3)                     # train.py:57-102 defaults for the fields used here
+             pair_sample_weight=0.2, lr=1e-3,                     # train.py:57-102 defaults for the fields used here
+             neg_sampler="uniform", capture_completion=False)    # this harness' own: where the completion batches come from
     a.update(kw)
     return types.SimpleNamespace(**a)
 
@@ -58,7 +72,19 @@ def completion_batches(triples: np.ndarray, num_ent: int, batch_size: int, k: in
         yield tr, neg
 
 
-def train_completion_component(model: JMAC, opt, ei1, et1, ei2, et2, feeddict, triples1, triples2, n1, n2, args, generator=None):
+def train_completion_component(model: JMAC, opt, ei1, et1, ei2, et2, feeddict, triples1, triples2, n1, n2, args, generator=None,
+                               state: dict = None):
+    """One completion epoch on a KG pair (train.py:328-364): every full batch of KG 1, then of KG 2.  ``state`` (optional): a
+    dict that lives as long as the triple lists and graphs do (train_epoch: until the next refresh); the "filtered" mode keeps
+    its samplers and captured steps there and leaves the epoch's per-step losses (device, [steps]) under "step_losses"."""
+    mode = getattr(args, "neg_sampler", "uniform")
+    if mode == "filtered":
+        return _train_completion_filtered(model, opt, ei1, et1, ei2, et2, feeddict, triples1, triples2, n1, n2, args, generator,
+                                          {} if state is None else state)
+    if mode != "uniform":
+        raise ValueError("args.neg_sampler must be 'uniform' or 'filtered' (got %r)" % (mode,))
+    if getattr(args, "capture_completion", False):
+        raise ValueError("args.capture_completion needs args.neg_sampler == 'filtered' (the uniform batches are new tensors every step)")
     losses = []
     for triples, n_ent, source in ((triples1, n1, True), (triples2, n2, False)):
         for tr, neg in completion_batches(triples, n_ent, args.batch_size, args.num_negative, ei1.device, generator):
@@ -71,6 +97,74 @@ def train_completion_component(model: JMAC, opt, ei1, et1, ei2, et2, feeddict, t
             opt.step()
             losses.append(loss.detach())
     return float(torch.stack(losses).mean()) if losses else float("nan")
+
+
+_CAPTURE_WARMUP = 3      # eager steps in front of a capture (bench.py:try_capture): real training steps of the epoch
+
+
+def _train_completion_filtered(model, opt, ei1, et1, ei2, et2, feeddict, triples1, triples2, n1, n2, args, generator, state):
+    dev = ei1.device
+    capture = bool(getattr(args, "capture_completion", False))
+    sides = state.get("completion_sides")
+    if sides is None:                                      # once per (pair, refresh): the CSR of the true tails, the batch buffers
+        sides = state["completion_sides"] = [
+            {"sampler": CompletionSampler(tr, n, args.batch_size, args.num_negative, dev), "source": src, "graph": None}
+            for tr, n, src in ((triples1, n1, True), (triples2, n2, False)) if len(tr) >= args.batch_size]
+    links = feeddict["links"]
+    if len(links) and not (isinstance(links, torch.Tensor) and links.device == dev):
+        # host seed links (train.py:190-193 hands out numpy arrays) would be uploaded by every step, which a stream capture
+        # refuses: upload them once per refresh -- completion_loss cuts and checks the columns of a device tensor once
+        if "links" not in state:
+            state["links"] = torch.as_tensor(np.asarray(links.cpu() if isinstance(links, torch.Tensor) else links).astype(np.int64)).to(dev)
+        feeddict = dict(feeddict, links=state["links"])
+    per_side = []
+    for side in sides:
+        sampler, source = side["sampler"], side["source"]
+        steps = len(sampler)
+        out = side.setdefault("losses", torch.zeros(steps, dtype=torch.float32, device=dev))
+        slot = side.setdefault("slot", torch.zeros(1, dtype=torch.int64, device=dev))
+        sampler.new_epoch(generator)
+
+        def step():
+            opt.zero_grad(set_to_none=True)
+            loss = model.completion_loss(sampler.next_batch(), ei1, et1, ei2, et2, feeddict, source)
+            loss.backward()
+            opt.step()
+            out.index_copy_(0, slot, loss.detach().reshape(1))          # device-side slot: a replay writes the next one
+            slot.add_(1)
+
+        slot.zero_()
+        done = 0
+        if not capture:
+            for _ in range(steps):
+                step()
+        else:
+            if side["graph"] is None and steps > _CAPTURE_WARMUP:
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for _ in range(_CAPTURE_WARMUP):
+                        step()
+                torch.cuda.current_stream().wait_stream(s)
+                torch.cuda.synchronize()
+                done = _CAPTURE_WARMUP
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    step()
+                side["graph"] = g
+            if side["graph"] is None:                      # an epoch no longer than the warm-up: nothing left to replay
+                for _ in range(steps):
+                    step()
+            else:
+                for _ in range(steps - done):
+                    side["graph"].replay()
+                sampler.skip(steps - done)
+        per_side.append(out.clone())
+    if not per_side:
+        state["step_losses"] = torch.zeros(0, dtype=torch.float32, device=dev)
+        return float("nan")
+    state["step_losses"] = torch.cat(per_side)
+    return float(state["step_losses"].mean())
 
 
 def train_alignment_component(model: JMAC, opt, ei1, et1, ei2, et2, feeddict):
@@ -139,9 +233,10 @@ def train_epoch(model: JMAC, kgs: Dict[str, KnowledgeGraph], seeds_train: Dict[T
             st["g1"] = entr.align_data_processing(new1, dev)           # train-mode graph: head <- tail, one direction
             st["g2"] = entr.align_data_processing(new2, dev)
             st["tr"] = (new1, new2)
+            st["completion"] = {}                                      # "filtered": samplers and captured steps of this refresh
         (ei1, et1), (ei2, et2) = st["g1"], st["g2"]
         closs = train_completion_component(model, opt_c, ei1, et1, ei2, et2, st["feeddict"], st["tr"][0], st["tr"][1],
-                                           kg1.num_entity, kg2.num_entity, args, generator)
+                                           kg1.num_entity, kg2.num_entity, args, generator, state=st["completion"])
         aloss = train_alignment_component(model, opt_a, ei1, et1, ei2, et2, st["feeddict"])
         log.append({"pair": (l1, l2), "completion_loss": closs, "align_loss": aloss, "links": len(st["feeddict"]["links"]),
                     "triples": (len(st["tr"][0]), len(st["tr"][1])), "entropy": st["entropy"][0]})

@@ -1,0 +1,130 @@
+"""Completion batches built on the device: the reference's filtered negative sampler as one launch per batch.
+
+Replaces ``completion_data_processing`` (train.py:262-285: the ``(h, r) -> tails`` dictionary), ``TrainDataset``
+(modules/load/data_loader.py:36-47: ``np.random.choice(all_ent[mask], num_negative, replace=False)`` per triple, in DataLoader
+worker processes) and the ``repeat`` / ``cat`` of train.py:347-352:
+
+    TrueTailIndex       the dictionary as a CSR on the device, built once per triple list (i.e. once per EnTr refresh)
+    CompletionSampler   persistent batch buffers + ``jmac_sample_completion_batch`` (csrc/sample.hip): ``next_batch()`` is one
+                        launch, no host read, and returns THE SAME tensors every time -- a step that starts with it captures
+                        in a hipGraph and every replay trains on the next batch of the epoch
+
+The draw is the reference's distribution (uniform, without replacement, from the entities that are not a true tail of the
+row's ``(h, r)``) over a Philox stream of its own -- include/jmac_hip.h states it; tests/sampler_ref.py restates it in numpy.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ._lib import check, lib, mark_index_range, ptr, require_device, stream
+
+
+class TrueTailIndex:
+    """``(h, r) -> sorted distinct tails`` of a triple list (what ``data.true_tail_dict`` returns as a dictionary) as a CSR:
+    ``keys`` int64 [nk, 2] in lexicographic order, ``tail_ptr`` int32 [nk + 1], ``tail_idx`` int32, and ``key_of_triple``
+    int32 [T]: the CSR row that holds triple i's ``(h, r)``."""
+
+    def __init__(self, keys, tail_ptr, tail_idx, key_of_triple):
+        self.keys, self.tail_ptr, self.tail_idx, self.key_of_triple = keys, tail_ptr, tail_idx, key_of_triple
+
+    @classmethod
+    def from_triples(cls, triples, device) -> "TrueTailIndex":
+        t = torch.as_tensor(np.asarray(triples, dtype=np.int64).reshape(-1, 3) if not isinstance(triples, torch.Tensor) else triples)
+        t = t.to(device=device, dtype=torch.int64).reshape(-1, 3)
+        if not len(t):
+            raise ValueError("TrueTailIndex: empty triple list")
+        if len(t) >= 1 << 31 or int(t.min()) < 0 or int(t.max()) >= 1 << 31:
+            raise ValueError("TrueTailIndex: ids must lie in [0, 2^31) and the list must have fewer than 2^31 triples")
+        nrel, nent = int(t[:, 1].max()) + 1, int(t[:, 2].max()) + 1
+        hr, key_of_triple = torch.unique(t[:, 0] * nrel + t[:, 1], return_inverse=True)       # sorted: (h, r) lexicographic
+        pair = torch.unique(key_of_triple * nent + t[:, 2])                                    # sorted: by key, then tail
+        counts = torch.bincount(torch.div(pair, nent, rounding_mode="floor"), minlength=len(hr))
+        tail_ptr = torch.zeros(len(hr) + 1, dtype=torch.int64, device=t.device)
+        tail_ptr[1:] = torch.cumsum(counts, 0)
+        keys = torch.stack((torch.div(hr, nrel, rounding_mode="floor"), hr % nrel), 1)
+        return cls(keys, tail_ptr.to(torch.int32), (pair % nent).to(torch.int32), key_of_triple.to(torch.int32))
+
+    def longest(self) -> int:
+        p = self.tail_ptr
+        return int((p[1:] - p[:-1]).max())
+
+
+class CompletionSampler:
+    """The batches of one KG's completion epochs (train.py:338-352), on the device.
+
+    ``new_epoch(generator)`` draws the epoch's order; ``len(sampler)`` full batches follow (the ragged last batch is skipped:
+    train.py:342-346); ``next_batch()`` returns ``{"batch_h", "batch_r", "batch_t"}`` for ``JMAC.completion_loss``, each
+    int64 ``[B (K + 1)]``; ``neg`` is the ``[B, K]`` view of the negatives.  ``seed``: two int64 words (or one int: the second
+    word is 0) that key the Philox stream; None draws them from torch's generator of the device."""
+
+    def __init__(self, triples, num_ent: int, batch_size: int, num_negative: int, device, seed=None):
+        device = torch.device(device)
+        tr = np.ascontiguousarray(np.asarray(triples.cpu() if isinstance(triples, torch.Tensor) else triples, dtype=np.int64).reshape(-1, 3))
+        self.num_ent, self.B, self.K, self.T = int(num_ent), int(batch_size), int(num_negative), len(tr)
+        if not 1 <= self.K <= 64:
+            raise ValueError("CompletionSampler: num_negative must lie in [1, 64] (got %d)" % self.K)
+        if self.B < 1 or self.T < self.B:
+            raise ValueError("CompletionSampler: need 1 <= batch_size <= len(triples) (got %d, %d)" % (self.B, self.T))
+        if not 1 <= self.num_ent < 1 << 31:
+            raise ValueError("CompletionSampler: num_ent must lie in [1, 2^31)")
+        if tr[:, [0, 2]].min() < 0 or tr[:, [0, 2]].max() >= self.num_ent or tr[:, 1].min() < 0:   # the reference: IndexError
+            raise IndexError("CompletionSampler: triple ids out of range: entities in [%d, %d], valid range [0, %d); relations >= %d"
+                             % (tr[:, [0, 2]].min(), tr[:, [0, 2]].max(), self.num_ent, tr[:, 1].min()))
+        self.triples = torch.from_numpy(tr).to(device)
+        self.index = TrueTailIndex.from_triples(self.triples, device)
+        if self.num_ent - self.index.longest() < self.K:        # np.random.choice(..., replace=False) raises ValueError there
+            raise ValueError("CompletionSampler: a (head, relation) with %d true tails leaves fewer than num_negative = %d of the "
+                             "%d entities" % (self.index.longest(), self.K, self.num_ent))
+        require_device(self.triples)                            # the batches are built by a kernel: there is no CPU path
+        n = self.B * (self.K + 1)
+        # The kernel rewrites these three in place on every launch WITHOUT bumping their _version.  Nothing on the completion path
+        # caches on their identity or version: losses._PAIR_INDEX keys on the link columns only, model._link_columns on the links
+        # tensor, and check_index_range is settled by the marks below (the triples were range-checked above; a negative is in
+        # [0, num_ent) by construction), so no launch of a step reads anything back.
+        self.batch_h = mark_index_range(torch.zeros(n, dtype=torch.int64, device=device), self.num_ent)
+        self.batch_r = mark_index_range(torch.zeros(n, dtype=torch.int64, device=device), int(tr[:, 1].max()) + 1)
+        self.batch_t = mark_index_range(torch.zeros(n, dtype=torch.int64, device=device), self.num_ent)
+        self.neg = self.batch_t[self.B:].view(self.B, self.K)
+        self._batch = {"batch_h": self.batch_h, "batch_r": self.batch_r, "batch_t": self.batch_t}
+        self.perm = torch.arange(self.T, dtype=torch.int64, device=device)
+        self.step = torch.zeros(2, dtype=torch.int64, device=device)      # [0] launches so far, [1] batch number in the epoch
+        if seed is None:
+            self.seed = torch.empty(2, dtype=torch.int64, device=device).random_()
+        else:
+            words = [int(seed), 0] if np.ndim(seed) == 0 else [int(s) for s in seed]
+            if len(words) != 2:
+                raise ValueError("CompletionSampler: seed is one int or two")
+            self.seed = torch.tensor(words, dtype=torch.int64).to(device)
+        self._served = None                                                # batches handed out eagerly this epoch (None: no epoch yet)
+
+    def __len__(self):
+        return self.T // self.B
+
+    def new_epoch(self, generator=None):
+        """A new order, written into the SAME ``perm`` buffer (a captured launch stays valid), and batch number 0.  The
+        draw counter ``step[0]`` runs on, so no epoch repeats an earlier epoch's negatives."""
+        self.perm.copy_(torch.randperm(self.T, device=self.perm.device, generator=generator))
+        self.step[1:].zero_()
+        self._served = 0
+        return self
+
+    def skip(self, n: int):
+        """Account on the host for ``n`` batches produced by replays of a captured ``next_batch()``."""
+        self._served += int(n)
+
+    def next_batch(self):
+        """Launch; the same three tensors every time.  Raises StopIteration after ``len(self)`` eager calls of an epoch (a
+        call inside a stream capture does not run and is not counted: its replays are, through ``skip``)."""
+        if self._served is None:
+            raise RuntimeError("CompletionSampler: call new_epoch() first")
+        if not torch.cuda.is_current_stream_capturing():
+            if self._served >= len(self):
+                raise StopIteration
+            self._served += 1
+        ix = self.index
+        check(lib().jmac_sample_completion_batch(ptr(self.triples), self.T, ptr(self.perm), ptr(ix.key_of_triple), ptr(ix.tail_ptr),
+                                                 ptr(ix.tail_idx), self.num_ent, self.B, self.K, ptr(self.seed), ptr(self.step),
+                                                 ptr(self.batch_h), ptr(self.batch_r), ptr(self.batch_t), stream()),
+              "jmac_sample_completion_batch")
+        return self._batch
