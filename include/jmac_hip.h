@@ -609,6 +609,23 @@ int jmac_triple_l1_margin_bwd_exact2_f32(const float* ent, int64_t lde, const fl
                                          int32_t acc_ent, float* drel, int64_t rows_rel, int32_t acc_rel,
                                          jmac_stream_t stream);
 
+/* The same adjoint in ONE pass over the rows: the forward of a pass that needs table gradients.  Writes score [B (K + 1)] --
+ * bit-identical to jmac_triple_l1_fwd_f32's with period = B -- and adds the integer counts of the adjoint above (2 w sgn(.), w
+ * from the fresh scores and gamma) into cnt_ent / cnt_rel (dense, pitch d, ZERO on entry) at the windows [ent_off ..),
+ * [rel_off ..): they do not depend on the loss' incoming gradient.  One workgroup per run b (the K + 1 triples b, B + kB + b that
+ * share (h, r)); a run adds its h row, its r row and the positive's tail row once, each negative's tail row once; a negative
+ * whose (h, r) is not the run's is still handled correctly.  The tables then hold what jmac_triple_l1_margin_bwd_exact2_f32 holds
+ * before its scaling pass, and jmac_margin_counts_scale_clear_f32 is that pass alone: dent / drel (dense, all rows, first writer
+ * or on top of their contents where acc_ent / acc_rel != 0) = cnt * gloss / (2 B K), cnt = 0 again.  The caller owns the tables
+ * between the two calls (jmac_amd.losses: one pair per pending autograd node).  Same limits as the adjoint above. */
+int jmac_triple_l1_margin_fwd_counts_f32(const float* ent, int64_t lde, const float* rel, int64_t ldr, const int64_t* h,
+                                         const int64_t* r, const int64_t* t, int64_t B, int64_t K, int64_t d,
+                                         const float* gamma, int64_t ent_off, int64_t rel_off, float* cnt_ent,
+                                         float* cnt_rel, float* score, jmac_stream_t stream);
+int jmac_margin_counts_scale_clear_f32(float* cnt_ent, float* cnt_rel, const float* gloss, int64_t B, int64_t K, int64_t d,
+                                       float* dent, int64_t rows_ent, int32_t acc_ent, float* drel, int64_t rows_rel,
+                                       int32_t acc_rel, jmac_stream_t stream);
+
 /* out[0] = mean(x[0..n)) + (add_to ? add_to[0] : 0), fixed summation order -- a step's loss terms chain through add_to instead
  * of through element-wise adds. */
 int jmac_vec_mean_acc_f32(const float* x, int64_t n, const float* add_to, float* out, jmac_stream_t stream);

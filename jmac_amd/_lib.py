@@ -142,6 +142,8 @@ _SIGS = {
     "jmac_pair_cosine_bwd_rows_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, vp, vp, f32, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp]),
     "jmac_triple_l1_margin_bwd_exact2_f32": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp,
                                                        vp, i64, i32, vp, i64, i32, vp]),
+    "jmac_triple_l1_margin_fwd_counts_f32": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
+    "jmac_margin_counts_scale_clear_f32": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, i64, i32, vp, i64, i32, vp]),
     "jmac_vec_mean_acc_f32": (C.c_int, [vp, i64, vp, vp, vp]),
     "jmac_margin_loss_fwd_acc_f32": (C.c_int, [vp, i64, i64, vp, vp, vp, vp]),
     "jmac_margin_loss_bwd_f32": (C.c_int, [vp, i64, i64, vp, vp, vp, vp]),

@@ -27,8 +27,11 @@ __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f 
 // `period` is a HINT about the batch layout of the reference (train.py:347-352: sub.repeat(K+1), rel.repeat(K+1),
 // cat(obj, negatives)): triples x, x+period, x+2*period ... are expected to share (h, r).  One wave takes such a
 // run: the E[h] + R[r] row is read once, and in the backward the run's contributions to dE[h] / dR[r] are summed
-// in registers and added once (28 atomic rows per positive instead of 78, and K+1 times fewer adds into the few
-// hot relation rows).  A triple of the run whose (h, r) differs is handled on its own: any input is correct.
+// in registers and added once PER WAVE.  The launchers below cut a run into `parts` interleaved sub-runs (run_parts:
+// 9 at B = 1000, K = 25), one wave each, so a run flushes its h row and its r row `parts` times: 26 + 2 * 9 = 44
+// atomic rows per positive where one wave per run would add 28 and no grouping 78.  The one-pass kernel further down
+// (triple_l1_margin_fwd_counts_kernel: one WORKGROUP per run) flushes each of the two rows once.
+// A triple of the run whose (h, r) differs is handled on its own: any input is correct.
 template <int NK>
 __global__ __launch_bounds__(kBlock) void triple_l1_fwd_kernel(const float* __restrict__ ent, int64_t lde,
                                                                const float* __restrict__ rel, int64_t ldr,
@@ -199,6 +202,180 @@ __global__ __launch_bounds__(kBlock) void triple_l1_bwd_kernel(const float* __re
             x += pair ? 2 * stride : stride;
         }
         flush();
+    }
+}
+
+// ---- one-pass completion loss: the scores and the integer counts of the exact margin adjoint together ------------------------
+// For run b the margin loss compares score[b] with score[B + kB + b], k < K, only: the K decisions 2w = 2 / 1 / 0 and the signs
+// of E[h] + R[r] - E[t] are local to the run, and the integer each element contributes to the count tables (2w * sgn: what
+// triple_l1_bwd_kernel<.., true> adds) does not depend on the upstream gradient -- that enters in scale_clear_flat2_kernel only.
+// So the forward forms the counts from the rows it has loaded anyway, and the backward is the scaling pass alone.
+// One WORKGROUP per run, its NW waves sharing the K negatives (two per trip, both tail rows in flight).  Every wave forms
+// E[h] + R[r] and the positive's score itself (the rows are cache hits after the first wave; no barrier before the decisions),
+// with the per-lane order and the wave reduction of triple_l1_fwd_kernel: the scores, hence the decisions, hence the integers
+// are that kernel's bit for bit, whichever wave computes them.  The negatives' tail rows take their atomics at once; the h / r
+// contributions and sum 2w stay in registers, are reduced through LDS, and the run flushes its h row, its r row and the
+// positive's tail row ONCE (wave w takes the 64-element chunks k = w mod NW): 2 rows per run where the `parts` scheme of the
+// backward above flushes 2 * 9.  A negative whose (h, r) is not the run's takes its own E[h] + R[r] and its own three adds.
+// Waves per run, us per launch at B = 1000, K = 25, d = 300 (profiles/r7_onepass_loss.txt): 2: 22.2, 3: 18.9, 4: 17.3, 5: 19.6,
+// 6: 22.0, 8: 20.7 -- more waves repeat the shared row loads and lengthen the reduction, fewer lengthen each wave's chain.
+constexpr int kOnePassWaves = 4;
+__device__ __forceinline__ float margin_w2(float diff, float gamma) { return diff > -gamma ? 2.f : (diff == -gamma ? 1.f : 0.f); }
+// an index every lane loaded from the same address, moved to scalar registers: the rows it selects are then addressed as
+// scalar base + lane offset (one VGPR for all chunks of all rows instead of a 64-bit address pair per chunk and row)
+__device__ __forceinline__ int64_t uniform(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+template <int NK, int NW>
+__global__ __launch_bounds__(64 * NW) void triple_l1_margin_fwd_counts_kernel(const float* __restrict__ ent, int64_t lde,
+                                                                              const float* __restrict__ rel, int64_t ldr,
+                                                                              const int64_t* __restrict__ h, const int64_t* __restrict__ r,
+                                                                              const int64_t* __restrict__ t, int B, int K, int d,
+                                                                              const float* __restrict__ gamma_p, float* __restrict__ score,
+                                                                              float* __restrict__ cnt_ent, float* __restrict__ cnt_rel) {
+    __shared__ float red[NW][NK * 64];
+    __shared__ float red_g[NW];
+    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+    const float gamma = gamma_p[0];
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        const int64_t ih = uniform(h[b]), ir = uniform(r[b]), itp = uniform(t[b]);
+        float hr[NK], tp[NK], acc[NK];
+        {
+            const float* ph = ent + ih * lde;
+            const float* pr = rel + ir * ldr;
+            const float* pt = ent + itp * lde;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int c = lane + 64 * k;
+                hr[k] = c < d ? ph[c] + pr[c] : 0.f;
+                tp[k] = c < d ? pt[c] : 0.f;
+                acc[k] = 0.f;
+            }
+        }
+        float pos = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            if (lane + 64 * k < d) pos += fabsf(hr[k] - tp[k]);
+        pos = wave_sum(pos);
+        if (wave == 0 && lane == 0) score[b] = pos;
+        float g2w = 0.f;                                          // sum of 2w over this wave's negatives
+        // a negative on its own: (h, r) of its own where they differ from the run's (then all three rows take atomics at once)
+        auto single = [&](int64_t x, int64_t xh, int64_t xr, int64_t xt) {
+            const bool own = xh != ih || xr != ir;                // wave-uniform
+            const float* ph = ent + xh * lde;
+            const float* pr = rel + xr * ldr;
+            const float* pt = ent + xt * lde;
+            float df[NK], s = 0.f;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int c = lane + 64 * k;
+                const float a = own ? (c < d ? ph[c] + pr[c] : 0.f) : hr[k];
+                df[k] = a - (c < d ? pt[c] : 0.f);
+                if (c < d) s += fabsf(df[k]);
+            }
+            s = wave_sum(s);
+            if (lane == 0) score[x] = s;
+            const float w2 = margin_w2(pos - s, gamma);
+            g2w += w2;
+            float* qt = cnt_ent + xt * d;
+            float* qh = cnt_ent + xh * d;
+            float* qr = cnt_rel + xr * d;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int c = lane + 64 * k;
+                const float v = -w2 * sgn(df[k]);
+                if (c < d && v != 0.f) {
+                    atomicAdd(qt + c, -v);
+                    if (own) {
+                        atomicAdd(qh + c, v);
+                        atomicAdd(qr + c, v);
+                    } else {
+                        acc[k] += v;
+                    }
+                }
+            }
+        };
+        for (int j = wave; j < K; j += 2 * NW) {
+            const bool in2 = j + NW < K;
+            const int64_t x = (int64_t)B + (int64_t)j * B + b;
+            const int64_t x2 = in2 ? x + (int64_t)NW * B : x;
+            const int64_t xh = uniform(h[x]), xr = uniform(r[x]), xt = uniform(t[x]);
+            const int64_t xh2 = uniform(h[x2]), xr2 = uniform(r[x2]), xt2 = uniform(t[x2]);
+            if (xh != ih || xr != ir || xh2 != ih || xr2 != ir) {   // wave-uniform; not the layout `period` promises
+                single(x, xh, xr, xt);
+                if (in2) single(x2, xh2, xr2, xt2);
+                continue;
+            }
+            const float* pt = ent + xt * lde;
+            const float* pt2 = ent + xt2 * lde;
+            float tv[NK], tv2[NK];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int c = lane + 64 * k;
+                tv[k] = c < d ? pt[c] : 0.f;
+                tv2[k] = c < d ? pt2[c] : 0.f;
+            }
+            float s[2] = {0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                if (lane + 64 * k < d) {
+                    s[0] += fabsf(hr[k] - tv[k]);
+                    s[1] += fabsf(hr[k] - tv2[k]);
+                }
+            }
+            wave_sum_n<2>(s);
+            if (lane == 0) {
+                score[x] = s[0];
+                if (in2) score[x2] = s[1];
+            }
+            const float w2a = margin_w2(pos - s[0], gamma);
+            const float w2b = in2 ? margin_w2(pos - s[1], gamma) : 0.f;
+            g2w += w2a + w2b;
+            float* qt = cnt_ent + xt * d;
+            float* qt2 = cnt_ent + xt2 * d;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int c = lane + 64 * k;
+                if (c < d) {
+                    const float v = -w2a * sgn(hr[k] - tv[k]);
+                    const float v2 = -w2b * sgn(hr[k] - tv2[k]);
+                    acc[k] += v + v2;
+                    if (v != 0.f) atomicAdd(qt + c, -v);
+                    if (v2 != 0.f) atomicAdd(qt2 + c, -v2);
+                }
+            }
+        }
+        // one flush per run: the waves' h / r accumulators and sum 2w meet in LDS; the positive's own term G sgn(.) joins here
+#pragma unroll
+        for (int k = 0; k < NK; ++k) red[wave][lane + 64 * k] = acc[k];
+        if (lane == 0) red_g[wave] = g2w;
+        __syncthreads();
+        float G = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) G += red_g[w];
+        float* qh = cnt_ent + ih * d;
+        float* qr = cnt_rel + ir * d;
+        float* qp = cnt_ent + itp * d;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            if (k % NW != wave) continue;                          // wave-uniform: chunk k belongs to wave k mod NW
+            const int c = lane + 64 * k;
+            if (c < d) {
+                float tot = 0.f;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) tot += red[w][c];
+                const float vp = G * sgn(hr[k] - tp[k]);
+                tot += vp;
+                if (tot != 0.f) {
+                    atomicAdd(qh + c, tot);
+                    atomicAdd(qr + c, tot);
+                }
+                if (vp != 0.f) atomicAdd(qp + c, -vp);
+            }
+        }
+        __syncthreads();                                           // red is reused by the block's next run
     }
 }
 
@@ -382,6 +559,17 @@ __global__ __launch_bounds__(kBlock) void scale_clear_flat2_kernel(float4* __res
         *po = v;
         if (c.x != 0.f || c.y != 0.f || c.z != 0.f || c.w != 0.f) *pc = make_float4(0.f, 0.f, 0.f, 0.f);
     }
+}
+
+// dent / drel (dense, all rows) = cnt * gloss / (2 B K) (+ their contents where acc_* says so), cnt = 0 again
+inline void launch_scale_clear(float* cnt_ent, float* cnt_rel, const float* gloss, int64_t B, int64_t K, int64_t d, float* dent,
+                               int64_t rows_ent, int32_t acc_ent, float* drel, int64_t rows_rel, int32_t acc_rel, hipStream_t st) {
+    const int64_t na4 = rows_ent * d / 4, nb4 = rows_rel * d / 4;
+    int64_t blocks = (na4 + nb4 + kBlock - 1) / kBlock;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(scale_clear_flat2_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, reinterpret_cast<float4*>(cnt_ent),
+                       reinterpret_cast<float4*>(dent), na4, reinterpret_cast<float4*>(cnt_rel), reinterpret_cast<float4*>(drel), nb4, gloss,
+                       1.f / (2.f * (float)B * (float)K), (int)acc_ent, (int)acc_rel);
 }
 
 inline unsigned wave_grid(int64_t units) {
@@ -639,12 +827,34 @@ int jmac_triple_l1_margin_bwd_exact2_f32(const float* ent, int64_t lde, const fl
     JMAC_DISPATCH_NK(nk, hipLaunchKernelGGL((triple_l1_bwd_kernel<NK, true>), dim3(wave_grid(period * parts)), dim3(kBlock), 0, st,
                                             ent, lde, rel, ldr, h, r, t, T, period, parts, (int)d, score, cnt_ent + ent_off * d, d,
                                             cnt_rel + rel_off * d, d, MarginArgs{gamma, B, K}));
-    const int64_t na4 = rows_ent * d / 4, nb4 = rows_rel * d / 4;
-    int64_t blocks = (na4 + nb4 + kBlock - 1) / kBlock;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(scale_clear_flat2_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, reinterpret_cast<float4*>(cnt_ent),
-                       reinterpret_cast<float4*>(dent), na4, reinterpret_cast<float4*>(cnt_rel), reinterpret_cast<float4*>(drel), nb4, gloss,
-                       1.f / (2.f * (float)B * (float)K), (int)acc_ent, (int)acc_rel);
+    launch_scale_clear(cnt_ent, cnt_rel, gloss, B, K, d, dent, rows_ent, acc_ent, drel, rows_rel, acc_rel, st);
+    return (int)hipGetLastError();
+}
+
+int jmac_triple_l1_margin_fwd_counts_f32(const float* ent, int64_t lde, const float* rel, int64_t ldr, const int64_t* h, const int64_t* r,
+                                         const int64_t* t, int64_t B, int64_t K, int64_t d, const float* gamma, int64_t ent_off,
+                                         int64_t rel_off, float* cnt_ent, float* cnt_rel, float* score, jmac_stream_t stream) {
+    if (B <= 0 || K <= 0 || d <= 0 || B >= INT32_MAX || K >= INT32_MAX || ent_off < 0 || rel_off < 0) return JMAC_EINVAL;
+    if (d > 512 || d % 4) return JMAC_EDIM;
+    if (!ent || !rel || !h || !r || !t || !gamma || !cnt_ent || !cnt_rel || !score) return JMAC_EINVAL;
+    if (4 * B * K >= (1LL << 24)) return JMAC_ERANGE;       // a row's integer sum could leave fp32's exact range
+    constexpr int NW = kOnePassWaves;
+    const int nk = (int)((d + 63) / 64);
+    const unsigned grid = (unsigned)(B < 65536 ? B : 65536);
+    JMAC_DISPATCH_NK(nk, hipLaunchKernelGGL((triple_l1_margin_fwd_counts_kernel<NK, NW>), dim3(grid), dim3(64 * NW), 0, (hipStream_t)stream,
+                                            ent, lde, rel, ldr, h, r, t, (int)B, (int)K, (int)d, gamma, score, cnt_ent + ent_off * d,
+                                            cnt_rel + rel_off * d));
+    return (int)hipGetLastError();
+}
+
+int jmac_margin_counts_scale_clear_f32(float* cnt_ent, float* cnt_rel, const float* gloss, int64_t B, int64_t K, int64_t d, float* dent,
+                                       int64_t rows_ent, int32_t acc_ent, float* drel, int64_t rows_rel, int32_t acc_rel,
+                                       jmac_stream_t stream) {
+    if (B <= 0 || K <= 0 || d <= 0 || rows_ent <= 0 || rows_rel <= 0) return JMAC_EINVAL;
+    if (d % 4) return JMAC_EDIM;
+    if (!cnt_ent || !cnt_rel || !gloss || !dent || !drel) return JMAC_EINVAL;
+    if ((((uintptr_t)cnt_ent | (uintptr_t)cnt_rel | (uintptr_t)dent | (uintptr_t)drel) & 15) != 0) return JMAC_EINVAL;
+    launch_scale_clear(cnt_ent, cnt_rel, gloss, B, K, d, dent, rows_ent, acc_ent, drel, rows_rel, acc_rel, (hipStream_t)stream);
     return (int)hipGetLastError();
 }
 

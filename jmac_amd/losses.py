@@ -290,32 +290,80 @@ def _wptr(t: torch.Tensor, off: int) -> int:
     return t.data_ptr() + off * t.stride(0) * t.element_size()
 
 
-_CNT: dict = {}               # (device, rows_ent, rows_rel, d) -> persistent count tables of the exact margin adjoint (always zero between calls)
+_CNT: dict = {}               # (device, rows_ent, rows_rel, d, captured, serial) -> (cnt_ent, cnt_rel) AT REST: all zeros, nobody's
+_CNT_DIRTY: list = []         # (key, pair) a node counted into and never scaled (its backward did not run): cleared before reuse
+_CNT_PINNED: list = []        # pairs a captured graph adds into without clearing them: never handed out again, never freed
+_CNT_SERIAL = [0]
 
 
-def _count_tables(dev, rows_e: int, rows_r: int, d: int):
-    """The zero-at-rest integer tables jmac_triple_l1_margin_bwd_exact2_f32 accumulates into (and clears again): one pair per
-    table shape, shared by every loss op of that shape on the device's stream.  Inside a stream capture an unseen shape gets
-    tables of its own (zero-filled inside the capture, not remembered: they belong to the graph's pool)."""
-    key = (str(dev), int(rows_e), int(rows_r), int(d))
-    hit = _CNT.get(key)
-    if hit is None:
-        hit = (torch.zeros((rows_e, d), dtype=torch.float32, device=dev), torch.zeros((rows_r, d), dtype=torch.float32, device=dev))
-        if not torch.cuda.is_current_stream_capturing():
-            _CNT[key] = hit
-    return hit
+class _Lease:
+    """A node's hold on one pair of count tables between its forward (jmac_triple_l1_margin_fwd_counts_f32 has counted into them)
+    and its backward (the scaling pass leaves them at zero).  Ownership rule: a pair is in ``_CNT`` only while it is zero and
+    nobody's; a pending node holds its pair here, so two nodes alive at once never share one; a lease that dies without its
+    backward (loss discarded, exception) leaves its pair in ``_CNT_DIRTY``, which ``_take_tables`` zero-fills before anyone counts
+    into it again.  Pairs a stream capture baked into a graph are kept apart (``captured`` in the key) and go to nodes inside
+    captures only: an eager node, which can stay pending across a replay, never gets one."""
+
+    __slots__ = ("key", "pair")
+
+    def __init__(self, key, pair):
+        self.key, self.pair = key, pair
+
+    def release(self, clean: bool, reusable: bool = True) -> None:
+        key, pair, self.pair = self.key, self.pair, None
+        if pair is None or key is None:                # (key None: tables of a capture's own pool, gone with the graph)
+            return
+        if not reusable or (key[4] and not clean):     # a graph keeps adding into them at every replay
+            _CNT_PINNED.append(pair)
+        elif clean:
+            _CNT[key] = pair
+        else:
+            _CNT_DIRTY.append((key, pair))
+
+    def __del__(self):
+        try:
+            self.release(False)
+        except Exception:                              # pragma: no cover  (interpreter shutdown)
+            pass
+
+
+def _take_tables(dev, rows_e: int, rows_r: int, d: int) -> _Lease:
+    """A zeroed pair of count tables for one node (see _Lease).  Inside a stream capture: a pair at rest that earlier captures
+    used, else one of the eager pool (pinned to captures from now on), else tables of the graph's own pool, zero-filled inside
+    the capture and not remembered."""
+    shape = (str(dev), int(rows_e), int(rows_r), int(d))
+    capturing = torch.cuda.is_current_stream_capturing()
+    for want in ((True, False) if capturing else (False,)):
+        for key in _CNT:
+            if key[:4] == shape and key[4] == want:
+                return _Lease(key[:4] + (capturing, key[5]), _CNT.pop(key))
+    if not capturing:
+        for i, (key, pair) in enumerate(_CNT_DIRTY):
+            if key[:4] == shape and not key[4]:
+                del _CNT_DIRTY[i]
+                pair[0].zero_()
+                pair[1].zero_()
+                return _Lease(key, pair)
+    pair = (torch.zeros((rows_e, d), dtype=torch.float32, device=dev), torch.zeros((rows_r, d), dtype=torch.float32, device=dev))
+    if capturing:
+        return _Lease(None, pair)
+    _CNT_SERIAL[0] += 1
+    return _Lease(shape + (False, _CNT_SERIAL[0]), pair)
 
 
 class _LayerLoss(torch.autograd.Function):
     """One layer's term of completion_loss (src/jmac_model.py:331-380) as ONE node:
         loss = add_to + margin_loss(||ent[h] + rel[r] - ent[t]||_1) [+ mean_x (1 - cos(ent[c0[x]], ent[c1[x]]))]
-    (the bracket: alignment_loss_simple on the seed links, both sides windows of the same stacked table).  The backward writes
+    (the bracket: alignment_loss_simple on the seed links, both sides windows of the same stacked table).  Where a table gradient
+    is needed the forward is ONE pass over the triples that leaves the scores and, in a pair of count tables the node holds until
+    its backward, the integer counts of the exact L1 adjoint (they do not depend on the incoming gradient).  The backward writes
     ONE gradient per table, each row exactly once: the cosine adjoint row by row (first writer, zeros where no link touches a
-    row), then the exact-integer L1 adjoint from its persistent count tables on top -- no zero fill, no add of two gradient
-    contributions, no scalar arithmetic launches."""
+    row), then the scaling pass over the count tables on top -- no second gather, no zero fill, no add of two gradient
+    contributions, no scalar arithmetic launches.  A second backward through a retained graph finds the counts gone and takes
+    the two-pass adjoint from the saved scores (the same bits)."""
 
     @staticmethod
-    def forward(ctx, ent, rel, h, r, t, margin, add_to, c0, c1, B, K, eoff, roff, coff0, coff1):
+    def forward(ctx, ent, rel, h, r, t, margin, add_to, c0, c1, B, K, eoff, roff, coff0, coff1, counts):
         require_device(ent, rel, h, r, t, margin)
         ent, rel = _rows(ent), _rows(rel)
         T, d = h.numel(), ent.shape[1]
@@ -324,8 +372,17 @@ class _LayerLoss(torch.autograd.Function):
         dev = ent.device
         score = torch.empty(T, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        check(lib().jmac_triple_l1_fwd_f32(_wptr(ent, eoff), ent.stride(0), _wptr(rel, roff), rel.stride(0), ptr(h), ptr(r), ptr(t),
-                                           T, B, d, ptr(score), stream()), "jmac_triple_l1_fwd_f32")
+        ctx.lease = None
+        if counts:                                     # a table gradient will be asked for (the caller looked: no grad mode in here)
+            lease = _take_tables(dev, int(ent.shape[0]), int(rel.shape[0]), d)
+            cnt_e, cnt_r = lease.pair
+            check(lib().jmac_triple_l1_margin_fwd_counts_f32(_wptr(ent, eoff), ent.stride(0), _wptr(rel, roff), rel.stride(0), ptr(h),
+                                                             ptr(r), ptr(t), B, K, d, ptr(margin), eoff, roff, ptr(cnt_e), ptr(cnt_r),
+                                                             ptr(score), stream()), "jmac_triple_l1_margin_fwd_counts_f32")
+            ctx.lease = lease
+        else:
+            check(lib().jmac_triple_l1_fwd_f32(_wptr(ent, eoff), ent.stride(0), _wptr(rel, roff), rel.stride(0), ptr(h), ptr(r), ptr(t),
+                                               T, B, d, ptr(score), stream()), "jmac_triple_l1_fwd_f32")
         check(lib().jmac_margin_loss_fwd_acc_f32(ptr(score), B, K, ptr(margin), ptr(add_to), ptr(loss), stream()),
               "jmac_margin_loss_fwd_acc_f32")
         stats = None
@@ -354,13 +411,24 @@ class _LayerLoss(torch.autograd.Function):
         drel = torch.empty((rows_r, d), dtype=torch.float32, device=dev)
         if c0 is not None:                             # first writer of dent: every row once, zeros where no link touches it
             _pair_cosine_rows_bwd(ent, ent, c0, c1, coff0, coff1, True, stats, None, g, float(c0.numel()), de1=dent)
-        cnt_e, cnt_r = _count_tables(dev, rows_e, rows_r, d)
-        check(lib().jmac_triple_l1_margin_bwd_exact2_f32(_wptr(ent, eoff), ent.stride(0), _wptr(rel, roff), rel.stride(0), ptr(h), ptr(r),
-                                                         ptr(t), B, K, d, ptr(score), ptr(margin), ptr(g), eoff, roff, ptr(cnt_e),
-                                                         ptr(cnt_r), ptr(dent), rows_e, 1 if c0 is not None else 0, ptr(drel), rows_r, 0,
-                                                         stream()), "jmac_triple_l1_margin_bwd_exact2_f32")
+        lease, ctx.lease = ctx.lease, None
+        if lease is not None and lease.pair is not None:           # the forward's counts: the scaling pass is all that is left
+            cnt_e, cnt_r = lease.pair
+            same = lease.key is None or lease.key[4] == torch.cuda.is_current_stream_capturing()
+            check(lib().jmac_margin_counts_scale_clear_f32(ptr(cnt_e), ptr(cnt_r), ptr(g), B, K, d, ptr(dent), rows_e,
+                                                           1 if c0 is not None else 0, ptr(drel), rows_r, 0, stream()),
+                  "jmac_margin_counts_scale_clear_f32")
+            lease.release(True, reusable=same)         # (counted eagerly, cleared by a graph or the reverse: not at rest in between)
+        else:                                          # a second backward (retained graph): count again from the saved scores
+            lease = _take_tables(dev, rows_e, rows_r, d)      # (counted and cleared by the one call)
+            cnt_e, cnt_r = lease.pair
+            check(lib().jmac_triple_l1_margin_bwd_exact2_f32(_wptr(ent, eoff), ent.stride(0), _wptr(rel, roff), rel.stride(0), ptr(h),
+                                                             ptr(r), ptr(t), B, K, d, ptr(score), ptr(margin), ptr(g), eoff, roff,
+                                                             ptr(cnt_e), ptr(cnt_r), ptr(dent), rows_e, 1 if c0 is not None else 0,
+                                                             ptr(drel), rows_r, 0, stream()), "jmac_triple_l1_margin_bwd_exact2_f32")
+            lease.release(True)
         _fresh(dent, drel)
-        return (dent, drel, None, None, None, None, (g if has_add else None), None, None, None, None, None, None, None, None)
+        return (dent, drel, None, None, None, None, (g if has_add else None), None, None, None, None, None, None, None, None, None)
 
 
 def completion_layer_loss(ent: torch.Tensor, rel: torch.Tensor, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor, batch_size: int,
@@ -393,7 +461,8 @@ def completion_layer_loss(ent: torch.Tensor, rel: torch.Tensor, h: torch.Tensor,
     if add_to is not None:
         add_to = add_to.reshape(1)
     return _LayerLoss.apply(ent, rel, _index(h, en, dev, "batch_h"), _index(r, rn, dev, "batch_r"), _index(t, en, dev, "batch_t"),
-                            margin.reshape(1).to(torch.float32), add_to, c0, c1, B, (T - B) // B, eoff, roff, coff0, coff1)
+                            margin.reshape(1).to(torch.float32), add_to, c0, c1, B, (T - B) // B, eoff, roff, coff0, coff1,
+                            torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad))
 
 
 def triple_l1_margin_loss(ent: torch.Tensor, rel: torch.Tensor, h: torch.Tensor, r: torch.Tensor, t: torch.Tensor,
