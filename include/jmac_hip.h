@@ -419,6 +419,22 @@ int jmac_softmax_entropy_f32(const float* A, int64_t lda, const float* B, int64_
                              int64_t n2, int64_t d, float scale, float* ent_rows, float* ent_cols,
                              void* ws, size_t ws_bytes, jmac_stream_t stream);
 
+/* Softmax STATISTICS of S = A B^T (n1 x n2) without the matrix: the products are the fp32-MFMA products of jmac_sim_matrix_f32,
+ * bit for bit, and are reduced in the product kernel's epilogue -- S is never written; the workspace holds partial statistics,
+ * O((n1 + n2) * n / 64) words (about an eighth of one matrix), never n1 * n2.  With the logits z = scale * S, scale > 0:
+ *   row_max[i] = max_j S[i,j]  (the raw similarity, == jmac_sim_matrix_f32's row maximum bitwise)
+ *   row_arg[i] = the column of that maximum; TIES: the lowest index
+ *   row_sum[i] = sum_j e^(scale (S[i,j] - row_max[i]))           (softmax(z)[i, row_arg[i]] == 1 / row_sum[i])
+ *   row_ent[i] = log(l) - t / l,  l = row_sum[i],  t = sum_j e^(z - max z) (z - max z)   (the entropy of softmax_j(z[i,:]))
+ * and col_* the same along the columns (col_arg[j]: the lowest row index of column j's maximum).  Every output pointer may be
+ * NULL (not wanted); at least one must be given.  Run-to-run bitwise reproducible and independent of the device's CU count:
+ * partials are stored per 64-column / 64-row part and merged in ascending order.  lda, ldb % 4 == 0 (d padded with zeros). */
+size_t jmac_sim_softmax_stats_workspace_bytes(int64_t n1, int64_t n2);
+int jmac_sim_softmax_stats_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                               float scale, float* row_max, int32_t* row_arg, float* row_sum, float* row_ent, float* col_max,
+                               int32_t* col_arg, float* col_sum, float* col_ent, void* ws, size_t ws_bytes,
+                               jmac_stream_t stream);
+
 /* Softmax of an existing score matrix S [n1,n2] (row-major) with rows in `row_mask` and columns in `col_mask` (uint8, 1 = keep;
  * NULL mask = keep all) left as they are and every other entry replaced by `fill` (train.py:252-257: fill = -1), all scaled by
  * `scale`, then

@@ -5,6 +5,8 @@
 //  * jmac_sim_matrix_f32    torch.mm(ILL_vec, KG_vec.t())                modules/utils/util.py:52, train.py:239
 //  * jmac_row_topk_f32 / jmac_sim_topk_f32   sim.topk(k, dim=1)          modules/utils/util.py:53
 //  * jmac_softmax_entropy_f32, jmac_row_softmax_f32                      train.py:241-257
+//  * jmac_sim_softmax_stats_f32  the same softmax's maxima, arg-maxima, sums and entropies per row and per column from the
+//                                product's epilogue, the matrix never written                   train.py:160-169, 231-259
 //
 // L1 distance is |a-b| accumulation: not a contraction, so it runs on the VALU (register-tiled through
 // LDS); the similarity matrices are contractions and run on the matrix cores with the fp32-input MFMA
@@ -431,10 +433,77 @@ struct SimFilter {
     int n_off;               // the product covers columns [n_off, n_off + N) of the full matrix: candidate index = n_off + n
 };
 
-template <bool FILTER, int WJ>
+// STATS = true: the scores are not stored either.  Every wave reduces its 64 x 64 part of the tile to partial softmax statistics of
+// the logits z = scale * S, once along its rows and once along its columns (jmac_sim_softmax_stats_f32): per row and 64-column
+// part (max S, l = sum e^(z - max z), t = sum e^(z - max z) (z - max z), first column of the maximum), per column and 64-row part
+// the same.  A part's maximum is exact (taken before the exponentials), the parts are combined by sim_stats_merge_kernel with the
+// online form.  Partials are addressed by the part's POSITION in the matrix, written once with plain stores and merged in
+// ascending order: the results do not depend on the grid, the tile walk or the device's CU count.  The reductions stay in
+// registers (DPP inside a 16-lane row, one cross-lane exchange per further step): no wave touches the operand LDS buffers behind
+// the last slab's barrier, as in the other two epilogues.  Runs on the 128 x 128 tile only (launch_sim_stats).
+struct SimStats {
+    float4* rpart;           // [ceil(N / 64)][M]    (max S, l, t, column index bits)
+    float* cpart;            // [ceil(M / 64)][N][3] (scale * max S, l, t): the format of col_softmax_stats_kernel; NULL: rows only
+    float2* cbest;           // [ceil(M / 64)][N]    (max S, row index bits)
+    float scale;             // > 0
+};
+template <bool STATS> struct SgExt { typedef SimFilter type; };
+template <> struct SgExt<true> { typedef SimStats type; };
+
+// the DPP-selected lane's v (old = 0 with bound_ctrl: every source lane of the controls used here exists; ROWS: rows written)
+template <int CTRL, int ROWS = 0xF>
+__device__ __forceinline__ float sg_dpp_f(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROWS, 0xF, true));
+}
+// max(v, v of the DPP-selected lane) as ONE instruction.  Through fmaxf the compiler emits a move, a NaN-quieting v_max x, x of
+// the moved value (it knows nothing about it) and the v_max: three.  s_nop 1 = the two wait states between a VALU write of v and
+// a DPP read of it (nothing pads the inside of an asm statement).  No NaN reaches these (excluded elements are -inf).
+#define JMAC_SG_MAX_DPP(v, ctrl) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(v) : "v"(v))
+__device__ __forceinline__ float sg_max(float a, float b) {
+    float d;
+    asm("v_max_f32_e32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+// Reductions over the 32 lanes of a half-wave.  xor 1, xor 2 as quad permutes, then row_half_mirror and row_mirror (the values
+// are uniform inside the groups they exchange): every lane of a 16-lane row holds its row's result.
+// max: the other row's value comes through one bpermute, every lane of the half ends with the same bits.
+__device__ __forceinline__ float sg_half_max(float v) {
+    JMAC_SG_MAX_DPP(v, "quad_perm:[1,0,3,2]");
+    JMAC_SG_MAX_DPP(v, "quad_perm:[2,3,0,1]");
+    JMAC_SG_MAX_DPP(v, "row_half_mirror");
+    JMAC_SG_MAX_DPP(v, "row_mirror");
+    return sg_max(v, __shfl_xor(v, 16, 64));
+}
+// sum: row_bcast:15 adds the lower row's sum into the upper row -- only lanes 16..31 / 48..63 hold the half's sum (lower + upper)
+__device__ __forceinline__ float sg_half_sum_upper(float v) {
+    v += sg_dpp_f<0xB1>(v);
+    v += sg_dpp_f<0x4E>(v);
+    v += sg_dpp_f<0x141>(v);
+    v += sg_dpp_f<0x140>(v);
+    return v + sg_dpp_f<0x142, 0xA>(v);
+}
+// Both halves' values of x in every lane: lo = x of lane (l & 31), hi = x of lane (l & 31) + 32.  v_permlane32_swap of two copies
+// (inline asm with its wait states, for the reason given at halves_meet in aggregate.hip).
+__device__ __forceinline__ void sg_halves(float x, float& lo, float& hi) {
+    lo = x;
+    hi = x;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(lo), "+v"(hi));
+}
+// e^x and e^x x of one logit difference x = scale (s - max) <= 0; an excluded element (s = -inf, or the whole part excluded:
+// NaN) is clamped to -1e30, where e^x is 0 and the product -0
+__device__ __forceinline__ void sg_exp_term(float s, float mx, float scale, float& l, float& t) {
+    const float x = fmaxf(scale * (s - mx), -1e30f);
+    const float e = fast_exp(x);
+    l += e;
+    t = fmaf(e, x, t);
+}
+
+template <bool FILTER, int WJ, bool STATS = false>
 __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                           int64_t ldb, int M, int N, int d, float* __restrict__ C, int64_t ldc,
-                                                          int tiles_m, int tiles_n, int super_order, int n_ids, SimFilter flt) {
+                                                          int tiles_m, int tiles_n, int super_order, int n_ids,
+                                                          typename SgExt<STATS>::type flt) {
+    static_assert(!(STATS && (FILTER || WJ != 2)), "the statistics epilogue is written for the plain 128 x 128 tile");
     // LDS image of one operand slab (16 k): plane (q, h) holds, for every tile row, the 4 floats k = 8q + 4h .. +3.
     // Lane (r = l&31, h = l>>5) of a wave reads its float4 of row r from plane (q, h): 32 lanes x 16 B contiguous,
     // conflict free for ds_read_b128's lane groups.  The MFMA step s of a sub-slab contracts k = {8q+s, 8q+4+s}.
@@ -625,7 +694,95 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
         }
         // C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
         const bool full = m0 + SG_T <= M && n0 + SG_TN <= N;      // block-uniform: interior tiles store without bounds tests
-        if constexpr (FILTER) {
+        if constexpr (STATS) {
+            const float scale = flt.scale;
+            const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
+            const int ncol[2] = {ncol0 + r, ncol0 + 32 + r};
+            // elements outside the matrix (ragged tiles: the clamped loads' duplicates) leave both reductions as -inf
+            const int mlim = M - mrow0 - 4 * h;                       // row (i, reg) of this lane is inside iff its base < mlim
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) {
+                        // min(s, +inf) = s inside, min(s, -inf) outside; the bound's sign comes from the two differences' sign bits
+                        // (64 compare masks would not fit the scalar registers)
+                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                        const unsigned inside = (unsigned)(rbase - mlim) & (unsigned)(ncol[j] - N) & 0x80000000u;
+                        acc[i][j][reg] = fminf(acc[i][j][reg], __uint_as_float(0xff800000u ^ inside));
+                    }
+            // rows: (i, reg) is one row per half-wave, its 64 columns are 2 registers x 32 lanes.  The maximum reaches every lane
+            // (the exponentials need it), the two sums only the half's upper 16 lanes, and lane 16 of the half stores the row at
+            // once (16 bytes; results kept for one wide store at the end would stay live through all 32 chains and spill).  The
+            // first column of the maximum is scalar work: ballots of v == max, lowest set bit of each half.
+            float4* const rdst = flt.rpart + (int64_t)(ncol0 >> 6) * M + mrow0 + 4 * h;
+            const bool rstore = r == 16 && ncol0 < N;                 // (a part wholly outside the matrix does not exist)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                    const float v0 = acc[i][0][reg], v1 = acc[i][1][reg];
+                    const float mx = sg_half_max(sg_max(v0, v1));
+                    const unsigned long long e0 = __ballot(v0 == mx), e1 = __ballot(v1 == mx);
+                    // per half: bits 0..31 = its lanes' j = 0 columns, 32..63 = their j = 1 columns, i.e. the part's column order
+                    const int al = __builtin_ffsll((long long)((e0 & 0xffffffffull) | (e1 << 32))) - 1;      // wave-uniform
+                    const int ah = __builtin_ffsll((long long)((e0 >> 32) | (e1 & 0xffffffff00000000ull))) - 1;
+                    float l = 0.f, t = 0.f;
+                    sg_exp_term(v0, mx, scale, l, t);
+                    sg_exp_term(v1, mx, scale, l, t);
+                    l = sg_half_sum_upper(l);
+                    t = sg_half_sum_upper(t);
+                    if (rstore && rbase < mlim) rdst[rbase] = make_float4(mx, l, t, __int_as_float(ncol0 + (h ? ah : al)));
+                    // two rows' chains interleave (they fill each other's DPP wait states), no more
+                    if (reg & 1) __builtin_amdgcn_sched_barrier(0);
+                }
+            // columns: a lane holds 32 rows of its column per j, the other half-wave the other 32
+            if (flt.cpart != nullptr) {
+                float cm[2], cl[2], ct[2];
+                int ca[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    float mx = -INFINITY;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) mx = sg_max(mx, acc[i][j][reg]);
+                    float lo, hi;
+                    sg_halves(mx, lo, hi);
+                    mx = sg_max(lo, hi);
+                    // the lane's rows in DESCENDING order: the last match is its lowest row of the maximum (128: none)
+                    int a = 128;
+                    float l = 0.f, t = 0.f;
+#pragma unroll
+                    for (int i = 1; i >= 0; --i)
+#pragma unroll
+                        for (int reg = 15; reg >= 0; --reg) {
+                            a = acc[i][j][reg] == mx ? i * 32 + (reg & 3) + 8 * (reg >> 2) : a;
+                            sg_exp_term(acc[i][j][reg], mx, scale, l, t);
+                            if ((reg & 3) == 0) __builtin_amdgcn_sched_barrier(0);
+                        }
+                    sg_halves(l, lo, hi);
+                    cl[j] = lo + hi;
+                    sg_halves(t, lo, hi);
+                    ct[j] = lo + hi;
+                    sg_halves(__int_as_float(a + 4 * h), lo, hi);
+                    ca[j] = mrow0 + min(__float_as_int(lo), __float_as_int(hi));
+                    cm[j] = mx;
+                }
+                // the lower half-wave stores the columns of j = 0, the upper half those of j = 1
+                const int col = h ? ncol[1] : ncol[0];
+                if (col < N && mrow0 < M) {
+                    const int64_t e = (int64_t)(mrow0 >> 6) * N + col;
+                    const float mxs = h ? cm[1] : cm[0];
+                    flt.cpart[e * 3 + 0] = scale * mxs;
+                    flt.cpart[e * 3 + 1] = h ? cl[1] : cl[0];
+                    flt.cpart[e * 3 + 2] = h ? ct[1] : ct[0];
+                    flt.cbest[e] = make_float2(mxs, __int_as_float(h ? ca[1] : ca[0]));
+                }
+            }
+        } else if constexpr (FILTER) {
             // Passing elements are rare (~k * N / Ns per row: under 1 % of the tile).  A returned global atomic per passing
             // element inside the scan would cost one memory round trip each (measured: the product ran 1.6x longer); the wave
             // first compacts its passing elements into a small LDS list (ballot + prefix popcount, no memory traffic) and
@@ -1591,14 +1748,14 @@ struct SimGeom {
 
 // persistent grids: as many blocks as are resident at once (occupancy query: 3 per CU for the 128 x 128 tile -- 64 accumulation
 // VGPRs, 33 KB of LDS -- and 2 for 128 x 256), rounded down to a multiple of 8 so that a block's tile ids stay on its XCD
-template <bool FILTER, int WJ>
+template <bool FILTER, int WJ, bool STATS = false>
 int sim_resident(int dev) {
     static int resident_of[64] = {0};                                     // per device: CU counts may differ between devices
     int& resident = resident_of[dev >= 0 && dev < 64 ? dev : 0];
     if (resident == 0 || dev >= 64) {
         int cus = 256, occ = SgTile<WJ>::OCC;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(sim_gemm_kernel<FILTER, WJ>), kBlock, 0) != hipSuccess || occ < 1)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(sim_gemm_kernel<FILTER, WJ, STATS>), kBlock, 0) != hipSuccess || occ < 1)
             occ = SgTile<WJ>::OCC;
         resident = (cus * occ) / 8 * 8;
         if (resident < 8) resident = 8;
@@ -1662,6 +1819,105 @@ int launch_sim(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t
                    : launch_sim_wj<false, 4>(A, lda, B, ldb, M, N, d, C, ldc, st, flt, dev);
     return flt ? launch_sim_wj<true, 2>(A, lda, B, ldb, M, N, d, C, ldc, st, flt, dev)
                : launch_sim_wj<false, 2>(A, lda, B, ldb, M, N, d, C, ldc, st, flt, dev);
+}
+
+// the product with the statistics epilogue: always the 128 x 128 tile (one partial layout: a part is 64 rows or 64 columns)
+int launch_sim_stats(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimStats& sx,
+                     hipStream_t st) {
+    if (d % 4) return JMAC_EDIM;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const SimGeom<2> g(M, N);
+    if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
+    const int resident = sim_resident<false, 2, true>(dev);
+    const unsigned grid = (unsigned)(g.n_ids < resident ? g.n_ids : resident);
+    hipLaunchKernelGGL((sim_gemm_kernel<false, 2, true>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d,
+                       (float*)nullptr, (int64_t)0, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, sx);
+    return (int)hipGetLastError();
+}
+
+// 64 rows (blocks [0, row_blocks)) or 64 columns (the blocks behind them) per block.  Wave g combines the g-th quarter of a
+// line's partials in ascending part order with the arithmetic of col_softmax_merge_kernel (loads four parts ahead: one thread
+// walking all of a line's parts alone is a chain of dependent memory latencies), wave 0 then combines the four quarters in
+// order.  The maximum moves on strict > only, so ties keep the lowest index.  Every output is optional.
+constexpr int SM_G = kBlock / 64;
+struct SsState {
+    float m = -INFINITY, z = 0.f, y = 0.f, best = -INFINITY;      // m: max logit, best: max similarity
+    int arg = 0;
+    __device__ __forceinline__ void push(float pm, float pz, float py, float pbest, int parg) {
+        if (!(pz > 0.f)) return;                                   // nothing behind this partial
+        if (pbest > best) {
+            best = pbest;
+            arg = parg;
+        }
+        const float mn = fmaxf(m, pm);
+        const float fa = expf(m - mn), fb = expf(pm - mn);
+        const float da = m - mn, db = pm - mn;
+        const float ya = z > 0.f ? fa * (y + da * z) : 0.f;
+        const float yb = fb * (py + db * pz);
+        y = ya + yb;
+        z = fa * z + fb * pz;
+        m = mn;
+    }
+};
+__global__ __launch_bounds__(kBlock) void sim_stats_merge_kernel(const float4* __restrict__ rpart, const float* __restrict__ cpart,
+                                                                 const float2* __restrict__ cbest, int n1, int n2, float scale,
+                                                                 int row_blocks, float* __restrict__ row_max, int32_t* __restrict__ row_arg,
+                                                                 float* __restrict__ row_sum, float* __restrict__ row_ent,
+                                                                 float* __restrict__ col_max, int32_t* __restrict__ col_arg,
+                                                                 float* __restrict__ col_sum, float* __restrict__ col_ent) {
+    __shared__ float sh[SM_G][4][64];
+    __shared__ int sha[SM_G][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const bool rows = (int)blockIdx.x < row_blocks;
+    const int e = ((int)blockIdx.x - (rows ? 0 : row_blocks)) * 64 + lane;
+    const int n = rows ? n1 : n2, parts = ((rows ? n2 : n1) + 63) / 64;
+    const int per = (parts + SM_G - 1) / SM_G, p0 = g * per, p1 = min(parts, p0 + per);
+    const int ec = min(e, n - 1);
+    SsState s;
+    for (int pb = p0; pb < p1; pb += 4) {
+        float pm[4], pz[4], py[4], pbest[4];
+        int parg[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t at = (int64_t)min(pb + k, p1 - 1) * n + ec;
+            if (rows) {
+                const float4 q = rpart[at];
+                pbest[k] = q.x; pm[k] = scale * q.x; pz[k] = q.y; py[k] = q.z; parg[k] = __float_as_int(q.w);
+            } else {
+                const float2 bq = cbest[at];
+                pm[k] = cpart[at * 3]; pz[k] = cpart[at * 3 + 1]; py[k] = cpart[at * 3 + 2]; pbest[k] = bq.x; parg[k] = __float_as_int(bq.y);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (pb + k < p1) s.push(pm[k], pz[k], py[k], pbest[k], parg[k]);
+    }
+    sh[g][0][lane] = s.m; sh[g][1][lane] = s.z; sh[g][2][lane] = s.y; sh[g][3][lane] = s.best;
+    sha[g][lane] = s.arg;
+    __syncthreads();
+    if (g != 0 || e >= n) return;
+    for (int q = 1; q < SM_G; ++q) s.push(sh[q][0][lane], sh[q][1][lane], sh[q][2][lane], sh[q][3][lane], sha[q][lane]);
+    float* const omax = rows ? row_max : col_max;
+    int32_t* const oarg = rows ? row_arg : col_arg;
+    float* const osum = rows ? row_sum : col_sum;
+    float* const oent = rows ? row_ent : col_ent;
+    if (omax) omax[e] = s.best;
+    if (oarg) oarg[e] = s.arg;
+    if (osum) osum[e] = s.z;
+    if (oent) oent[e] = logf(s.z) - s.y / s.z;
+}
+
+struct SsWs { size_t rpart, cpart, cbest, total; };
+SsWs ss_layout(int64_t n1, int64_t n2) {
+    SsWs w{};
+    const size_t pn = (size_t)((n2 + 63) / 64), pm = (size_t)((n1 + 63) / 64);
+    size_t off = 0;
+    w.rpart = off; off += align_up(pn * (size_t)n1 * 16);
+    w.cpart = off; off += align_up(pm * (size_t)n2 * 12);
+    w.cbest = off; off += align_up(pm * (size_t)n2 * 8);
+    w.total = off + 256;
+    return w;
 }
 
 int launch_topk(const float* S, int64_t lds, int64_t L, int64_t N, int32_t k, float* val, int32_t* idx, hipStream_t st) {
@@ -1881,6 +2137,35 @@ int jmac_softmax_entropy_f32(const float* A, int64_t lda, const float* B, int64_
     hipLaunchKernelGGL(row_entropy_kernel, dim3((unsigned)n1), dim3(kBlock), 0, st, S, n2, (int)n2, scale, ent_rows);
     return jmac_col_softmax_f32(S, n2, n1, n2, nullptr, nullptr, 0.f, scale, nullptr, 0, ent_cols, (char*)ws + soff,
                                 ws_bytes - soff, stream);
+}
+
+size_t jmac_sim_softmax_stats_workspace_bytes(int64_t n1, int64_t n2) {
+    if (n1 < 0 || n2 < 0) return 0;
+    return ss_layout(n1, n2).total;
+}
+
+int jmac_sim_softmax_stats_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, float scale,
+                               float* row_max, int32_t* row_arg, float* row_sum, float* row_ent, float* col_max, int32_t* col_arg,
+                               float* col_sum, float* col_ent, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (n1 < 0 || n2 < 0 || d <= 0 || !(scale > 0.f)) return JMAC_EINVAL;
+    if (n1 == 0 || n2 == 0) return JMAC_OK;
+    const bool want_rows = row_max || row_arg || row_sum || row_ent, want_cols = col_max || col_arg || col_sum || col_ent;
+    if (!A || !B || !(want_rows || want_cols)) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4) return JMAC_EDIM;
+    if (n1 >= INT32_MAX || n2 >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_sim_softmax_stats_workspace_bytes(n1, n2)) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const SsWs w = ss_layout(n1, n2);
+    SimStats sx{};
+    sx.rpart = (float4*)((char*)ws + w.rpart);
+    sx.cpart = want_cols ? (float*)((char*)ws + w.cpart) : nullptr;
+    sx.cbest = (float2*)((char*)ws + w.cbest);
+    sx.scale = scale;
+    if (int rc = launch_sim_stats(A, lda, B, ldb, n1, n2, d, sx, st)) return rc;
+    const int rb = want_rows ? (int)((n1 + 63) / 64) : 0, cb = want_cols ? (int)((n2 + 63) / 64) : 0;
+    hipLaunchKernelGGL(sim_stats_merge_kernel, dim3((unsigned)(rb + cb)), dim3(kBlock), 0, st, sx.rpart, sx.cpart, sx.cbest, (int)n1,
+                       (int)n2, scale, rb, row_max, row_arg, row_sum, row_ent, col_max, col_arg, col_sum, col_ent);
+    return (int)hipGetLastError();
 }
 
 int jmac_csls_apply_f32(const float* S, int64_t lds, int64_t n1, int64_t n2, const float* r1, const float* r2, float* out,

@@ -2,7 +2,8 @@
 
 Host-side mirror of ``seed_enlargement_triple_transferring`` (train.py:138-211), ``transfer_knowledge``
 (train.py:297-325) and ``align_data_processing`` (train.py:116-135).  The similarity work runs on the HIP kernels
-(``scoring.alignment_quality`` = compute_alignment_quality, ``scoring.get_neg``); the python dict / set / string-key
+(``scoring.alignment_quality`` = compute_alignment_quality or its matrix-free form ``scoring.alignment_stats``,
+``scoring.get_neg``); the python dict / set / string-key
 loops of the reference become array operations with the same results IN THE SAME ORDER, including the reference's
 quirks:
 
@@ -110,29 +111,44 @@ def align_data_processing(triple_list, device) -> Tuple[torch.Tensor, torch.Tens
     return ei, torch.from_numpy(np.ascontiguousarray(t[:, 1])).to(device)
 
 
-def seed_enlargement_triple_transferring(output1, output2, align_test_src, align_test_dst, global_entropies, seed_index,
-                                         train_align_pairs, triples1, triples2, global_seeds, ent_bases1, rel_bases1,
-                                         ent_bases2, rel_bases2, kg1, kg2, args, generator=None):
-    """train.py:138-211 with the same arguments and return tuple.  ``output1/2``: the L2-normalised alignment
-    embeddings of ``get_emb`` ON THE HIP DEVICE; ``kg1/kg2`` need a ``triple_keys`` attribute (int64 codes, or the
-    reference's set of strings).  ``generator``: optional torch.Generator for the multinomial draw (train.py:166)."""
-    entropy_t, simi, _ = scoring.alignment_quality(output1, output2, align_test_src, align_test_dst)
-    entropy = float(entropy_t)
+def _enlargement_pairs(entropy: float, global_entropies, seed_index, n_test: int, args, row_weights, row_best, generator):
+    """train.py:147-169: the stored entropy decides how many pairs are drawn.  ``row_weights()`` -> the [N1] multinomial
+    weights (the largest softmax entry of every row), ``row_best(src)`` -> the arg-max columns of the rows ``src``; both are
+    only called when pairs are drawn.  Returns the new (source, target) pairs [P, 2]."""
     prev = global_entropies[seed_index]
-    additional = np.zeros((0, 2), dtype=np.int64)
     if prev == -1:
         global_entropies[seed_index] = entropy
+        return np.zeros((0, 2), dtype=np.int64)
+    sample_percent = (prev - entropy) / prev * args.pair_sample_weight
+    if sample_percent < 0:
+        sample_percent = 0
+        global_entropies[seed_index] = entropy
+    num_pairs = int(sample_percent * n_test)
+    if num_pairs <= 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    src_nodes = row_weights().multinomial(num_pairs, replacement=False, generator=generator)
+    dst_nodes = row_best(src_nodes)
+    return torch.stack([src_nodes, dst_nodes], 1).cpu().numpy().astype(np.int64)
+
+
+def seed_enlargement_triple_transferring(output1, output2, align_test_src, align_test_dst, global_entropies, seed_index,
+                                         train_align_pairs, triples1, triples2, global_seeds, ent_bases1, rel_bases1,
+                                         ent_bases2, rel_bases2, kg1, kg2, args, generator=None, matrix_free=False):
+    """train.py:138-211 with the same arguments and return tuple.  ``output1/2``: the L2-normalised alignment
+    embeddings of ``get_emb`` ON THE HIP DEVICE; ``kg1/kg2`` need a ``triple_keys`` attribute (int64 codes, or the
+    reference's set of strings).  ``generator``: optional torch.Generator for the multinomial draw (train.py:166).
+    ``matrix_free``: take the entropy, the draw's weights and the arg-max columns from ``scoring.alignment_stats`` (no
+    N1 x N2 matrix is written) instead of from the softmax matrices of ``scoring.alignment_quality``."""
+    if matrix_free:
+        entropy_t, best_prob, best, _, _ = scoring.alignment_stats(output1, output2, align_test_src, align_test_dst)
+        row_weights = lambda: best_prob                                                     # noqa: E731
+        row_best = lambda src: best.index_select(0, src)                                    # noqa: E731
     else:
-        sample_percent = (prev - entropy) / prev * args.pair_sample_weight
-        if sample_percent < 0:
-            sample_percent = 0
-            global_entropies[seed_index] = entropy
-        num_pairs = int(sample_percent * len(align_test_src))
-        if num_pairs > 0:
-            max_values = simi.max(dim=1)[0]
-            src_nodes = max_values.multinomial(num_pairs, replacement=False, generator=generator)
-            dst_nodes = simi.index_select(0, src_nodes).max(dim=1)[1]
-            additional = torch.stack([src_nodes, dst_nodes], 1).cpu().numpy().astype(np.int64)
+        entropy_t, simi, _ = scoring.alignment_quality(output1, output2, align_test_src, align_test_dst)
+        row_weights = lambda: simi.max(dim=1)[0]                                            # noqa: E731
+        row_best = lambda src: simi.index_select(0, src).max(dim=1)[1]                      # noqa: E731
+    additional = _enlargement_pairs(float(entropy_t), global_entropies, seed_index, len(align_test_src), args, row_weights,
+                                    row_best, generator)
     pairs = np.asarray(train_align_pairs, dtype=np.int64).reshape(-1, 2)
     if len(additional):
         pairs = additional if not len(pairs) else np.concatenate([pairs, additional], axis=0)

@@ -39,11 +39,12 @@ from .data import KnowledgeGraph
 from .model import JMAC
 
 
-def make_args(dim=300, batch_size=1000, num_negative=25, device="cuda", **kw):
+def make_args(dim=300, batch_size=1000, num_negative=25, device="cuda", entr_matrix_free=False, **kw):
     a = dict(dim=dim, dropout=0.4, leaky_relu_w=0.05, comp_op="sub", num_gcn_layer=2, num_negative=num_negative,
              margin_align=1.0, margin_completion=5.0, batch_size=batch_size, no_name_info=False, device=device,
              pair_sample_weight=0.2, lr=1e-3,                     # train.py:57-102 defaults for the fields used here
-             neg_sampler="uniform", capture_completion=False)    # this harness' own: where the completion batches come from
+             neg_sampler="uniform", capture_completion=False,    # this harness' own: where the completion batches come from
+             entr_matrix_free=entr_matrix_free)                   # EnTr refresh from scoring.alignment_stats (no N1 x N2 matrix)
     a.update(kw)
     return types.SimpleNamespace(**a)
 
@@ -226,7 +227,8 @@ def train_epoch(model: JMAC, kgs: Dict[str, KnowledgeGraph], seeds_train: Dict[T
             test_pairs = seeds_test.get((l1, l2), links)
             new1, new2, k1, k2, feed, _ = entr.seed_enlargement_triple_transferring(
                 o1, o2, test_pairs[:, 0].tolist(), test_pairs[:, 1].tolist(), st["entropy"], 0, st["seeds"][0], tr1, tr2,
-                st["seeds"], eb1, rb1, eb2, rb2, kg1, kg2, args, generator=generator)
+                st["seeds"], eb1, rb1, eb2, rb2, kg1, kg2, args, generator=generator,
+                matrix_free=getattr(args, "entr_matrix_free", False))
             kg1.triple_keys, kg2.triple_keys = k1, k2
             kg1.transferred_triples, kg2.transferred_triples = new1, new2
             st["feeddict"] = feed

@@ -6,9 +6,12 @@
     sim_topk / get_neg   == mm + topk                                         modules/utils/util.py:31-54
     align_entropy        == first half of compute_alignment_quality           train.py:235-248
     alignment_quality    == compute_alignment_quality                         train.py:231-259
+    alignment_stats      == what seed_enlargement_triple_transferring reads of it (entropy, row / column maxima and
+                            arg-maxima of the two softmax matrices) without any N1 x N2 matrix   train.py:138-169
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -274,6 +277,94 @@ def alignment_quality(emb1: torch.Tensor, emb2: torch.Tensor, list1, list2, scal
     return entropy, row_softmax(simi, m1, m2, -1.0, scale)[0], col_softmax(simi, m1, m2, -1.0, scale)[0]
 
 
+SoftmaxStats = namedtuple("SoftmaxStats", "row_max row_arg row_sum row_ent col_max col_arg col_sum col_ent")
+
+
+def sim_softmax_stats(a: torch.Tensor, b: torch.Tensor, scale: float = 20.0, cols: bool = True) -> SoftmaxStats:
+    """Per row (and, with ``cols``, per column) of S = a @ b.T, which is never written: the maximum (bit-identical to
+    ``sim_matrix(a, b).max``), its first index (int32), sum_j e^(scale (S - max)) and the entropy of softmax(scale S).
+    ``cols=False`` leaves the four column fields None."""
+    require_device(a, b)
+    a, b = _rows16(a), _rows16(b)
+    n1, d = a.shape
+    n2 = b.shape[0]
+    if n1 == 0 or n2 == 0:
+        raise ValueError("sim_softmax_stats: empty operand")
+    dev = a.device
+
+    def vec(n, dtype=torch.float32):
+        return torch.empty(n, dtype=dtype, device=dev)
+    r = [vec(n1), vec(n1, torch.int32), vec(n1), vec(n1)]
+    c = [vec(n2), vec(n2, torch.int32), vec(n2), vec(n2)] if cols else [None] * 4
+    L = lib()
+    ws_bytes = int(L.jmac_sim_softmax_stats_workspace_bytes(n1, n2))
+    ws = workspace(ws_bytes, dev)
+    check(L.jmac_sim_softmax_stats_f32(ptr(a), d, ptr(b), d, n1, n2, d, float(scale), *[ptr(t) for t in r + c], ptr(ws), ws_bytes,
+                                       stream()), "jmac_sim_softmax_stats_f32")
+    return SoftmaxStats(*(r + c))
+
+
+def _best_with_constant(x: torch.Tensor, l: torch.Tensor, arg: torch.Tensor, index_of: torch.Tensor, c: int, first_masked: int,
+                        fill: float, scale: float):
+    """Largest softmax entry and its index for lines of the masked matrix: ``x`` / ``l`` / ``arg`` are the maximum, the sum
+    e^(scale (s - x)) and the arg-max over the line's KEPT entries (positions into ``index_of``, ascending ids), and ``c`` further
+    entries, the lowest of them at index ``first_masked``, all hold ``fill``."""
+    idx = index_of[arg.long()]
+    if c == 0:
+        return 1.0 / l, idx
+    f = torch.full_like(x, fill)
+    M = torch.maximum(x, f)
+    denom = l * torch.exp(scale * (x - M)) + c * torch.exp(scale * (f - M))
+    fm = torch.full_like(idx, first_masked)
+    idx = torch.where(x < f, fm, torch.where(x == f, torch.minimum(idx, fm), idx))     # first maximum of the masked line
+    return 1.0 / denom, idx
+
+
+def _first_missing(sorted_ids: np.ndarray, n: int) -> int:
+    """The lowest id in [0, n) that ``sorted_ids`` (ascending, distinct) does not list; n if it lists all."""
+    gap = np.nonzero(sorted_ids != np.arange(len(sorted_ids)))[0]
+    return int(gap[0]) if len(gap) else len(sorted_ids)
+
+
+def alignment_stats(emb1: torch.Tensor, emb2: torch.Tensor, list1, list2, scale: float = 20.0):
+    """What the EnTr refresh reads of compute_alignment_quality (train.py:231-259, consumer :160-169) WITHOUT its matrices:
+    ``(entropy, row_best_prob [N1], row_best [N1] int64, col_best_prob [N2], col_best [N2] int64)`` with
+    ``row_best_prob, row_best == alignment_quality(...)[1].max(1)`` and ``col_* == alignment_quality(...)[2].max(1)``.
+
+    Outside list1 x list2 the masked matrix holds the constant f = -1, so a kept row with maximum x and sum
+    l = sum e^(scale (s - x)) over its |list2| kept entries and c = N2 - |set(list2)| constant ones has
+    M = max(x, f), best probability 1 / (l e^(scale (x - M)) + c e^(scale (f - M))); a row outside list1 is all-equal:
+    1 / N2 at index 0.  Everything comes from ONE statistics launch on the n1 x n2 sub-product (``sim_softmax_stats``); a list
+    with repeated entries takes a second one, because the entropy half counts a repeated entity as often as it is listed
+    (train.py:236-237) and the masked half once.  ``list1`` / ``list2`` are host sequences."""
+    require_device(emb1, emb2)
+    dev = emb1.device
+    N1, N2 = emb1.shape[0], emb2.shape[0]
+    l1, l2 = np.asarray(list1, dtype=np.int64).reshape(-1), np.asarray(list2, dtype=np.int64).reshape(-1)
+    if not len(l1) or not len(l2):
+        raise ValueError("alignment_stats: empty list")
+    check_index_range(l1, N1, "list1")
+    check_index_range(l2, N2, "list2")
+    u1, u2 = np.unique(l1), np.unique(l2)                       # ascending: the kernel's lowest position is the lowest id
+    t1, t2 = torch.from_numpy(u1).to(dev), torch.from_numpy(u2).to(dev)
+    st = sim_softmax_stats(emb1.index_select(0, t1), emb2.index_select(0, t2), scale)
+    if len(u1) == len(l1) and len(u2) == len(l2):               # a permutation of the listed rows: the same means
+        entropy = st.row_ent.mean() + st.col_ent.mean()
+    else:
+        se = sim_softmax_stats(emb1.index_select(0, torch.from_numpy(l1).to(dev)), emb2.index_select(0, torch.from_numpy(l2).to(dev)),
+                               scale)
+        entropy = se.row_ent.mean() + se.col_ent.mean()
+    row_p = torch.full((N1,), 1.0 / N2, dtype=torch.float32, device=dev)
+    row_i = torch.zeros(N1, dtype=torch.int64, device=dev)
+    col_p = torch.full((N2,), 1.0 / N1, dtype=torch.float32, device=dev)
+    col_i = torch.zeros(N2, dtype=torch.int64, device=dev)
+    p, i = _best_with_constant(st.row_max, st.row_sum, st.row_arg, t2, N2 - len(u2), _first_missing(u2, N2), -1.0, scale)
+    row_p[t1], row_i[t1] = p, i
+    p, i = _best_with_constant(st.col_max, st.col_sum, st.col_arg, t1, N1 - len(u1), _first_missing(u1, N1), -1.0, scale)
+    col_p[t2], col_i[t2] = p, i
+    return entropy, row_p, row_i, col_p, col_i
+
+
 # ---- DBPv1 call sites (row a18): ONE embedding table on both sides ------------------------------------------------
 def get_neg_dbpv1(ILL, output_layer: torch.Tensor, k: int) -> torch.Tensor:
     """get_neg(ILL, output_layer, k), JMAC_DBPv1/modules/utils/util.py:35-58: the k most similar rows of the WHOLE
@@ -293,6 +384,16 @@ def alignment_quality_dbpv1(embedding: torch.Tensor, list1, list2, scale: float 
     p_rows, h_rows = row_softmax(simi, None, None, 0.0, scale, True, True)
     p_cols, h_cols = col_softmax(simi, None, None, 0.0, scale, True, True)
     return h_rows.mean() + h_cols.mean(), p_rows, p_cols
+
+
+def alignment_stats_dbpv1(embedding: torch.Tensor, list1, list2, scale: float = 20.0):
+    """The [T1, T2] form of ``alignment_stats`` (no mask): ``(entropy, p_rows.max(1) values [T1], indices [T1] int64,
+    p_cols.max(1) values [T2], indices [T2] int64)`` of ``alignment_quality_dbpv1`` from one statistics launch."""
+    dev = embedding.device
+    l1 = torch.as_tensor(list1, dtype=torch.long, device=dev)
+    l2 = torch.as_tensor(list2, dtype=torch.long, device=dev)
+    st = sim_softmax_stats(embedding.index_select(0, l1), embedding.index_select(0, l2), scale)
+    return (st.row_ent.mean() + st.col_ent.mean(), 1.0 / st.row_sum, st.row_arg.long(), 1.0 / st.col_sum, st.col_arg.long())
 
 
 # ---- alignment evaluation (next row f1: modules/finding/similarity.py:13-84, alignment.py:10-112) -------------
