@@ -381,6 +381,48 @@ int jmac_linkpred_rank_bf16(const jmac_link_layer_t* layers, int32_t n_layers, c
                             int32_t pred_head, const int32_t* gold, const int32_t* filt_ptr, const int32_t* filt_idx,
                             int64_t B, int64_t N, int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream);
 
+/* The known tails of every (head, relation) as a sorted CSR on the device (jmac_amd.sampling.TrueTailIndex): the filter of a
+ * whole run, built once, instead of one CSR per batch.  key[i] = h << 32 | r, strictly ascending; the tails of key i are
+ * tail_idx[tail_ptr[i] .. tail_ptr[i+1]), ascending and distinct, in the row space of the candidate table.  For head
+ * prediction the caller builds it from the triples' columns (t, r, h). */
+typedef struct {
+    const int64_t* key;        /* [n_keys] ascending (h << 32 | r) */
+    int64_t        n_keys;
+    const int32_t* tail_ptr;   /* [n_keys + 1] */
+    const int32_t* tail_idx;   /* ascending within a key */
+} jmac_tail_index_t;
+
+/* jmac_linkpred_rank_* with the filter of query b taken from the index: one wave of the query's block searches
+ * (h[b] << 32 | r[b]) in key, 64 probes per round -- 3 rounds of dependent loads for up to 262 144 keys, where a one-lane
+ * binary search takes 18 (15 at ja's 19 520 keys) -- and the block reads the range from LDS; a query whose key is absent
+ * ranks raw, and so does every query when index is NULL.  Everything after the lookup is jmac_linkpred_rank_*'s code: the
+ * ranks are the same integers as with a CSR that holds the same lists.  Workspace: jmac_linkpred_rank_workspace_bytes. */
+int jmac_linkpred_rank_indexed_f32(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                                   int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B,
+                                   int64_t N, int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream);
+int jmac_linkpred_rank_indexed_bf16(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                                    int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B,
+                                    int64_t N, int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
+/* Link-prediction top-k: the model's predictions without the [B,N] matrix.  val[b,j], idx[b,j] for j < k are the k smallest
+ * dist[b,n] over the n in [0,N) that the index does not list for (h[b], r[b]) -- EVERY listed entry is excluded, there is no
+ * gold -- in ascending distance, equal distances by ascending index.  dist is jmac_linkpred_rank_*'s single running fp32 sum
+ * over (layer, k), bit for bit: jmac_linkpred_rank_indexed_*(gold = idx[b,j]) is j + 1 for every returned entry.  A query with
+ * fewer than k unlisted candidates ends its row with idx = -1, val = +inf.  index NULL: nothing is excluded.
+ * 1 <= k <= 64 and k <= N (JMAC_EINVAL), d <= 512 (JMAC_EDIM); n_layers and the LDS limit as jmac_linkpred_rank_*.
+ * N >= 8192: a column sample is scored into the workspace, its k-th smallest unlisted distance bounds the row's, the other
+ * columns append the entries under that bound to a per-row list (integer atomics claim the slots; the list is sorted
+ * afterwards), and one block per query selects; the workspace holds no B x N buffer.  A row whose list overflows (a constant
+ * table, a huge tie) is recomputed and selected in passes: slow, exact.  N < 8192: the [B,N] scores go through the workspace.
+ * No float atomics; results do not depend on the grid or the CU count, and two calls return identical bits. */
+size_t jmac_linkpred_topk_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers, int32_t k);
+int jmac_linkpred_topk_f32(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                           int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k,
+                           float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
+int jmac_linkpred_topk_bf16(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                            int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k,
+                            float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
 /* rank[b] = 1 + #{n : score[b,n] < score[b,gold] or (== and n < gold[b])}, where entries listed in
  * the filter CSR (filt_ptr [B+1], filt_idx) other than the gold are skipped.  descending == 0: `score` is a
  * DISTANCE (the reference's predictions = -dist, sorted descending); descending != 0: `score` is a SIMILARITY

@@ -36,6 +36,11 @@ class LinkLayer(C.Structure):
     _fields_ = [("ent", vp), ("ld_ent", i64), ("rel", vp), ("ld_rel", i64), ("table", vp), ("ld_table", i64)]
 
 
+class TailIndex(C.Structure):
+    """jmac_tail_index_t"""
+    _fields_ = [("key", vp), ("n_keys", i64), ("tail_ptr", vp), ("tail_idx", vp)]
+
+
 class AggFwdJob(C.Structure):
     """jmac_agg_fwd_job_t"""
     _fields_ = [("P", vp), ("ldp", i64), ("QZ", vp), ("ldqz", i64), ("RR", vp), ("ldrr", i64), ("a_att", vp), ("col", vp), ("etype", vp),
@@ -120,6 +125,11 @@ _SIGS = {
     "jmac_linkpred_rank_workspace_bytes": (sz, [i64, i64, i32]),
     "jmac_linkpred_rank_f32": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     "jmac_linkpred_rank_bf16": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, i64, i64, i64, vp, vp, sz, vp]),
+    "jmac_linkpred_rank_indexed_f32": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp, sz, vp]),
+    "jmac_linkpred_rank_indexed_bf16": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp, sz, vp]),
+    "jmac_linkpred_topk_workspace_bytes": (sz, [i64, i64, i64, i32, i32]),
+    "jmac_linkpred_topk_f32": (C.c_int, [vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
+    "jmac_linkpred_topk_bf16": (C.c_int, [vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
     "jmac_sim_matrix_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, i64, vp]),
     "jmac_sim_topk_workspace_bytes": (sz, [i64, i64, i32]),
     "jmac_sim_topk_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, sz, vp]),

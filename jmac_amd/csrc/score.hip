@@ -2,6 +2,9 @@
 //
 //  * jmac_l1_score_f32      torch.cdist(er, all_kg_emb, p=1)            src/jmac_model.py:312
 //  * jmac_filtered_rank_f32 filter + sort + np.where ranking loop        src/validate.py:50-64
+//  * jmac_linkpred_rank_{,indexed_}*  forward_linkpred + that loop, ranks only; the filter from a per-batch CSR or from the
+//                            device-resident known-tail index                 src/jmac_model.py:302-313, src/validate.py:50-64
+//  * jmac_linkpred_topk_*   the k nearest tails the index does not list (the model's predictions; no counterpart)
 //  * jmac_sim_matrix_f32    torch.mm(ILL_vec, KG_vec.t())                modules/utils/util.py:52, train.py:239
 //  * jmac_row_topk_f32 / jmac_sim_topk_f32   sim.topk(k, dim=1)          modules/utils/util.py:53
 //  * jmac_softmax_entropy_f32, jmac_row_softmax_f32                      train.py:241-257
@@ -196,7 +199,41 @@ struct LinkRankArgs {
     void* er;                             // workspace [nl][B][dq] of TT
     float* gs;                            // workspace [B]
     int32_t* rank;                        // [B]: the counters themselves
+    // known-tail index (jmac_tail_index_t): key != nullptr replaces the per-batch CSR -- filt_ptr / filt_idx then hold the
+    // index's tail_ptr / tail_idx and query b's range is looked up under (h_b << 32 | r_b)
+    const int64_t* key;
+    int64_t n_keys;
+    // top-k (jmac_linkpred_topk_*): the tile kernel's STORE and FILTER epilogues score columns [n_off, N)
+    int2* rng;                            // workspace [B]: every query's [begin, end) in filt_idx (the prep kernel's lookup)
+    int32_t n_off;
+    float* S;                             // STORE: S[b * ldS + n - n_off] = -dist[b, n]
+    int64_t ldS;
+    const float* ntau;                    // FILTER: ntau[b * tau_stride] = -tau_b; (dist, n) with -dist >= -tau_b are appended
+    int32_t tau_stride, cap;
+    int32_t* cnt;                         // [B] entries appended (may exceed cap: that row overflowed)
+    float* cval;                          // [B, cap] -dist
+    int32_t* cidx;                        // [B, cap] n
 };
+
+// [begin, end) of query (h, r)'s tails in the index, searched by ONE WAVE (all 64 lanes call this): every round the lanes
+// probe 64 evenly spaced keys of the remaining range and a ballot picks the bracket -- 3 rounds of dependent loads for up to
+// 262 144 keys (a one-lane binary search needs 18), 6 at 2^31.  An absent key has no tails.  The result is wave-uniform.
+__device__ __forceinline__ int2 tail_range(const LinkRankArgs& a, int h, int r) {
+    const int64_t q = ((int64_t)h << 32) | (int64_t)(uint32_t)r;
+    const int lane = threadIdx.x & 63;
+    int64_t lo = 0, hi = a.n_keys;                                 // the first key >= q lies in [lo, hi]
+    while (lo < hi) {
+        const int64_t step = (hi - lo + 63) >> 6, p = lo + lane * step;
+        const bool below = p < hi && a.key[p] < q;                 // ascending keys: the lanes that see a smaller key are a prefix
+        const int c = __popcll(__ballot(below));
+        if (c == 0) break;                                         // key[lo] >= q
+        const int64_t last = lo + (int64_t)(c - 1) * step;         // the last probe below q; the next probe (if any) is not
+        hi = last + step < hi ? last + step : hi;
+        lo = last + 1;
+    }
+    if (lo < a.n_keys && a.key[lo] == q) return make_int2(a.filt_ptr[lo], a.filt_ptr[lo + 1]);
+    return make_int2(0, 0);
+}
 
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float x) {
     uint32_t u = __float_as_uint(x);
@@ -211,18 +248,26 @@ __device__ __forceinline__ void st1(bf16_t* p, float v) { *p = f32_to_bf16_rne(v
 // (the gold first, then the filter entries), LR_ROWS at a time: their table rows are staged into LDS with coalesced loads, then
 // one lane per candidate runs the SAME sequential sum the tile kernel runs (bit-identical distances: exact ties resolve by
 // index as in the materialised path); (3) rank[b] starts at 1 - #{filtered entries before the gold}
+// INDEXED: the filter range comes from the known-tail index -- wave 0 searches (h_b, r_b), the block reads the range from LDS.
+// RANK = false (top-k): only (1) and the lookup, whose range goes to a.rng[b].
 constexpr int LR_ROWS = 16;                        // at most; fewer when nl * d is large (60 KB of LDS)
-template <typename TT>
+template <typename TT, bool INDEXED, bool RANK = true>
 __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) {
     extern __shared__ float lr_sh[];                // [nl*dq] query rows (widened) + [LR_ROWS][nl*dq + 1] candidate rows
     __shared__ float gs_sh;
     __shared__ int cand[LR_ROWS];
     __shared__ int red[kBlock / 64];
+    __shared__ int2 rng_sh;
     const int b = blockIdx.x, d = a.d, dq = a.dq, W = a.nl * dq, WS = W + 1;
     float* const erow = lr_sh;
     float* const crow = lr_sh + W;
-    const int hb = a.h[b], rb = a.r[b], g = a.gold[b];
+    const int hb = a.h[b], rb = a.r[b], g = RANK ? a.gold[b] : 0;
     TT* const er = static_cast<TT*>(a.er);
+    if constexpr (INDEXED)
+        if (threadIdx.x < 64) {                     // wave 0 looks the range up while the others start on the query rows
+            const int2 rg = tail_range(a, hb, rb);
+            if (threadIdx.x == 0) rng_sh = rg;
+        }
     for (int l = 0; l < a.nl; ++l)
         for (int k = threadIdx.x; k < dq; k += kBlock) {
             float v = 0.f;
@@ -231,7 +276,17 @@ __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) 
             st1(dst, v);
             erow[l * dq + k] = ld1(dst);            // what the tile kernel will read back (bf16: rounded)
         }
-    const int f0 = a.filt_ptr ? a.filt_ptr[b] : 0, f1 = a.filt_ptr ? a.filt_ptr[b + 1] : 0;
+    int f0, f1;
+    if constexpr (INDEXED) {
+        __syncthreads();
+        f0 = rng_sh.x, f1 = rng_sh.y;
+    } else {
+        f0 = a.filt_ptr ? a.filt_ptr[b] : 0, f1 = a.filt_ptr ? a.filt_ptr[b + 1] : 0;
+    }
+    if constexpr (!RANK) {
+        if (threadIdx.x == 0) a.rng[b] = make_int2(f0, f1);
+        return;
+    }
     const int n_list = 1 + (f1 - f0);               // entry 0 = the gold
     float gs = 0.f;
     int cnt = 0;
@@ -291,15 +346,21 @@ __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) 
     }
 }
 
-// the L1 score tile kernel over the concatenated (layer, k) axis; epilogue: count the entries that rank before the gold
-template <typename TT, bool VEC>
+// the L1 score tile kernel over the concatenated (layer, k) axis.  One slab loop, three epilogues:
+//   LR_COUNT   count the entries that rank before the gold                                   (jmac_linkpred_rank_*)
+//   LR_STORE   S[b, n - n_off] = -dist[b, n]: the column sample (or the whole narrow matrix)  (jmac_linkpred_topk_*)
+//   LR_FILTER  append (-dist, n) where dist <= tau_b to row b's candidate list; the 16 lanes of a row claim their slots with
+//              ONE integer atomic (list order varies from run to run; the select kernel sorts, so the results do not)
+// STORE and FILTER cover columns [n_off, N).
+enum { LR_COUNT = 0, LR_STORE = 1, LR_FILTER = 2 };
+template <typename TT, bool VEC, int EPI = LR_COUNT>
 __global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) {
     __shared__ __attribute__((aligned(16))) float As[2][L1_K][L1_LD];
     __shared__ __attribute__((aligned(16))) float Bs[2][L1_K][L1_LD];
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
     const int B = a.B, N = a.N, d = a.d;
-    const int b0 = blockIdx.y * L1_T, n0 = blockIdx.x * L1_T;
+    const int b0 = blockIdx.y * L1_T, n0 = (EPI == LR_COUNT ? 0 : a.n_off) + blockIdx.x * L1_T;
     const int lrow = tid >> 2, lk = (tid & 3) * 4;
     const int64_t arow = b0 + lrow, brow = n0 + lrow;
     float acc[4][4];
@@ -364,6 +425,59 @@ __global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) 
             sstore(Bs[cur ^ 1], rb, k1, brow < N);
         }
         __syncthreads();
+    }
+    if constexpr (EPI == LR_STORE) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + ty * 4 + i;
+            if (b >= B) continue;
+            const int n = n0 + tx * 4;
+            float* o = a.S + (int64_t)b * a.ldS + (n - a.n_off);
+            if (n + 3 < N && (a.ldS % 4 == 0) && (a.n_off % 4 == 0)) st4(o, make_float4(-acc[i][0], -acc[i][1], -acc[i][2], -acc[i][3]));
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (n + j < N) o[j] = -acc[i][j];
+            }
+        }
+        return;
+    }
+    if constexpr (EPI == LR_FILTER) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + ty * 4 + i;
+            const bool row_ok = b < B;
+            const float nt = row_ok ? a.ntau[(int64_t)b * a.tau_stride] : INFINITY;
+            bool pass[4];
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                pass[j] = row_ok && n0 + tx * 4 + j < N && -acc[i][j] >= nt;
+                c += pass[j] ? 1 : 0;
+            }
+            if (!__any(c)) continue;                          // wave-uniform: most tiles append nothing
+            int inc = c;                                      // inclusive prefix over the row's 16 lanes
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                const int t = __shfl_up(inc, o, 16);
+                if (tx >= o) inc += t;
+            }
+            const int tot = __shfl(inc, 15, 16);
+            int base = 0;
+            if (tx == 0 && tot) base = atomicAdd(a.cnt + b, tot);
+            base = __shfl(base, 0, 16);
+            int slot = base + inc - c;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (pass[j]) {
+                    if (slot < a.cap) {
+                        a.cval[(int64_t)b * a.cap + slot] = -acc[i][j];
+                        a.cidx[(int64_t)b * a.cap + slot] = n0 + tx * 4 + j;
+                    }
+                    ++slot;
+                }
+        }
+        return;
     }
     // count: 4 rows x 4 columns per thread; the 16 threads of a row (tx = 0..15: consecutive lanes) are summed with DPP
 #pragma unroll
@@ -1449,6 +1563,204 @@ __global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
+// link-prediction top-k (jmac_linkpred_topk_*): the k nearest unlisted candidates of every query.  Scores travel NEGATED
+// (-dist), so "k smallest distances, lower index first" is the k largest with row_topk_kernel's tie rule.
+// ------------------------------------------------------------------------------------------------
+// one block per query: its listed tails among the stored columns [0, ncols) -> -inf (never selected before an unlisted one)
+__global__ __launch_bounds__(kBlock) void link_mask_kernel(float* __restrict__ S, int64_t ldS, int ncols, const int2* __restrict__ rng,
+                                                           const int32_t* __restrict__ tail_idx) {
+    const int b = blockIdx.x;
+    const int2 r = rng[b];
+    for (int f = r.x + threadIdx.x; f < r.y; f += kBlock) {
+        const int n = tail_idx[f];
+        if (n >= 0 && n < ncols) S[(int64_t)b * ldS + n] = -INFINITY;
+    }
+}
+
+// row_topk_kernel's (-dist, index) -> (dist, index); a masked entry (fewer than k unlisted candidates) -> (+inf, -1)
+__global__ __launch_bounds__(kBlock) void link_topk_finish_kernel(float* __restrict__ val, int32_t* __restrict__ idx, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float v = val[i];
+    if (v == -INFINITY) {
+        val[i] = INFINITY;
+        idx[i] = -1;
+    } else {
+        val[i] = v == 0.f ? 0.f : -v;
+    }
+}
+
+__device__ __forceinline__ bool tail_listed(const int32_t* __restrict__ tail_idx, int f0, int f1, int n) {
+    while (f0 < f1) {
+        const int mid = (f0 + f1) >> 1;
+        const int t = tail_idx[mid];
+        if (t == n) return true;
+        if (t < n) f0 = mid + 1;
+        else f1 = mid;
+    }
+    return false;
+}
+
+// one block per query: the k best of (candidate list + the sample's k best), listed candidates dropped (the sample's were
+// masked before its selection).  Every unlisted n with dist <= tau_b is in that set and at least k of them exist (tau_b is
+// the k-th smallest unlisted SAMPLE distance), so its k best are the row's; a sample entry tied with tau_b outside the
+// sample's k best has k entries before it already.
+// A row whose list overflowed (a constant table, a huge tie, or fewer than k unlisted sample entries: tau_b = +inf) recomputes
+// its N distances with the prep kernel's sequential sum -- the tile kernel's bits -- one lane per candidate, once per pass of
+// the two-pass selection and once per arg-max round if the top bin overflows too.  Slow by design, exact.
+template <typename TT>
+__global__ __launch_bounds__(kBlock) void link_select_kernel(LinkRankArgs a, int k, const float* __restrict__ sval,
+                                                             const int32_t* __restrict__ sidx, float* __restrict__ val,
+                                                             int32_t* __restrict__ idx) {
+    extern __shared__ float ls_sh[];                           // [nl * dq] the query's rows (overflow path)
+    __shared__ int hist[TK_BINS];
+    __shared__ unsigned long long skey[TK_CAP];
+    __shared__ int sh_bin, sh_above, sh_cnt;
+    __shared__ float wv[kBlock / 64];
+    __shared__ int wi[kBlock / 64];
+    __shared__ float pick_v;
+    __shared__ int pick_i;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int2 r = a.rng[b];
+    const int32_t* const tails = a.filt_idx;
+    float* const ov = val + (int64_t)b * k;
+    int32_t* const oi = idx + (int64_t)b * k;
+    auto pack = [](float negd, int n) { return ((unsigned long long)tk_key(negd) << 32) | (unsigned)(~n); };
+    auto emit = [&](int c, unsigned long long e) {
+        if (e == 0ull) {                                       // padding: fewer than k unlisted candidates
+            oi[c] = -1;
+            ov[c] = INFINITY;
+            return;
+        }
+        oi[c] = (int)~(unsigned)(e & 0xffffffffull);
+        const unsigned key = (unsigned)(e >> 32);              // invert tk_key
+        const float v = __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+        ov[c] = v == 0.f ? 0.f : -v;
+    };
+    // skey[0, Cn) -> descending bitonic sort (cand_select_kernel's) -> the first k
+    auto select = [&](int Cn) {
+        int P = 64;
+        while (P < Cn) P <<= 1;
+        for (int c = Cn + tid; c < P; c += kBlock) skey[c] = 0ull;
+        __syncthreads();
+        for (int size = 2; size <= P; size <<= 1)
+            for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                for (int t = tid; t < (P >> 1); t += kBlock) {
+                    const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                    const bool desc = (lo & size) == 0;
+                    const unsigned long long x = skey[lo], y = skey[hi];
+                    if ((x < y) == desc) {
+                        skey[lo] = y;
+                        skey[hi] = x;
+                    }
+                }
+                __syncthreads();
+            }
+        for (int c = tid; c < k; c += kBlock) emit(c, skey[c]);
+    };
+    const int C = a.cnt[b];
+    if (C + k <= a.cap) {                                      // the normal case (cap <= TK_CAP)
+        for (int c = tid; c < C; c += kBlock) {
+            const int n = a.cidx[(int64_t)b * a.cap + c];
+            skey[c] = tail_listed(tails, r.x, r.y, n) ? 0ull : pack(a.cval[(int64_t)b * a.cap + c], n);
+        }
+        for (int c = tid; c < k; c += kBlock) {
+            const float v = sval[(int64_t)b * k + c];
+            skey[C + c] = v == -INFINITY ? 0ull : pack(v, sidx[(int64_t)b * k + c]);
+        }
+        __syncthreads();
+        select(C + k);
+        return;
+    }
+    // ---- overflow: two-pass selection over recomputed distances
+    const int d = a.d, dq = a.dq, W = a.nl * dq;
+    for (int i = tid; i < W; i += kBlock) {
+        const int l = i / dq, q = i - l * dq;
+        ls_sh[i] = ld1(static_cast<const TT*>(a.er) + ((int64_t)l * a.B + b) * dq + q);
+    }
+    for (int i = tid; i < TK_BINS; i += kBlock) hist[i] = 0;
+    if (tid == 0) sh_cnt = 0;
+    __syncthreads();
+    auto for_each_unlisted = [&](auto f) {                      // f(n, -dist[b, n]) for every n in [0, N) the index does not list
+        for (int n = tid; n < a.N; n += kBlock) {
+            if (tail_listed(tails, r.x, r.y, n)) continue;
+            float acc = 0.f;
+            for (int l = 0; l < a.nl; ++l) {
+                const TT* row = static_cast<const TT*>(a.tab[l]) + (int64_t)n * a.ld_tab[l];
+                const float* e = ls_sh + l * dq;
+                for (int q = 0; q < d; ++q) acc = add_absdiff(acc, e[q], ld1(row + q));
+            }
+            f(n, -acc);
+        }
+    };
+    for_each_unlisted([&](int n, float v) { atomicAdd(&hist[tk_key(v) >> 20], 1); });
+    __syncthreads();
+    if (tid == 0) {                                            // (rare path: a serial scan from the top bin is fine)
+        int above = 0, bin = TK_BINS - 1;
+        for (; bin > 0; --bin) {
+            if (above + hist[bin] >= k) break;
+            above += hist[bin];
+        }
+        sh_bin = bin;
+        sh_above = above;
+    }
+    __syncthreads();
+    const int bstar = sh_bin;
+    const int C2 = sh_above + hist[bstar];                     // < k: the row has fewer than k unlisted candidates (bin 0 reached)
+    if (C2 <= TK_CAP) {
+        for_each_unlisted([&](int n, float v) {
+            if ((int)(tk_key(v) >> 20) >= bstar) skey[atomicAdd(&sh_cnt, 1)] = pack(v, n);
+        });
+        __syncthreads();
+        select(C2);
+        return;
+    }
+    // ---- even the top bin overflows (e.g. a constant table): k rounds of arg-max after the previous pick
+    float pv = INFINITY;
+    int pi = -1;
+    for (int rr = 0; rr < k; ++rr) {
+        float bv = -INFINITY;
+        int bi = INT32_MAX;
+        for_each_unlisted([&](int n, float v) {
+            const bool after = (v < pv) || (v == pv && n > pi);
+            const bool better = (v > bv) || (v == bv && n < bi);
+            if (after && better) {
+                bv = v;
+                bi = n;
+            }
+        });
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float xv = __shfl_xor(bv, o, 64);
+            const int xi = __shfl_xor(bi, o, 64);
+            if (xv > bv || (xv == bv && xi < bi)) {
+                bv = xv;
+                bi = xi;
+            }
+        }
+        if ((tid & 63) == 0) {
+            wv[tid >> 6] = bv;
+            wi[tid >> 6] = bi;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < kBlock / 64; ++w)
+                if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) {
+                    bv = wv[w];
+                    bi = wi[w];
+                }
+            pick_v = bv;
+            pick_i = bi;
+            ov[rr] = bi == INT32_MAX ? INFINITY : (bv == 0.f ? 0.f : -bv);
+            oi[rr] = bi == INT32_MAX ? -1 : bi;
+        }
+        __syncthreads();
+        pv = pick_v;
+        pi = pick_i;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // column top-k values (CSLS column term, similarity.py:58-78 on the transposed matrix) without transposing:
 // one lane per column (a wave reads 256 contiguous bytes of a row), rows split over the 4 waves of a block and over
 // gridDim.y row ranges; every (block, wave) keeps its column's k largest values in registers (branch-free bubble
@@ -1930,11 +2242,12 @@ int launch_topk(const float* S, int64_t lds, int64_t L, int64_t N, int32_t k, fl
 
 template <typename TT>
 static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
-                            const int32_t* gold, const int32_t* filt_ptr, const int32_t* filt_idx, int64_t B, int64_t N, int64_t d,
-                            int32_t* rank, void* ws, size_t ws_bytes, hipStream_t st) {
+                            const int32_t* gold, const int32_t* filt_ptr, const int32_t* filt_idx, const jmac_tail_index_t* index,
+                            int64_t B, int64_t N, int64_t d, int32_t* rank, void* ws, size_t ws_bytes, hipStream_t st) {
     if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_layers > LR_MAX_LAYERS) return JMAC_EINVAL;
     if (B == 0) return JMAC_OK;
     if (!layers || !h || !r || !gold || !rank || (filt_ptr && !filt_idx)) return JMAC_EINVAL;
+    if (index && (index->n_keys < 0 || index->n_keys >= INT32_MAX || !index->key || !index->tail_ptr || !index->tail_idx)) return JMAC_EINVAL;
     if (B >= INT32_MAX || N >= INT32_MAX || d > 512) return JMAC_ERANGE;
     if (!ws || ws_bytes < jmac_linkpred_rank_workspace_bytes(B, d, n_layers)) return JMAC_EWORKSPACE;
     LinkRankArgs a{};
@@ -1949,6 +2262,9 @@ static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, c
     }
     a.sign = pred_head ? -1.f : 1.f;
     a.h = h; a.r = r; a.gold = gold; a.filt_ptr = filt_ptr; a.filt_idx = filt_idx;
+    if (index) {
+        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
+    }
     a.gs = (float*)ws;
     a.er = (char*)ws + align_up((size_t)B * 4);
     a.rank = rank;
@@ -1957,7 +2273,8 @@ static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, c
     if (rows < 1) return JMAC_ERANGE;
     a.rows = (int32_t)(rows < LR_ROWS ? rows : LR_ROWS);
     const size_t shm = (size_t)(W + a.rows * (W + 1)) * sizeof(float);
-    hipLaunchKernelGGL((link_rank_prep_kernel<TT>), dim3((unsigned)B), dim3(kBlock), shm, st, a);
+    if (index) hipLaunchKernelGGL((link_rank_prep_kernel<TT, true>), dim3((unsigned)B), dim3(kBlock), shm, st, a);
+    else hipLaunchKernelGGL((link_rank_prep_kernel<TT, false>), dim3((unsigned)B), dim3(kBlock), shm, st, a);
     dim3 grid((unsigned)((N + L1_T - 1) / L1_T), (unsigned)((B + L1_T - 1) / L1_T));
     if (vec) hipLaunchKernelGGL((link_rank_tile_kernel<TT, true>), grid, dim3(kBlock), 0, st, a);
     else hipLaunchKernelGGL((link_rank_tile_kernel<TT, false>), grid, dim3(kBlock), 0, st, a);
@@ -2024,14 +2341,28 @@ size_t jmac_linkpred_rank_workspace_bytes(int64_t B, int64_t d, int32_t n_layers
 int jmac_linkpred_rank_f32(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
                            int32_t pred_head, const int32_t* gold, const int32_t* filt_ptr, const int32_t* filt_idx, int64_t B,
                            int64_t N, int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    return launch_link_rank<float>(layers, n_layers, h, r, pred_head, gold, filt_ptr, filt_idx, B, N, d, rank, ws, ws_bytes,
+    return launch_link_rank<float>(layers, n_layers, h, r, pred_head, gold, filt_ptr, filt_idx, nullptr, B, N, d, rank, ws, ws_bytes,
                                    (hipStream_t)stream);
 }
 
 int jmac_linkpred_rank_bf16(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
                             int32_t pred_head, const int32_t* gold, const int32_t* filt_ptr, const int32_t* filt_idx, int64_t B,
                             int64_t N, int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    return launch_link_rank<bf16_t>(layers, n_layers, h, r, pred_head, gold, filt_ptr, filt_idx, B, N, d, rank, ws, ws_bytes,
+    return launch_link_rank<bf16_t>(layers, n_layers, h, r, pred_head, gold, filt_ptr, filt_idx, nullptr, B, N, d, rank, ws, ws_bytes,
+                                    (hipStream_t)stream);
+}
+
+int jmac_linkpred_rank_indexed_f32(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                                   int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N,
+                                   int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return launch_link_rank<float>(layers, n_layers, h, r, pred_head, gold, nullptr, nullptr, index, B, N, d, rank, ws, ws_bytes,
+                                   (hipStream_t)stream);
+}
+
+int jmac_linkpred_rank_indexed_bf16(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                                    int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N,
+                                    int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return launch_link_rank<bf16_t>(layers, n_layers, h, r, pred_head, gold, nullptr, nullptr, index, B, N, d, rank, ws, ws_bytes,
                                     (hipStream_t)stream);
 }
 
@@ -2114,6 +2445,122 @@ int jmac_sim_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, 
     hipLaunchKernelGGL(cand_select_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt, f.cval,
                        f.cidx, ST_CAP, val0, (const int32_t*)(wb + w.idx0), val, idx);
     return (int)hipGetLastError();
+}
+
+}  // extern "C"
+
+// ---- link-prediction top-k: jmac_sim_topk_f32's scheme around the L1 tile loop -------------------------------------------
+struct LtWs { size_t er, rng, s0, val0, idx0, cnt, cval, cidx, total; int64_t ldS; };
+static LtWs lt_layout(int64_t B, int64_t N, int64_t d, int64_t nl, int64_t k) {
+    LtWs w{};
+    size_t off = 0;
+    w.er = off;  off += align_up((size_t)nl * (size_t)B * (size_t)((d + 3) / 4 * 4) * 4);
+    w.rng = off; off += align_up((size_t)B * 8);
+    if (!st_fused(N, k)) {                                    // narrow tables: the [B, N] scores, then the row pass
+        w.ldS = (N + 3) / 4 * 4;
+        w.s0 = off; off += align_up((size_t)B * (size_t)w.ldS * 4);
+    } else {                                                  // sample scores + candidate lists: no B x N buffer
+        w.ldS = st_sample(N);
+        w.s0 = off;   off += align_up((size_t)B * (size_t)w.ldS * 4);
+        w.val0 = off; off += align_up((size_t)B * (size_t)k * 4);
+        w.idx0 = off; off += align_up((size_t)B * (size_t)k * 4);
+        w.cnt = off;  off += align_up((size_t)B * 4);
+        w.cval = off; off += align_up((size_t)B * ST_CAP * 4);
+        w.cidx = off; off += align_up((size_t)B * ST_CAP * 4);
+    }
+    w.total = off + 256;
+    return w;
+}
+
+template <typename TT, int EPI>
+static void launch_link_tile(const LinkRankArgs& a, bool vec, int64_t ncols, hipStream_t st) {
+    dim3 grid((unsigned)((ncols + L1_T - 1) / L1_T), (unsigned)((a.B + L1_T - 1) / L1_T));
+    if (vec) hipLaunchKernelGGL((link_rank_tile_kernel<TT, true, EPI>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((link_rank_tile_kernel<TT, false, EPI>), grid, dim3(kBlock), 0, st, a);
+}
+
+template <typename TT>
+static int launch_link_topk(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
+                            const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k, float* val, int32_t* idx,
+                            void* ws, size_t ws_bytes, hipStream_t st) {
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_layers > LR_MAX_LAYERS) return JMAC_EINVAL;
+    if (k <= 0 || k > ST_KMAX || k > N) return JMAC_EINVAL;
+    if (d > 512) return JMAC_EDIM;
+    if (B == 0) return JMAC_OK;
+    if (!layers || !h || !r || !val || !idx) return JMAC_EINVAL;
+    if (index && (index->n_keys < 0 || index->n_keys >= INT32_MAX || !index->key || !index->tail_ptr || !index->tail_idx)) return JMAC_EINVAL;
+    if (B >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_linkpred_topk_workspace_bytes(B, N, d, n_layers, k)) return JMAC_EWORKSPACE;
+    LinkRankArgs a{};
+    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
+    bool vec = d % 4 == 0;
+    for (int l = 0; l < n_layers; ++l) {
+        if (!layers[l].ent || !layers[l].rel || !layers[l].table) return JMAC_EINVAL;
+        a.ent[l] = layers[l].ent; a.rel[l] = layers[l].rel; a.tab[l] = layers[l].table;
+        a.ld_ent[l] = layers[l].ld_ent; a.ld_rel[l] = layers[l].ld_rel; a.ld_tab[l] = layers[l].ld_table;
+        if (a.ld_tab[l] % 4 || ((uintptr_t)a.tab[l] % (4 * sizeof(TT)))) vec = false;
+    }
+    const int64_t W = (int64_t)n_layers * a.dq;
+    if (W + 1 > 60 * 1024 / 4 - W) return JMAC_ERANGE;         // jmac_linkpred_rank_*'s LDS limit
+    a.sign = pred_head ? -1.f : 1.f;
+    a.h = h; a.r = r;
+    const LtWs w = lt_layout(B, N, d, n_layers, k);
+    char* wb = (char*)ws;
+    a.er = wb + w.er;
+    a.rng = (int2*)(wb + w.rng);
+    float* S0 = (float*)(wb + w.s0);
+    // 1. the query rows and every query's range in the index
+    if (index) {
+        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
+        hipLaunchKernelGGL((link_rank_prep_kernel<TT, true, false>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a);
+    } else {
+        hipLaunchKernelGGL((link_rank_prep_kernel<TT, false, false>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a);
+    }
+    a.S = S0; a.ldS = w.ldS; a.n_off = 0;
+    if (!st_fused(N, k)) {
+        launch_link_tile<TT, LR_STORE>(a, vec, N, st);
+        if (index) hipLaunchKernelGGL(link_mask_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, S0, w.ldS, (int)N, a.rng, a.filt_idx);
+        if (int rc = launch_topk(S0, w.ldS, B, N, k, val, idx, st)) return rc;
+        hipLaunchKernelGGL(link_topk_finish_kernel, dim3((unsigned)((B * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, val, idx, B * k);
+        return (int)hipGetLastError();
+    }
+    // 2. tau_b = k-th smallest unlisted distance among the first Ns columns: an upper bound of the row's final k-th distance
+    const int64_t Ns = w.ldS;
+    float* val0 = (float*)(wb + w.val0);
+    int32_t* idx0 = (int32_t*)(wb + w.idx0);
+    LinkRankArgs as = a;
+    as.N = (int32_t)Ns;
+    launch_link_tile<TT, LR_STORE>(as, vec, Ns, st);
+    if (index) hipLaunchKernelGGL(link_mask_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, S0, Ns, (int)Ns, a.rng, a.filt_idx);
+    if (int rc = launch_topk(S0, Ns, B, Ns, k, val0, idx0, st)) return rc;
+    // 3. the remaining columns with the filtering epilogue: candidates instead of the matrix
+    a.ntau = val0 + (k - 1); a.tau_stride = k; a.cap = ST_CAP;
+    a.cnt = (int32_t*)(wb + w.cnt); a.cval = (float*)(wb + w.cval); a.cidx = (int32_t*)(wb + w.cidx);
+    a.n_off = (int32_t)Ns;
+    if (hipMemsetAsync(a.cnt, 0, (size_t)B * 4, st) != hipSuccess) return (int)hipGetLastError();
+    launch_link_tile<TT, LR_FILTER>(a, vec, N - Ns, st);
+    // 4. the k best unlisted of every candidate list (+ the sample's k best)
+    hipLaunchKernelGGL((link_select_kernel<TT>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a, (int)k, val0, idx0, val, idx);
+    return (int)hipGetLastError();
+}
+
+extern "C" {
+
+size_t jmac_linkpred_topk_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers, int32_t k) {
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || k <= 0) return 0;
+    return lt_layout(B, N, d, n_layers, k).total;
+}
+
+int jmac_linkpred_topk_f32(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
+                           const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k, float* val, int32_t* idx,
+                           void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return launch_link_topk<float>(layers, n_layers, h, r, pred_head, index, B, N, d, k, val, idx, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int jmac_linkpred_topk_bf16(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
+                            const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k, float* val, int32_t* idx,
+                            void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return launch_link_topk<bf16_t>(layers, n_layers, h, r, pred_head, index, B, N, d, k, val, idx, ws, ws_bytes, (hipStream_t)stream);
 }
 
 size_t jmac_softmax_entropy_workspace_bytes(int64_t n1, int64_t n2) {

@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import entr, scoring
-from .sampling import CompletionSampler
+from .sampling import CompletionSampler, TrueTailIndex
 from .data import KnowledgeGraph
 from .model import JMAC
 
@@ -178,13 +178,27 @@ def train_alignment_component(model: JMAC, opt, ei1, et1, ei2, et2, feeddict):
     return float(loss.detach())
 
 
+def _true_tail_index(kg: KnowledgeGraph, device):
+    """``kg.true_tail`` as a device index, built once and kept on the KG object; rebuilt when the dictionary object or the
+    device changes."""
+    if not kg.true_tail:                                   # nothing known: every query ranks raw
+        return None
+    device = torch.device(device)
+    hit = getattr(kg, "_true_tail_index", None)
+    if hit is None or hit[0] is not kg.true_tail or hit[1] != device:
+        hit = (kg.true_tail, device, TrueTailIndex.from_dict(kg.true_tail, device))
+        kg._true_tail_index = hit
+    return hit[2]
+
+
 @torch.no_grad()
 def evaluate_completion(model: JMAC, kg: KnowledgeGraph, ei, et, args, split="val", filtered=True, fused=True, eval_batch=None):
     """CompletionEvaluator.test (src/validate.py:22-80) with the encoder run once instead of once per batch.
     The reference scores 1 000 queries at a time (``args.batch_size``) because it materialises their [B, N] distance matrix.  The
     fused path has no matrix and a query's rank does not depend on what else is in its call, so it takes ``eval_batch`` queries
     per call -- default: up to 16 384, i.e. a whole DBP-5L split at once (the per-call query preparation and the last partial
-    round of tiles are paid once); the materialised path keeps the reference's batches."""
+    round of tiles are paid once); the materialised path keeps the reference's batches.  The fused path's filter is the KG's
+    ``TrueTailIndex`` on the device (no per-query host work); the materialised path packs the reference's per-batch lists."""
     model.eval()
     data = {"val": kg.val_data, "test": kg.test_data, "train": kg.train_data}[split]
     eb, rb = [kg.entity_id_base, kg.upper_entity_base], [kg.relation_id_base, kg.upper_relation_base]
@@ -193,13 +207,14 @@ def evaluate_completion(model: JMAC, kg: KnowledgeGraph, ei, et, args, split="va
     step = int(eval_batch or (16384 if fused else args.batch_size))
     for s in range(0, len(data), step):
         b = data[s:s + step]
-        h, r, t = b[:, 0].tolist(), b[:, 1].tolist(), b[:, 2].tolist()
-        fp = fi = None
-        if filtered:
-            fp, fi = scoring.build_filter_csr(h, r, kg.true_tail, ei.device)
-        if fused:       # ranks without the [B, N] matrix
-            ranks.append(model.linkpred_ranks(h, r, t, ei, et, eb, rb, fp, fi, cached=cached))
+        if fused:       # ranks without the [B, N] matrix; the filter is looked up in the KG's known-tail index on the device
+            index = _true_tail_index(kg, ei.device) if filtered else None
+            ranks.append(model.linkpred_ranks(b[:, 0], b[:, 1], b[:, 2], ei, et, eb, rb, cached=cached, index=index))
         else:           # the reference's two steps: forward_linkpred, then the ranking loop
+            h, r, t = b[:, 0].tolist(), b[:, 1].tolist(), b[:, 2].tolist()
+            fp = fi = None
+            if filtered:
+                fp, fi = scoring.build_filter_csr(h, r, kg.true_tail, ei.device)
             dist = model.forward_linkpred(h, r, ei, et, range(kg.num_entity), eb, rb, cached=cached)
             ranks.append(scoring.filtered_rank(dist, torch.as_tensor(t, dtype=torch.int32, device=dist.device), fp, fi))
     rk = torch.cat(ranks).double()

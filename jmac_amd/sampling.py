@@ -23,10 +23,14 @@ from ._lib import check, lib, mark_index_range, ptr, require_device, stream
 class TrueTailIndex:
     """``(h, r) -> sorted distinct tails`` of a triple list (what ``data.true_tail_dict`` returns as a dictionary) as a CSR:
     ``keys`` int64 [nk, 2] in lexicographic order, ``tail_ptr`` int32 [nk + 1], ``tail_idx`` int32, and ``key_of_triple``
-    int32 [T]: the CSR row that holds triple i's ``(h, r)``."""
+    int32 [T]: the CSR row that holds triple i's ``(h, r)`` (None for an index built ``from_dict``: only the sampler reads it).
+    ``key_code`` int64 [nk] = ``h << 32 | r``: strictly ascending (the same order, ids < 2^31) -- what the link-prediction
+    kernels binary-search (``jmac_tail_index_t``: scoring.linkpred_ranks / linkpred_topk with ``index=``).  Ids are rows of the
+    candidate table, i.e. KG-local.  For head prediction build the index from the triples' columns ``[2, 1, 0]``."""
 
-    def __init__(self, keys, tail_ptr, tail_idx, key_of_triple):
+    def __init__(self, keys, tail_ptr, tail_idx, key_of_triple=None):
         self.keys, self.tail_ptr, self.tail_idx, self.key_of_triple = keys, tail_ptr, tail_idx, key_of_triple
+        self.key_code = ((keys[:, 0] << 32) | keys[:, 1]).contiguous()
 
     @classmethod
     def from_triples(cls, triples, device) -> "TrueTailIndex":
@@ -44,6 +48,31 @@ class TrueTailIndex:
         tail_ptr[1:] = torch.cumsum(counts, 0)
         keys = torch.stack((torch.div(hr, nrel, rounding_mode="floor"), hr % nrel), 1)
         return cls(keys, tail_ptr.to(torch.int32), (pair % nent).to(torch.int32), key_of_triple.to(torch.int32))
+
+    @classmethod
+    def from_dict(cls, true_tail, device) -> "TrueTailIndex":
+        """The same CSR from a ``{(h, r): tails}`` dictionary (``data.true_tail_dict``, ``KnowledgeGraph.true_tail``):
+        ``from_dict(true_tail_dict(t), dev)`` equals ``from_triples(t, dev)`` field by field (``key_of_triple`` aside)."""
+        if not len(true_tail):
+            raise ValueError("TrueTailIndex: empty dictionary")
+        items = sorted(true_tail.items(), key=lambda kv: (int(kv[0][0]), int(kv[0][1])))
+        keys = np.array([k for k, _ in items], dtype=np.int64).reshape(-1, 2)
+        lens = np.fromiter((len(v) for _, v in items), dtype=np.int64, count=len(items))
+        flat = (np.concatenate([np.asarray(v, dtype=np.int64).reshape(-1) for _, v in items]) if lens.sum()
+                else np.zeros(0, dtype=np.int64))
+        if len(flat) >= 1 << 31 or keys.min() < 0 or keys.max() >= 1 << 31 or (len(flat) and (flat.min() < 0 or flat.max() >= 1 << 31)):
+            raise ValueError("TrueTailIndex: ids must lie in [0, 2^31) and the lists must hold fewer than 2^31 tails")
+        nent = int(flat.max()) + 1 if len(flat) else 1
+        pair = np.unique(np.repeat(np.arange(len(items), dtype=np.int64), lens) * nent + flat)     # sorted: by key, then tail
+        tail_ptr = np.zeros(len(items) + 1, dtype=np.int64)
+        tail_ptr[1:] = np.cumsum(np.bincount(pair // nent, minlength=len(items)))
+        return cls(torch.from_numpy(keys).to(device), torch.from_numpy(tail_ptr.astype(np.int32)).to(device),
+                   torch.from_numpy((pair % nent).astype(np.int32)).to(device), None)
+
+    def c_struct(self):
+        """``jmac_tail_index_t`` over this index's device buffers (keep the index alive while a launch reads it)."""
+        from ._lib import TailIndex
+        return TailIndex(ptr(self.key_code), len(self.key_code), ptr(self.tail_ptr), ptr(self.tail_idx))
 
     def longest(self) -> int:
         p = self.tail_ptr

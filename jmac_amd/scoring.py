@@ -68,21 +68,14 @@ def linkpred_dist(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequence
     return dist
 
 
-def linkpred_ranks(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequence[torch.Tensor], e_index, r_index, gold,
-                   filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
-                   pred_head: bool = False, table_dtype=torch.float32) -> torch.Tensor:
-    """Filtered ranks of the gold tails -- ``filtered_rank(linkpred_dist(...), gold, filt_ptr, filt_idx)`` without the
-    [B, N] distance matrix (forward_linkpred src/jmac_model.py:302-313 + the ranking loop of src/validate.py:50-64, i.e. what
-    CompletionEvaluator.test needs).  The distance of a candidate is one running fp32 sum over (layer, k) where the
-    materialised path rounds once more per layer: same rank unless the gold is tied with a neighbour at fp32 rounding."""
+def _link_layers(comp_layers, comp_rel_layers, bf16: bool):
+    """(jmac_link_layer_t array, tensors to keep alive, N, d) of the (entity table, relation table) layers."""
     from ._lib import LinkLayer
     require_device(*comp_layers, *comp_rel_layers)
     nl = len(comp_layers)
     if nl != len(comp_rel_layers) or not 1 <= nl <= 4:
         raise ValueError("1..4 layers of (entity table, relation table)")
-    dev = comp_layers[0].device
     N, d = comp_layers[0].shape
-    bf16 = table_dtype == torch.bfloat16
     keep, arr = [], (LinkLayer * nl)()
     for l, (ent, rel) in enumerate(zip(comp_layers, comp_rel_layers)):
         if ent.shape != (N, d) or rel.shape[1] != d:
@@ -91,12 +84,47 @@ def linkpred_ranks(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequenc
         tab = _rows16(ent.to(torch.bfloat16), True) if bf16 else ent
         keep += [ent, rel, tab]
         arr[l] = LinkLayer(ptr(ent), ent.stride(0), ptr(rel), rel.stride(0), ptr(tab), tab.stride(0))
-    check_index_range(e_index, N, "e_index")
-    check_index_range(r_index, comp_rel_layers[0].shape[0], "r_index")
-    check_index_range(gold, N, "gold")
-    h = torch.as_tensor(e_index, device=dev).to(torch.int32).contiguous()
-    r = torch.as_tensor(r_index, device=dev).to(torch.int32).contiguous()
-    g = torch.as_tensor(gold, device=dev).to(torch.int32).contiguous()
+    return arr, keep, N, d
+
+
+def _query_column(x, n: int, what: str, dev) -> torch.Tensor:
+    """A column of query ids (list, numpy array or tensor), range-checked, as a contiguous int32 device tensor."""
+    check_index_range(x, n, what)
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.int64).reshape(-1)))
+    return x.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _tail_index(index, dev):
+    """(byref(jmac_tail_index_t) or None, the struct to keep alive) of a sampling.TrueTailIndex."""
+    import ctypes
+    if index is None:
+        return None, None
+    require_device(index.key_code, index.tail_ptr, index.tail_idx)
+    if index.key_code.device != dev:
+        raise ValueError("index lives on %s, the tables on %s" % (index.key_code.device, dev))
+    st = index.c_struct()
+    return ctypes.byref(st), st
+
+
+def linkpred_ranks(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequence[torch.Tensor], e_index, r_index, gold,
+                   filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                   pred_head: bool = False, table_dtype=torch.float32, index=None) -> torch.Tensor:
+    """Filtered ranks of the gold tails -- ``filtered_rank(linkpred_dist(...), gold, filt_ptr, filt_idx)`` without the
+    [B, N] distance matrix (forward_linkpred src/jmac_model.py:302-313 + the ranking loop of src/validate.py:50-64, i.e. what
+    CompletionEvaluator.test needs).  The distance of a candidate is one running fp32 sum over (layer, k) where the
+    materialised path rounds once more per layer: same rank unless the gold is tied with a neighbour at fp32 rounding.
+    ``index``: a sampling.TrueTailIndex instead of the per-batch CSR -- every query's filter is looked up on the device
+    (the same ranks as the CSR of the same lists; a query whose (h, r) the index does not hold ranks raw).  ``e_index``,
+    ``r_index`` and ``gold`` may be lists, numpy arrays or device tensors."""
+    if index is not None and (filt_ptr is not None or filt_idx is not None):
+        raise ValueError("linkpred_ranks: pass either index or filt_ptr / filt_idx, not both")
+    bf16 = table_dtype == torch.bfloat16
+    arr, keep, N, d = _link_layers(comp_layers, comp_rel_layers, bf16)
+    nl, dev = len(comp_layers), comp_layers[0].device
+    h = _query_column(e_index, N, "e_index", dev)
+    r = _query_column(r_index, comp_rel_layers[0].shape[0], "r_index", dev)
+    g = _query_column(gold, N, "gold", dev)
     B = h.numel()
     if r.numel() != B or g.numel() != B:
         raise ValueError("e_index, r_index and gold must have one entry per query")
@@ -104,10 +132,46 @@ def linkpred_ranks(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequenc
     L = lib()
     ws_bytes = int(L.jmac_linkpred_rank_workspace_bytes(B, d, nl))
     ws = workspace(ws_bytes, dev)
+    if index is not None:
+        ix, _keep_ix = _tail_index(index, dev)
+        name = "jmac_linkpred_rank_indexed_bf16" if bf16 else "jmac_linkpred_rank_indexed_f32"
+        check(getattr(L, name)(arr, nl, ptr(h), ptr(r), 1 if pred_head else 0, ptr(g), ix, B, N, d, ptr(rank), ptr(ws), ws_bytes,
+                               stream()), name)
+        return rank
     fn, name = (L.jmac_linkpred_rank_bf16, "jmac_linkpred_rank_bf16") if bf16 else (L.jmac_linkpred_rank_f32, "jmac_linkpred_rank_f32")
     check(fn(arr, nl, ptr(h), ptr(r), 1 if pred_head else 0, ptr(g), ptr(filt_ptr), ptr(filt_idx), B, N, d, ptr(rank), ptr(ws),
              ws_bytes, stream()), name)
     return rank
+
+
+def linkpred_topk(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequence[torch.Tensor], e_index, r_index, k: int,
+                  index=None, pred_head: bool = False, table_dtype=torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The model's predictions: ``(idx int64 [B, k], dist fp32 [B, k])``, the k nearest candidates of every ``(h, r)`` under
+    linkpred_ranks' distance, ascending (equal distances: lower index first), without the [B, N] matrix.  ``index``: a
+    sampling.TrueTailIndex whose listed tails -- the facts already known -- are excluded (None: nothing is).  A query with
+    fewer than k candidates left ends its row with ``idx = -1, dist = +inf``.  1 <= k <= 64.  The distances are bit for bit
+    those the ranks are decided on: ``linkpred_ranks(gold=idx[:, j], index=index)`` is ``j + 1``."""
+    bf16 = table_dtype == torch.bfloat16
+    arr, keep, N, d = _link_layers(comp_layers, comp_rel_layers, bf16)
+    nl, dev = len(comp_layers), comp_layers[0].device
+    k = int(k)
+    if not 1 <= k <= 64 or k > N:
+        raise ValueError("linkpred_topk: k must lie in [1, min(64, N)] (got %d, N = %d)" % (k, N))
+    h = _query_column(e_index, N, "e_index", dev)
+    r = _query_column(r_index, comp_rel_layers[0].shape[0], "r_index", dev)
+    B = h.numel()
+    if r.numel() != B:
+        raise ValueError("e_index and r_index must have one entry per query")
+    idx = torch.empty((B, k), dtype=torch.int32, device=dev)
+    val = torch.empty((B, k), dtype=torch.float32, device=dev)
+    L = lib()
+    ws_bytes = int(L.jmac_linkpred_topk_workspace_bytes(B, N, d, nl, k))
+    ws = workspace(ws_bytes, dev)
+    ix, _keep_ix = _tail_index(index, dev)
+    name = "jmac_linkpred_topk_bf16" if bf16 else "jmac_linkpred_topk_f32"
+    check(getattr(L, name)(arr, nl, ptr(h), ptr(r), 1 if pred_head else 0, ix, B, N, d, k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
+                           stream()), name)
+    return idx.to(torch.int64), val
 
 
 def build_filter_csr(heads, rels, true_tail: Dict, device) -> Tuple[torch.Tensor, torch.Tensor]:
