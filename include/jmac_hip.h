@@ -510,6 +510,27 @@ int jmac_csls_apply_f32(const float* S, int64_t lds, int64_t n1, int64_t n2, con
 int jmac_csls_rank_f32(const float* S, int64_t lds, int64_t n1, int64_t n2, const float* r1, const float* r2,
                        const int32_t* gold, int32_t* rank, jmac_stream_t stream);
 
+/* Matrix-free alignment evaluation: the two entry points above without the stored matrix.  S = A B^T (n1 x n2) is the product of
+ * jmac_sim_matrix_f32, bit for bit, and is never written; c(i,j) = 2*S[i,j] - r1[i] - r2[j], computed in that order everywhere.
+ * r1 == r2 == NULL: plain similarity, c = S; give both or neither (JMAC_EINVAL).  lda, ldb, d % 4 == 0 (JMAC_EDIM).
+ *
+ * jmac_sim_csls_rank_f32: rank[i] = 1 + #{j < n2 : c(i,j) > c(i,gold[i]) or (== and j < gold[i])}, jmac_csls_rank_f32's rule.  A prep
+ * launch takes every row's gold value from the product's own contraction sequence; the product then runs with a count epilogue
+ * (compare, reduce inside the wave, integer atomics only): bitwise reproducible, independent of grid and CU count.  gold entries
+ * in [0, n2) are the caller's to vouch for.  Workspace O(n1): nothing grows with n2. */
+size_t jmac_sim_csls_rank_workspace_bytes(int64_t n1, int64_t n2);
+int jmac_sim_csls_rank_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                           const float* r1, const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes,
+                           jmac_stream_t stream);
+/* jmac_sim_csls_topk_f32: per row of A the k columns with the largest c(i,j), descending, ties -> lower index first; val [n1,k]
+ * (may be NULL), idx [n1,k] int32; 1 <= k <= min(64, n2) (JMAC_EINVAL).  jmac_sim_topk_f32's scheme with the rescored value in
+ * every stage (sample threshold, filter epilogue, overflow recompute); below 8192 columns the scores are staged in the
+ * workspace.  With NULL r1 / r2 the result is jmac_sim_topk_f32's bit for bit.  Workspace: jmac_sim_topk_workspace_bytes's. */
+size_t jmac_sim_csls_topk_workspace_bytes(int64_t n1, int64_t n2, int32_t k);
+int jmac_sim_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                           const float* r1, const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes,
+                           jmac_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Small fp32 GEMM for the relation-side projections (replaces the torch.mm calls on the ~10^3-row
  * relation tables: src/jmac_model.py:40-42 rel_transform_weight1/2, :195-196 relation MLPs, and the

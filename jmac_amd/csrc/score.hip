@@ -561,8 +561,29 @@ struct SimStats {
     float2* cbest;           // [ceil(M / 64)][N]    (max S, row index bits)
     float scale;             // > 0
 };
-template <bool STATS> struct SgExt { typedef SimFilter type; };
-template <> struct SgExt<true> { typedef SimStats type; };
+// CSLS = SG_CSLS_COUNT / SG_CSLS_FILTER: the scores are not stored, and every epilogue decision is taken on the CSLS-rescored value
+// c(m, n) = csls_value(S[m, n], r1[m], r2[n]) (jmac_sim_csls_rank_f32 / jmac_sim_csls_topk_f32).
+//   COUNT   per row m: the columns whose c beats the row's gold value gval[m] (larger, or equal with a column index below
+//           gold[m]) are counted inside the wave and added to rank[m] with ONE integer atomic per (wave, row): sums of integers,
+//           so the result is the same bits whatever the grid, the tile or the order of the blocks.
+//   FILTER  the SimFilter scheme with tau, the comparison and the appended value all in c.
+struct SimCsls {
+    SimFilter f;             // FILTER: as above (tau in c; n_off also offsets r2).  COUNT: unused
+    const float* r1;         // [M]; NULL (with r2): c = S
+    const float* r2;         // [n_off + N]
+    const float* gval;       // COUNT: [M] c(m, gold[m]), the bits this kernel produces for that element (csls_gold_kernel)
+    const int32_t* gold;     // COUNT: [M]
+    int32_t* rank;           // COUNT: [M], preset to 1
+};
+constexpr int SG_CSLS_COUNT = 1, SG_CSLS_FILTER = 2;
+template <bool STATS, int CSLS = 0> struct SgExt { typedef SimFilter type; };
+template <> struct SgExt<true, 0> { typedef SimStats type; };
+template <> struct SgExt<false, SG_CSLS_COUNT> { typedef SimCsls type; };
+template <> struct SgExt<false, SG_CSLS_FILTER> { typedef SimCsls type; };
+
+// THE rescored value, in this order everywhere it is computed.  2 s is exact in fp32, so fma(2, s, -r1) and the unfused form round
+// identically: the bits do not depend on the compiler's contraction choice.
+__device__ __forceinline__ float csls_value(float s, float r1, float r2) { return 2.f * s - r1 - r2; }
 
 // the DPP-selected lane's v (old = 0 with bound_ctrl: every source lane of the controls used here exists; ROWS: rows written)
 template <int CTRL, int ROWS = 0xF>
@@ -612,12 +633,18 @@ __device__ __forceinline__ void sg_exp_term(float s, float mx, float scale, floa
     t = fmaf(e, x, t);
 }
 
-template <bool FILTER, int WJ, bool STATS = false>
+template <bool FILTER, int WJ, bool STATS = false, int CSLS = 0>
 __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                           int64_t ldb, int M, int N, int d, float* __restrict__ C, int64_t ldc,
                                                           int tiles_m, int tiles_n, int super_order, int n_ids,
-                                                          typename SgExt<STATS>::type flt) {
+                                                          typename SgExt<STATS, CSLS>::type ext) {
     static_assert(!(STATS && (FILTER || WJ != 2)), "the statistics epilogue is written for the plain 128 x 128 tile");
+    static_assert(CSLS == 0 || (!STATS && FILTER == (CSLS == SG_CSLS_FILTER)), "CSLS: the count form or the filter form");
+    const auto& flt = [&]() -> const auto& {
+        if constexpr (CSLS != 0) return ext.f;
+        else return ext;
+    }();
+    (void)flt;
     // LDS image of one operand slab (16 k): plane (q, h) holds, for every tile row, the 4 floats k = 8q + 4h .. +3.
     // Lane (r = l&31, h = l>>5) of a wave reads its float4 of row r from plane (q, h): 32 lanes x 16 B contiguous,
     // conflict free for ds_read_b128's lane groups.  The MFMA step s of a sub-slab contracts k = {8q+s, 8q+4+s}.
@@ -808,7 +835,55 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
         }
         // C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
         const bool full = m0 + SG_T <= M && n0 + SG_TN <= N;      // block-uniform: interior tiles store without bounds tests
-        if constexpr (STATS) {
+        if constexpr (CSLS == SG_CSLS_COUNT) {
+            // lane l <-> row l of the wave's 64-row block for everything that is per row: ONE coalesced load each, the value
+            // of accumulator row (i, reg) comes out with v_readlane (rows (i, reg, h = 0 / 1) are 4 apart), as tau below
+            const int mrow = min(m0 + wm * 64 + lane, M - 1);
+            float grow = ext.gval[mrow];
+            int gcol = ext.gold[mrow];
+            const bool rescore = ext.r1 != nullptr;
+            float r1row = rescore ? ext.r1[mrow] : 0.f;
+            float r2col[SG_WJ];
+            unsigned long long inside[SG_WJ];                  // columns >= N hold zero-padded operands: they never count
+#pragma unroll
+            for (int j = 0; j < SG_WJ; ++j) {
+                const int n = n0 + wn * 32 * SG_WJ + j * 32 + r;
+                r2col[j] = rescore ? ext.r2[min(n, N - 1)] : 0.f;
+                inside[j] = __ballot(n < N);
+            }
+            int hits = 0;                                      // of row `lane` of the block
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);           // compile-time
+                    // One row pair at a time: the empty statement makes this pair's v_readlane sources depend on the previous
+                    // pair's sum.  Left free, the scheduler hoists all 192 lane reads and keeps all 64 popcounts in scalar
+                    // registers (218 / 346 spilled SGPRs at WJ = 2 / 4).
+                    asm volatile("" : "+v"(grow), "+v"(r1row), "+v"(gcol), "+v"(hits));
+                    // (both lane reads first, then a select: read inside the arms of `h ? :` they become two exec-masked branches)
+                    const float gs0 = bcast_f(grow, rbase), gs1 = bcast_f(grow, rbase + 4);
+                    const float ra0 = bcast_f(r1row, rbase), ra1 = bcast_f(r1row, rbase + 4);
+                    const int g0 = __builtin_amdgcn_readlane(gcol, rbase), g1 = __builtin_amdgcn_readlane(gcol, rbase + 4);
+                    const float gs = h ? gs1 : gs0, r1v = h ? ra1 : ra0;
+                    const int g = h ? g1 : g0;
+                    int c0 = 0, c1 = 0;                        // wave-uniform: the hits of row rbase / rbase + 4
+#pragma unroll
+                    for (int j = 0; j < SG_WJ; ++j) {
+                        const int n = n0 + wn * 32 * SG_WJ + j * 32 + r;
+                        const float v = rescore ? csls_value(acc[i][j][reg], r1v, r2col[j]) : acc[i][j][reg];
+                        const unsigned long long mask = __ballot(v > gs || (v == gs && n < g)) & inside[j];
+                        c0 += __popc((unsigned)mask);
+                        c1 += __popc((unsigned)(mask >> 32));
+                    }
+                    // every lane is written exactly once per tile: (i, reg) -> rbase, rbase + 4 covers 0 .. 63 (a select on
+                    // lane == rbase instead keeps 64 loop-invariant compare masks alive across the tile loop: 95 spilled SGPRs)
+                    asm("s_nop 0\n\tv_writelane_b32 %0, %1, %2\n\tv_writelane_b32 %0, %3, %4"
+                        : "+v"(hits)
+                        : "s"(c0), "n"(rbase), "s"(c1), "n"(rbase + 4));
+                }
+            if (hits != 0 && m0 + wm * 64 + lane < M) atomicAdd(ext.rank + m0 + wm * 64 + lane, hits);      // rows >= M: no such row
+        } else if constexpr (STATS) {
             const float scale = flt.scale;
             const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
             const int ncol[2] = {ncol0 + r, ncol0 + 32 + r};
@@ -918,6 +993,13 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
             // thresholds of the wave's 64 rows: ONE coalesced load (lane l <-> row l of the wave's row block); the value for
             // accumulator register (i, reg) comes out of it with two v_readlane (rows (i, reg, h = 0 / 1) are 4 apart)
             const float trow = flt.tau[(int64_t)min(m0 + wm * 64 + lane, M - 1) * flt.tau_stride];
+            // CSLS: the row terms travel like tau, a lane's WJ column terms are loaded once per tile
+            float r1row = 0.f, r2col[CSLS == SG_CSLS_FILTER ? SG_WJ : 1] = {};
+            if constexpr (CSLS == SG_CSLS_FILTER) {
+                r1row = ext.r1[min(m0 + wm * 64 + lane, M - 1)];
+#pragma unroll
+                for (int j = 0; j < SG_WJ; ++j) r2col[j] = ext.r2[flt.n_off + min(n0 + wn * 32 * SG_WJ + j * 32 + r, N - 1)];
+            }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -925,10 +1007,13 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
                     const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);           // compile-time
                     const int m = m0 + wm * 64 + rbase + 4 * h;
                     const float tau = h ? bcast_f(trow, rbase + 4) : bcast_f(trow, rbase);
+                    float r1v = 0.f;
+                    if constexpr (CSLS == SG_CSLS_FILTER) r1v = h ? bcast_f(r1row, rbase + 4) : bcast_f(r1row, rbase);
 #pragma unroll
                     for (int j = 0; j < SG_WJ; ++j) {
                         const int n = n0 + wn * 32 * SG_WJ + j * 32 + r;
-                        const float v = acc[i][j][reg];
+                        float v = acc[i][j][reg];
+                        if constexpr (CSLS == SG_CSLS_FILTER) v = csls_value(v, r1v, r2col[j]);
                         const bool pass = m < M && n < N && v >= tau;
                         const unsigned long long mask = __ballot(pass);
                         if (mask != 0ull) {                    // wave-uniform
@@ -1419,11 +1504,14 @@ __device__ __forceinline__ void for_each_row_score(const float* __restrict__ aro
     }
 }
 
-__global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
-                                                             int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
-                                                             const float* __restrict__ cval, const int* __restrict__ cidx_g, int cap,
-                                                             const float* __restrict__ sval, const int32_t* __restrict__ sidx,
-                                                             float* __restrict__ val, int32_t* __restrict__ idx) {
+// CS: the lists hold CSLS-rescored values (jmac_sim_csls_topk_f32), so a recomputed score is rescored too before it is used
+template <bool CS>
+__device__ __forceinline__ void cand_select_body(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                 int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
+                                                 const float* __restrict__ cval, const int* __restrict__ cidx_g, int cap,
+                                                 const float* __restrict__ sval, const int32_t* __restrict__ sidx,
+                                                 float* __restrict__ val, int32_t* __restrict__ idx, const float* __restrict__ r1,
+                                                 const float* __restrict__ r2) {
     __shared__ int hist[TK_BINS];
     __shared__ unsigned ckey[TK_CAP];
     __shared__ int cidx[TK_CAP];
@@ -1487,10 +1575,16 @@ __global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __rest
     }
     // ---- overflow: two-pass selection over recomputed scores
     const float* arow = A + (int64_t)b * lda;
+    float r1b = 0.f;
+    if constexpr (CS) r1b = r1[b];
+    auto rescored = [&](int n, float v) -> float {
+        if constexpr (CS) return csls_value(v, r1b, r2[n]);
+        else return v;
+    };
     for (int i = tid; i < TK_BINS; i += kBlock) hist[i] = 0;
     if (tid == 0) sh_cnt = 0;
     __syncthreads();
-    for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) { atomicAdd(&hist[tk_key(v) >> 20], 1); });
+    for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) { atomicAdd(&hist[tk_key(rescored(n, v)) >> 20], 1); });
     __syncthreads();
     if (tid == 0) {                                            // (rare path: a serial scan from the top bin is fine)
         int above = 0, bin = TK_BINS - 1;
@@ -1506,7 +1600,7 @@ __global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __rest
     C = sh_above + hist[bstar];
     if (C <= TK_CAP) {
         for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) {
-            const unsigned key = tk_key(v);
+            const unsigned key = tk_key(rescored(n, v));
             if ((int)(key >> 20) >= bstar) {
                 const int slot = atomicAdd(&sh_cnt, 1);
                 ckey[slot] = key;
@@ -1524,6 +1618,7 @@ __global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __rest
         float bv = -INFINITY;
         int bi = INT32_MAX;
         for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) {
+            v = rescored(n, v);
             const bool after = (v < pv) || (v == pv && n > pi);
             const bool better = (v > bv) || (v == bv && n < bi);
             if (after && better) {
@@ -1560,6 +1655,72 @@ __global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __rest
         pv = pick_v;
         pi = pick_i;
     }
+}
+
+__global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                             int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
+                                                             const float* __restrict__ cval, const int* __restrict__ cidx_g, int cap,
+                                                             const float* __restrict__ sval, const int32_t* __restrict__ sidx,
+                                                             float* __restrict__ val, int32_t* __restrict__ idx) {
+    cand_select_body<false>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx_g, cap, sval, sidx, val, idx, nullptr, nullptr);
+}
+__global__ __launch_bounds__(kBlock) void cand_select_csls_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                                  int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
+                                                                  const float* __restrict__ cval, const int* __restrict__ cidx_g,
+                                                                  int cap, const float* __restrict__ sval,
+                                                                  const int32_t* __restrict__ sidx, float* __restrict__ val,
+                                                                  int32_t* __restrict__ idx, const float* __restrict__ r1,
+                                                                  const float* __restrict__ r2) {
+    cand_select_body<true>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx_g, cap, sval, sidx, val, idx, r1, r2);
+}
+
+// c(i, gold[i]) of every row, from the product's own contraction sequence (for_each_row_score's: v_mfma_f32_32x32x2_f32 over k in
+// sim_gemm_kernel's order), so that the value carries the bits the tile kernel produces for that element -- the count epilogue's
+// "equal, lower index first" test is then exact at the gold column itself.  One wave per 32 rows: row t of the MFMA tile is row t
+// of A, column t the gold row of B; only the diagonal is kept.  Also presets rank[i] = 1.
+__global__ __launch_bounds__(kBlock) void csls_gold_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                           int64_t ldb, int M, int d, const float* __restrict__ r1,
+                                                           const float* __restrict__ r2, const int32_t* __restrict__ gold,
+                                                           float* __restrict__ gval, int32_t* __restrict__ rank) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int m0 = (blockIdx.x * (kBlock / 64) + wave) * 32;
+    if (m0 >= M) return;                                       // wave-uniform
+    const int m = min(m0 + r, M - 1), g = gold[m];
+    const float* arow = A + (int64_t)m * lda;
+    const float* brow = Bm + (int64_t)g * ldb;
+    const int nk = (d + SG_K - 1) / SG_K;
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    for (int kt = 0; kt < nk; ++kt)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int k = kt * SG_K + 8 * q + 4 * h;
+            float4 a4 = ld4(arow + min(k, d - 4)), b4 = ld4(brow + min(k, d - 4));
+            if (k >= d) a4 = b4 = f4zero();
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
+        }
+    // C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  Element (t, t) lives in lane t + 32 ((t >> 2) & 1),
+    // register (t & 3) + 4 (t >> 3): the lane whose r is t holds it iff its h matches
+    if (h != ((r >> 2) & 1) || m0 + r >= M) return;
+    const int want = (r & 3) + 4 * (r >> 3);
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s = q == want ? acc[q] : s;
+    gval[m] = r1 != nullptr ? csls_value(s, r1[m], r2[g]) : s;
+    rank[m] = 1;
+}
+
+// S[i][j] = csls_value(S[i][j], r1[i], r2[j]) in place: the column sample (or a narrow matrix) staged in the workspace
+__global__ __launch_bounds__(kBlock) void csls_inplace_kernel(float* __restrict__ S, int64_t lds, int n2, const float* __restrict__ r1,
+                                                              const float* __restrict__ r2) {
+    float* row = S + (int64_t)blockIdx.x * lds;
+    const float a = r1[blockIdx.x];
+    for (int n = threadIdx.x; n < n2; n += kBlock) row[n] = csls_value(row[n], a, r2[n]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2013,7 +2174,7 @@ __global__ __launch_bounds__(kBlock) void csls_apply_kernel(const float* __restr
     const int64_t total = n1 * n2;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
         const int64_t r = i / n2, c = i % n2;
-        out[r * ldo + c] = 2.f * S[r * lds + c] - r1[r] - r2[c];
+        out[r * ldo + c] = csls_value(S[r * lds + c], r1[r], r2[c]);
     }
 }
 
@@ -2027,10 +2188,10 @@ __global__ __launch_bounds__(kBlock) void csls_rank_kernel(const float* __restri
     const float* row = S + (int64_t)i * lds;
     const float a = r1[i];
     const int g = gold[i];
-    const float gs = 2.f * row[g] - a - r2[g];
+    const float gs = csls_value(row[g], a, r2[g]);
     int cnt = 0;
     for (int n = threadIdx.x; n < n2; n += kBlock) {
-        const float v = 2.f * row[n] - a - r2[n];
+        const float v = csls_value(row[n], a, r2[n]);
         cnt += (v > gs || (v == gs && n < g)) ? 1 : 0;
     }
     cnt = wave_sum_i(cnt);
@@ -2060,14 +2221,14 @@ struct SimGeom {
 
 // persistent grids: as many blocks as are resident at once (occupancy query: 3 per CU for the 128 x 128 tile -- 64 accumulation
 // VGPRs, 33 KB of LDS -- and 2 for 128 x 256), rounded down to a multiple of 8 so that a block's tile ids stay on its XCD
-template <bool FILTER, int WJ, bool STATS = false>
+template <bool FILTER, int WJ, bool STATS = false, int CSLS = 0>
 int sim_resident(int dev) {
     static int resident_of[64] = {0};                                     // per device: CU counts may differ between devices
     int& resident = resident_of[dev >= 0 && dev < 64 ? dev : 0];
     if (resident == 0 || dev >= 64) {
         int cus = 256, occ = SgTile<WJ>::OCC;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(sim_gemm_kernel<FILTER, WJ, STATS>), kBlock, 0) != hipSuccess || occ < 1)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(sim_gemm_kernel<FILTER, WJ, STATS, CSLS>), kBlock, 0) != hipSuccess || occ < 1)
             occ = SgTile<WJ>::OCC;
         resident = (cus * occ) / 8 * 8;
         if (resident < 8) resident = 8;
@@ -2146,6 +2307,35 @@ int launch_sim_stats(const float* A, int64_t lda, const float* B, int64_t ldb, i
     hipLaunchKernelGGL((sim_gemm_kernel<false, 2, true>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d,
                        (float*)nullptr, (int64_t)0, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, sx);
     return (int)hipGetLastError();
+}
+
+// the product with a CSLS epilogue (count or filter): launch_sim's geometry and tile choice, the new arguments in SimCsls
+template <int WJ, int CSLS>
+int launch_sim_csls_wj(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, hipStream_t st,
+                       const SimCsls& cx, int dev) {
+    constexpr bool FILTER = CSLS == SG_CSLS_FILTER;
+    const SimGeom<WJ> g(M, N);
+    if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
+    const int resident = sim_resident<FILTER, WJ, false, CSLS>(dev);
+    const unsigned grid = (unsigned)(g.n_ids < resident ? g.n_ids : resident);
+    hipLaunchKernelGGL((sim_gemm_kernel<FILTER, WJ, false, CSLS>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d,
+                       (float*)nullptr, (int64_t)0, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, cx);
+    return (int)hipGetLastError();
+}
+template <int CSLS>
+int launch_sim_csls(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimCsls& cx,
+                    hipStream_t st) {
+    if (M == 0 || N == 0) return 0;
+    if (d % 4) return JMAC_EDIM;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    constexpr bool FILTER = CSLS == SG_CSLS_FILTER;
+    const SimGeom<2> g2(M, N);
+    const SimGeom<4> g4(M, N);
+    const int64_t r2 = sim_resident<FILTER, 2, false, CSLS>(dev), r4 = sim_resident<FILTER, 4, false, CSLS>(dev);
+    const int64_t cost2 = (g2.tiles + r2 - 1) / r2 * r2, cost4 = (g4.tiles + r4 - 1) / r4 * r4 * 2;
+    if (g4.tiles >= r4 && cost4 <= cost2) return launch_sim_csls_wj<4, CSLS>(A, lda, B, ldb, M, N, d, st, cx, dev);
+    return launch_sim_csls_wj<2, CSLS>(A, lda, B, ldb, M, N, d, st, cx, dev);
 }
 
 // 64 rows (blocks [0, row_blocks)) or 64 columns (the blocks behind them) per block.  Wave g combines the g-th quarter of a
@@ -2715,6 +2905,70 @@ int jmac_csls_rank_f32(const float* S, int64_t lds, int64_t n1, int64_t n2, cons
     if (!S || !r1 || !r2 || !gold || !rank) return JMAC_EINVAL;
     if (n2 >= INT32_MAX) return JMAC_ERANGE;
     hipLaunchKernelGGL(csls_rank_kernel, dim3((unsigned)n1), dim3(kBlock), 0, (hipStream_t)stream, S, lds, (int)n2, r1, r2, gold, rank);
+    return (int)hipGetLastError();
+}
+
+size_t jmac_sim_csls_rank_workspace_bytes(int64_t n1, int64_t n2) {
+    if (n1 < 0 || n2 < 0) return 0;
+    return align_up((size_t)n1 * 4) + 256;                   // the rows' gold values: nothing grows with n2
+}
+
+int jmac_sim_csls_rank_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, const float* r1,
+                           const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (n1 < 0 || n2 <= 0 || d <= 0 || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (n1 == 0) return JMAC_OK;
+    if (!A || !B || !gold || !rank) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
+    if (n1 >= INT32_MAX || n2 >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_sim_csls_rank_workspace_bytes(n1, n2)) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    SimCsls cx{};
+    cx.r1 = r1; cx.r2 = r2; cx.gval = (float*)ws; cx.gold = gold; cx.rank = rank;
+    hipLaunchKernelGGL(csls_gold_kernel, dim3((unsigned)((n1 + 32 * (kBlock / 64) - 1) / (32 * (kBlock / 64)))), dim3(kBlock), 0, st, A, lda,
+                       B, ldb, (int)n1, (int)d, r1, r2, gold, (float*)ws, rank);
+    return launch_sim_csls<SG_CSLS_COUNT>(A, lda, B, ldb, n1, n2, d, cx, st);
+}
+
+size_t jmac_sim_csls_topk_workspace_bytes(int64_t L, int64_t N, int32_t k) {
+    return jmac_sim_topk_workspace_bytes(L, N, k);            // the same layout: r1 / r2 are the caller's
+}
+
+int jmac_sim_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                           const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (L == 0) return JMAC_OK;
+    if (!A || !B || !idx) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
+    if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_sim_csls_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
+    if (!r1) return jmac_sim_topk_f32(A, lda, B, ldb, L, N, d, k, val, idx, ws, ws_bytes, stream);      // c = S: that entry point's bits
+    hipStream_t st = (hipStream_t)stream;
+    if (!st_fused(N, k)) {                                   // narrow matrices: scores to the workspace, rescored there, then the row pass
+        float* S = (float*)ws;
+        if (int rc = launch_sim(A, lda, B, ldb, L, N, d, S, N, st)) return rc;
+        hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, N, (int)N, r1, r2);
+        return launch_topk(S, N, L, N, k, val, idx, st);
+    }
+    // jmac_sim_topk_f32's three steps with c in every one of them: 1. tau[m] = k-th largest c of row m among the first Ns columns
+    const StWs w = st_layout(L, N, k);
+    char* wb = (char*)ws;
+    const int64_t Ns = st_sample(N);
+    float* S0 = (float*)(wb + w.s0);
+    float* val0 = (float*)(wb + w.val0);
+    if (int rc = launch_sim(A, lda, B, ldb, L, Ns, d, S0, Ns, st)) return rc;
+    hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S0, Ns, (int)Ns, r1, r2);
+    if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, (int32_t*)(wb + w.idx0), st)) return rc;
+    // 2. the remaining columns: the filter epilogue rescores, compares with tau and appends c
+    SimCsls cx{};
+    cx.r1 = r1; cx.r2 = r2;
+    cx.f.tau = val0 + (k - 1); cx.f.tau_stride = k;
+    cx.f.cnt = (int*)(wb + w.cnt); cx.f.cval = (float*)(wb + w.cval); cx.f.cidx = (int*)(wb + w.cidx); cx.f.cap = ST_CAP;
+    cx.f.n_off = (int)Ns;
+    if (hipMemsetAsync(cx.f.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
+    if (int rc = launch_sim_csls<SG_CSLS_FILTER>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, cx, st)) return rc;
+    // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes and rescores
+    hipLaunchKernelGGL(cand_select_csls_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, cx.f.cnt,
+                       cx.f.cval, cx.f.cidx, ST_CAP, val0, (const int32_t*)(wb + w.idx0), val, idx, r1, r2);
     return (int)hipGetLastError();
 }
 

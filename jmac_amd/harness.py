@@ -222,6 +222,28 @@ def evaluate_completion(model: JMAC, kg: KnowledgeGraph, ei, et, args, split="va
     return float((rk <= 1).double().mean()), float((rk <= 10).double().mean()), float((1.0 / rk).mean())
 
 
+@torch.no_grad()
+def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, top_k=(1, 5, 10),
+                       matrix_free=True):
+    """test_alignment_ (train.py:105-113) on the test pairs of a KG pair: row i of ``pairs`` aligns entity pairs[i, 0] of kg1
+    with pairs[i, 1] of kg2 (ids local to their KG).  ``graphs``: ((ei1, et1), (ei2, et2)).  One encoder pass in eval mode, the
+    alignment embeddings of the listed entities gathered on the device, then scoring.alignment_test -- by default its
+    matrix-free form (no len(pairs)^2 matrix).  Returns (top_k, hits [%], mr, mrr)."""
+    (ei1, et1), (ei2, et2) = graphs
+    b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
+    b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
+    was_training = model.training
+    model.eval()
+    (a1, _), (a2, _) = model.get_emb_blocks([b1, b2], on_device=True)
+    model.train(was_training)
+    pairs = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    scoring.check_index_range(pairs[:, 0], a1.shape[0], "pairs[:, 0]")
+    scoring.check_index_range(pairs[:, 1], a2.shape[0], "pairs[:, 1]")
+    p = torch.from_numpy(pairs).to(a1.device)
+    return scoring.alignment_test(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), top_k, "cosine", False, csls_k,
+                                  matrix_free=matrix_free)
+
+
 def train_epoch(model: JMAC, kgs: Dict[str, KnowledgeGraph], seeds_train: Dict[Tuple[str, str], np.ndarray],
                 seeds_test: Dict[Tuple[str, str], np.ndarray], opt_c, opt_a, args, state: dict, refresh: bool,
                 generator=None) -> List[dict]:

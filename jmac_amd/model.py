@@ -267,12 +267,17 @@ class JMAC(nn.Module):
             return [self.forward_base(*b) for b in blocks]
         return [st.block(k) for k in range(len(blocks))]
 
-    def get_emb_blocks(self, blocks, pyt=False):
-        """[get_emb(*b) for b in blocks] with one encoder pass (train.py:450-451 calls get_emb once per KG of the pair)."""
+    def get_emb_blocks(self, blocks, pyt=False, on_device=False):
+        """[get_emb(*b) for b in blocks] with one encoder pass (train.py:450-451 calls get_emb once per KG of the pair).
+        ``on_device``: the same rows as device tensors, for consumers that score them there (no host copy)."""
         outs = []
         for align_out, comp_layers, _ in self.forward_blocks(blocks):
-            a = ops.row_normalize(align_out).detach().cpu()
-            c = ops.row_normalize(comp_layers[-1]).detach().cpu()
+            a = ops.row_normalize(align_out).detach()
+            c = ops.row_normalize(comp_layers[-1]).detach()
+            if on_device:
+                outs.append((a, c))
+                continue
+            a, c = a.cpu(), c.cpu()
             outs.append((a, c) if pyt else (a.numpy(), c.numpy()))
         return outs
 
@@ -337,6 +342,23 @@ class JMAC(nn.Module):
         layers = range(self.args.num_gcn_layer)
         return scoring.linkpred_topk([comp_layers[l] for l in layers], [comp_rel_layers[l] for l in layers], e_index, r_index,
                                      k, index, pred_head, table_dtype=getattr(self, "table_dtype", torch.float32))
+
+    def alignment_topk(self, e_index, k, blocks, csls_k=10, metric="cosine", normalize=False, emb=None):
+        """The k best matches in KG 2 for the entities ``e_index`` of KG 1 (ids local to their KG): ``(idx int64 [B, k], val fp32
+        [B, k])`` under the evaluator's CSLS-rescored similarity (scoring.alignment_topk: test_alignment_, train.py:105-113, without
+        the matrix), best first, over ALL entities of both KGs -- the neighbourhood terms are those of the two whole tables.
+        ``blocks``: the pair's two (edge_index, edge_type, ent_bases, rel_bases); ``emb``: their alignment embeddings
+        ``(a1, a2)`` on the device (``get_emb_blocks(blocks, on_device=True)``), if the caller has them."""
+        if emb is None:
+            (a1, _), (a2, _) = self.get_emb_blocks(blocks, on_device=True)
+        else:
+            a1, a2 = emb
+        a, b = scoring._alignment_operands(a1, a2, metric, normalize)
+        terms = scoring.csls_terms(a, b, csls_k) if int(csls_k) > 0 else None
+        q = _idx(e_index, a1.device, a1.shape[0])
+        if terms is not None:
+            terms = (terms[0].index_select(0, q), terms[1])
+        return scoring.alignment_topk(a.index_select(0, q), b, k, csls_k, "inner", False, terms=terms)
 
     # ---- losses (src/jmac_model.py:237-292, :316-380): gathers + L1 / cosine fused in HIP (jmac_amd.losses),
     # the margin arithmetic on the resulting [T] / [L] vectors stays in torch ----------------------------

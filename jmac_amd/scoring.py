@@ -489,28 +489,120 @@ def csls_rank(sim: torch.Tensor, k: int, gold) -> torch.Tensor:
     return rank
 
 
+def _alignment_operands(embed1: torch.Tensor, embed2: torch.Tensor, metric: str, normalize: bool):
+    """The two operands of sim()'s product (similarity.py:13-55) for the metrics train.py uses ('cosine', 'inner')."""
+    if normalize or metric == "cosine":
+        from .ops import row_normalize
+        return row_normalize(embed1.detach()), row_normalize(embed2.detach())
+    if metric != "inner":
+        raise NotImplementedError("metric %r (train.py:105-113 uses 'cosine')" % metric)
+    return embed1, embed2
+
+
 def alignment_sim(embed1: torch.Tensor, embed2: torch.Tensor, metric: str = "cosine", normalize: bool = False,
                   csls_k: int = 0) -> torch.Tensor:
     """sim(), similarity.py:13-55, for the metrics train.py uses ('cosine', 'inner')."""
-    if normalize or metric == "cosine":
-        from .ops import row_normalize
-        embed1, embed2 = row_normalize(embed1.detach()), row_normalize(embed2.detach())
-    elif metric != "inner":
-        raise NotImplementedError("metric %r (train.py:105-113 uses 'cosine')" % metric)
+    embed1, embed2 = _alignment_operands(embed1, embed2, metric, normalize)
     s = sim_matrix(embed1, embed2)
     return csls_sim(s, csls_k) if csls_k > 0 else s
 
 
+# ---- the same evaluation without the n1 x n2 matrix ------------------------------------------------------------------
+CSLS_KMAX = 64
+
+
+def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(r1 [n1], r2 [n2])`` of csls_sim (similarity.py:58-78) for S = a @ b.T, which is never written: r1[i] is the mean of
+    the ``csls_k`` largest entries of row i, r2[j] of column j.  Two fused top-k products: ``sim_topk(a, b)`` for the rows,
+    ``sim_topk(b, a)`` for the columns -- every element of b a^T is the same commuting products in the same contraction order
+    as the transposed element of a b^T, so both equal the stored forms (``row_topk(sim_matrix(a, b), k)[0].mean(1)``,
+    ``col_topk_values(sim_matrix(a, b), k).mean(1)``) bit for bit.  1 <= csls_k <= 64."""
+    csls_k = int(csls_k)
+    if not 1 <= csls_k <= CSLS_KMAX or csls_k > min(a.shape[0], b.shape[0]):
+        raise ValueError("csls_terms: csls_k must lie in [1, min(%d, n1, n2)] (got %d)" % (CSLS_KMAX, csls_k))
+    r1 = sim_topk(a, b, csls_k, return_values=True)[1].mean(1)
+    r2 = sim_topk(b, a, csls_k, return_values=True)[1].mean(1)
+    return r1, r2
+
+
+def _csls_operands(emb1, emb2, csls_k, metric, normalize, terms):
+    require_device(emb1, emb2)
+    a, b = _alignment_operands(emb1, emb2, metric, normalize)
+    a, b = _rows16(a.detach()), _rows16(b.detach())
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("the two embedding tables disagree in width")
+    r1 = r2 = None
+    if int(csls_k) > 0:
+        r1, r2 = terms if terms is not None else csls_terms(a, b, csls_k)
+        r1, r2 = r1.contiguous(), r2.contiguous()
+        if r1.shape != (a.shape[0],) or r2.shape != (b.shape[0],) or r1.dtype != torch.float32 or r2.dtype != torch.float32:
+            raise ValueError("terms must be fp32 vectors of n1 and n2 entries")
+        require_device(r1, r2)
+    return a, b, r1, r2
+
+
+def alignment_ranks(emb1: torch.Tensor, emb2: torch.Tensor, gold, csls_k: int = 10, metric: str = "cosine",
+                    normalize: bool = False, terms=None) -> torch.Tensor:
+    """int32 ranks [n1]: the 1-based rank of column gold[i] in row i of ``alignment_sim(emb1, emb2, metric, normalize, csls_k)``
+    (descending, ties -> lower index first) == ``csls_rank(sim_matrix(..), csls_k, gold)`` (``csls_k = 0``:
+    ``filtered_rank(sim_matrix(..), gold, descending=True)``) bit for bit, without the n1 x n2 matrix: the count runs in the
+    product's epilogue.  ``terms``: ``csls_terms`` of the same operands, if the caller has them already."""
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    n1, d = a.shape
+    n2 = b.shape[0]
+    check_index_range(gold, n2, "gold")
+    gold = torch.as_tensor(gold, device=a.device).to(torch.int32).contiguous()
+    if gold.numel() != n1:
+        raise ValueError("gold must have one entry per row of emb1")
+    rank = torch.empty(n1, dtype=torch.int32, device=a.device)
+    L = lib()
+    ws_bytes = int(L.jmac_sim_csls_rank_workspace_bytes(n1, n2))
+    ws = workspace(ws_bytes, a.device)
+    check(L.jmac_sim_csls_rank_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(gold), ptr(rank), ptr(ws), ws_bytes,
+                                   stream()), "jmac_sim_csls_rank_f32")
+    return rank
+
+
+def alignment_topk(emb1: torch.Tensor, emb2: torch.Tensor, k: int, csls_k: int = 10, metric: str = "cosine",
+                   normalize: bool = False, terms=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The alignment itself: ``(idx int64 [n1, k], val fp32 [n1, k])``, per row of emb1 the k best matches among the rows of emb2
+    under ``alignment_sim(.., csls_k)``, best first (ties -> lower index first) == ``row_topk(alignment_sim(..), k)`` bit for
+    bit, without the n1 x n2 matrix (greedy_alignment's alignment_rest, alignment.py:10-112, is column 0).  1 <= k <= 64."""
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    n1, d = a.shape
+    n2 = b.shape[0]
+    k = int(k)
+    if not 1 <= k <= 64 or k > n2:
+        raise ValueError("alignment_topk: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
+    idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
+    val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
+    L = lib()
+    ws_bytes = int(L.jmac_sim_csls_topk_workspace_bytes(n1, n2, k))
+    ws = workspace(ws_bytes, a.device)
+    check(L.jmac_sim_csls_topk_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
+                                   stream()), "jmac_sim_csls_topk_f32")
+    return idx.to(torch.int64), val
+
+
+def _rank_summary(rank: torch.Tensor, top_k):
+    rank = rank.to(torch.float64)
+    hits = [float((rank <= k).double().mean().item() * 100.0) for k in top_k]
+    return list(top_k), [round(h, 3) for h in hits], float(rank.mean().item()), float((1.0 / rank).mean().item())
+
+
 def alignment_test(embeds1: torch.Tensor, embeds2: torch.Tensor, top_k=(1, 5, 10), metric: str = "cosine",
-                   normalize: bool = False, csls_k: int = 10):
+                   normalize: bool = False, csls_k: int = 10, matrix_free: bool = False):
     """test() / greedy_alignment() / calculate_rank(accurate=True), evaluation.py:20-28, alignment.py:10-112:
-    row i of embeds1 is aligned with row i of embeds2.  Returns (top_k, hits [%], mr, mrr)."""
+    row i of embeds1 is aligned with row i of embeds2.  Returns (top_k, hits [%], mr, mrr).  ``matrix_free``: the same ranks,
+    hence the same tuple, from ``csls_terms`` + ``alignment_ranks`` -- three products, no n x n matrix."""
+    if matrix_free:
+        gold = torch.arange(embeds1.shape[0], device=embeds1.device, dtype=torch.int32)
+        return _rank_summary(alignment_ranks(embeds1, embeds2, gold, csls_k, metric, normalize), top_k)
     s = alignment_sim(embeds1, embeds2, metric, normalize, 0)
     n = s.shape[0]
     gold = torch.arange(n, device=s.device, dtype=torch.int32)
     if csls_k > 0:                                                     # CSLS rescoring fused into the rank count
-        rank = csls_rank(s, csls_k, gold).to(torch.float64)
+        rank = csls_rank(s, csls_k, gold)
     else:
-        rank = filtered_rank(s, gold, descending=True).to(torch.float64)   # 1-based position in the descending order
-    hits = [float((rank <= k).double().mean().item() * 100.0) for k in top_k]
-    return list(top_k), [round(h, 3) for h in hits], float(rank.mean().item()), float((1.0 / rank).mean().item())
+        rank = filtered_rank(s, gold, descending=True)                 # 1-based position in the descending order
+    return _rank_summary(rank, top_k)
