@@ -16,6 +16,7 @@
 // (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate), so top-k indices are decided on
 // full-precision scores.
 #include "common.h"
+#include "topk_select.h"
 #include <type_traits>
 
 using namespace jmac;
@@ -23,6 +24,7 @@ using namespace jmac;
 namespace {
 
 constexpr int kBlock = 256;
+static_assert(TK_THREADS == kBlock, "the selection routines stride by the block size");
 
 // ------------------------------------------------------------------------------------------------
 // L1 score: 64x64 output tile per block, 4x4 per thread, K staged 16 at a time (transposed in LDS)
@@ -1295,15 +1297,6 @@ __global__ __launch_bounds__(kBlock, 2) void sim_gemm_glds_kernel(const float* _
 // Two streaming passes over the row instead of k; rows whose candidate set exceeds the LDS list (e.g. constant rows)
 // take k rounds of (value, index) arg-max over the row in place.
 // ------------------------------------------------------------------------------------------------
-constexpr int TK_BINS = 4096, TK_CAP = 1024;
-
-__device__ __forceinline__ unsigned tk_key(float v) {          // ascending float order == ascending unsigned order
-    const unsigned u = v == 0.f ? 0u : __float_as_uint(v);    // -0 and +0 compare equal: one key
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// a beats b: larger value, or equal value and lower index
-__device__ __forceinline__ bool tk_beats(unsigned ka, int ia, unsigned kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
-
 __global__ __launch_bounds__(kBlock) void row_topk_kernel(const float* __restrict__ S, int64_t lds, int N, int k,
                                                           float* __restrict__ val, int32_t* __restrict__ idx) {
     __shared__ int hist[TK_BINS];
@@ -1311,10 +1304,7 @@ __global__ __launch_bounds__(kBlock) void row_topk_kernel(const float* __restric
     __shared__ int cidx[TK_CAP];
     __shared__ int chunk_sum[kBlock];
     __shared__ int sh_bin, sh_above, sh_cnt;
-    __shared__ float wv[kBlock / 64];
-    __shared__ int wi[kBlock / 64];
-    __shared__ float pick_v;
-    __shared__ int pick_i;
+    __shared__ TkExchange xch;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = S + (int64_t)b * lds;
     const bool vec = (((uintptr_t)row) & 15) == 0;
@@ -1422,50 +1412,16 @@ __global__ __launch_bounds__(kBlock) void row_topk_kernel(const float* __restric
         }
         return;
     }
-    // ---- fallback: k rounds of arg-max after the previous pick
-    float pv = INFINITY;
-    int pi = -1;
-    for (int r = 0; r < k; ++r) {
-        float bv = -INFINITY;
-        int bi = INT32_MAX;
-        for (int n = tid; n < N; n += kBlock) {
-            const float v = row[n];
-            const bool after = (v < pv) || (v == pv && n > pi);       // not yet picked
-            const bool better = (v > bv) || (v == bv && n < bi);
-            if (after && better) {
-                bv = v;
-                bi = n;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if ((tid & 63) == 0) {
-            wv[tid >> 6] = bv;
-            wi[tid >> 6] = bi;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < kBlock / 64; ++w)
-                if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) {
-                    bv = wv[w];
-                    bi = wi[w];
-                }
-            pick_v = bv;
-            pick_i = bi;
-            if (val) val[(int64_t)b * k + r] = bv;
-            idx[(int64_t)b * k + r] = bi == INT32_MAX ? -1 : bi;
-        }
-        __syncthreads();
-        pv = pick_v;
-        pi = pick_i;
-    }
+    // ---- fallback: k rounds of arg-max over the stored row
+    tk_argmax_rounds(
+        xch, k,
+        [&](auto f) {
+            for (int n = tid; n < N; n += kBlock) f(n, row[n]);
+        },
+        [&](int r, float v, int n) {
+            if (val) val[(int64_t)b * k + r] = v;
+            idx[(int64_t)b * k + r] = n == INT32_MAX ? -1 : n;
+        });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1477,103 +1433,67 @@ __global__ __launch_bounds__(kBlock) void row_topk_kernel(const float* __restric
 // are the GEMM's -- once per pass of the two-pass selection (and per arg-max round if even that overflows).  Slow by design:
 // it exists so that degenerate inputs still get the exact answer.
 // ------------------------------------------------------------------------------------------------
+// One 32 x 32 tile of the product with sim_gemm_kernel's contraction sequence per output element: four v_mfma_f32_32x32x2_f32 per
+// (kt, q), planes k = 16 kt + 8 q + 4 h, clamped loads zeroed past d.  Lane (r = lane & 31, h = lane >> 5) supplies row r of
+// both operands; ROW0: only tile row 0 carries A (one row of A against 32 rows of B), the rest is padding.
+template <bool ROW0>
+__device__ __forceinline__ f32x16 sim_tile_32x32(const float* __restrict__ arow, const float* __restrict__ brow, int d) {
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int nk = (d + SG_K - 1) / SG_K;
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    for (int kt = 0; kt < nk; ++kt)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int k = kt * SG_K + 8 * q + 4 * h;
+            float4 a4 = ld4(arow + min(k, d - 4)), b4 = ld4(brow + min(k, d - 4));
+            if (k >= d) a4 = b4 = f4zero();
+            if (ROW0 && r != 0) a4 = f4zero();
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
+        }
+    return acc;
+}
+
 template <class F>
 __device__ __forceinline__ void for_each_row_score(const float* __restrict__ arow, const float* __restrict__ Bm, int64_t ldb, int N,
                                                    int d, F f) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
-    const int nk = (d + SG_K - 1) / SG_K;
     for (int n0 = wave * 32; n0 < N; n0 += 32 * (kBlock / 64)) {
-        f32x16 acc;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-        const float* brow = Bm + (int64_t)min(n0 + r, N - 1) * ldb;
-        for (int kt = 0; kt < nk; ++kt)
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int k = kt * SG_K + 8 * q + 4 * h;
-                float4 a4 = ld4(arow + min(k, d - 4)), b4 = ld4(brow + min(k, d - 4));
-                if (k >= d) a4 = b4 = f4zero();
-                if (r != 0) a4 = f4zero();                     // row 0 of the 32x32 tile is the row; the rest is padding
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-            }
+        const f32x16 acc = sim_tile_32x32<true>(arow, Bm + (int64_t)min(n0 + r, N - 1) * ldb, d);
         if (h == 0 && n0 + r < N) f(n0 + r, acc[0]);           // C/D map: row 0 = register 0 of the lanes with h == 0
     }
 }
 
 // CS: the lists hold CSLS-rescored values (jmac_sim_csls_topk_f32), so a recomputed score is rescored too before it is used
+// (r1 / r2 are not read otherwise)
 template <bool CS>
-__device__ __forceinline__ void cand_select_body(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
-                                                 int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
-                                                 const float* __restrict__ cval, const int* __restrict__ cidx_g, int cap,
-                                                 const float* __restrict__ sval, const int32_t* __restrict__ sidx,
-                                                 float* __restrict__ val, int32_t* __restrict__ idx, const float* __restrict__ r1,
-                                                 const float* __restrict__ r2) {
-    __shared__ int hist[TK_BINS];
-    __shared__ unsigned ckey[TK_CAP];
-    __shared__ int cidx[TK_CAP];
-    __shared__ unsigned long long skey[TK_CAP];
-    __shared__ int sh_bin, sh_above, sh_cnt;
-    __shared__ float wv[kBlock / 64];
-    __shared__ int wi[kBlock / 64];
-    __shared__ float pick_v;
-    __shared__ int pick_i;
+__global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                             int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
+                                                             const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
+                                                             const float* __restrict__ sval, const int32_t* __restrict__ sidx,
+                                                             float* __restrict__ val, int32_t* __restrict__ idx,
+                                                             const float* __restrict__ r1, const float* __restrict__ r2) {
+    __shared__ TkShared tk;
     const int b = blockIdx.x, tid = threadIdx.x;
-    int C = cnt[b];
-    // the Cn candidates in LDS -> their k best: a bitonic sort of (key, ~index) pairs, descending (value descending, lower
-    // index first).  Ranking every candidate against every other one costs Cn^2 compares per row: 70 us for 3 000 rows of
-    // ~300 candidates; the sort is Cn log^2 Cn.
-    auto select = [&](int Cn) {
-        int P = 64;
-        while (P < Cn) P <<= 1;                                // <= TK_CAP (a power of two)
-        for (int c = tid; c < P; c += kBlock)
-            skey[c] = c < Cn ? (((unsigned long long)ckey[c] << 32) | (unsigned)(~cidx[c])) : 0ull;
-        __syncthreads();
-        for (int size = 2; size <= P; size <<= 1)
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int t = tid; t < (P >> 1); t += kBlock) {
-                    const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                    const bool desc = (lo & size) == 0;        // descending runs first: the result is descending overall
-                    const unsigned long long x = skey[lo], y = skey[hi];
-                    if ((x < y) == desc) {
-                        skey[lo] = y;
-                        skey[hi] = x;
-                    }
-                }
-                __syncthreads();
-            }
-        for (int c = tid; c < k; c += kBlock) {
-            const unsigned long long e = skey[c];
-            const int ic = (int)~(unsigned)(e & 0xffffffffull);
-            idx[(int64_t)b * k + c] = ic;
-            if (val) {
-                const unsigned key = (unsigned)(e >> 32);      // invert tk_key
-                const unsigned u = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-                val[(int64_t)b * k + c] = __uint_as_float(u);
-            }
-        }
+    const int C = cnt[b];
+    auto emit = [&](int c, unsigned long long e) {
+        idx[(int64_t)b * k + c] = tk_unpack_index(e);
+        if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
     };
     if (C + k <= cap) {                                        // the normal case (cap <= TK_CAP)
         // candidates: the row's list (columns past the sample) + the sample's own k best (the threshold came from them; a
         // sample element tied with tau but outside that list has a higher index than every listed tie: it cannot win)
-        for (int c = tid; c < C; c += kBlock) {
-            const float v = cval[(int64_t)b * cap + c];
-            ckey[c] = tk_key(v);
-            cidx[c] = cidx_g[(int64_t)b * cap + c];
-        }
-        for (int c = tid; c < k; c += kBlock) {
-            const float v = sval[(int64_t)b * k + c];
-            ckey[C + c] = tk_key(v);
-            cidx[C + c] = sidx[(int64_t)b * k + c];
-        }
-        __syncthreads();
-        select(C + k);
+        for (int c = tid; c < C; c += kBlock) tk.skey[c] = tk_pack(cval[(int64_t)b * cap + c], cidx[(int64_t)b * cap + c]);
+        for (int c = tid; c < k; c += kBlock) tk.skey[C + c] = tk_pack(sval[(int64_t)b * k + c], sidx[(int64_t)b * k + c]);
+        tk_sort_emit(tk.skey, C + k, k, emit);
         return;
     }
-    // ---- overflow: two-pass selection over recomputed scores
+    // ---- overflow: the selection over recomputed scores
     const float* arow = A + (int64_t)b * lda;
     float r1b = 0.f;
     if constexpr (CS) r1b = r1[b];
@@ -1581,100 +1501,11 @@ __device__ __forceinline__ void cand_select_body(const float* __restrict__ A, in
         if constexpr (CS) return csls_value(v, r1b, r2[n]);
         else return v;
     };
-    for (int i = tid; i < TK_BINS; i += kBlock) hist[i] = 0;
-    if (tid == 0) sh_cnt = 0;
-    __syncthreads();
-    for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) { atomicAdd(&hist[tk_key(rescored(n, v)) >> 20], 1); });
-    __syncthreads();
-    if (tid == 0) {                                            // (rare path: a serial scan from the top bin is fine)
-        int above = 0, bin = TK_BINS - 1;
-        for (; bin > 0; --bin) {
-            if (above + hist[bin] >= k) break;
-            above += hist[bin];
-        }
-        sh_bin = bin;
-        sh_above = above;
-    }
-    __syncthreads();
-    const int bstar = sh_bin;
-    C = sh_above + hist[bstar];
-    if (C <= TK_CAP) {
-        for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) {
-            const unsigned key = tk_key(rescored(n, v));
-            if ((int)(key >> 20) >= bstar) {
-                const int slot = atomicAdd(&sh_cnt, 1);
-                ckey[slot] = key;
-                cidx[slot] = n;
-            }
-        });
-        __syncthreads();
-        select(C);
-        return;
-    }
-    // ---- even the top bin overflows (e.g. a constant row): k rounds of arg-max after the previous pick
-    float pv = INFINITY;
-    int pi = -1;
-    for (int rr = 0; rr < k; ++rr) {
-        float bv = -INFINITY;
-        int bi = INT32_MAX;
-        for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) {
-            v = rescored(n, v);
-            const bool after = (v < pv) || (v == pv && n > pi);
-            const bool better = (v > bv) || (v == bv && n < bi);
-            if (after && better) {
-                bv = v;
-                bi = n;
-            }
-        });
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if ((tid & 63) == 0) {
-            wv[tid >> 6] = bv;
-            wi[tid >> 6] = bi;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < kBlock / 64; ++w)
-                if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) {
-                    bv = wv[w];
-                    bi = wi[w];
-                }
-            pick_v = bv;
-            pick_i = bi;
-            if (val) val[(int64_t)b * k + rr] = bv;
-            idx[(int64_t)b * k + rr] = bi == INT32_MAX ? -1 : bi;
-        }
-        __syncthreads();
-        pv = pick_v;
-        pi = pick_i;
-    }
+    tk_select_recomputed(
+        tk, k, [&](auto f) { for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) { f(n, rescored(n, v)); }); }, emit);
 }
 
-__global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
-                                                             int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
-                                                             const float* __restrict__ cval, const int* __restrict__ cidx_g, int cap,
-                                                             const float* __restrict__ sval, const int32_t* __restrict__ sidx,
-                                                             float* __restrict__ val, int32_t* __restrict__ idx) {
-    cand_select_body<false>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx_g, cap, sval, sidx, val, idx, nullptr, nullptr);
-}
-__global__ __launch_bounds__(kBlock) void cand_select_csls_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
-                                                                  int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
-                                                                  const float* __restrict__ cval, const int* __restrict__ cidx_g,
-                                                                  int cap, const float* __restrict__ sval,
-                                                                  const int32_t* __restrict__ sidx, float* __restrict__ val,
-                                                                  int32_t* __restrict__ idx, const float* __restrict__ r1,
-                                                                  const float* __restrict__ r2) {
-    cand_select_body<true>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx_g, cap, sval, sidx, val, idx, r1, r2);
-}
-
-// c(i, gold[i]) of every row, from the product's own contraction sequence (for_each_row_score's: v_mfma_f32_32x32x2_f32 over k in
+// c(i, gold[i]) of every row, from the product's own contraction sequence (sim_tile_32x32: v_mfma_f32_32x32x2_f32 over k in
 // sim_gemm_kernel's order), so that the value carries the bits the tile kernel produces for that element -- the count epilogue's
 // "equal, lower index first" test is then exact at the gold column itself.  One wave per 32 rows: row t of the MFMA tile is row t
 // of A, column t the gold row of B; only the diagonal is kept.  Also presets rank[i] = 1.
@@ -1687,23 +1518,7 @@ __global__ __launch_bounds__(kBlock) void csls_gold_kernel(const float* __restri
     const int m0 = (blockIdx.x * (kBlock / 64) + wave) * 32;
     if (m0 >= M) return;                                       // wave-uniform
     const int m = min(m0 + r, M - 1), g = gold[m];
-    const float* arow = A + (int64_t)m * lda;
-    const float* brow = Bm + (int64_t)g * ldb;
-    const int nk = (d + SG_K - 1) / SG_K;
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    for (int kt = 0; kt < nk; ++kt)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int k = kt * SG_K + 8 * q + 4 * h;
-            float4 a4 = ld4(arow + min(k, d - 4)), b4 = ld4(brow + min(k, d - 4));
-            if (k >= d) a4 = b4 = f4zero();
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-        }
+    const f32x16 acc = sim_tile_32x32<false>(A + (int64_t)m * lda, Bm + (int64_t)g * ldb, d);
     // C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  Element (t, t) lives in lane t + 32 ((t >> 2) & 1),
     // register (t & 3) + 4 (t >> 3): the lane whose r is t holds it iff its h matches
     if (h != ((r >> 2) & 1) || m0 + r >= M) return;
@@ -1774,74 +1589,41 @@ __global__ __launch_bounds__(kBlock) void link_select_kernel(LinkRankArgs a, int
                                                              const int32_t* __restrict__ sidx, float* __restrict__ val,
                                                              int32_t* __restrict__ idx) {
     extern __shared__ float ls_sh[];                           // [nl * dq] the query's rows (overflow path)
-    __shared__ int hist[TK_BINS];
-    __shared__ unsigned long long skey[TK_CAP];
-    __shared__ int sh_bin, sh_above, sh_cnt;
-    __shared__ float wv[kBlock / 64];
-    __shared__ int wi[kBlock / 64];
-    __shared__ float pick_v;
-    __shared__ int pick_i;
+    __shared__ TkShared tk;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int2 r = a.rng[b];
     const int32_t* const tails = a.filt_idx;
     float* const ov = val + (int64_t)b * k;
     int32_t* const oi = idx + (int64_t)b * k;
-    auto pack = [](float negd, int n) { return ((unsigned long long)tk_key(negd) << 32) | (unsigned)(~n); };
     auto emit = [&](int c, unsigned long long e) {
         if (e == 0ull) {                                       // padding: fewer than k unlisted candidates
             oi[c] = -1;
             ov[c] = INFINITY;
             return;
         }
-        oi[c] = (int)~(unsigned)(e & 0xffffffffull);
-        const unsigned key = (unsigned)(e >> 32);              // invert tk_key
-        const float v = __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+        oi[c] = tk_unpack_index(e);
+        const float v = tk_unpack_value(e);
         ov[c] = v == 0.f ? 0.f : -v;
-    };
-    // skey[0, Cn) -> descending bitonic sort (cand_select_kernel's) -> the first k
-    auto select = [&](int Cn) {
-        int P = 64;
-        while (P < Cn) P <<= 1;
-        for (int c = Cn + tid; c < P; c += kBlock) skey[c] = 0ull;
-        __syncthreads();
-        for (int size = 2; size <= P; size <<= 1)
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int t = tid; t < (P >> 1); t += kBlock) {
-                    const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                    const bool desc = (lo & size) == 0;
-                    const unsigned long long x = skey[lo], y = skey[hi];
-                    if ((x < y) == desc) {
-                        skey[lo] = y;
-                        skey[hi] = x;
-                    }
-                }
-                __syncthreads();
-            }
-        for (int c = tid; c < k; c += kBlock) emit(c, skey[c]);
     };
     const int C = a.cnt[b];
     if (C + k <= a.cap) {                                      // the normal case (cap <= TK_CAP)
         for (int c = tid; c < C; c += kBlock) {
             const int n = a.cidx[(int64_t)b * a.cap + c];
-            skey[c] = tail_listed(tails, r.x, r.y, n) ? 0ull : pack(a.cval[(int64_t)b * a.cap + c], n);
+            tk.skey[c] = tail_listed(tails, r.x, r.y, n) ? 0ull : tk_pack(a.cval[(int64_t)b * a.cap + c], n);
         }
         for (int c = tid; c < k; c += kBlock) {
             const float v = sval[(int64_t)b * k + c];
-            skey[C + c] = v == -INFINITY ? 0ull : pack(v, sidx[(int64_t)b * k + c]);
+            tk.skey[C + c] = v == -INFINITY ? 0ull : tk_pack(v, sidx[(int64_t)b * k + c]);
         }
-        __syncthreads();
-        select(C + k);
+        tk_sort_emit(tk.skey, C + k, k, emit);
         return;
     }
-    // ---- overflow: two-pass selection over recomputed distances
+    // ---- overflow: the selection over recomputed distances
     const int d = a.d, dq = a.dq, W = a.nl * dq;
     for (int i = tid; i < W; i += kBlock) {
         const int l = i / dq, q = i - l * dq;
         ls_sh[i] = ld1(static_cast<const TT*>(a.er) + ((int64_t)l * a.B + b) * dq + q);
     }
-    for (int i = tid; i < TK_BINS; i += kBlock) hist[i] = 0;
-    if (tid == 0) sh_cnt = 0;
-    __syncthreads();
     auto for_each_unlisted = [&](auto f) {                      // f(n, -dist[b, n]) for every n in [0, N) the index does not list
         for (int n = tid; n < a.N; n += kBlock) {
             if (tail_listed(tails, r.x, r.y, n)) continue;
@@ -1854,71 +1636,7 @@ __global__ __launch_bounds__(kBlock) void link_select_kernel(LinkRankArgs a, int
             f(n, -acc);
         }
     };
-    for_each_unlisted([&](int n, float v) { atomicAdd(&hist[tk_key(v) >> 20], 1); });
-    __syncthreads();
-    if (tid == 0) {                                            // (rare path: a serial scan from the top bin is fine)
-        int above = 0, bin = TK_BINS - 1;
-        for (; bin > 0; --bin) {
-            if (above + hist[bin] >= k) break;
-            above += hist[bin];
-        }
-        sh_bin = bin;
-        sh_above = above;
-    }
-    __syncthreads();
-    const int bstar = sh_bin;
-    const int C2 = sh_above + hist[bstar];                     // < k: the row has fewer than k unlisted candidates (bin 0 reached)
-    if (C2 <= TK_CAP) {
-        for_each_unlisted([&](int n, float v) {
-            if ((int)(tk_key(v) >> 20) >= bstar) skey[atomicAdd(&sh_cnt, 1)] = pack(v, n);
-        });
-        __syncthreads();
-        select(C2);
-        return;
-    }
-    // ---- even the top bin overflows (e.g. a constant table): k rounds of arg-max after the previous pick
-    float pv = INFINITY;
-    int pi = -1;
-    for (int rr = 0; rr < k; ++rr) {
-        float bv = -INFINITY;
-        int bi = INT32_MAX;
-        for_each_unlisted([&](int n, float v) {
-            const bool after = (v < pv) || (v == pv && n > pi);
-            const bool better = (v > bv) || (v == bv && n < bi);
-            if (after && better) {
-                bv = v;
-                bi = n;
-            }
-        });
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float xv = __shfl_xor(bv, o, 64);
-            const int xi = __shfl_xor(bi, o, 64);
-            if (xv > bv || (xv == bv && xi < bi)) {
-                bv = xv;
-                bi = xi;
-            }
-        }
-        if ((tid & 63) == 0) {
-            wv[tid >> 6] = bv;
-            wi[tid >> 6] = bi;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < kBlock / 64; ++w)
-                if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) {
-                    bv = wv[w];
-                    bi = wi[w];
-                }
-            pick_v = bv;
-            pick_i = bi;
-            ov[rr] = bi == INT32_MAX ? INFINITY : (bv == 0.f ? 0.f : -bv);
-            oi[rr] = bi == INT32_MAX ? -1 : bi;
-        }
-        __syncthreads();
-        pv = pick_v;
-        pi = pick_i;
-    }
+    tk_select_recomputed(tk, k, for_each_unlisted, emit);       // (its first barrier completes ls_sh)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2236,26 +1954,59 @@ int sim_resident(int dev) {
     return resident;
 }
 
-template <bool FILTER, int WJ>
-int launch_sim_wj(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
-                  hipStream_t st, const SimFilter* flt, int dev) {
+#if defined(JMAC_SG_FORCE_WJ)
+constexpr int SG_FORCE_WJ = JMAC_SG_FORCE_WJ;                             // ablation builds: the tile of the plain and the filter product
+#else
+constexpr int SG_FORCE_WJ = 0;
+#endif
+
+// one launch of the product with tile width WJ and the epilogue <FILTER, STATS, CSLS>; ext = that epilogue's arguments
+template <bool FILTER, int WJ, bool STATS, int CSLS>
+int launch_sim_tile(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
+                    hipStream_t st, const typename SgExt<STATS, CSLS>::type& ext, int dev) {
     const SimGeom<WJ> g(M, N);
     if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
-    const int resident = sim_resident<FILTER, WJ>(dev);
+    const int resident = sim_resident<FILTER, WJ, STATS, CSLS>(dev);
     const unsigned grid = (unsigned)(g.n_ids < resident ? g.n_ids : resident);
-    hipLaunchKernelGGL((sim_gemm_kernel<FILTER, WJ>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d, C, ldc,
-                       g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, flt ? *flt : SimFilter{});
+    hipLaunchKernelGGL((sim_gemm_kernel<FILTER, WJ, STATS, CSLS>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d,
+                       C, ldc, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, ext);
     return (int)hipGetLastError();
 }
 
-int launch_sim(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
-               hipStream_t st, const SimFilter* flt = nullptr) {
+// THE launcher of the similarity product, whatever the epilogue.  The statistics epilogue always runs on the 128 x 128 tile (one
+// partial layout: a part is 64 rows or 64 columns).  The others choose.  Which tile?  Both give the same bits.  A round of resident
+// blocks is (resident blocks) x (tile area) of matrix-pipe work, and the wide tile does a given amount of it ~3.5 % faster (fewer
+// barriers and operand bytes per flop) -- but its rounds are coarser.  Take it when its quantised makespan, rounds x resident x
+// area, is no larger than the narrow tile's (measured, config-5 shapes: 12 000^2 and 3 000 x 30 000 tie on that count and gain
+// 3.4 / 3.5 %; 10 500^2 needs 7 168 against 6 912 units and loses 4 %).
+template <bool FILTER, bool STATS = false, int CSLS = 0>
+int launch_sim_epi(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
+                   hipStream_t st, const typename SgExt<STATS, CSLS>::type& ext) {
     if (M == 0 || N == 0) return 0;
     if (d % 4) return JMAC_EDIM;
     int dev = 0;
     (void)hipGetDevice(&dev);
+    if constexpr (!STATS) {
+        bool wide = SG_FORCE_WJ == 4;
+        if (CSLS != 0 || SG_FORCE_WJ == 0) {
+            const SimGeom<2> g2(M, N);
+            const SimGeom<4> g4(M, N);
+            const int64_t r2 = sim_resident<FILTER, 2, STATS, CSLS>(dev), r4 = sim_resident<FILTER, 4, STATS, CSLS>(dev);
+            const int64_t cost2 = (g2.tiles + r2 - 1) / r2 * r2, cost4 = (g4.tiles + r4 - 1) / r4 * r4 * 2;
+            wide = g4.tiles >= r4 && cost4 <= cost2;
+        }
+        if (wide) return launch_sim_tile<FILTER, 4, STATS, CSLS>(A, lda, B, ldb, M, N, d, C, ldc, st, ext, dev);
+    }
+    return launch_sim_tile<FILTER, 2, STATS, CSLS>(A, lda, B, ldb, M, N, d, C, ldc, st, ext, dev);
+}
+
+// the stored product (flt == nullptr) or the filter epilogue
+int launch_sim(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
+               hipStream_t st, const SimFilter* flt = nullptr) {
 #if JMAC_SG_GLDS
-    if (!flt) {                                                           // closed experiment: the LDS-DMA form of the plain product
+    if (!flt && M != 0 && N != 0 && d % 4 == 0) {                         // closed experiment: the LDS-DMA form of the plain product
+        int dev = 0;
+        (void)hipGetDevice(&dev);
         const SimGeom<2> g(M, N);
         if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
         static const float* zero_of[64] = {nullptr};
@@ -2273,69 +2024,16 @@ int launch_sim(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t
         return (int)hipGetLastError();
     }
 #endif
-    // Which tile?  Both give the same bits.  A round of resident blocks is (resident blocks) x (tile area) of matrix-pipe work, and
-    // the wide tile does a given amount of it ~3.5 % faster (fewer barriers and operand bytes per flop) -- but its rounds are coarser.
-    // Take it when its quantised makespan, rounds x resident x area, is no larger than the narrow tile's (measured, config-5 shapes:
-    // 12 000^2 and 3 000 x 30 000 tie on that count and gain 3.4 / 3.5 %; 10 500^2 needs 7 168 against 6 912 units and loses 4 %).
-#if defined(JMAC_SG_FORCE_WJ)
-    const bool wide = JMAC_SG_FORCE_WJ == 4;
-#else
-    const SimGeom<2> g2(M, N);
-    const SimGeom<4> g4(M, N);
-    const int64_t r2 = flt ? sim_resident<true, 2>(dev) : sim_resident<false, 2>(dev);
-    const int64_t r4 = flt ? sim_resident<true, 4>(dev) : sim_resident<false, 4>(dev);
-    const int64_t cost2 = (g2.tiles + r2 - 1) / r2 * r2, cost4 = (g4.tiles + r4 - 1) / r4 * r4 * 2;
-    const bool wide = g4.tiles >= r4 && cost4 <= cost2;
-#endif
-    if (wide)
-        return flt ? launch_sim_wj<true, 4>(A, lda, B, ldb, M, N, d, C, ldc, st, flt, dev)
-                   : launch_sim_wj<false, 4>(A, lda, B, ldb, M, N, d, C, ldc, st, flt, dev);
-    return flt ? launch_sim_wj<true, 2>(A, lda, B, ldb, M, N, d, C, ldc, st, flt, dev)
-               : launch_sim_wj<false, 2>(A, lda, B, ldb, M, N, d, C, ldc, st, flt, dev);
+    return flt ? launch_sim_epi<true>(A, lda, B, ldb, M, N, d, C, ldc, st, *flt) : launch_sim_epi<false>(A, lda, B, ldb, M, N, d, C, ldc, st, SimFilter{});
 }
-
-// the product with the statistics epilogue: always the 128 x 128 tile (one partial layout: a part is 64 rows or 64 columns)
 int launch_sim_stats(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimStats& sx,
                      hipStream_t st) {
-    if (d % 4) return JMAC_EDIM;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const SimGeom<2> g(M, N);
-    if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
-    const int resident = sim_resident<false, 2, true>(dev);
-    const unsigned grid = (unsigned)(g.n_ids < resident ? g.n_ids : resident);
-    hipLaunchKernelGGL((sim_gemm_kernel<false, 2, true>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d,
-                       (float*)nullptr, (int64_t)0, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, sx);
-    return (int)hipGetLastError();
-}
-
-// the product with a CSLS epilogue (count or filter): launch_sim's geometry and tile choice, the new arguments in SimCsls
-template <int WJ, int CSLS>
-int launch_sim_csls_wj(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, hipStream_t st,
-                       const SimCsls& cx, int dev) {
-    constexpr bool FILTER = CSLS == SG_CSLS_FILTER;
-    const SimGeom<WJ> g(M, N);
-    if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
-    const int resident = sim_resident<FILTER, WJ, false, CSLS>(dev);
-    const unsigned grid = (unsigned)(g.n_ids < resident ? g.n_ids : resident);
-    hipLaunchKernelGGL((sim_gemm_kernel<FILTER, WJ, false, CSLS>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d,
-                       (float*)nullptr, (int64_t)0, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, cx);
-    return (int)hipGetLastError();
+    return launch_sim_epi<false, true>(A, lda, B, ldb, M, N, d, nullptr, 0, st, sx);
 }
 template <int CSLS>
 int launch_sim_csls(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimCsls& cx,
                     hipStream_t st) {
-    if (M == 0 || N == 0) return 0;
-    if (d % 4) return JMAC_EDIM;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    constexpr bool FILTER = CSLS == SG_CSLS_FILTER;
-    const SimGeom<2> g2(M, N);
-    const SimGeom<4> g4(M, N);
-    const int64_t r2 = sim_resident<FILTER, 2, false, CSLS>(dev), r4 = sim_resident<FILTER, 4, false, CSLS>(dev);
-    const int64_t cost2 = (g2.tiles + r2 - 1) / r2 * r2, cost4 = (g4.tiles + r4 - 1) / r4 * r4 * 2;
-    if (g4.tiles >= r4 && cost4 <= cost2) return launch_sim_csls_wj<4, CSLS>(A, lda, B, ldb, M, N, d, st, cx, dev);
-    return launch_sim_csls_wj<2, CSLS>(A, lda, B, ldb, M, N, d, st, cx, dev);
+    return launch_sim_epi<CSLS == SG_CSLS_FILTER, false, CSLS>(A, lda, B, ldb, M, N, d, nullptr, 0, st, cx);
 }
 
 // 64 rows (blocks [0, row_blocks)) or 64 columns (the blocks behind them) per block.  Wave g combines the g-th quarter of a
@@ -2575,18 +2273,65 @@ static inline int64_t st_sample(int64_t N) {
     int64_t ns = N / 12 > 2048 ? N / 12 : 2048;            // expected candidates per row ~ k * N / Ns <= 12k (cap: 1024)
     return (ns + 127) / 128 * 128;
 }
-struct StWs { size_t s0, val0, idx0, cnt, cval, cidx, total; };
+// a row's candidate list and its sample's k best: the part of the workspace the fused forms share (off: running offset)
+struct CandWs { size_t val0, idx0, cnt, cval, cidx; };
+static CandWs cand_layout(size_t& off, int64_t rows, int64_t k) {
+    CandWs c{};
+    c.val0 = off; off += align_up((size_t)rows * (size_t)k * 4);
+    c.idx0 = off; off += align_up((size_t)rows * (size_t)k * 4);
+    c.cnt = off;  off += align_up((size_t)rows * 4);
+    c.cval = off; off += align_up((size_t)rows * ST_CAP * 4);
+    c.cidx = off; off += align_up((size_t)rows * ST_CAP * 4);
+    return c;
+}
+struct StWs { size_t s0; CandWs c; size_t total; };
 static StWs st_layout(int64_t L, int64_t N, int64_t k) {
     StWs w{};
     size_t off = 0;
     w.s0 = off;   off += align_up((size_t)L * (size_t)st_sample(N) * 4);
-    w.val0 = off; off += align_up((size_t)L * (size_t)k * 4);
-    w.idx0 = off; off += align_up((size_t)L * (size_t)k * 4);
-    w.cnt = off;  off += align_up((size_t)L * 4);
-    w.cval = off; off += align_up((size_t)L * ST_CAP * 4);
-    w.cidx = off; off += align_up((size_t)L * ST_CAP * 4);
+    w.c = cand_layout(off, L, k);
     w.total = off + 256;
     return w;
+}
+
+// jmac_sim_topk_f32 (r1 == nullptr) and jmac_sim_csls_topk_f32: every step works on c = csls_value(S, r1, r2), or on S itself
+static int sim_topk_impl(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                         const float* r2, int32_t k, float* val, int32_t* idx, void* ws, hipStream_t st) {
+    // the product of A with B's first n rows, stored (and rescored) in the workspace
+    auto scores = [&](float* S, int64_t n) -> int {
+        if (int rc = launch_sim(A, lda, B, ldb, L, n, d, S, n, st)) return rc;
+        if (r1) hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2);
+        return 0;
+    };
+    if (!st_fused(N, k)) {                                   // narrow matrices: scores to the workspace, then the row pass
+        float* S = (float*)ws;
+        if (int rc = scores(S, N)) return rc;
+        return launch_topk(S, N, L, N, k, val, idx, st);
+    }
+    // 1. tau[m] = k-th largest score of row m among the first Ns columns: a lower bound of the row's final k-th score
+    const StWs w = st_layout(L, N, k);
+    char* wb = (char*)ws;
+    const int64_t Ns = st_sample(N);
+    float* S0 = (float*)(wb + w.s0);
+    float* val0 = (float*)(wb + w.c.val0);
+    int32_t* idx0 = (int32_t*)(wb + w.c.idx0);
+    if (int rc = scores(S0, Ns)) return rc;
+    if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, idx0, st)) return rc;
+    // 2. the product over the REMAINING columns with the filtering epilogue: candidates instead of the matrix
+    SimCsls cx{};
+    cx.r1 = r1; cx.r2 = r2;
+    SimFilter& f = cx.f;
+    f.tau = val0 + (k - 1); f.tau_stride = k;
+    f.cnt = (int*)(wb + w.c.cnt); f.cval = (float*)(wb + w.c.cval); f.cidx = (int*)(wb + w.c.cidx); f.cap = ST_CAP;
+    f.n_off = (int)Ns;
+    if (hipMemsetAsync(f.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
+    if (int rc = r1 ? launch_sim_csls<SG_CSLS_FILTER>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, cx, st)
+                    : launch_sim(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, nullptr, 0, st, &f))
+        return rc;
+    // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes (and rescores)
+    hipLaunchKernelGGL(r1 ? cand_select_kernel<true> : cand_select_kernel<false>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb,
+                       (int)N, (int)d, (int)k, f.cnt, f.cval, f.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2);
+    return (int)hipGetLastError();
 }
 
 size_t jmac_sim_topk_workspace_bytes(int64_t L, int64_t N, int32_t k) {
@@ -2610,37 +2355,13 @@ int jmac_sim_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, 
     if (!A || !B || !idx) return JMAC_EINVAL;
     if (lda % 4 || ldb % 4) return JMAC_EDIM;
     if (!ws || ws_bytes < jmac_sim_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (!st_fused(N, k)) {                                   // narrow matrices: scores to the workspace, then the row pass
-        float* S = (float*)ws;
-        if (int rc = launch_sim(A, lda, B, ldb, L, N, d, S, N, st)) return rc;
-        return launch_topk(S, N, L, N, k, val, idx, st);
-    }
-    // 1. tau[m] = k-th largest score of row m among the first Ns columns: a lower bound of the row's final k-th score
-    const StWs w = st_layout(L, N, k);
-    char* wb = (char*)ws;
-    const int64_t Ns = st_sample(N);
-    float* S0 = (float*)(wb + w.s0);
-    float* val0 = (float*)(wb + w.val0);
-    if (int rc = launch_sim(A, lda, B, ldb, L, Ns, d, S0, Ns, st)) return rc;
-    if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, (int32_t*)(wb + w.idx0), st)) return rc;
-    // 2. the product over the REMAINING columns with the filtering epilogue: candidates instead of the matrix
-    SimFilter f{};
-    f.tau = val0 + (k - 1); f.tau_stride = k;
-    f.cnt = (int*)(wb + w.cnt); f.cval = (float*)(wb + w.cval); f.cidx = (int*)(wb + w.cidx); f.cap = ST_CAP;
-    f.n_off = (int)Ns;
-    if (hipMemsetAsync(f.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
-    if (int rc = launch_sim(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, nullptr, 0, st, &f)) return rc;
-    // 3. the k best of every candidate list (+ the sample's k best)
-    hipLaunchKernelGGL(cand_select_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt, f.cval,
-                       f.cidx, ST_CAP, val0, (const int32_t*)(wb + w.idx0), val, idx);
-    return (int)hipGetLastError();
+    return sim_topk_impl(A, lda, B, ldb, L, N, d, nullptr, nullptr, k, val, idx, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"
 
 // ---- link-prediction top-k: jmac_sim_topk_f32's scheme around the L1 tile loop -------------------------------------------
-struct LtWs { size_t er, rng, s0, val0, idx0, cnt, cval, cidx, total; int64_t ldS; };
+struct LtWs { size_t er, rng, s0; CandWs c; size_t total; int64_t ldS; };
 static LtWs lt_layout(int64_t B, int64_t N, int64_t d, int64_t nl, int64_t k) {
     LtWs w{};
     size_t off = 0;
@@ -2652,11 +2373,7 @@ static LtWs lt_layout(int64_t B, int64_t N, int64_t d, int64_t nl, int64_t k) {
     } else {                                                  // sample scores + candidate lists: no B x N buffer
         w.ldS = st_sample(N);
         w.s0 = off;   off += align_up((size_t)B * (size_t)w.ldS * 4);
-        w.val0 = off; off += align_up((size_t)B * (size_t)k * 4);
-        w.idx0 = off; off += align_up((size_t)B * (size_t)k * 4);
-        w.cnt = off;  off += align_up((size_t)B * 4);
-        w.cval = off; off += align_up((size_t)B * ST_CAP * 4);
-        w.cidx = off; off += align_up((size_t)B * ST_CAP * 4);
+        w.c = cand_layout(off, B, k);
     }
     w.total = off + 256;
     return w;
@@ -2716,8 +2433,8 @@ static int launch_link_topk(const jmac_link_layer_t* layers, int32_t n_layers, c
     }
     // 2. tau_b = k-th smallest unlisted distance among the first Ns columns: an upper bound of the row's final k-th distance
     const int64_t Ns = w.ldS;
-    float* val0 = (float*)(wb + w.val0);
-    int32_t* idx0 = (int32_t*)(wb + w.idx0);
+    float* val0 = (float*)(wb + w.c.val0);
+    int32_t* idx0 = (int32_t*)(wb + w.c.idx0);
     LinkRankArgs as = a;
     as.N = (int32_t)Ns;
     launch_link_tile<TT, LR_STORE>(as, vec, Ns, st);
@@ -2725,7 +2442,7 @@ static int launch_link_topk(const jmac_link_layer_t* layers, int32_t n_layers, c
     if (int rc = launch_topk(S0, Ns, B, Ns, k, val0, idx0, st)) return rc;
     // 3. the remaining columns with the filtering epilogue: candidates instead of the matrix
     a.ntau = val0 + (k - 1); a.tau_stride = k; a.cap = ST_CAP;
-    a.cnt = (int32_t*)(wb + w.cnt); a.cval = (float*)(wb + w.cval); a.cidx = (int32_t*)(wb + w.cidx);
+    a.cnt = (int32_t*)(wb + w.c.cnt); a.cval = (float*)(wb + w.c.cval); a.cidx = (int32_t*)(wb + w.c.cidx);
     a.n_off = (int32_t)Ns;
     if (hipMemsetAsync(a.cnt, 0, (size_t)B * 4, st) != hipSuccess) return (int)hipGetLastError();
     launch_link_tile<TT, LR_FILTER>(a, vec, N - Ns, st);
@@ -2941,35 +2658,7 @@ int jmac_sim_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t 
     if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
     if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
     if (!ws || ws_bytes < jmac_sim_csls_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
-    if (!r1) return jmac_sim_topk_f32(A, lda, B, ldb, L, N, d, k, val, idx, ws, ws_bytes, stream);      // c = S: that entry point's bits
-    hipStream_t st = (hipStream_t)stream;
-    if (!st_fused(N, k)) {                                   // narrow matrices: scores to the workspace, rescored there, then the row pass
-        float* S = (float*)ws;
-        if (int rc = launch_sim(A, lda, B, ldb, L, N, d, S, N, st)) return rc;
-        hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, N, (int)N, r1, r2);
-        return launch_topk(S, N, L, N, k, val, idx, st);
-    }
-    // jmac_sim_topk_f32's three steps with c in every one of them: 1. tau[m] = k-th largest c of row m among the first Ns columns
-    const StWs w = st_layout(L, N, k);
-    char* wb = (char*)ws;
-    const int64_t Ns = st_sample(N);
-    float* S0 = (float*)(wb + w.s0);
-    float* val0 = (float*)(wb + w.val0);
-    if (int rc = launch_sim(A, lda, B, ldb, L, Ns, d, S0, Ns, st)) return rc;
-    hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S0, Ns, (int)Ns, r1, r2);
-    if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, (int32_t*)(wb + w.idx0), st)) return rc;
-    // 2. the remaining columns: the filter epilogue rescores, compares with tau and appends c
-    SimCsls cx{};
-    cx.r1 = r1; cx.r2 = r2;
-    cx.f.tau = val0 + (k - 1); cx.f.tau_stride = k;
-    cx.f.cnt = (int*)(wb + w.cnt); cx.f.cval = (float*)(wb + w.cval); cx.f.cidx = (int*)(wb + w.cidx); cx.f.cap = ST_CAP;
-    cx.f.n_off = (int)Ns;
-    if (hipMemsetAsync(cx.f.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
-    if (int rc = launch_sim_csls<SG_CSLS_FILTER>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, cx, st)) return rc;
-    // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes and rescores
-    hipLaunchKernelGGL(cand_select_csls_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, cx.f.cnt,
-                       cx.f.cval, cx.f.cidx, ST_CAP, val0, (const int32_t*)(wb + w.idx0), val, idx, r1, r2);
-    return (int)hipGetLastError();
+    return sim_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream);      // r1 == NULL: c = S, jmac_sim_topk_f32's bits
 }
 
 }  // extern "C"
