@@ -530,6 +530,34 @@ size_t jmac_sim_csls_topk_workspace_bytes(int64_t n1, int64_t n2, int32_t k);
 int jmac_sim_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
                            const float* r1, const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes,
                            jmac_stream_t stream);
+/* jmac_sim_csls_topk_viable_f32: the same top-k over the VIABLE columns of every row only -- column j is viable for row m iff
+ * tk(c(m,j), row_id[m]) > best[j], where tk(v, i) is the 64-bit word (order-preserving key of v) << 32 | ~i: larger value first,
+ * equal values -> lower index first, the order of every top-k here; best[j] = 0 means nothing is held.  The rows of A are a gathered
+ * subset of the suitors of jmac_stable_match_f32 (below), row_id [n1] int32 names them (the tie-break), best [n2] is that entry
+ * point's reviewer state.  A row with fewer than k viable columns ends in (idx -1, val -inf); val is required.  The predicate
+ * runs in all three stages (sample threshold, filter epilogue, overflow recompute; a sample with fewer than k viable entries gives
+ * the threshold -inf: every viable column is listed, slow but exact), so with best all zero the result is jmac_sim_csls_topk_f32's
+ * bit for bit.  Error codes and workspace: jmac_sim_csls_topk_f32's. */
+int jmac_sim_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                                  const float* r1, const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k,
+                                  float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
+/* Stable one-to-one alignment (replaces galeshapley, modules/finding/alignment.py:115-168, run to convergence): deferred acceptance
+ * of the n1 suitors (rows) on candidate lists cand_idx / cand_val [n1, ld >= k] (int32 reviewer ids in [0, n2), best first, -1 ends
+ * a list, no id twice in a list; cand_val[i,p] = c(i, cand_idx[i,p]) fp32, finite).  Order relation on both sides: larger c first,
+ * equal c -> lower index first (suitor i prefers j to j' iff c(i,j) > c(i,j') or == and j < j'; reviewer j prefers i to i' iff
+ * c(i,j) > c(i',j) or == and i < i'); the result is the suitor-optimal stable matching of the instance the lists describe, which
+ * is unique: bitwise reproducible, independent of scheduling.  The fixpoint is reached on the device, no host read.
+ * State kept between calls (zero-fill BOTH before the first call): best [n2] uint64, the tk word (see above) of the best proposal
+ * reviewer j has received, 0 = free; ptr [n1] int32, the suitor's list position, bit 31 set while it holds that entry.  To continue
+ * with new lists for some suitors (jmac_sim_csls_topk_viable_f32's for the exhausted ones), overwrite their rows and zero their ptr.
+ * Out: match1 [n1] reviewer held or -1, match2 [n2] suitor kept or -1; counters [2] uint64 = {exhausted suitors (not holding, list
+ * not empty), proposals made by this call}; the exhausted suitors' ids, in no particular order, are the first counters[0] int32 of
+ * ws.  A suitor with an empty list is unmatched and not counted. */
+size_t jmac_stable_match_workspace_bytes(int64_t n1, int64_t n2);
+int jmac_stable_match_f32(const int32_t* cand_idx, const float* cand_val, int64_t ld, int64_t n1, int64_t n2, int32_t k, int32_t* ptr,
+                          uint64_t* best, int32_t* match1, int32_t* match2, uint64_t* counters, void* ws, size_t ws_bytes,
+                          jmac_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Small fp32 GEMM for the relation-side projections (replaces the torch.mm calls on the ~10^3-row

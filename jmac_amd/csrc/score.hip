@@ -577,11 +577,19 @@ struct SimCsls {
     const int32_t* gold;     // COUNT: [M]
     int32_t* rank;           // COUNT: [M], preset to 1
 };
-constexpr int SG_CSLS_COUNT = 1, SG_CSLS_FILTER = 2;
+// CSLS = SG_CSLS_VIABLE: the FILTER form for a suitor that may only list the reviewers it can still win (jmac_sim_csls_topk_viable_f32):
+// an element is appended iff it reaches tau AND tk_pack(c(m, n), row_id[m]) > best[n] -- it would displace what reviewer n holds.
+// r1 == NULL (with r2) is decided at run time here: c = S.
+struct SimViable : SimCsls {
+    const int32_t* row_id;               // [M] the suitor id of row m (the rows are a gathered subset): the tie-break of the word
+    const unsigned long long* best;      // [n_off + N] the reviewers' words, 0 = free
+};
+constexpr int SG_CSLS_COUNT = 1, SG_CSLS_FILTER = 2, SG_CSLS_VIABLE = 3;
 template <bool STATS, int CSLS = 0> struct SgExt { typedef SimFilter type; };
 template <> struct SgExt<true, 0> { typedef SimStats type; };
 template <> struct SgExt<false, SG_CSLS_COUNT> { typedef SimCsls type; };
 template <> struct SgExt<false, SG_CSLS_FILTER> { typedef SimCsls type; };
+template <> struct SgExt<false, SG_CSLS_VIABLE> { typedef SimViable type; };
 
 // THE rescored value, in this order everywhere it is computed.  2 s is exact in fp32, so fma(2, s, -r1) and the unfused form round
 // identically: the bits do not depend on the compiler's contraction choice.
@@ -641,7 +649,8 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
                                                           int tiles_m, int tiles_n, int super_order, int n_ids,
                                                           typename SgExt<STATS, CSLS>::type ext) {
     static_assert(!(STATS && (FILTER || WJ != 2)), "the statistics epilogue is written for the plain 128 x 128 tile");
-    static_assert(CSLS == 0 || (!STATS && FILTER == (CSLS == SG_CSLS_FILTER)), "CSLS: the count form or the filter form");
+    static_assert(CSLS == 0 || (!STATS && FILTER == (CSLS == SG_CSLS_FILTER || CSLS == SG_CSLS_VIABLE)), "CSLS: the count form or a filter form");
+    constexpr bool VIABLE = CSLS == SG_CSLS_VIABLE;
     const auto& flt = [&]() -> const auto& {
         if constexpr (CSLS != 0) return ext.f;
         else return ext;
@@ -996,11 +1005,26 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
             // accumulator register (i, reg) comes out of it with two v_readlane (rows (i, reg, h = 0 / 1) are 4 apart)
             const float trow = flt.tau[(int64_t)min(m0 + wm * 64 + lane, M - 1) * flt.tau_stride];
             // CSLS: the row terms travel like tau, a lane's WJ column terms are loaded once per tile
-            float r1row = 0.f, r2col[CSLS == SG_CSLS_FILTER ? SG_WJ : 1] = {};
+            float r1row = 0.f, r2col[CSLS == SG_CSLS_FILTER || VIABLE ? SG_WJ : 1] = {};
             if constexpr (CSLS == SG_CSLS_FILTER) {
                 r1row = ext.r1[min(m0 + wm * 64 + lane, M - 1)];
 #pragma unroll
                 for (int j = 0; j < SG_WJ; ++j) r2col[j] = ext.r2[flt.n_off + min(n0 + wn * 32 * SG_WJ + j * 32 + r, N - 1)];
+            }
+            // VIABLE: the rows' suitor ids travel like tau too, a lane's WJ reviewer words are loaded once per tile
+            int ridrow = 0;
+            unsigned long long bcol[VIABLE ? SG_WJ : 1] = {};
+            bool rescore = false;                              // block-uniform
+            if constexpr (VIABLE) {
+                rescore = ext.r1 != nullptr;
+                ridrow = ext.row_id[min(m0 + wm * 64 + lane, M - 1)];
+                if (rescore) r1row = ext.r1[min(m0 + wm * 64 + lane, M - 1)];
+#pragma unroll
+                for (int j = 0; j < SG_WJ; ++j) {
+                    const int n = flt.n_off + min(n0 + wn * 32 * SG_WJ + j * 32 + r, N - 1);
+                    if (rescore) r2col[j] = ext.r2[n];
+                    bcol[j] = ext.best[n];
+                }
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -1010,13 +1034,17 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
                     const int m = m0 + wm * 64 + rbase + 4 * h;
                     const float tau = h ? bcast_f(trow, rbase + 4) : bcast_f(trow, rbase);
                     float r1v = 0.f;
-                    if constexpr (CSLS == SG_CSLS_FILTER) r1v = h ? bcast_f(r1row, rbase + 4) : bcast_f(r1row, rbase);
+                    if constexpr (CSLS == SG_CSLS_FILTER || VIABLE) r1v = h ? bcast_f(r1row, rbase + 4) : bcast_f(r1row, rbase);
+                    int rid = 0;
+                    if constexpr (VIABLE) rid = h ? bcast_i(ridrow, rbase + 4) : bcast_i(ridrow, rbase);
 #pragma unroll
                     for (int j = 0; j < SG_WJ; ++j) {
                         const int n = n0 + wn * 32 * SG_WJ + j * 32 + r;
                         float v = acc[i][j][reg];
                         if constexpr (CSLS == SG_CSLS_FILTER) v = csls_value(v, r1v, r2col[j]);
-                        const bool pass = m < M && n < N && v >= tau;
+                        if constexpr (VIABLE) v = rescore ? csls_value(v, r1v, r2col[j]) : v;
+                        bool pass = m < M && n < N && v >= tau;
+                        if constexpr (VIABLE) pass = pass && tk_pack(v, rid) > bcol[j];
                         const unsigned long long mask = __ballot(pass);
                         if (mask != 0ull) {                    // wave-uniform
                             const int np = __popcll(mask);
@@ -1471,19 +1499,29 @@ __device__ __forceinline__ void for_each_row_score(const float* __restrict__ aro
 
 // CS: the lists hold CSLS-rescored values (jmac_sim_csls_topk_f32), so a recomputed score is rescored too before it is used
 // (r1 / r2 are not read otherwise)
-template <bool CS>
-__global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
-                                                             int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
-                                                             const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
-                                                             const float* __restrict__ sval, const int32_t* __restrict__ sidx,
-                                                             float* __restrict__ val, int32_t* __restrict__ idx,
-                                                             const float* __restrict__ r1, const float* __restrict__ r2) {
+// VIABLE (jmac_sim_csls_topk_viable_f32): the lists hold viable columns only; the sample's k best may end in masked (-inf)
+// entries and a recomputed row skips the columns whose word best[n] the row's own word tk_pack(c, row_id[b]) does not beat;
+// what is missing of the k comes out as (idx -1, val -inf).  CS is then decided at run time (r1 != NULL).
+template <bool CS, bool VIABLE>
+__device__ __forceinline__ void cand_select_body(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                 int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
+                                                 const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
+                                                 const float* __restrict__ sval, const int32_t* __restrict__ sidx,
+                                                 float* __restrict__ val, int32_t* __restrict__ idx,
+                                                 const float* __restrict__ r1, const float* __restrict__ r2,
+                                                 const int32_t* __restrict__ row_id, const unsigned long long* __restrict__ best) {
     __shared__ TkShared tk;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int C = cnt[b];
     auto emit = [&](int c, unsigned long long e) {
-        idx[(int64_t)b * k + c] = tk_unpack_index(e);
-        if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
+        if constexpr (VIABLE) {
+            const bool none = e == 0ull || tk_unpack_value(e) == -INFINITY;
+            idx[(int64_t)b * k + c] = none ? -1 : tk_unpack_index(e);
+            val[(int64_t)b * k + c] = none ? -INFINITY : tk_unpack_value(e);
+        } else {
+            idx[(int64_t)b * k + c] = tk_unpack_index(e);
+            if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
+        }
     };
     if (C + k <= cap) {                                        // the normal case (cap <= TK_CAP)
         // candidates: the row's list (columns past the sample) + the sample's own k best (the threshold came from them; a
@@ -1497,12 +1535,47 @@ __global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __rest
     const float* arow = A + (int64_t)b * lda;
     float r1b = 0.f;
     if constexpr (CS) r1b = r1[b];
+    if constexpr (VIABLE) r1b = r1 != nullptr ? r1[b] : 0.f;
     auto rescored = [&](int n, float v) -> float {
         if constexpr (CS) return csls_value(v, r1b, r2[n]);
+        else if constexpr (VIABLE) return r1 != nullptr ? csls_value(v, r1b, r2[n]) : v;
         else return v;
     };
-    tk_select_recomputed(
-        tk, k, [&](auto f) { for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) { f(n, rescored(n, v)); }); }, emit);
+    if constexpr (VIABLE) {
+        const int rid = row_id[b];
+        tk_select_recomputed(
+            tk, k,
+            [&](auto f) {
+                for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) {
+                    const float c = rescored(n, v);
+                    if (tk_pack(c, rid) > best[n]) f(n, c);
+                });
+            },
+            emit);
+    } else {
+        tk_select_recomputed(
+            tk, k, [&](auto f) { for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) { f(n, rescored(n, v)); }); }, emit);
+    }
+}
+
+template <bool CS>
+__global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                             int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
+                                                             const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
+                                                             const float* __restrict__ sval, const int32_t* __restrict__ sidx,
+                                                             float* __restrict__ val, int32_t* __restrict__ idx,
+                                                             const float* __restrict__ r1, const float* __restrict__ r2) {
+    cand_select_body<CS, false>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx, cap, sval, sidx, val, idx, r1, r2, nullptr, nullptr);
+}
+__global__ __launch_bounds__(kBlock) void cand_select_viable_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                                    int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
+                                                                    const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
+                                                                    const float* __restrict__ sval, const int32_t* __restrict__ sidx,
+                                                                    float* __restrict__ val, int32_t* __restrict__ idx,
+                                                                    const float* __restrict__ r1, const float* __restrict__ r2,
+                                                                    const int32_t* __restrict__ row_id,
+                                                                    const unsigned long long* __restrict__ best) {
+    cand_select_body<false, true>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx, cap, sval, sidx, val, idx, r1, r2, row_id, best);
 }
 
 // c(i, gold[i]) of every row, from the product's own contraction sequence (sim_tile_32x32: v_mfma_f32_32x32x2_f32 over k in
@@ -1536,6 +1609,23 @@ __global__ __launch_bounds__(kBlock) void csls_inplace_kernel(float* __restrict_
     float* row = S + (int64_t)blockIdx.x * lds;
     const float a = r1[blockIdx.x];
     for (int n = threadIdx.x; n < n2; n += kBlock) row[n] = csls_value(row[n], a, r2[n]);
+}
+// the same pass for the viable top-k: rescored (r1 != NULL), and an entry whose word does not beat its reviewer's becomes -inf
+__global__ __launch_bounds__(kBlock) void viable_inplace_kernel(float* __restrict__ S, int64_t lds, int n2, const float* __restrict__ r1,
+                                                                const float* __restrict__ r2, const int32_t* __restrict__ row_id,
+                                                                const unsigned long long* __restrict__ best) {
+    float* row = S + (int64_t)blockIdx.x * lds;
+    const float a = r1 != nullptr ? r1[blockIdx.x] : 0.f;
+    const int rid = row_id[blockIdx.x];
+    for (int n = threadIdx.x; n < n2; n += kBlock) {
+        const float c = r1 != nullptr ? csls_value(row[n], a, r2[n]) : row[n];
+        row[n] = tk_pack(c, rid) > best[n] ? c : -INFINITY;
+    }
+}
+// row_topk_kernel's output over such a masked row: a masked entry among the k (fewer than k viable columns) -> (-inf, -1)
+__global__ __launch_bounds__(kBlock) void viable_topk_finish_kernel(const float* __restrict__ val, int32_t* __restrict__ idx, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n && val[i] == -INFINITY) idx[i] = -1;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2295,18 +2385,25 @@ static StWs st_layout(int64_t L, int64_t N, int64_t k) {
 }
 
 // jmac_sim_topk_f32 (r1 == nullptr) and jmac_sim_csls_topk_f32: every step works on c = csls_value(S, r1, r2), or on S itself
+// best != nullptr (jmac_sim_csls_topk_viable_f32): of the columns n with tk_pack(c(m, n), row_id[m]) > best[n] only -- one more
+// predicate in each stage; a row with fewer than k of them ends in (idx -1, val -inf)
 static int sim_topk_impl(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
-                         const float* r2, int32_t k, float* val, int32_t* idx, void* ws, hipStream_t st) {
-    // the product of A with B's first n rows, stored (and rescored) in the workspace
+                         const float* r2, int32_t k, float* val, int32_t* idx, void* ws, hipStream_t st,
+                         const int32_t* row_id = nullptr, const unsigned long long* best = nullptr) {
+    // the product of A with B's first n rows, stored (and rescored, and masked) in the workspace
     auto scores = [&](float* S, int64_t n) -> int {
         if (int rc = launch_sim(A, lda, B, ldb, L, n, d, S, n, st)) return rc;
-        if (r1) hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2);
+        if (best) hipLaunchKernelGGL(viable_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2, row_id, best);
+        else if (r1) hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2);
         return 0;
     };
     if (!st_fused(N, k)) {                                   // narrow matrices: scores to the workspace, then the row pass
         float* S = (float*)ws;
         if (int rc = scores(S, N)) return rc;
-        return launch_topk(S, N, L, N, k, val, idx, st);
+        if (int rc = launch_topk(S, N, L, N, k, val, idx, st)) return rc;
+        if (best)
+            hipLaunchKernelGGL(viable_topk_finish_kernel, dim3((unsigned)((L * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, val, idx, L * k);
+        return (int)hipGetLastError();
     }
     // 1. tau[m] = k-th largest score of row m among the first Ns columns: a lower bound of the row's final k-th score
     const StWs w = st_layout(L, N, k);
@@ -2318,19 +2415,24 @@ static int sim_topk_impl(const float* A, int64_t lda, const float* B, int64_t ld
     if (int rc = scores(S0, Ns)) return rc;
     if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, idx0, st)) return rc;
     // 2. the product over the REMAINING columns with the filtering epilogue: candidates instead of the matrix
-    SimCsls cx{};
-    cx.r1 = r1; cx.r2 = r2;
+    SimViable cx{};
+    cx.r1 = r1; cx.r2 = r2; cx.row_id = row_id; cx.best = best;
     SimFilter& f = cx.f;
     f.tau = val0 + (k - 1); f.tau_stride = k;
     f.cnt = (int*)(wb + w.c.cnt); f.cval = (float*)(wb + w.c.cval); f.cidx = (int*)(wb + w.c.cidx); f.cap = ST_CAP;
     f.n_off = (int)Ns;
     if (hipMemsetAsync(f.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
-    if (int rc = r1 ? launch_sim_csls<SG_CSLS_FILTER>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, cx, st)
-                    : launch_sim(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, nullptr, 0, st, &f))
+    if (int rc = best ? launch_sim_epi<true, false, SG_CSLS_VIABLE>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, nullptr, 0, st, cx)
+                 : r1 ? launch_sim_csls<SG_CSLS_FILTER>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, cx, st)
+                      : launch_sim(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, nullptr, 0, st, &f))
         return rc;
     // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes (and rescores)
-    hipLaunchKernelGGL(r1 ? cand_select_kernel<true> : cand_select_kernel<false>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb,
-                       (int)N, (int)d, (int)k, f.cnt, f.cval, f.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2);
+    if (best)
+        hipLaunchKernelGGL(cand_select_viable_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt,
+                           f.cval, f.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2, row_id, best);
+    else
+        hipLaunchKernelGGL(r1 ? cand_select_kernel<true> : cand_select_kernel<false>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb,
+                           (int)N, (int)d, (int)k, f.cnt, f.cval, f.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2);
     return (int)hipGetLastError();
 }
 
@@ -2659,6 +2761,19 @@ int jmac_sim_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t 
     if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
     if (!ws || ws_bytes < jmac_sim_csls_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
     return sim_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream);      // r1 == NULL: c = S, jmac_sim_topk_f32's bits
+}
+
+int jmac_sim_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                                  const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k, float* val, int32_t* idx,
+                                  void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (L == 0) return JMAC_OK;
+    if (!A || !B || !row_id || !best || !val || !idx) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
+    if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_sim_csls_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
+    return sim_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream, row_id,
+                         reinterpret_cast<const unsigned long long*>(best));
 }
 
 }  // extern "C"

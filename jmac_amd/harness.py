@@ -244,6 +244,31 @@ def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pa
                                   matrix_free=matrix_free)
 
 
+@torch.no_grad()
+def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, k=16):
+    """stable_alignment (JMAC_DBPv1/modules/finding/alignment.py:90-134) on the test pairs of a KG pair, run to convergence: the
+    pairs' embeddings are selected as in ``evaluate_alignment``, the one-to-one matching comes from scoring.stable_alignment (no
+    len(pairs)^2 matrix).  Returns (precision [%], stats): "stable alignment precision" (:128-133), the share of matched suitors
+    i with match1[i] == i, and the run's refills / proposals / unmatched / complete."""
+    (ei1, et1), (ei2, et2) = graphs
+    b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
+    b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
+    was_training = model.training
+    model.eval()
+    (a1, _), (a2, _) = model.get_emb_blocks([b1, b2], on_device=True)
+    model.train(was_training)
+    pairs = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    scoring.check_index_range(pairs[:, 0], a1.shape[0], "pairs[:, 0]")
+    scoring.check_index_range(pairs[:, 1], a2.shape[0], "pairs[:, 1]")
+    p = torch.from_numpy(pairs).to(a1.device)
+    k = min(int(k), len(pairs))
+    match1, _, stats = scoring.stable_alignment(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), k, csls_k, "cosine", False)
+    matched = match1 >= 0
+    hits = (match1 == torch.arange(match1.numel(), device=match1.device)) & matched
+    precision = 100.0 * float(hits.sum().item()) / max(1, int(matched.sum().item()))
+    return precision, stats
+
+
 def train_epoch(model: JMAC, kgs: Dict[str, KnowledgeGraph], seeds_train: Dict[Tuple[str, str], np.ndarray],
                 seeds_test: Dict[Tuple[str, str], np.ndarray], opt_c, opt_a, args, state: dict, refresh: bool,
                 generator=None) -> List[dict]:

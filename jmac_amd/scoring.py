@@ -584,6 +584,159 @@ def alignment_topk(emb1: torch.Tensor, emb2: torch.Tensor, k: int, csls_k: int =
     return idx.to(torch.int64), val
 
 
+# ---- stable one-to-one alignment (galeshapley, modules/finding/alignment.py:115-168, run to convergence) ---------------------------
+class _StableState:
+    """The device state of one deferred-acceptance run (jmac_stable_match_f32): candidate lists, list positions, the reviewers'
+    words and the outputs.  ``step()`` runs the lists to their fixpoint and returns (exhausted, proposals) -- its one host read."""
+
+    def __init__(self, idx: torch.Tensor, val: torch.Tensor, n2: int):
+        dev = idx.device
+        self.idx, self.val, self.n2 = idx, val, int(n2)
+        self.n1, self.k = idx.shape
+        self.ptr = torch.zeros(self.n1, dtype=torch.int32, device=dev)
+        self.best = torch.zeros(self.n2, dtype=torch.int64, device=dev)          # the 64-bit words; 0 = free
+        self.match1 = torch.empty(self.n1, dtype=torch.int32, device=dev)
+        self.match2 = torch.empty(self.n2, dtype=torch.int32, device=dev)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.ws_bytes = int(lib().jmac_stable_match_workspace_bytes(self.n1, self.n2))
+        self.ws = workspace(self.ws_bytes, dev)
+
+    def step(self) -> Tuple[int, int]:
+        check(lib().jmac_stable_match_f32(ptr(self.idx), ptr(self.val), self.k, self.n1, self.n2, self.k, ptr(self.ptr), ptr(self.best),
+                                          ptr(self.match1), ptr(self.match2), ptr(self.counters), ptr(self.ws), self.ws_bytes, stream()),
+              "jmac_stable_match_f32")
+        exhausted, proposals = self.counters.tolist()
+        return int(exhausted), int(proposals)
+
+    def exhausted_ids(self, n: int) -> torch.Tensor:
+        """int32 [n], ascending (the kernel lists them in no particular order)"""
+        return self.ws[:4 * n].view(torch.int32).sort().values
+
+
+def _candidate_lists(idx: torch.Tensor, val: torch.Tensor, n2: int, what: str):
+    require_device(idx, val)
+    if idx.dim() != 2 or idx.shape != val.shape or val.dtype != torch.float32:
+        raise ValueError("%s: idx and val must be [n1, k] tensors, val fp32" % what)
+    k = idx.shape[1]
+    if not 1 <= k <= 64 or k > int(n2):
+        raise ValueError("%s: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (what, k, int(n2)))
+    return idx.to(torch.int32).contiguous(), val.contiguous()
+
+
+def stable_matching(idx: torch.Tensor, val: torch.Tensor, n2: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(match1 int64 [n1], match2 int64 [n2])``: the suitor-optimal stable matching of the instance with exactly these incomplete
+    lists (no refill).  Row i of ``idx`` [n1, k] names suitor i's acceptable reviewers in [0, n2), best first, -1 ends the list;
+    ``val[i, p]`` is c(i, idx[i, p]).  Both sides prefer the larger value and, on equal values, the lower index; -1 = unmatched /
+    free.  Deferred acceptance with one 64-bit word per reviewer, run to its fixpoint on the device."""
+    idx, val = _candidate_lists(idx, val, n2, "stable_matching")
+    st = _StableState(idx, val, n2)
+    st.step()
+    return st.match1.to(torch.int64), st.match2.to(torch.int64)
+
+
+def alignment_topk_viable(emb1: torch.Tensor, emb2: torch.Tensor, k: int, best: torch.Tensor, row_id=None, csls_k: int = 10,
+                          metric: str = "cosine", normalize: bool = False, terms=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``alignment_topk`` over the reviewers a suitor can still win: column j counts for row m only if the word of
+    (c(m, j), row_id[m]) -- larger c first, equal c -> lower id -- is above ``best[j]`` (int64 [n2], the reviewers' 64-bit words of
+    a deferred-acceptance run, 0 = free).  ``row_id`` (default 0 .. n1-1) names the suitor each row stands for.  A row with fewer
+    than k such columns ends in (idx -1, val -inf).  With ``best`` all zero this is ``alignment_topk`` bit for bit."""
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    n1, d = a.shape
+    n2 = b.shape[0]
+    k = int(k)
+    if not 1 <= k <= 64 or k > n2:
+        raise ValueError("alignment_topk_viable: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
+    require_device(best)
+    if best.dtype != torch.int64 or best.shape != (n2,):
+        raise ValueError("best must be an int64 vector of n2 words")
+    rid = torch.arange(n1, dtype=torch.int32, device=a.device) if row_id is None else \
+        torch.as_tensor(row_id, device=a.device).to(torch.int32).contiguous()
+    if rid.shape != (n1,):
+        raise ValueError("row_id must have one entry per row of emb1")
+    idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
+    val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
+    L = lib()
+    ws_bytes = int(L.jmac_sim_csls_topk_workspace_bytes(n1, n2, k))
+    ws = workspace(ws_bytes, a.device)
+    check(L.jmac_sim_csls_topk_viable_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(rid), ptr(best.contiguous()), k,
+                                          ptr(val), ptr(idx), ptr(ws), ws_bytes, stream()), "jmac_sim_csls_topk_viable_f32")
+    return idx.to(torch.int64), val
+
+
+def _refill_chunk_rows(n1: int, n2: int, d: int, k: int, ws_bytes: int) -> int:
+    """Most rows L whose top-k workspace AND gathered operand rows fit ``ws_bytes`` together (both grow linearly with L)."""
+    L = lib()
+    need = lambda rows: int(L.jmac_sim_csls_topk_workspace_bytes(rows, n2, k)) + rows * d * 4 + 256      # noqa: E731
+    rows = n1
+    while rows > 1 and need(rows) > ws_bytes:
+        rows = max(1, min(rows - 1, rows * ws_bytes // need(rows)))
+    return rows
+
+
+def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k: int = 10, metric: str = "cosine",
+                     normalize: bool = False, terms=None, max_refills: Optional[int] = None):
+    """A one-to-one alignment: ``(match1 int64 [n1], val1 fp32 [n1], stats)``, the suitor-optimal stable matching of the full
+    n1 x n2 instance under c = ``alignment_sim(emb1, emb2, metric, normalize, csls_k)`` (suitors: rows of emb1; both sides prefer the
+    larger c, ties -> lower index), without the matrix.  ``match1[i]`` is suitor i's reviewer or -1 (exactly max(0, n1 - n2)
+    suitors when the run is complete), ``val1[i] = c(i, match1[i])`` or -inf.
+
+    Every suitor starts on ``alignment_topk``'s k candidates; deferred acceptance runs on the lists; a suitor all of whose
+    candidates have rejected it gets the k best of the reviewers it could still win (the viable top-k), and so on until nobody is
+    left without candidates.  A reviewer only trades up, so a reviewer left out of a refill would have rejected the suitor anyway:
+    the result is that of the full lists.  One host read per round.  ``stats``: refills (rounds of refill), proposals, unmatched,
+    complete (False only when ``max_refills`` stopped the loop; suitors still open are -1 then)."""
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    n1, d = a.shape
+    n2 = b.shape[0]
+    k = int(k)
+    if not 1 <= k <= 64 or k > n2:
+        raise ValueError("stable_alignment: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
+    dev = a.device
+    L = lib()
+    idx = torch.empty((n1, k), dtype=torch.int32, device=dev)
+    val = torch.empty((n1, k), dtype=torch.float32, device=dev)
+    # one workspace for every top-k of the run; a refill's gathered rows of `a` live in its tail
+    ws_bytes = max(int(L.jmac_sim_csls_topk_workspace_bytes(n1, n2, k)), int(L.jmac_sim_csls_topk_workspace_bytes(1, n2, k)) + d * 4 + 256)
+    ws = workspace(ws_bytes, dev)
+    check(L.jmac_sim_csls_topk_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
+                                   stream()), "jmac_sim_csls_topk_f32")
+    st = _StableState(idx, val, n2)
+    refills = proposals = 0
+    complete = True
+    chunk = 0
+    while n1 > 0:
+        exhausted, made = st.step()
+        proposals += made
+        if exhausted == 0:
+            break
+        if max_refills is not None and refills >= int(max_refills):
+            complete = False
+            break
+        ids = st.exhausted_ids(exhausted)
+        chunk = chunk or _refill_chunk_rows(n1, n2, d, k, ws_bytes)
+        for lo in range(0, exhausted, chunk):
+            rid = ids[lo:lo + chunk].contiguous()
+            rows = rid.numel()
+            sel = rid.to(torch.int64)
+            top_bytes = int(L.jmac_sim_csls_topk_workspace_bytes(rows, n2, k))
+            sub = ws[ws_bytes - rows * d * 4:].view(torch.float32).view(rows, d)       # (ws_bytes and the offset: multiples of 16)
+            torch.index_select(a, 0, sel, out=sub)
+            r1s = r1.index_select(0, sel) if r1 is not None else None
+            nidx = torch.empty((rows, k), dtype=torch.int32, device=dev)
+            nval = torch.empty((rows, k), dtype=torch.float32, device=dev)
+            check(L.jmac_sim_csls_topk_viable_f32(ptr(sub), d, ptr(b), d, rows, n2, d, ptr(r1s), ptr(r2), ptr(rid), ptr(st.best), k,
+                                                  ptr(nval), ptr(nidx), ptr(ws), top_bytes, stream()), "jmac_sim_csls_topk_viable_f32")
+            idx[sel] = nidx
+            val[sel] = nval
+            st.ptr[sel] = 0
+        refills += 1
+    m1 = st.match1.to(torch.int64)
+    held = (st.ptr & 0x7fffffff).to(torch.int64).clamp_(max=k - 1).unsqueeze(1)
+    val1 = torch.where(m1 >= 0, val.gather(1, held).squeeze(1), torch.full_like(val[:, 0], float("-inf")))
+    stats = {"refills": refills, "proposals": proposals, "unmatched": int((m1 < 0).sum().item()), "complete": complete}
+    return m1, val1, stats
+
+
 def _rank_summary(rank: torch.Tensor, top_k):
     rank = rank.to(torch.float64)
     hits = [float((rank <= k).double().mean().item() * 100.0) for k in top_k]
