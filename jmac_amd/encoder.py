@@ -218,7 +218,8 @@ _TRACKERS = None      # list while an encoder node's forward runs: the num_batch
 # -- ``torch.autograd.grad(loss, [comp0])``, ``comp0.retain_grad()``, a tensor hook on it -- sees loss gradient + the node's input
 # gradient after this backward ran.  ``loss.backward()`` (the training loop, train.py:358) has no such observer; a caller that
 # inspects the layer-0 output's gradient sets ``encoder.INPLACE_GRADS = False`` (the sum is then formed out of place).  A backward
-# that is itself recorded (create_graph=True) never takes a buffer over.
+# that is itself recorded (create_graph=True) never takes a buffer over.  The entity table's buffer is taken where conv1_completion's
+# backward starts (``_completion_layer_bwd``); the relation table's has up to three writers, ordered in one place (``_RelCompGrad``).
 INPLACE_GRADS = True
 INPLACE_COUNT = 0         # tests: how many incoming gradient buffers a backward took over
 
@@ -374,7 +375,7 @@ def _row_order(cfg, graph: RelGraph, N: int):
     """The class order for this call, or None: enough rows, fp32 tables, and few enough active rows."""
     if not ACTIVE_ROWS or N < ACTIVE_ROWS_MIN_N or graph.E == 0 or graph.num_src != graph.N or cfg.table_dtype != torch.float32:
         return None
-    seg = getattr(cfg, "seg", None)
+    seg = cfg.seg
     if seg is not None and (seg.offsets[-1] != N or (seg.nb > 1 and not ACTIVE_ROWS_STACKED)):
         return None
     key = tuple(seg.offsets) if (seg is not None and seg.nb > 1) else None
@@ -731,8 +732,7 @@ class _LayerNode(torch.autograd.Function):
         w2g, tt, rr = t.ch.fwd_tasks()
         run_levels([[w2g, tt], [rr]])
         y = _empty(X.device, N, d)
-        t.st = _layer_fwd(lay, X, t.wc, t.ch.RR, pl[4].reshape(-1), cfg.graph, cfg.training, y, seg=getattr(cfg, "seg", None),
-                          compact=t.rc.on)
+        t.st = _layer_fwd(lay, X, t.wc, t.ch.RR, pl[4].reshape(-1), cfg.graph, cfg.training, y, seg=cfg.seg, compact=t.rc.on)
         t.st.y = None                                            # the output reaches the backward through save_for_backward
         if CAPTURE is not None:                                  # tests: the very tables the kernel gathered + the relation
             CAPTURE["layer.tables"] = (t.st.PQZ, t.rc.full_rows(t.st.RR))   # transform's activation (its sign is its pre-activation's)
@@ -768,8 +768,101 @@ def layer_supported(lay, X, R) -> bool:
 
 def layer_forward(lay, X, R, graph: RelGraph):
     """The layer's output on the fused node (lay: jmac_amd.layer.RelationAwareLayer / RelationalAwareLayer)."""
-    cfg = SimpleNamespace(layers=(lay,), graph=graph, training=lay.training)
+    cfg = SimpleNamespace(layers=(lay,), graph=graph, training=lay.training, seg=None)
     return _LayerNode.apply(cfg, X, R, *_layer_inputs(lay))
+
+
+# ---- the completion branch: conv1_completion on (E, Rc) + the rel_linear11/12 MLP (src/jmac_model.py:187-195, 211-218) ------------
+# forward_no_name is this branch alone, forward_name runs it beside the alignment layers; what differs is marked at the call sites.
+def _add_levels(levels, first, tasks_and_grads):
+    """(task levels, gradients) of a bwd_tasks call: the tasks into ``levels`` from level ``first`` on -> the gradients."""
+    task_levels, grads = tasks_and_grads
+    for i, lv in enumerate(task_levels):
+        levels[first + i].extend(lv)
+    return grads
+
+
+def _completion_rel_fwd(t, graph, lc, pc, wc, Rc, L11, L12, mslope, d, also=()):
+    """t.rc, t.chc, t.mlc -> (the tables ``also`` on the compact rows, the chain's forward tasks, the MLP's): for the caller's levels."""
+    t.rc = _RelCompact(graph, Rc.shape[0])
+    *others, Rc_u = t.rc.gather([*also, Rc])
+    t.chc = _Chain(lc, Rc_u, pc[0], pc[1], pc[2], wc, d)
+    t.mlc = _RelMLP(Rc, L11, L12, mslope)                              # rel_c1 (:195): an OUTPUT, all nr rows
+    return others, t.chc.fwd_tasks(), t.mlc.fwd_tasks()
+
+
+def _capture_layer(name, ent, rel, st, ch, rc, ro=None):
+    """CAPTURE (tests): a layer call's inputs, the very tables its aggregation kernel gathered (class order ``ro``: back in the caller's;
+    P / Q rows no edge names hold whatever the buffer held -- zeroed for the tests' arithmetic), the relation transform's activation."""
+    PQZ_c = st.PQZ
+    if ro is not None:
+        d = st.wc.shape[0]
+        PQZ_c = torch.zeros_like(st.PQZ)
+        PQZ_c[:, 2 * d:] = st.PQZ[:, 2 * d:]
+        for r0, r1 in ro.dst_ranges:
+            PQZ_c[r0:r1, :d] = st.PQZ[r0:r1, :d]
+        for r0, r1 in ro.src_ranges:
+            PQZ_c[r0:r1, d:2 * d] = st.PQZ[r0:r1, d:2 * d]
+        PQZ_c = PQZ_c[ro.new_of_old]
+    CAPTURE[name], CAPTURE[name + ".tables"] = (ent, rel), (PQZ_c, rc.full_rows(st.RR))
+    CAPTURE[name + ".rel_act"] = ch.T                                    # (its sign = the kink side)
+
+
+def _completion_outputs(t, E, Rc, ro=None):
+    """The branch's CAPTURE entries, and rel_c1 handed over.  c1 and rel_c1 are OUTPUTS: they reach the backward through
+    save_for_backward / not at all (an attribute on ctx would tie the output to its own grad_fn in a reference cycle)."""
+    if CAPTURE is not None:
+        _capture_layer("conv1_completion", E.detach(), Rc.detach(), t.sc, t.chc, t.rc, ro)
+    rel_c1, t.mlc.out, t.sc.y = t.mlc.out, None, None
+    return rel_c1
+
+
+class _RelCompGrad:
+    """d rel_comp of an encoder node's backward and the one place that orders its writers: the layer-0 loss gradient (a buffer taken
+    over, see INPLACE_GRADS), rel_c1's MLP (all nr rows: the full buffer) and conv1_completion's chain (the rows the edges name: a
+    compact buffer of its own where _RelCompact is on, the full one otherwise).  ``holds`` -- the full buffer holds a contribution --
+    is the one piece of state: a writer that finds it set accumulates.  ``mlp_tasks`` comes before ``chain_tasks``: the MLP writes
+    the full buffer at level 1, a chain that finds a contribution in the buffer it shares adds one level later."""
+
+    def __init__(self, rc, Rc, g_Rc0, mlp: bool, chain: bool):
+        self.rc, self.full = rc, _take_grad(g_Rc0, Rc.shape)
+        self.holds = self.full is not None
+        self.extra = None if self.holds else g_Rc0                       # not this node's to write: added at the end
+        if not self.holds and (mlp or (chain and not rc.on)):
+            self.full = _empty(Rc.device, *Rc.shape)
+        self.compact = _empty(Rc.device, rc.n, Rc.shape[1]) if (chain and rc.on) else None
+
+    def mlp_tasks(self, levels, mlc, g):
+        """rel_c1 = MLP(rel_comp) needs only the loss' gradient: levels 0-1 -> (d W1, d W2)."""
+        grads = _add_levels(levels, 0, mlc.bwd_tasks(g, self.full, self.holds))
+        self.holds = True
+        return grads
+
+    def chain_tasks(self, levels, chc, dRR, dwc):
+        """-> (d W1, d W2, d loop) of conv1_completion's chain."""
+        if self.compact is not None:                                     # own buffer: no ordering against the MLP's write
+            return _add_levels(levels, 0, chc.bwd_tasks(dRR, dwc, self.compact, False))
+        grads = _add_levels(levels, 1 if self.holds else 0, chc.bwd_tasks(dRR, dwc, self.full, self.holds))
+        self.holds = True
+        return grads
+
+    def finish(self, others=()):
+        """After the levels ran: ONE expand launch for ``others`` (items of _RelCompact.scatter) and the chain's compact buffer
+        -> (the others' full tables, d rel_comp -- None: nothing was written)."""
+        mine = [(self.compact, self.full if self.holds else None, True)] if self.compact is not None else []
+        outs = self.rc.scatter([*others, *mine]) if (others or mine) else []
+        own = outs[-1] if mine else (self.full if self.holds else None)
+        return outs[:len(others)], _plus(own, self.extra)
+
+
+def _completion_layer_bwd(t, c1, graph, gy, gy2, g_E0, take=True):
+    """conv1_completion's node side in a backward -> (dE, what is left of g_E0 for the caller to add, _layer_bwd's results).  dE is
+    the layer-0 loss gradient's buffer where it may be taken over (``take`` False: the caller does, later), else a fresh one."""
+    sc = SimpleNamespace(**vars(t.sc))                                   # c1 is an output: never stored on ctx.t (reference cycle)
+    sc.y = c1
+    taken = _take_grad(g_E0, c1.shape) if take else None
+    dE = taken if taken is not None else _empty(c1.device, *c1.shape)
+    return dE, (g_E0 if taken is None else None), _layer_bwd(sc, graph, gy, gy2, dE, taken is not None)
 
 
 # ---- forward_name ---------------------------------------------------------------------------------------------------------
@@ -845,9 +938,8 @@ class _EncoderName(torch.autograd.Function):
             out = _EncoderName._forward(ctx, cfg, *tensors)
             done = {id(c) for c in ctx.t.bumped}
             _bump_trackers([c for c in _TRACKERS if id(c) not in done])       # (none left in practice)
-            seg = getattr(cfg, "seg", None)
-            if seg is not None and seg.nb > 1 and ctx.t.bumped:               # one forward_base call per block in the reference:
-                torch._foreach_add_(ctx.t.bumped, seg.nb - 1)                 # num_batches_tracked moves by the block count
+            if cfg.seg is not None and cfg.seg.nb > 1 and ctx.t.bumped:       # one forward_base call per block in the reference:
+                torch._foreach_add_(ctx.t.bumped, cfg.seg.nb - 1)             # num_batches_tracked moves by the block count
             return out
         finally:
             _TRACKERS = None
@@ -880,24 +972,20 @@ class _EncoderName(torch.autograd.Function):
         # ... and the step's dropout seeds: the model's persistent seed words advanced by one (no torch RNG op per step)
         seeds = None
         if training and p_drop > 0.0:
-            state = _drop_seed_state(getattr(cfg, "cache", None), dev)
+            state = _drop_seed_state(cfg.cache, dev)
             seeds = (state, torch.empty(2, dtype=torch.int64, device=dev)) if state is not None else None
         t.wc = _wcat_pack([p[3] for p in (pa, pc, p2)], [p[5] for p in (pa, pc, p2)], d, copy=(u11[:d], t.w[:d]),
                           counters=t.bumped, seed=seeds)
         # ---- relation side: three dependency levels, one launch each; the layers' chains on the rows the edges name
-        t.rc = _RelCompact(graph, Rc.shape[0])
-        Ra_u, Rc_u = t.rc.gather([Ra, Rc])
+        (Ra_u,), fc, mc = _completion_rel_fwd(t, graph, lc, pc, t.wc[1], Rc, L11, L12, mslope, d, also=[Ra])
         t.cha = _Chain(la, Ra_u, pa[0], pa[1], pa[2], t.wc[0], d)
-        t.chc = _Chain(lc, Rc_u, pc[0], pc[1], pc[2], t.wc[1], d)
-        t.mlc = _RelMLP(Rc, L11, L12, mslope)                          # rel_c1      (:195): an OUTPUT, all nr rows
         t.ch2 = _MlpChain(l2, Ra_u, L11u, L12u, mslope, p2[0], p2[1], p2[2], t.wc[2], d)   # rel_a_in (:196) + conv2's chain
-        fa, fc, f2, mc = t.cha.fwd_tasks(), t.chc.fwd_tasks(), t.ch2.fwd_tasks(), t.mlc.fwd_tasks()
+        fa, f2 = t.cha.fwd_tasks(), t.ch2.fwd_tasks()
         run_levels([[fa[0], fa[1], fc[0], fc[1], *f2[0], mc[0], gemm_task(NL, U11[d:], t.w[d:])],
                     [fa[2], fc[2], *f2[1], mc[1]],
                     f2[2]])
         # ---- node side.  cat buffers: cat0 = [comp0 | info] (:180), cat1 = [c1n | a1] (:192), catA = [align0 | a1 | a2] (:203)
-        t.cat0_lease = _cat0_take(getattr(cfg, "cache", None), info_n, N, d, dev,
-                                   persistent=getattr(cfg, "info_persistent", False))     # right block = info, already in place
+        t.cat0_lease = _cat0_take(cfg.cache, info_n, N, d, dev, persistent=cfg.info_persistent)   # right block = info, already in place
         t.cat0, t.cat1, t.catA = t.cat0_lease.buf, _empty(dev, N, 2 * d), _empty(dev, N, 3 * d)
         # dropout draws: two device-resident seed words per step (the model's persistent seed state, advanced by the weight-pack
         # launch above: fresh on every replay of a captured step); the normalise kernels draw from them, forward and backward -- no
@@ -909,7 +997,7 @@ class _EncoderName(torch.autograd.Function):
         align0 = t.catA[:, :d]
         torch.mm(t.cat0, t.w, out=align0)                                                       # :180
         a_att = [p[4].reshape(-1) for p in (pa, pc, p2)]
-        seg = getattr(cfg, "seg", None)
+        seg = cfg.seg
         c1 = _empty(dev, N, d)
         if PAIR_LAUNCHES and cfg.table_dtype == torch.float32:
             # conv1_alignment (:183) and conv1_completion (:190) do not depend on each other and share the graph: their tables first,
@@ -935,28 +1023,12 @@ class _EncoderName(torch.autograd.Function):
         if CAPTURE is not None:
             back = (lambda x: x[ro.new_of_old]) if ro is not None else (lambda x: x.clone())
             rel_a_in = torch.mm(F.leaky_relu(torch.mm(Ra.detach(), L11u.detach()), mslope), L12u.detach())   # (:196) on all rows
-            CAPTURE.update(conv1_alignment=(back(align0), Ra.detach()), conv1_completion=(E.detach(), Rc.detach()),
-                           conv2_alignment=(back(t.a_in), rel_a_in))
-            for name, st, ch in (("conv1_alignment", t.sa, t.cha), ("conv1_completion", t.sc, t.chc), ("conv2_alignment", t.s2, t.ch2)):
-                # the very tables the aggregation kernel gathered (class order: back in the caller's; P / Q rows no edge names hold
-                # whatever the buffer held -- zero them for the tests' arithmetic)
-                PQZ_c = st.PQZ
-                if ro is not None:
-                    PQZ_c = torch.zeros_like(st.PQZ)
-                    PQZ_c[:, 2 * d:] = st.PQZ[:, 2 * d:]
-                    for r0, r1 in ro.dst_ranges:
-                        PQZ_c[r0:r1, :d] = st.PQZ[r0:r1, :d]
-                    for r0, r1 in ro.src_ranges:
-                        PQZ_c[r0:r1, d:2 * d] = st.PQZ[r0:r1, d:2 * d]
-                    PQZ_c = PQZ_c[ro.new_of_old]
-                CAPTURE[name + ".tables"] = (PQZ_c, t.rc.full_rows(st.RR))
-                CAPTURE[name + ".rel_act"] = ch.T                        # the relation transform's activation (its sign = the kink side)
+            _capture_layer("conv1_alignment", back(align0), Ra.detach(), t.sa, t.cha, t.rc, ro)
+            _capture_layer("conv2_alignment", back(t.a_in), rel_a_in, t.s2, t.ch2, t.rc, ro)
             # rows of the compact relation tables (graph.rel_used, then the loop row), None = all rows
             CAPTURE["rel_used"] = graph.rel_used if t.rc.on else None
             CAPTURE["rel_linear11.act"], CAPTURE["rel_linear11_uni.act"] = t.mlc.M, t.ch2.M      # (the second: compact rows)
-        # c1 and rel_c1 are OUTPUTS: they reach the backward through save_for_backward / not at all (an attribute on ctx
-        # would tie the output to its own grad_fn in a reference cycle)
-        rel_c1, t.mlc.out, t.sc.y = t.mlc.out, None, None
+        rel_c1 = _completion_outputs(t, E, Rc, ro)
         ctx.t, ctx.cfg, ctx.dims = t, cfg, (N, d, di)
         ctx.save_for_backward(E, Rc, Ra, NL, U11, U21, Wall, L11, L12, L11u, L12u, c1)
         return align_out, c1, rel_c1, E, Rc            # E, Rc: layer 0 of the completion layers, as aliases (see INPLACE_GRADS)
@@ -971,8 +1043,6 @@ class _EncoderName(torch.autograd.Function):
         # alive past the step, which breaks a later stream capture
         ro = t.ro
         E_x, c1_y = (t.E_n, t.c1_n) if ro is not None else (E, c1)       # class order inside the node (forward)
-        sc = SimpleNamespace(**vars(t.sc))
-        sc.y = c1_y
         graph = ro.graph if ro is not None else cfg.graph
         dev = E.device
         have_align = g_align is not None
@@ -984,18 +1054,11 @@ class _EncoderName(torch.autograd.Function):
                 g_align = gout[0]
             if g_c1 is not None:
                 g_c1 = gout[-1]
-        dE = None
-        dRa = dRc = None
+        dE = dRa = None
+        dRc = g_Rc0                                          # (no gradient into this node's relation side: passed on as it came)
         dWall = dU21 = dU11 = dNL = gL11 = gL12 = gL11u = gL12u = None
         ga = gc = g2 = [None] * 8
         levels: List[List[GemmTask]] = [[] for _ in range(5)]
-
-        def add(first_level, tasks_and_grads):
-            task_levels, grads = tasks_and_grads
-            for i, lv in enumerate(task_levels):
-                levels[first_level + i].extend(lv)
-            return grads
-
         if have_align:
             g_align = g_align.contiguous()
             dcatA = torch.mm(g_align, Wall.t())                                  # [N,3d]: d align0 | d a1 | d a2
@@ -1015,12 +1078,7 @@ class _EncoderName(torch.autograd.Function):
             else:
                 gy = g_c1.contiguous()
             # the layer-0 loss gradient: this node's input gradient goes on top of it (class order: at the very end, below)
-            taken = _take_grad(g_E0, (N, d)) if ro is None else None
-            if taken is not None:
-                dE, g_E0 = taken, None
-            else:
-                dE = _empty(dev, N, d)
-            dRRc, dwcc, dac, gbwc = _layer_bwd(sc, graph, gy, gy2, dE, taken is not None)
+            dE, g_E0, (dRRc, dwcc, dac, gbwc) = _completion_layer_bwd(t, c1_y, graph, gy, gy2, g_E0, take=ro is None)
         if have_align:
             # conv1_alignment: its output fed cat1 and catA -> two gradient sources; its input is align0 = catA[:, :d]
             d_align0 = dcatA[:, :d]
@@ -1036,39 +1094,20 @@ class _EncoderName(torch.autograd.Function):
             levels[0].extend([gemm_task(dw[d:], U11[d:], dNL, tb=True, defer=True), gemm_task(NL, dw[d:], dU11[d:], ta=True, defer=True)])
         # ---- relation side.  The chains' relation gradients land in COMPACT buffers (the rows the edges name) and are put back
         # into full tables by one expand launch; rel_c1's MLP (an output: all rows) writes the full d rel_comp directly
-        wrote_c, dRc_full = False, None
         if have_align or g_relc1 is not None or have_c:
-            rc = t.rc
-            dRa_u = _empty(dev, rc.n, d) if have_align else None
-            # d rel_comp: the layer-0 loss gradient's buffer where this backward may take it over (every writer below then adds)
-            dRc_full = _take_grad(g_Rc0, Rc.shape)
-            wrote_c = dRc_full is not None                                        # "the full buffer holds a contribution"
-            if wrote_c:
-                g_Rc0 = None
-            elif g_relc1 is not None or (have_c and not rc.on):
-                dRc_full = _empty(dev, *Rc.shape)
-            dRc_u = (_empty(dev, rc.n, d) if rc.on else dRc_full) if have_c else None
+            dRa_u = _empty(dev, t.rc.n, d) if have_align else None
+            drc = _RelCompGrad(t.rc, Rc, g_Rc0, mlp=g_relc1 is not None, chain=have_c)
             if have_align:
-                cga = add(0, t.cha.bwd_tasks(dRRa, dwca, dRa_u, False))          # levels 0-1 -> d rel_align (first writer)
+                cga = _add_levels(levels, 0, t.cha.bwd_tasks(dRRa, dwca, dRa_u, False))      # levels 0-1 -> d rel_align (first writer)
                 lv2, cg2, (gL11u, gL12u) = t.ch2.bwd_tasks(dRR2, dwc2, dRa_u, True)     # levels 0-2; d rel_align += at level 2
-                add(0, (lv2, None))
-            if g_relc1 is not None:                                               # rel_c1 = MLP(rel_comp) needs only the loss' gradient:
-                gL11, gL12 = add(0, t.mlc.bwd_tasks(g_relc1.contiguous(), dRc_full, wrote_c))  # levels 0-1 -> d rel_comp
-                wrote_c = True
+                _add_levels(levels, 0, (lv2, None))
+            if g_relc1 is not None:
+                gL11, gL12 = drc.mlp_tasks(levels, t.mlc, g_relc1.contiguous())
             if have_c:
-                if rc.on:                            # own buffer: no ordering against the MLP's write
-                    cgc = add(0, t.chc.bwd_tasks(dRRc, dwcc, dRc_u, False))
-                else:                                # one buffer: the MLP writes it at level 1, the chain adds one level later
-                    cgc = add(1 if wrote_c else 0, t.chc.bwd_tasks(dRRc, dwcc, dRc_full, wrote_c))
+                cgc = drc.chain_tasks(levels, t.chc, dRRc, dwcc)
             run_levels(levels, balance=True)
-            items = ([(dRa_u, None, False)] if have_align else []) + ([(dRc_u, dRc_full if wrote_c else None, True)] if (have_c and rc.on) else [])
-            outs = rc.scatter(items) if items else []
-            if have_align:
-                dRa = outs[0]
-            if have_c and rc.on:
-                dRc = outs[-1]
-            elif have_c or wrote_c:
-                dRc = dRc_full
+            outs, dRc = drc.finish([(dRa_u, None, False)] if have_align else [])
+            dRa = outs[0] if have_align else None
         dwcs = ([dwca, dwc2] if have_align else []) + ([dwcc] if have_c else [])
         cut = _wcat_unpack(dwcs, d, copy=(dw[:d], dU11[:d]) if have_align else None) if dwcs else []
         if have_align:
@@ -1077,14 +1116,12 @@ class _EncoderName(torch.autograd.Function):
         if have_c:
             gc = _layer_grads(cgc, cut[-1], dac, gbwc, d)
         t.cat0_lease.release()
-        if dRc is None and wrote_c:                    # nothing but the taken-over layer-0 gradient
-            dRc = dRc_full
         if ro is not None and dE is not None:          # class order -> the caller's, onto the layer-0 loss gradient where it may
             taken = _take_grad(g_E0, (N, d))
             dE = _scatter_rows(dE, ro.pos32, dst=taken)
             if taken is not None:
                 g_E0 = None
-        dE, dRc = _plus(dE, g_E0), _plus(dRc, g_Rc0)   # layer-0 gradients this backward could not take over: added here
+        dE = _plus(dE, g_E0)                           # a layer-0 gradient this backward could not take over: added here
         return (None, dE, dRc, dRa, None, dNL, dU11, dU21, dWall, gL11, gL12, gL11u, gL12u, *ga, *gc, *g2)
 
 
@@ -1096,25 +1133,20 @@ class _EncoderNoName(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, E, Rc, L11, L12, *pc):
+        # (no _TRACKERS and no seg.nb - 1 bump here: _bn_fwd itself adds the block count to the one layer's counter)
         require_device(E, Rc)
         ctx.set_materialize_grads(False)
         (lc,) = cfg.layers
         N, d = E.shape
         t = SimpleNamespace()
         (t.wc,) = _wcat_pack([pc[3]], [pc[5]], d)
-        t.rc = _RelCompact(cfg.graph, Rc.shape[0])
-        (Rc_u,) = t.rc.gather([Rc])
-        t.chc = _Chain(lc, Rc_u, pc[0], pc[1], pc[2], t.wc, d)
-        t.mlc = _RelMLP(Rc, L11, L12, cfg.mlp_slope)
-        fc, mc = t.chc.fwd_tasks(), t.mlc.fwd_tasks()
+        _, fc, mc = _completion_rel_fwd(t, cfg.graph, lc, pc, t.wc, Rc, L11, L12, cfg.mlp_slope, d)
         run_levels([[fc[0], fc[1], mc[0]], [fc[2], mc[1]]])
         c1 = _empty(E.device, N, d)
+        # (no _RowOrder, no normalise / dropout in front of the layer: it reads the table itself, src/jmac_model.py:214)
         t.sc = _layer_fwd(lc, E, t.wc, t.chc.RR, pc[4].reshape(-1), cfg.graph, cfg.training, c1, table_dtype=cfg.table_dtype,
-                          seg=getattr(cfg, "seg", None), compact=t.rc.on)
-        if CAPTURE is not None:
-            CAPTURE.update(conv1_completion=(E.detach(), Rc.detach()))
-            CAPTURE["conv1_completion.tables"] = (t.sc.PQZ, t.rc.full_rows(t.sc.RR))
-        rel_c1, t.mlc.out, t.sc.y = t.mlc.out, None, None
+                          seg=cfg.seg, compact=t.rc.on)
+        rel_c1 = _completion_outputs(t, E, Rc)
         ctx.t, ctx.cfg, ctx.dims = t, cfg, (N, d)
         ctx.save_for_backward(E, Rc, L11, L12, c1)
         return c1, rel_c1, E, Rc                         # E, Rc: layer 0 of the completion layers, as aliases (see INPLACE_GRADS)
@@ -1124,59 +1156,30 @@ class _EncoderNoName(torch.autograd.Function):
         t, cfg = ctx.t, ctx.cfg
         N, d = ctx.dims
         E, Rc, L11, L12, c1 = ctx.saved_tensors
-        sc = SimpleNamespace(**vars(t.sc))                   # c1 is an output: never stored on ctx.t (reference cycle)
-        sc.y = c1
-        dev = E.device
-        dE = dRc = None
+        dE = gL11 = gL12 = None
         gc = [None] * 8
-        levels: List[List[GemmTask]] = [[] for _ in range(5)]
-        rc = t.rc
-        # d rel_comp: the layer-0 loss gradient's buffer where this backward may take it over (every writer below then adds)
-        dRc_full = _take_grad(g_Rc0, Rc.shape)
-        took_rc = dRc_full is not None
-        if took_rc:
-            g_Rc0 = None
-        elif g_relc1 is not None or not rc.on:
-            dRc_full = _empty(dev, *Rc.shape)
-        dRc_u = _empty(dev, rc.n, d) if rc.on else dRc_full
-        wrote = False                                        # the chain wrote dRc_u
+        levels: List[List[GemmTask]] = [[] for _ in range(3)]
+        drc = _RelCompGrad(t.rc, Rc, g_Rc0, mlp=g_relc1 is not None, chain=g_c1 is not None)
         if g_c1 is not None:
-            taken = _take_grad(g_E0, (N, d))
-            if taken is not None:
-                dE, g_E0 = taken, None
-            else:
-                dE = _empty(dev, N, d)
-            dRRc, dwcc, dac, gbwc = _layer_bwd(sc, cfg.graph, g_c1.contiguous(), None, dE, taken is not None)
-            lv, cgc = t.chc.bwd_tasks(dRRc, dwcc, dRc_u, took_rc and not rc.on)
-            for i, l in enumerate(lv):
-                levels[i].extend(l)
-            wrote = True
-        gL11 = gL12 = None
-        wrote_full = took_rc                                 # the full buffer holds a contribution
+            dE, g_E0, (dRRc, dwcc, dac, gbwc) = _completion_layer_bwd(t, c1, cfg.graph, g_c1.contiguous(), None, g_E0)
         if g_relc1 is not None:
-            first = (rc.on or not wrote) and not took_rc     # compact: the MLP has the full buffer to itself
-            lv, (gL11, gL12) = t.mlc.bwd_tasks(g_relc1.contiguous(), dRc_full, not first)
-            for i, l in enumerate(lv):
-                levels[(0 if (rc.on or not wrote) else 2) + i].extend(l)
-            wrote_full = True
-        run_levels(levels)
-        if rc.on and wrote:
-            (dRc_buf,) = rc.scatter([(dRc_u, dRc_full if wrote_full else None, True)])
-        else:
-            dRc_buf = dRc_full
-        wrote = wrote or wrote_full
+            gL11, gL12 = drc.mlp_tasks(levels, t.mlc, g_relc1.contiguous())
+        if g_c1 is not None:
+            cgc = drc.chain_tasks(levels, t.chc, dRRc, dwcc)
+        run_levels(levels)                                   # (no balance_levels: at most six products, none of them crowded)
+        dRc = drc.finish()[1]
         if g_c1 is not None:
             gc = _layer_grads(cgc, _wcat_unpack([dwcc], d)[0], dac, gbwc, d)
-        dRc = dRc_buf if wrote else None
-        return (None, _plus(dE, g_E0), _plus(dRc, g_Rc0), gL11, gL12, *gc)
+        return (None, _plus(dE, g_E0), dRc, gL11, gL12, *gc)
 
 
-def _cfg(model, layers, graph):
-    training = model.training
-    return SimpleNamespace(layers=layers, graph=graph, training=training,
+def _cfg(model, layers, graph, seg=None, cache=None, info_persistent=False):
+    """Every field the nodes read.  BatchNorm follows the layers' own mode; ``cache``: buffers that outlive a step (see _Cat0Slot)."""
+    return SimpleNamespace(layers=layers, graph=graph, training=layers[0].training,
                            p_drop=float(model.completion_dropout.p) if model.completion_dropout.training else 0.0,
                            mlp_slope=float(model.atv_mlp.negative_slope),
-                           table_dtype=getattr(model, "table_dtype", torch.float32))
+                           table_dtype=getattr(model, "table_dtype", torch.float32),
+                           seg=seg, cache=cache, info_persistent=bool(info_persistent))
 
 
 def forward_name(model, comp_att, rel_comp, rel_align, info, graph: RelGraph, seg: Optional[RowBlocks] = None,
@@ -1185,10 +1188,7 @@ def forward_name(model, comp_att, rel_comp, rel_align, info, graph: RelGraph, se
     block-diagonal union, the relation tables stacked likewise): BatchNorm statistics per block.  ``info_persistent``: the
     caller keeps ``info`` (a device tensor) alive and unchanged between calls -- its cat buffer may be cached."""
     la, lc, l2 = model.conv1_alignment, model.conv1_completion, model.conv2_alignment
-    cfg = _cfg(model, (la, lc, l2), graph)
-    cfg.training = la.training                                           # BatchNorm follows the layers' own mode
-    cfg.cache = model.__dict__.setdefault("_encoder_cache", {})          # buffers that outlive a step (see _Cat0Slot)
-    cfg.seg, cfg.info_persistent = seg, bool(info_persistent)
+    cfg = _cfg(model, (la, lc, l2), graph, seg, model.__dict__.setdefault("_encoder_cache", {}), info_persistent)
     # -> (align_out, c1, rel_c1, comp0, rel0): comp0 / rel0 alias comp_att / rel_comp -- hand THEM on as layer 0 of the completion
     # layers, so that the layer-0 loss gradient reaches this node's backward (see INPLACE_GRADS)
     return _EncoderName.apply(cfg, comp_att, rel_comp, rel_align, info, model.name_linear, model.uni_linear1_1,
@@ -1200,7 +1200,5 @@ def forward_name(model, comp_att, rel_comp, rel_align, info, graph: RelGraph, se
 def forward_no_name(model, comp_att, rel_comp, graph: RelGraph, seg: Optional[RowBlocks] = None):
     """(c1, rel_c1, comp0, rel0) of JMAC.forward_no_name on the fused node (comp0 / rel0: aliases of the inputs, as above)."""
     lc = model.conv1_completion
-    cfg = _cfg(model, (lc,), graph)
-    cfg.training = lc.training
-    cfg.seg = seg
-    return _EncoderNoName.apply(cfg, comp_att, rel_comp, model.rel_linear11, model.rel_linear12, *_layer_inputs(lc))
+    return _EncoderNoName.apply(_cfg(model, (lc,), graph, seg), comp_att, rel_comp, model.rel_linear11, model.rel_linear12,
+                                *_layer_inputs(lc))

@@ -37,21 +37,24 @@ def _model(d, n, nr, di, no_name, seed):
     return m
 
 
-def _run(m, fused, ei, et, n, nr, use, G):
-    """One forward + backward; ``use`` selects which outputs feed the scalar loss."""
+def _run(m, fused, ei, et, n, nr, use, G, after_forward=None, layer0_loss=None):
+    """One forward + backward; ``use`` selects which outputs feed the scalar loss.  ``after_forward``: called between the two;
+    ``layer0_loss(comp0, rel0)``: one more term, on layer 0 of the completion layers (G without "c0" / "r0": the only one there)."""
     m.fused_encoder = fused
     for lay in (m.conv1_alignment, m.conv2_alignment, m.conv1_completion):
         lay.fused = fused                                         # op by op all the way down: no node of encoder.py involved
     m.zero_grad(set_to_none=True)
     state = {k: v.clone() for k, v in m.state_dict().items() if "running" in k or "num_batches" in k}
     align_out, comp, rel = m.forward_base(ei, et, [0, n], [0, nr])
-    loss = 0
+    if after_forward is not None:
+        after_forward()
+    loss = 0 if layer0_loss is None else layer0_loss(comp[0], rel[0])
     if "align" in use:
         loss = loss + (align_out * G["align"]).sum()
     if "comp" in use:
-        loss = loss + (comp[1] * G["c1"]).sum() + (comp[0] * G["c0"]).sum()
+        loss = loss + (comp[1] * G["c1"]).sum() + ((comp[0] * G["c0"]).sum() if "c0" in G else 0)
     if "rel" in use:
-        loss = loss + (rel[1] * G["r1"]).sum() + (rel[0] * G["r0"]).sum()
+        loss = loss + (rel[1] * G["r1"]).sum() + ((rel[0] * G["r0"]).sum() if "r0" in G else 0)
     loss.backward()
     grads = {k: (p.grad.clone() if p.grad is not None else None) for k, p in m.named_parameters()}
     after = {k: v.clone() for k, v in m.state_dict().items() if "running" in k or "num_batches" in k}
@@ -59,11 +62,16 @@ def _run(m, fused, ei, et, n, nr, use, G):
     return (align_out.detach(), comp[1].detach(), rel[1].detach()), grads, after
 
 
-@pytest.mark.parametrize("use", [("align", "comp", "rel"), ("align",), ("comp", "rel"), ("rel",), ("comp",)])
+USES = [("align", "comp", "rel"), ("align",), ("comp", "rel"), ("rel",), ("comp",), ("align", "rel"), ("align", "comp")]
+# forward_no_name's "align" output IS completion layer 1: the patterns that would only repeat it, as the patterns it has
+NO_NAME_USE = {("align",): ("comp",), ("align", "rel"): ("comp", "rel"), ("align", "comp"): ("comp",)}
+
+
+@pytest.mark.parametrize("use", USES)
 @pytest.mark.parametrize("no_name", [False, True], ids=["name", "no-name"])
 def test_fused_encoder_equals_op_by_op_path(no_name, use):
-    if no_name and use == ("align",):
-        use = ("comp",)                                          # forward_no_name's "align" output IS completion layer 1
+    if no_name:
+        use = NO_NAME_USE.get(use, use)
     n, nr, d, di = 700, 37, 32, 20
     rng = np.random.default_rng(5)
     ei, et = random_graph(rng, n, nr, 2600, hub=300)
@@ -103,6 +111,131 @@ def test_fused_encoder_equals_op_by_op_path(no_name, use):
     assert_close(a1, a2, 2e-5, 1e-6, "eval align_out")
     assert_close(c1[1], c2[1], 2e-5, 1e-6, "eval c1")
     assert_close(r1[1], r2[1], 2e-5, 1e-6, "eval rel_c1")
+
+
+def _setup(no_name):
+    """The shapes of the test above on a graph whose edges name 9 of the 37 relation rows (so that COMPACT_RELATIONS has rows
+    to leave out) -> model (train mode), edges, the linear loss terms' weights."""
+    n, nr, d, di = 700, 37, 32, 20
+    rng = np.random.default_rng(5)
+    ei, et = random_graph(rng, n, 9, 2600, hub=300)
+    et = np.array([0, 3, 7, 8, 20, 21, 30, 35, 36])[et]
+    ei, et = torch.from_numpy(ei).to(DEV), torch.from_numpy(et).to(DEV)
+    m = _model(d, n, nr, di, no_name, 11)
+    gen = torch.Generator(device=DEV).manual_seed(3)
+    G = {k: torch.randn(s, device=DEV, generator=gen) for k, s in
+         (("align", (n, d)), ("c1", (n, d)), ("c0", (n, d)), ("r1", (nr, d)), ("r0", (nr, d)))}
+    m.train()
+    return m, ei, et, n, nr, G
+
+
+def _layer0_takeover(no_name, only_rel, compact):
+    """{INPLACE_GRADS: (parameter gradients, buffers taken over)} of one step whose layer-0 gradients come fresh out of
+    losses.triple_l1_margin_loss(comp[0], rel[0]); the other outputs enter through linear terms."""
+    from jmac_amd import encoder, losses
+    m, ei, et, n, nr, G = _setup(no_name)
+    gen = torch.Generator(device=DEV).manual_seed(7)
+    B, K = 64, 5
+    h, t = (torch.randint(0, n, (B * (K + 1),), device=DEV, generator=gen) for _ in range(2))
+    r = torch.randint(0, nr, (B * (K + 1),), device=DEV, generator=gen)
+    G = {k: v for k, v in G.items() if k not in ("c0", "r0")}        # layer 0 feeds the loss op alone: its gradient stays that op's buffer
+    layer0 = lambda comp0, rel0: losses.triple_l1_margin_loss(comp0, rel0, h, r, t, B, m.margin_completion).sum()
+    use = ("rel",) if only_rel else (("comp", "rel") if no_name else ("align", "comp", "rel"))
+    res = {}
+    for flag in (True, False):
+        encoder.INPLACE_GRADS, encoder.COMPACT_RELATIONS = flag, compact
+        try:
+            before = encoder.INPLACE_COUNT
+            _, grads, _ = _run(m, True, ei, et, n, nr, use, G, layer0_loss=layer0)
+            res[flag] = (grads, encoder.INPLACE_COUNT - before)
+        finally:
+            encoder.INPLACE_GRADS = encoder.COMPACT_RELATIONS = True
+    return res
+
+
+@pytest.mark.parametrize("compact", [True, False], ids=["compact", "all-rows"])
+@pytest.mark.parametrize("only_rel", [False, True], ids=["all-outputs", "rel-only"])
+@pytest.mark.parametrize("no_name", [False, True], ids=["name", "no-name"])
+def test_layer0_loss_gradients_are_taken_over_by_both_nodes(no_name, only_rel, compact):
+    """encoder._take_grad on forward_name AND forward_no_name, relation compaction on and off: a step whose layer-0 gradients are
+    buffers a loss op of this library has just allocated takes both over (INPLACE_COUNT moves by two) and leaves the gradients
+    of the form where autograd adds (INPLACE_GRADS = False) to rounding -- the association of the contributions differs, nothing
+    else (the bound of test_gpu_determinism's test of the bench step).  With only the relation outputs used conv1_completion's
+    backward does not run: there is no entity-side input gradient to put onto the loss' buffer, so the relation table's is the one
+    buffer taken (both nodes)."""
+    res = _layer0_takeover(no_name, only_rel, compact)
+    counts = (res[True][1], res[False][1])
+    print("buffers taken over (INPLACE_GRADS on, off):", counts)
+    assert counts == ((1 if only_rel else 2), 0), counts
+    n_checked = 0
+    for name, ref in res[False][0].items():
+        g = res[True][0][name]
+        if ref is None:
+            assert g is None, name
+            continue
+        err, bound = float((g - ref).abs().max()), 2e-6 * max(float(ref.abs().max()), 1e-30)
+        print("%-40s max|err| %.3e bound %.3e" % (name, err, bound))
+        assert err <= bound, name
+        n_checked += 1
+    assert n_checked >= 3, n_checked
+
+
+def _launch_plan(no_name, use, compact, monkeypatch):
+    from jmac_amd import encoder
+    m, ei, et, n, nr, G = _setup(no_name)
+    log, split = [], []
+    real = encoder.grouped_gemm
+
+    def counting(tasks):
+        k = len([t_ for t_ in tasks if t_ is not None])
+        log.extend(min(encoder.MAX_TASKS, k - i) for i in range(0, k, encoder.MAX_TASKS))       # (one launch per MAX_TASKS tasks)
+        return real(tasks)
+    monkeypatch.setattr(encoder, "grouped_gemm", counting)
+    monkeypatch.setattr(encoder, "COMPACT_RELATIONS", compact)
+    _run(m, True, ei, et, n, nr, use, G, after_forward=lambda: split.append(len(log)))
+    return tuple(log[:split[0]]), tuple(log[split[0]:])
+
+
+# Grouped-GEMM launches of one forward and one backward, as (tasks per launch forward, backward), by node, used outputs and
+# COMPACT_RELATIONS: the dependency levels of the relation side (jmac_amd/encoder.py: run_levels), counted on the device.  Level
+# order and accumulate flags are all that keeps the writers of a shared output apart, so a launch more, or a product in another
+# launch, is a changed schedule.  forward_no_name with all rows and both outputs used: rel_c1's MLP at levels 0-1, the chain adds
+# onto the same d rel_comp at levels 1-2 -- three launches, forward_name's schedule for the same branch.
+LAUNCH_PLAN = {
+    ("name", ("align", "comp", "rel"), True): ((9, 5, 1), (8, 11, 11)),
+    ("name", ("align", "comp", "rel"), False): ((9, 5, 1), (8, 10, 12)),
+    ("name", ("align",), True): ((9, 5, 1), (7, 10, 9)),
+    ("name", ("align",), False): ((9, 5, 1), (7, 10, 9)),
+    ("name", ("comp", "rel"), True): ((9, 5, 1), (4, 6)),
+    ("name", ("comp", "rel"), False): ((9, 5, 1), (2, 3, 5)),
+    ("name", ("rel",), True): ((9, 5, 1), (2, 2)),
+    ("name", ("rel",), False): ((9, 5, 1), (2, 2)),
+    ("name", ("comp",), True): ((9, 5, 1), (2, 4)),
+    ("name", ("comp",), False): ((9, 5, 1), (2, 4)),
+    ("name", ("align", "rel"), True): ((9, 5, 1), (8, 11, 11)),
+    ("name", ("align", "rel"), False): ((9, 5, 1), (8, 10, 12)),
+    ("name", ("align", "comp"), True): ((9, 5, 1), (7, 10, 9)),
+    ("name", ("align", "comp"), False): ((9, 5, 1), (7, 10, 9)),
+    ("no-name", ("align", "comp", "rel"), True): ((3, 2), (4, 6)),
+    ("no-name", ("align", "comp", "rel"), False): ((3, 2), (2, 4, 4)),
+    ("no-name", ("comp", "rel"), True): ((3, 2), (4, 6)),
+    ("no-name", ("comp", "rel"), False): ((3, 2), (2, 4, 4)),
+    ("no-name", ("rel",), True): ((3, 2), (2, 2)),
+    ("no-name", ("rel",), False): ((3, 2), (2, 2)),
+    ("no-name", ("comp",), True): ((3, 2), (2, 4)),
+    ("no-name", ("comp",), False): ((3, 2), (2, 4)),
+}
+
+
+@pytest.mark.parametrize("compact", [True, False], ids=["compact", "all-rows"])
+@pytest.mark.parametrize("use", USES)
+@pytest.mark.parametrize("no_name", [False, True], ids=["name", "no-name"])
+def test_grouped_launch_plan_of_the_encoder_nodes(no_name, use, compact, monkeypatch):
+    if no_name:
+        use = NO_NAME_USE.get(use, use)
+    got = _launch_plan(no_name, use, compact, monkeypatch)
+    print("launch plan", ("no-name" if no_name else "name", use, compact), got)
+    assert got == LAUNCH_PLAN["no-name" if no_name else "name", use, compact]
 
 
 def test_fused_encoder_keeps_its_name_block_buffer_across_steps():
