@@ -542,6 +542,25 @@ int jmac_sim_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, i
                                   const float* r1, const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k,
                                   float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
 
+/* Manhattan alignment (sim(metric='manhattan'), modules/finding/similarity.py:47-49): the three entry points above for
+ * s(i,j) = 1 - dist(i,j), dist(i,j) = the single running fp32 sum over k = 0 .. d-1 of |A[i,k] - B[j,k]| -- jmac_l1_score_f32's bits,
+ * the same from either side (|x - y| == |y - x|) -- and c(i,j) = 2*s(i,j) - r1[i] - r2[j]; r1 == r2 == NULL: c = s.  Every decision
+ * is taken on c, larger first, equal values -> lower index first; the n1 x n2 matrix is never written.  The L1 tile kernel of the
+ * link-prediction entry points runs with count / filter / viable epilogues on c; narrow matrices (n2 < 8192) are staged in the
+ * workspace.  lda, ldb % 4 == 0 (JMAC_EDIM); any d.  1 <= k <= min(64, n2); val is required.  Otherwise the contracts, error codes
+ * and workspace sizes of jmac_sim_csls_topk_f32, jmac_sim_csls_topk_viable_f32 and jmac_sim_csls_rank_f32. */
+size_t jmac_l1_csls_topk_workspace_bytes(int64_t n1, int64_t n2, int64_t d, int32_t k);
+int jmac_l1_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                          const float* r1, const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes,
+                          jmac_stream_t stream);
+int jmac_l1_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                                 const float* r1, const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k,
+                                 float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
+size_t jmac_l1_csls_rank_workspace_bytes(int64_t n1, int64_t n2);
+int jmac_l1_csls_rank_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                          const float* r1, const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes,
+                          jmac_stream_t stream);
+
 /* Stable one-to-one alignment (replaces galeshapley, modules/finding/alignment.py:115-168, run to convergence): deferred acceptance
  * of the n1 suitors (rows) on candidate lists cand_idx / cand_val [n1, ld >= k] (int32 reviewer ids in [0, n2), best first, -1 ends
  * a list, no id twice in a list; cand_val[i,p] = c(i, cand_idx[i,p]) fp32, finite).  Order relation on both sides: larger c first,

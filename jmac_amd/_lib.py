@@ -150,6 +150,11 @@ _SIGS = {
     "jmac_sim_csls_topk_workspace_bytes": (sz, [i64, i64, i32]),
     "jmac_sim_csls_topk_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp, vp, sz, vp]),
     "jmac_sim_csls_topk_viable_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+    "jmac_l1_csls_topk_workspace_bytes": (sz, [i64, i64, i64, i32]),
+    "jmac_l1_csls_topk_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp, vp, sz, vp]),
+    "jmac_l1_csls_topk_viable_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+    "jmac_l1_csls_rank_workspace_bytes": (sz, [i64, i64]),
+    "jmac_l1_csls_rank_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
     "jmac_stable_match_workspace_bytes": (sz, [i64, i64]),
     "jmac_stable_match_f32": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "jmac_gemm_f32": (C.c_int, [vp, i64, i32, vp, i64, i32, i64, i64, i64, vp, i64, vp]),

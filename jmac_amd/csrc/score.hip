@@ -44,6 +44,10 @@ __device__ __forceinline__ float add_absdiff(float acc, float a, float b) {
     return r;
 }
 
+// THE rescored value, in this order everywhere it is computed.  2 s is exact in fp32, so fma(2, s, -r1) and the unfused form round
+// identically: the bits do not depend on the compiler's contraction choice.
+__device__ __forceinline__ float csls_value(float s, float r1, float r2) { return 2.f * s - r1 - r2; }
+
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return __uint_as_float((uint32_t)(*p) << 16); }
 
@@ -215,6 +219,12 @@ struct LinkRankArgs {
     int32_t* cnt;                         // [B] entries appended (may exceed cap: that row overflowed)
     float* cval;                          // [B, cap] -dist
     int32_t* cidx;                        // [B, cap] n
+    // Manhattan alignment (jmac_l1_csls_*): nl = 1, er = the row operand itself (dq = its leading dimension), tab[0] = the column
+    // operand.  The LR_CSLS_* epilogues decide on c(b, n) = csls_value(1 - dist[b, n], r1[b], r2[n]) (r1 == NULL, with r2: on
+    // s = 1 - dist): gs holds c(b, gold_b), ntau the thresholds tau_b in c, cval the appended c.
+    const float *r1, *r2;                 // [B], [N]
+    const int32_t* row_id;                // VIABLE: [B] the suitor id of row b
+    const unsigned long long* best;       // VIABLE: [N] the reviewers' words, 0 = free
 };
 
 // [begin, end) of query (h, r)'s tails in the index, searched by ONE WAVE (all 64 lanes call this): every round the lanes
@@ -354,7 +364,12 @@ __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) 
 //   LR_FILTER  append (-dist, n) where dist <= tau_b to row b's candidate list; the 16 lanes of a row claim their slots with
 //              ONE integer atomic (list order varies from run to run; the select kernel sorts, so the results do not)
 // STORE and FILTER cover columns [n_off, N).
-enum { LR_COUNT = 0, LR_STORE = 1, LR_FILTER = 2 };
+// The same epilogues on the Manhattan alignment value c = csls_value(1 - dist, r1, r2), larger first (jmac_l1_csls_*; what
+// sim_gemm_kernel's SG_CSLS_* epilogues are to the cosine similarity):
+//   LR_CSLS_COUNT   count the columns whose c beats gs[b] = c(b, gold_b): larger, or equal with an index below gold_b
+//   LR_CSLS_FILTER  append (c, n) where c >= tau_b
+//   LR_CSLS_VIABLE  ... and tk_pack(c, row_id[b]) > best[n]: the suitor would displace what reviewer n holds
+enum { LR_COUNT = 0, LR_STORE = 1, LR_FILTER = 2, LR_CSLS_COUNT = 3, LR_CSLS_FILTER = 4, LR_CSLS_VIABLE = 5 };
 template <typename TT, bool VEC, int EPI = LR_COUNT>
 __global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) {
     __shared__ __attribute__((aligned(16))) float As[2][L1_K][L1_LD];
@@ -481,6 +496,67 @@ __global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) 
         }
         return;
     }
+    constexpr bool CSLS = EPI >= LR_CSLS_COUNT;
+    // alignment: the decided value of acc[i][j] is c, or s when there are no terms (cs is block-uniform)
+    const bool cs = CSLS && a.r1 != nullptr;
+    float r2v[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (CSLS)
+        if (cs) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r2v[j] = a.r2[min(n0 + tx * 4 + j, N - 1)];
+        }
+    auto decided = [&](float dist, float r1b, int j) -> float {
+        const float s = 1.f - dist;
+        return cs ? csls_value(s, r1b, r2v[j]) : s;
+    };
+    if constexpr (EPI == LR_CSLS_FILTER || EPI == LR_CSLS_VIABLE) {
+        unsigned long long bw[4] = {0ull, 0ull, 0ull, 0ull};
+        if constexpr (EPI == LR_CSLS_VIABLE) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bw[j] = a.best[min(n0 + tx * 4 + j, N - 1)];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + ty * 4 + i;
+            const bool row_ok = b < B;
+            const float nt = row_ok ? a.ntau[(int64_t)b * a.tau_stride] : INFINITY;
+            const float r1b = (cs && row_ok) ? a.r1[b] : 0.f;
+            int rid = 0;
+            if constexpr (EPI == LR_CSLS_VIABLE) rid = row_ok ? a.row_id[b] : 0;
+            bool pass[4];
+            float v[4];
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] = decided(acc[i][j], r1b, j);
+                pass[j] = row_ok && n0 + tx * 4 + j < N && v[j] >= nt;
+                if constexpr (EPI == LR_CSLS_VIABLE) pass[j] = pass[j] && tk_pack(v[j], rid) > bw[j];
+                c += pass[j] ? 1 : 0;
+            }
+            if (!__any(c)) continue;                          // the LR_FILTER append, with c for -dist
+            int inc = c;                                      // inclusive prefix over the row's 16 lanes
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                const int t = __shfl_up(inc, o, 16);
+                if (tx >= o) inc += t;
+            }
+            const int tot = __shfl(inc, 15, 16);
+            int base = 0;
+            if (tx == 0 && tot) base = atomicAdd(a.cnt + b, tot);
+            base = __shfl(base, 0, 16);
+            int slot = base + inc - c;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (pass[j]) {
+                    if (slot < a.cap) {
+                        a.cval[(int64_t)b * a.cap + slot] = v[j];
+                        a.cidx[(int64_t)b * a.cap + slot] = n0 + tx * 4 + j;
+                    }
+                    ++slot;
+                }
+        }
+        return;
+    }
     // count: 4 rows x 4 columns per thread; the 16 threads of a row (tx = 0..15: consecutive lanes) are summed with DPP
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -488,12 +564,18 @@ __global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) 
         const bool row_ok = b < B;
         const float gs = row_ok ? a.gs[b] : 0.f;
         const int g = row_ok ? a.gold[b] : 0;
+        const float r1b = (cs && row_ok) ? a.r1[b] : 0.f;
         int c = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int n = n0 + tx * 4 + j;
-            const float sc = acc[i][j];
-            c += (row_ok && n < N && (sc < gs || (sc == gs && n < g))) ? 1 : 0;
+            if constexpr (CSLS) {
+                const float sc = decided(acc[i][j], r1b, j);
+                c += (row_ok && n < N && (sc > gs || (sc == gs && n < g))) ? 1 : 0;
+            } else {
+                const float sc = acc[i][j];
+                c += (row_ok && n < N && (sc < gs || (sc == gs && n < g))) ? 1 : 0;
+            }
         }
         c += __shfl_xor(c, 1);
         c += __shfl_xor(c, 2);
@@ -590,10 +672,6 @@ template <> struct SgExt<true, 0> { typedef SimStats type; };
 template <> struct SgExt<false, SG_CSLS_COUNT> { typedef SimCsls type; };
 template <> struct SgExt<false, SG_CSLS_FILTER> { typedef SimCsls type; };
 template <> struct SgExt<false, SG_CSLS_VIABLE> { typedef SimViable type; };
-
-// THE rescored value, in this order everywhere it is computed.  2 s is exact in fp32, so fma(2, s, -r1) and the unfused form round
-// identically: the bits do not depend on the compiler's contraction choice.
-__device__ __forceinline__ float csls_value(float s, float r1, float r2) { return 2.f * s - r1 - r2; }
 
 // the DPP-selected lane's v (old = 0 with bound_ctrl: every source lane of the controls used here exists; ROWS: rows written)
 template <int CTRL, int ROWS = 0xF>
@@ -1497,12 +1575,27 @@ __device__ __forceinline__ void for_each_row_score(const float* __restrict__ aro
     }
 }
 
+// s(m, n) = 1 - dist(m, n) of ONE pair of rows with link_rank_tile_kernel's sum: the single running fp32 sum over k = 0 .. d-1 of
+// |a[k] - b[k]| (the tile's zero padding adds exact zeros), so the bits are the tile's.  One lane per pair.
+__device__ __forceinline__ float l1_row_sim(const float* __restrict__ arow, const float* __restrict__ brow, int d) {
+    float acc = 0.f;
+    for (int q = 0; q < d; ++q) acc = add_absdiff(acc, arow[q], brow[q]);
+    return 1.f - acc;
+}
+template <class F>
+__device__ __forceinline__ void for_each_row_l1(const float* __restrict__ arow, const float* __restrict__ Bm, int64_t ldb, int N,
+                                                int d, F f) {
+    for (int n = threadIdx.x; n < N; n += kBlock) f(n, l1_row_sim(arow, Bm + (int64_t)n * ldb, d));
+}
+
 // CS: the lists hold CSLS-rescored values (jmac_sim_csls_topk_f32), so a recomputed score is rescored too before it is used
 // (r1 / r2 are not read otherwise)
 // VIABLE (jmac_sim_csls_topk_viable_f32): the lists hold viable columns only; the sample's k best may end in masked (-inf)
 // entries and a recomputed row skips the columns whose word best[n] the row's own word tk_pack(c, row_id[b]) does not beat;
 // what is missing of the k comes out as (idx -1, val -inf).  CS is then decided at run time (r1 != NULL).
-template <bool CS, bool VIABLE>
+// L1 (jmac_l1_csls_topk_*): the Manhattan form -- a recomputed score is s = 1 - dist from the L1 tile kernel's sequential sum
+// (l1_row_sim), CS decided at run time
+template <bool CS, bool VIABLE, bool L1 = false>
 __device__ __forceinline__ void cand_select_body(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                  int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
                                                  const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
@@ -1535,18 +1628,22 @@ __device__ __forceinline__ void cand_select_body(const float* __restrict__ A, in
     const float* arow = A + (int64_t)b * lda;
     float r1b = 0.f;
     if constexpr (CS) r1b = r1[b];
-    if constexpr (VIABLE) r1b = r1 != nullptr ? r1[b] : 0.f;
+    if constexpr (VIABLE || L1) r1b = r1 != nullptr ? r1[b] : 0.f;
     auto rescored = [&](int n, float v) -> float {
         if constexpr (CS) return csls_value(v, r1b, r2[n]);
-        else if constexpr (VIABLE) return r1 != nullptr ? csls_value(v, r1b, r2[n]) : v;
+        else if constexpr (VIABLE || L1) return r1 != nullptr ? csls_value(v, r1b, r2[n]) : v;
         else return v;
+    };
+    auto for_each_score = [&](auto f) {
+        if constexpr (L1) for_each_row_l1(arow, Bm, ldb, N, d, f);
+        else for_each_row_score(arow, Bm, ldb, N, d, f);
     };
     if constexpr (VIABLE) {
         const int rid = row_id[b];
         tk_select_recomputed(
             tk, k,
             [&](auto f) {
-                for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) {
+                for_each_score([&](int n, float v) {
                     const float c = rescored(n, v);
                     if (tk_pack(c, rid) > best[n]) f(n, c);
                 });
@@ -1554,19 +1651,20 @@ __device__ __forceinline__ void cand_select_body(const float* __restrict__ A, in
             emit);
     } else {
         tk_select_recomputed(
-            tk, k, [&](auto f) { for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) { f(n, rescored(n, v)); }); }, emit);
+            tk, k, [&](auto f) { for_each_score([&](int n, float v) { f(n, rescored(n, v)); }); }, emit);
     }
 }
 
-template <bool CS>
+template <bool CS, bool L1 = false>
 __global__ __launch_bounds__(kBlock) void cand_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                              int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
                                                              const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
                                                              const float* __restrict__ sval, const int32_t* __restrict__ sidx,
                                                              float* __restrict__ val, int32_t* __restrict__ idx,
                                                              const float* __restrict__ r1, const float* __restrict__ r2) {
-    cand_select_body<CS, false>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx, cap, sval, sidx, val, idx, r1, r2, nullptr, nullptr);
+    cand_select_body<CS, false, L1>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx, cap, sval, sidx, val, idx, r1, r2, nullptr, nullptr);
 }
+template <bool L1 = false>
 __global__ __launch_bounds__(kBlock) void cand_select_viable_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                                     int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
                                                                     const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
@@ -1575,7 +1673,7 @@ __global__ __launch_bounds__(kBlock) void cand_select_viable_kernel(const float*
                                                                     const float* __restrict__ r1, const float* __restrict__ r2,
                                                                     const int32_t* __restrict__ row_id,
                                                                     const unsigned long long* __restrict__ best) {
-    cand_select_body<false, true>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx, cap, sval, sidx, val, idx, r1, r2, row_id, best);
+    cand_select_body<false, true, L1>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx, cap, sval, sidx, val, idx, r1, r2, row_id, best);
 }
 
 // c(i, gold[i]) of every row, from the product's own contraction sequence (sim_tile_32x32: v_mfma_f32_32x32x2_f32 over k in
@@ -1626,6 +1724,35 @@ __global__ __launch_bounds__(kBlock) void viable_inplace_kernel(float* __restric
 __global__ __launch_bounds__(kBlock) void viable_topk_finish_kernel(const float* __restrict__ val, int32_t* __restrict__ idx, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n && val[i] == -INFINITY) idx[i] = -1;
+}
+
+// ---- Manhattan alignment (jmac_l1_csls_*): csls_gold_kernel / csls_inplace_kernel / viable_inplace_kernel for s = 1 - dist ----
+// gval[m] = c(m, gold[m]) from l1_row_sim (the tile kernel's bits: the count's "equal, lower index first" is exact at the gold
+// column itself); rank[m] = 1.  One lane per row.
+__global__ __launch_bounds__(kBlock) void l1_csls_gold_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                              int64_t ldb, int M, int d, const float* __restrict__ r1,
+                                                              const float* __restrict__ r2, const int32_t* __restrict__ gold,
+                                                              float* __restrict__ gval, int32_t* __restrict__ rank) {
+    const int m = blockIdx.x * kBlock + threadIdx.x;
+    if (m >= M) return;
+    const int g = gold[m];
+    const float s = l1_row_sim(A + (int64_t)m * lda, Bm + (int64_t)g * ldb, d);
+    gval[m] = r1 != nullptr ? csls_value(s, r1[m], r2[g]) : s;
+    rank[m] = 1;
+}
+// a stored slab of -dist (the tile kernel's LR_STORE) -> c in place: s = 1 - dist, rescored when r1 != NULL, and with best != NULL
+// an entry whose word does not beat its reviewer's becomes -inf
+__global__ __launch_bounds__(kBlock) void l1_csls_inplace_kernel(float* __restrict__ S, int64_t lds, int n2, const float* __restrict__ r1,
+                                                                 const float* __restrict__ r2, const int32_t* __restrict__ row_id,
+                                                                 const unsigned long long* __restrict__ best) {
+    float* row = S + (int64_t)blockIdx.x * lds;
+    const float a = r1 != nullptr ? r1[blockIdx.x] : 0.f;
+    const int rid = best != nullptr ? row_id[blockIdx.x] : 0;
+    for (int n = threadIdx.x; n < n2; n += kBlock) {
+        const float s = 1.f + row[n];                          // == 1 - dist, bit for bit
+        const float c = r1 != nullptr ? csls_value(s, a, r2[n]) : s;
+        row[n] = (best == nullptr || tk_pack(c, rid) > best[n]) ? c : -INFINITY;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2428,7 +2555,7 @@ static int sim_topk_impl(const float* A, int64_t lda, const float* B, int64_t ld
         return rc;
     // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes (and rescores)
     if (best)
-        hipLaunchKernelGGL(cand_select_viable_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt,
+        hipLaunchKernelGGL(cand_select_viable_kernel<false>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt,
                            f.cval, f.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2, row_id, best);
     else
         hipLaunchKernelGGL(r1 ? cand_select_kernel<true> : cand_select_kernel<false>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb,
@@ -2774,6 +2901,120 @@ int jmac_sim_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, i
     if (!ws || ws_bytes < jmac_sim_csls_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
     return sim_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream, row_id,
                          reinterpret_cast<const unsigned long long*>(best));
+}
+
+}  // extern "C"
+
+// ---- Manhattan alignment: sim_topk_impl's steps around the L1 tile loop ------------------------------------------------------
+// s = 1 - dist(A_m, B_n) (similarity.py:47-49), c = csls_value(s, r1, r2) or s; the tile kernel reads its query rows straight from A
+// (one layer, er = A), so dist carries jmac_l1_score_f32's bits.
+static bool l1_align_args(LinkRankArgs& a, const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d,
+                          const float* r1, const float* r2) {
+    a.nl = 1; a.B = (int32_t)L; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)lda;
+    a.er = const_cast<float*>(A);
+    a.tab[0] = B; a.ld_tab[0] = ldb;
+    a.r1 = r1; a.r2 = r2;
+    return d % 4 == 0 && (((uintptr_t)A | (uintptr_t)B) % (4 * sizeof(float))) == 0;      // the vector form's loads (lda, ldb % 4 == 0)
+}
+
+static int l1_topk_impl(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                        const float* r2, int32_t k, float* val, int32_t* idx, void* ws, hipStream_t st,
+                        const int32_t* row_id = nullptr, const unsigned long long* best = nullptr) {
+    LinkRankArgs a{};
+    const bool vec = l1_align_args(a, A, lda, B, ldb, L, N, d, r1, r2);
+    a.row_id = row_id; a.best = best;
+    // c over B's first n rows, stored in the workspace: the tile kernel's -dist slab, rescored (and masked) in place
+    auto scores = [&](float* S, int64_t n) {
+        LinkRankArgs as = a;
+        as.N = (int32_t)n; as.S = S; as.ldS = n; as.n_off = 0;
+        launch_link_tile<float, LR_STORE>(as, vec, n, st);
+        hipLaunchKernelGGL(l1_csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2, row_id, best);
+    };
+    if (!st_fused(N, k)) {
+        float* S = (float*)ws;
+        scores(S, N);
+        if (int rc = launch_topk(S, N, L, N, k, val, idx, st)) return rc;
+        if (best)
+            hipLaunchKernelGGL(viable_topk_finish_kernel, dim3((unsigned)((L * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, val, idx, L * k);
+        return (int)hipGetLastError();
+    }
+    // 1. tau[m] = k-th largest c of row m among the first Ns columns
+    const StWs w = st_layout(L, N, k);
+    char* wb = (char*)ws;
+    const int64_t Ns = st_sample(N);
+    float* S0 = (float*)(wb + w.s0);
+    float* val0 = (float*)(wb + w.c.val0);
+    int32_t* idx0 = (int32_t*)(wb + w.c.idx0);
+    scores(S0, Ns);
+    if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, idx0, st)) return rc;
+    // 2. the remaining columns with the filtering epilogue
+    a.ntau = val0 + (k - 1); a.tau_stride = k; a.cap = ST_CAP;
+    a.cnt = (int32_t*)(wb + w.c.cnt); a.cval = (float*)(wb + w.c.cval); a.cidx = (int32_t*)(wb + w.c.cidx);
+    a.n_off = (int32_t)Ns;
+    if (hipMemsetAsync(a.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
+    if (best) launch_link_tile<float, LR_CSLS_VIABLE>(a, vec, N - Ns, st);
+    else launch_link_tile<float, LR_CSLS_FILTER>(a, vec, N - Ns, st);
+    // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes
+    if (best)
+        hipLaunchKernelGGL(cand_select_viable_kernel<true>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k,
+                           a.cnt, a.cval, a.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2, row_id, best);
+    else
+        hipLaunchKernelGGL((cand_select_kernel<false, true>), dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k,
+                           a.cnt, a.cval, a.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2);
+    return (int)hipGetLastError();
+}
+
+extern "C" {
+
+size_t jmac_l1_csls_topk_workspace_bytes(int64_t L, int64_t N, int64_t d, int32_t k) {
+    if (d <= 0) return 0;
+    return jmac_sim_topk_workspace_bytes(L, N, k);            // the same layout: the query rows are A's own, nothing grows with d
+}
+
+int jmac_l1_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                          const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (L == 0) return JMAC_OK;
+    if (!A || !B || !val || !idx) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4) return JMAC_EDIM;
+    if (L >= INT32_MAX || N >= INT32_MAX || lda >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_l1_csls_topk_workspace_bytes(L, N, d, k)) return JMAC_EWORKSPACE;
+    return l1_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream);
+}
+
+int jmac_l1_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                                 const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k, float* val, int32_t* idx,
+                                 void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (L == 0) return JMAC_OK;
+    if (!A || !B || !row_id || !best || !val || !idx) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4) return JMAC_EDIM;
+    if (L >= INT32_MAX || N >= INT32_MAX || lda >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_l1_csls_topk_workspace_bytes(L, N, d, k)) return JMAC_EWORKSPACE;
+    return l1_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream, row_id,
+                        reinterpret_cast<const unsigned long long*>(best));
+}
+
+size_t jmac_l1_csls_rank_workspace_bytes(int64_t n1, int64_t n2) {
+    return jmac_sim_csls_rank_workspace_bytes(n1, n2);        // the rows' gold values
+}
+
+int jmac_l1_csls_rank_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, const float* r1,
+                          const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (n1 < 0 || n2 <= 0 || d <= 0 || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (n1 == 0) return JMAC_OK;
+    if (!A || !B || !gold || !rank) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4) return JMAC_EDIM;
+    if (n1 >= INT32_MAX || n2 >= INT32_MAX || lda >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_l1_csls_rank_workspace_bytes(n1, n2)) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    LinkRankArgs a{};
+    const bool vec = l1_align_args(a, A, lda, B, ldb, n1, n2, d, r1, r2);
+    a.gs = (float*)ws; a.gold = gold; a.rank = rank;
+    hipLaunchKernelGGL(l1_csls_gold_kernel, dim3((unsigned)((n1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, A, lda, B, ldb, (int)n1, (int)d,
+                       r1, r2, gold, a.gs, rank);
+    launch_link_tile<float, LR_CSLS_COUNT>(a, vec, n2, st);
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@ def make_args(dim=300, batch_size=1000, num_negative=25, device="cuda", entr_mat
     a = dict(dim=dim, dropout=0.4, leaky_relu_w=0.05, comp_op="sub", num_gcn_layer=2, num_negative=num_negative,
              margin_align=1.0, margin_completion=5.0, batch_size=batch_size, no_name_info=False, device=device,
              pair_sample_weight=0.2, lr=1e-3,                     # train.py:57-102 defaults for the fields used here
+             eval_metric="cosine", eval_norm=False,              # the alignment evaluator's sim() (train.py:95-96, :112)
              neg_sampler="uniform", capture_completion=False,    # this harness' own: where the completion batches come from
              entr_matrix_free=entr_matrix_free)                   # EnTr refresh from scoring.alignment_stats (no N1 x N2 matrix)
     a.update(kw)
@@ -228,7 +229,8 @@ def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pa
     """test_alignment_ (train.py:105-113) on the test pairs of a KG pair: row i of ``pairs`` aligns entity pairs[i, 0] of kg1
     with pairs[i, 1] of kg2 (ids local to their KG).  ``graphs``: ((ei1, et1), (ei2, et2)).  One encoder pass in eval mode, the
     alignment embeddings of the listed entities gathered on the device, then scoring.alignment_test -- by default its
-    matrix-free form (no len(pairs)^2 matrix).  Returns (top_k, hits [%], mr, mrr)."""
+    matrix-free form (no len(pairs)^2 matrix) -- under ``args.eval_metric`` ('cosine', 'inner', 'manhattan') and ``args.eval_norm``
+    (train.py:95-96; absent: 'cosine', False).  Returns (top_k, hits [%], mr, mrr)."""
     (ei1, et1), (ei2, et2) = graphs
     b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
     b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
@@ -240,8 +242,8 @@ def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pa
     scoring.check_index_range(pairs[:, 0], a1.shape[0], "pairs[:, 0]")
     scoring.check_index_range(pairs[:, 1], a2.shape[0], "pairs[:, 1]")
     p = torch.from_numpy(pairs).to(a1.device)
-    return scoring.alignment_test(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), top_k, "cosine", False, csls_k,
-                                  matrix_free=matrix_free)
+    return scoring.alignment_test(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), top_k, getattr(args, "eval_metric", "cosine"),
+                                  bool(getattr(args, "eval_norm", False)), csls_k, matrix_free=matrix_free)
 
 
 @torch.no_grad()
@@ -262,7 +264,8 @@ def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGr
     scoring.check_index_range(pairs[:, 1], a2.shape[0], "pairs[:, 1]")
     p = torch.from_numpy(pairs).to(a1.device)
     k = min(int(k), len(pairs))
-    match1, _, stats = scoring.stable_alignment(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), k, csls_k, "cosine", False)
+    match1, _, stats = scoring.stable_alignment(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), k, csls_k,
+                                                getattr(args, "eval_metric", "cosine"), bool(getattr(args, "eval_norm", False)))
     matched = match1 >= 0
     hits = (match1 == torch.arange(match1.numel(), device=match1.device)) & matched
     precision = 100.0 * float(hits.sum().item()) / max(1, int(matched.sum().item()))

@@ -354,11 +354,12 @@ class JMAC(nn.Module):
         else:
             a1, a2 = emb
         a, b = scoring._alignment_operands(a1, a2, metric, normalize)
-        terms = scoring.csls_terms(a, b, csls_k) if int(csls_k) > 0 else None
+        down = "manhattan" if metric == "manhattan" else "inner"               # the operands are prepared: not again below
+        terms = scoring.csls_terms(a, b, csls_k, down) if int(csls_k) > 0 else None
         q = _idx(e_index, a1.device, a1.shape[0])
         if terms is not None:
             terms = (terms[0].index_select(0, q), terms[1])
-        return scoring.alignment_topk(a.index_select(0, q), b, k, csls_k, "inner", False, terms=terms)
+        return scoring.alignment_topk(a.index_select(0, q), b, k, csls_k, down, False, terms=terms)
 
     def alignment_stable(self, e_index, blocks, k=16, csls_k=10, metric="cosine", normalize=False, max_refills=None, emb=None):
         """A one-to-one alignment of the entities ``e_index`` of KG 1 (suitors, ids local to their KG) with ALL entities of KG 2
@@ -371,11 +372,12 @@ class JMAC(nn.Module):
         else:
             a1, a2 = emb
         a, b = scoring._alignment_operands(a1, a2, metric, normalize)
-        terms = scoring.csls_terms(a, b, csls_k) if int(csls_k) > 0 else None
+        down = "manhattan" if metric == "manhattan" else "inner"
+        terms = scoring.csls_terms(a, b, csls_k, down) if int(csls_k) > 0 else None
         q = _idx(e_index, a1.device, a1.shape[0])
         if terms is not None:
             terms = (terms[0].index_select(0, q), terms[1])
-        return scoring.stable_alignment(a.index_select(0, q), b, k, csls_k, "inner", False, terms=terms, max_refills=max_refills)
+        return scoring.stable_alignment(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, max_refills=max_refills)
 
     # ---- losses (src/jmac_model.py:237-292, :316-380): gathers + L1 / cosine fused in HIP (jmac_amd.losses),
     # the margin arithmetic on the resulting [T] / [L] vectors stays in torch ----------------------------

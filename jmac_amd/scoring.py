@@ -490,20 +490,26 @@ def csls_rank(sim: torch.Tensor, k: int, gold) -> torch.Tensor:
 
 
 def _alignment_operands(embed1: torch.Tensor, embed2: torch.Tensor, metric: str, normalize: bool):
-    """The two operands of sim()'s product (similarity.py:13-55) for the metrics train.py uses ('cosine', 'inner')."""
+    """The two operands of sim() (similarity.py:13-55) for 'cosine', 'inner' (a product) and 'manhattan' (1 - L1 distance):
+    L2-normalised rows for 'cosine' and under ``normalize``."""
     if normalize or metric == "cosine":
         from .ops import row_normalize
         return row_normalize(embed1.detach()), row_normalize(embed2.detach())
-    if metric != "inner":
-        raise NotImplementedError("metric %r (train.py:105-113 uses 'cosine')" % metric)
+    if metric not in ("inner", "manhattan"):
+        raise NotImplementedError("metric %r ('cosine', 'inner' and 'manhattan' are built; train.py:105-113 uses 'cosine')" % metric)
     return embed1, embed2
+
+
+def _l1_metric(metric: str) -> bool:
+    """Which machine a metric runs on: the L1 tile kernel ('manhattan') or the similarity product (every other one)."""
+    return metric == "manhattan"
 
 
 def alignment_sim(embed1: torch.Tensor, embed2: torch.Tensor, metric: str = "cosine", normalize: bool = False,
                   csls_k: int = 0) -> torch.Tensor:
-    """sim(), similarity.py:13-55, for the metrics train.py uses ('cosine', 'inner')."""
+    """sim(), similarity.py:13-55, for 'cosine', 'inner' and 'manhattan' (``1 - l1_scores``, similarity.py:47-49), stored."""
     embed1, embed2 = _alignment_operands(embed1, embed2, metric, normalize)
-    s = sim_matrix(embed1, embed2)
+    s = 1.0 - l1_scores(embed1.detach(), embed2.detach()) if _l1_metric(metric) else sim_matrix(embed1, embed2)
     return csls_sim(s, csls_k) if csls_k > 0 else s
 
 
@@ -511,15 +517,39 @@ def alignment_sim(embed1: torch.Tensor, embed2: torch.Tensor, metric: str = "cos
 CSLS_KMAX = 64
 
 
-def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def _l1_topk(a: torch.Tensor, b: torch.Tensor, k: int, r1=None, r2=None, row_id=None, best=None):
+    """(idx int32 [n1, k], val fp32 [n1, k]) of jmac_l1_csls_topk_f32 / _viable_f32 on prepared operands (``_rows16``)."""
+    n1, d = a.shape
+    n2 = b.shape[0]
+    idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
+    val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
+    L = lib()
+    ws_bytes = int(L.jmac_l1_csls_topk_workspace_bytes(n1, n2, d, k))
+    ws = workspace(ws_bytes, a.device)
+    if best is None:
+        check(L.jmac_l1_csls_topk_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
+                                      stream()), "jmac_l1_csls_topk_f32")
+    else:
+        check(L.jmac_l1_csls_topk_viable_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(row_id), ptr(best), k, ptr(val),
+                                             ptr(idx), ptr(ws), ws_bytes, stream()), "jmac_l1_csls_topk_viable_f32")
+    return idx, val
+
+
+def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int, metric: str = "inner") -> Tuple[torch.Tensor, torch.Tensor]:
     """``(r1 [n1], r2 [n2])`` of csls_sim (similarity.py:58-78) for S = a @ b.T, which is never written: r1[i] is the mean of
     the ``csls_k`` largest entries of row i, r2[j] of column j.  Two fused top-k products: ``sim_topk(a, b)`` for the rows,
     ``sim_topk(b, a)`` for the columns -- every element of b a^T is the same commuting products in the same contraction order
     as the transposed element of a b^T, so both equal the stored forms (``row_topk(sim_matrix(a, b), k)[0].mean(1)``,
-    ``col_topk_values(sim_matrix(a, b), k).mean(1)``) bit for bit.  1 <= csls_k <= 64."""
+    ``col_topk_values(sim_matrix(a, b), k).mean(1)``) bit for bit.  1 <= csls_k <= 64.
+    ``metric="manhattan"``: the same terms of S = 1 - l1_scores(a, b) from two fused L1 top-k passes; |x - y| == |y - x| and the
+    sum runs over k in the same order from either side, so the transposed pass has the stored matrix's bits as well."""
     csls_k = int(csls_k)
     if not 1 <= csls_k <= CSLS_KMAX or csls_k > min(a.shape[0], b.shape[0]):
         raise ValueError("csls_terms: csls_k must lie in [1, min(%d, n1, n2)] (got %d)" % (CSLS_KMAX, csls_k))
+    if _l1_metric(metric):
+        require_device(a, b)
+        a, b = _rows16(a.detach()), _rows16(b.detach())
+        return _l1_topk(a, b, csls_k)[1].mean(1), _l1_topk(b, a, csls_k)[1].mean(1)
     r1 = sim_topk(a, b, csls_k, return_values=True)[1].mean(1)
     r2 = sim_topk(b, a, csls_k, return_values=True)[1].mean(1)
     return r1, r2
@@ -533,7 +563,7 @@ def _csls_operands(emb1, emb2, csls_k, metric, normalize, terms):
         raise ValueError("the two embedding tables disagree in width")
     r1 = r2 = None
     if int(csls_k) > 0:
-        r1, r2 = terms if terms is not None else csls_terms(a, b, csls_k)
+        r1, r2 = terms if terms is not None else csls_terms(a, b, csls_k, metric)
         r1, r2 = r1.contiguous(), r2.contiguous()
         if r1.shape != (a.shape[0],) or r2.shape != (b.shape[0],) or r1.dtype != torch.float32 or r2.dtype != torch.float32:
             raise ValueError("terms must be fp32 vectors of n1 and n2 entries")
@@ -546,7 +576,8 @@ def alignment_ranks(emb1: torch.Tensor, emb2: torch.Tensor, gold, csls_k: int = 
     """int32 ranks [n1]: the 1-based rank of column gold[i] in row i of ``alignment_sim(emb1, emb2, metric, normalize, csls_k)``
     (descending, ties -> lower index first) == ``csls_rank(sim_matrix(..), csls_k, gold)`` (``csls_k = 0``:
     ``filtered_rank(sim_matrix(..), gold, descending=True)``) bit for bit, without the n1 x n2 matrix: the count runs in the
-    product's epilogue.  ``terms``: ``csls_terms`` of the same operands, if the caller has them already."""
+    product's epilogue (``metric="manhattan"``: in the L1 tile kernel's, against ``1 - l1_scores``).  ``terms``: ``csls_terms`` of the
+    same operands and metric, if the caller has them already."""
     a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
     n1, d = a.shape
     n2 = b.shape[0]
@@ -556,10 +587,11 @@ def alignment_ranks(emb1: torch.Tensor, emb2: torch.Tensor, gold, csls_k: int = 
         raise ValueError("gold must have one entry per row of emb1")
     rank = torch.empty(n1, dtype=torch.int32, device=a.device)
     L = lib()
-    ws_bytes = int(L.jmac_sim_csls_rank_workspace_bytes(n1, n2))
+    name = "jmac_l1_csls_rank" if _l1_metric(metric) else "jmac_sim_csls_rank"
+    ws_bytes = int(getattr(L, name + "_workspace_bytes")(n1, n2))
     ws = workspace(ws_bytes, a.device)
-    check(L.jmac_sim_csls_rank_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(gold), ptr(rank), ptr(ws), ws_bytes,
-                                   stream()), "jmac_sim_csls_rank_f32")
+    check(getattr(L, name + "_f32")(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(gold), ptr(rank), ptr(ws), ws_bytes,
+                                    stream()), name + "_f32")
     return rank
 
 
@@ -574,6 +606,9 @@ def alignment_topk(emb1: torch.Tensor, emb2: torch.Tensor, k: int, csls_k: int =
     k = int(k)
     if not 1 <= k <= 64 or k > n2:
         raise ValueError("alignment_topk: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
+    if _l1_metric(metric):
+        idx, val = _l1_topk(a, b, k, r1, r2)
+        return idx.to(torch.int64), val
     idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
     val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
     L = lib()
@@ -653,6 +688,9 @@ def alignment_topk_viable(emb1: torch.Tensor, emb2: torch.Tensor, k: int, best: 
         torch.as_tensor(row_id, device=a.device).to(torch.int32).contiguous()
     if rid.shape != (n1,):
         raise ValueError("row_id must have one entry per row of emb1")
+    if _l1_metric(metric):
+        idx, val = _l1_topk(a, b, k, r1, r2, rid, best.contiguous())
+        return idx.to(torch.int64), val
     idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
     val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
     L = lib()
@@ -663,10 +701,19 @@ def alignment_topk_viable(emb1: torch.Tensor, emb2: torch.Tensor, k: int, best: 
     return idx.to(torch.int64), val
 
 
-def _refill_chunk_rows(n1: int, n2: int, d: int, k: int, ws_bytes: int) -> int:
-    """Most rows L whose top-k workspace AND gathered operand rows fit ``ws_bytes`` together (both grow linearly with L)."""
+def _topk_entry_points(metric: str, d: int):
+    """(workspace_bytes(rows, n2, k), top-k, viable top-k) of the machine ``metric`` runs on; the two take the same arguments."""
     L = lib()
-    need = lambda rows: int(L.jmac_sim_csls_topk_workspace_bytes(rows, n2, k)) + rows * d * 4 + 256      # noqa: E731
+    if _l1_metric(metric):
+        return (lambda rows, n2, k: int(L.jmac_l1_csls_topk_workspace_bytes(rows, n2, d, k)),
+                (L.jmac_l1_csls_topk_f32, "jmac_l1_csls_topk_f32"), (L.jmac_l1_csls_topk_viable_f32, "jmac_l1_csls_topk_viable_f32"))
+    return (lambda rows, n2, k: int(L.jmac_sim_csls_topk_workspace_bytes(rows, n2, k)),
+            (L.jmac_sim_csls_topk_f32, "jmac_sim_csls_topk_f32"), (L.jmac_sim_csls_topk_viable_f32, "jmac_sim_csls_topk_viable_f32"))
+
+
+def _refill_chunk_rows(n1: int, n2: int, d: int, k: int, ws_bytes: int, topk_bytes) -> int:
+    """Most rows L whose top-k workspace AND gathered operand rows fit ``ws_bytes`` together (both grow linearly with L)."""
+    need = lambda rows: topk_bytes(rows, n2, k) + rows * d * 4 + 256      # noqa: E731
     rows = n1
     while rows > 1 and need(rows) > ws_bytes:
         rows = max(1, min(rows - 1, rows * ws_bytes // need(rows)))
@@ -692,14 +739,13 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
     if not 1 <= k <= 64 or k > n2:
         raise ValueError("stable_alignment: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
     dev = a.device
-    L = lib()
+    topk_bytes, (topk, topk_name), (viable, viable_name) = _topk_entry_points(metric, d)
     idx = torch.empty((n1, k), dtype=torch.int32, device=dev)
     val = torch.empty((n1, k), dtype=torch.float32, device=dev)
     # one workspace for every top-k of the run; a refill's gathered rows of `a` live in its tail
-    ws_bytes = max(int(L.jmac_sim_csls_topk_workspace_bytes(n1, n2, k)), int(L.jmac_sim_csls_topk_workspace_bytes(1, n2, k)) + d * 4 + 256)
+    ws_bytes = max(topk_bytes(n1, n2, k), topk_bytes(1, n2, k) + d * 4 + 256)
     ws = workspace(ws_bytes, dev)
-    check(L.jmac_sim_csls_topk_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
-                                   stream()), "jmac_sim_csls_topk_f32")
+    check(topk(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes, stream()), topk_name)
     st = _StableState(idx, val, n2)
     refills = proposals = 0
     complete = True
@@ -713,19 +759,19 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
             complete = False
             break
         ids = st.exhausted_ids(exhausted)
-        chunk = chunk or _refill_chunk_rows(n1, n2, d, k, ws_bytes)
+        chunk = chunk or _refill_chunk_rows(n1, n2, d, k, ws_bytes, topk_bytes)
         for lo in range(0, exhausted, chunk):
             rid = ids[lo:lo + chunk].contiguous()
             rows = rid.numel()
             sel = rid.to(torch.int64)
-            top_bytes = int(L.jmac_sim_csls_topk_workspace_bytes(rows, n2, k))
+            top_bytes = topk_bytes(rows, n2, k)
             sub = ws[ws_bytes - rows * d * 4:].view(torch.float32).view(rows, d)       # (ws_bytes and the offset: multiples of 16)
             torch.index_select(a, 0, sel, out=sub)
             r1s = r1.index_select(0, sel) if r1 is not None else None
             nidx = torch.empty((rows, k), dtype=torch.int32, device=dev)
             nval = torch.empty((rows, k), dtype=torch.float32, device=dev)
-            check(L.jmac_sim_csls_topk_viable_f32(ptr(sub), d, ptr(b), d, rows, n2, d, ptr(r1s), ptr(r2), ptr(rid), ptr(st.best), k,
-                                                  ptr(nval), ptr(nidx), ptr(ws), top_bytes, stream()), "jmac_sim_csls_topk_viable_f32")
+            check(viable(ptr(sub), d, ptr(b), d, rows, n2, d, ptr(r1s), ptr(r2), ptr(rid), ptr(st.best), k, ptr(nval), ptr(nidx), ptr(ws),
+                         top_bytes, stream()), viable_name)
             idx[sel] = nidx
             val[sel] = nval
             st.ptr[sel] = 0
