@@ -344,6 +344,46 @@ int jmac_row_normalize_dropseed_bwd_f32(const float* x, int64_t ldx, const float
                                         float eps, float* gx, int64_t ldgx, int32_t accumulate,
                                         jmac_stream_t stream);
 
+/* Fused row passes of the encoder node's completion chain (jmac_amd/encoder.py, FUSE_ROW_PASSES): the normalise + dropout passes
+ * above folded into the launch that produces their input or consumes their output, with an optional row permutation on the way.
+ * Common to the four: d % 4 == 0 and d <= 512 (a wave holds whole rows in registers), leading dimensions % 4 == 0, 16-byte
+ * aligned bases; seed as for jmac_row_normalize_dropseed_*_f32, NULL = no dropout; the draws are indexed by the row r the
+ * kernel works on (NOT by row_map[r]); row_map [N] int64 device (may be NULL = identity), entries in [0, N) -- not checked.
+ *
+ * jmac_rows_normalize_dropseed_fwd_f32: row r of the result is x[row_map[r]]: the gathered rows themselves -> x_rows (may be NULL),
+ *   their normalised + dropped form -> y, 1 / max(||row||, eps) -> inv.  The bits of a jmac_rows_compact_f32 gather followed by
+ *   jmac_row_normalize_dropseed_fwd_f32.
+ * jmac_bn_tanh_normalize_dropseed_fwd_f32: jmac_bn_tanh_fwd2_f32 (same statistics launches, same arguments up to ldy) whose apply
+ *   pass also writes row r to y_rows[row_map[r]] (both NULL or both given) and the normalised + dropped row (norm taken from the
+ *   registers) to yn, inv [N].  The bits of jmac_bn_tanh_fwd2_f32, a gather and jmac_row_normalize_dropseed_fwd_f32 of y.
+ * jmac_bn_tanh_bwd_normadj_f32: jmac_bn_tanh_bwd2_f32 whose first incoming gradient is not a table but the adjoint that
+ *   jmac_row_normalize_dropseed_bwd_f32(x = y, inv, seed, p_drop, g) would write, formed per row in registers by both of its
+ *   passes; the second one (may be NULL) is read as gy2[row_map[r]].  The column sums keep jmac_bn_tanh_bwd2_f32's
+ *   association: the bits of the adjoint launch, a gather of gy2 and jmac_bn_tanh_bwd2_f32.
+ * jmac_row_normalize_dropseed_bwd_rows_f32: dst[row_map[r]] (+)= adjoint of row r (as jmac_row_normalize_dropseed_bwd_f32)
+ *   + add[r] (may be NULL); accumulate != 0 adds onto dst.  dst must not alias the inputs.  The bits of the accumulating
+ *   adjoint launch followed by jmac_rows_expand_f32. */
+int jmac_rows_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, const int64_t* row_map, int64_t N, int64_t d,
+                                         float eps, const int64_t* seed, float p_drop, float* x_rows, int64_t ldxr,
+                                         float* y, int64_t ldy, float* inv, jmac_stream_t stream);
+int jmac_bn_tanh_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, int64_t N, int64_t d, const float* weight,
+                                            const float* bias, float* running_mean, float* running_var,
+                                            int32_t training, float momentum, float eps, float* y, int64_t ldy,
+                                            const int64_t* row_map, float* y_rows, int64_t ldyr, float norm_eps,
+                                            const int64_t* seed, float p_drop, float* yn, int64_t ldyn, float* inv,
+                                            float* save_mean, float* save_invstd, void* ws, size_t ws_bytes,
+                                            jmac_stream_t stream);
+int jmac_bn_tanh_bwd_normadj_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, const float* inv,
+                                 const float* g, int64_t ldg, float norm_eps, const int64_t* seed, float p_drop,
+                                 const float* gy2, int64_t ldgy2, const int64_t* row_map, int64_t N, int64_t d,
+                                 const float* weight, const float* save_mean, const float* save_invstd,
+                                 int32_t training, float* gx, int64_t ldgx, float* gweight, float* gbias, void* ws,
+                                 size_t ws_bytes, jmac_stream_t stream);
+int jmac_row_normalize_dropseed_bwd_rows_f32(const float* x, int64_t ldx, const float* inv, const int64_t* seed,
+                                             float p_drop, const float* g, int64_t ldg, const float* add,
+                                             int64_t ldadd, const int64_t* row_map, int64_t N, int64_t d, float eps,
+                                             float* dst, int64_t lddst, int32_t accumulate, jmac_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Completion scoring (replaces: torch.cdist(er, all_kg_emb, p=1), src/jmac_model.py:312; the
  * filter/sort/np.where ranking loop of src/validate.py:50-64).

@@ -106,6 +106,13 @@ _SIGS = {
     "jmac_row_normalize_drop_bwd_f32": (C.c_int, [vp, i64, vp, vp, i64, f32, vp, i64, i64, i64, f32, vp, i64, i32, vp]),
     "jmac_row_normalize_dropseed_fwd_f32": (C.c_int, [vp, i64, i64, i64, f32, vp, f32, vp, i64, vp, vp]),
     "jmac_row_normalize_dropseed_bwd_f32": (C.c_int, [vp, i64, vp, vp, f32, vp, i64, i64, i64, f32, vp, i64, i32, vp]),
+    "jmac_rows_normalize_dropseed_fwd_f32": (C.c_int, [vp, i64, vp, i64, i64, f32, vp, f32, vp, i64, vp, i64, vp, vp]),
+    "jmac_bn_tanh_normalize_dropseed_fwd_f32": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, i32, f32, f32, vp, i64, vp, vp, i64,
+                                                          f32, vp, f32, vp, i64, vp, vp, vp, vp, sz, vp]),
+    "jmac_bn_tanh_bwd_normadj_f32": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, f32, vp, f32, vp, i64, vp, i64, i64, vp, vp, vp,
+                                               i32, vp, i64, vp, vp, vp, sz, vp]),
+    "jmac_row_normalize_dropseed_bwd_rows_f32": (C.c_int, [vp, i64, vp, vp, f32, vp, i64, vp, i64, vp, i64, i64, f32, vp, i64,
+                                                           i32, vp]),
     "jmac_gemm_grouped_f32": (C.c_int, [C.POINTER(GemmTask), i32, vp]),
     "jmac_wcat_pack_seed_f32": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i64, vp, vp, i64, C.POINTER(vp), i32, vp, vp, vp]),
     "jmac_adam_step_f32": (C.c_int, [C.POINTER(AdamTask), i32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32,

@@ -5,6 +5,8 @@
 // HBM-bound streaming passes with 16 B per lane.  Column statistics use sums shifted by row 0 of the
 // column (single pass, no catastrophic cancellation), reduced deterministically: per-block partial
 // rows -> one finalising block.  No atomics.
+#include <initializer_list>
+
 #include "common.h"
 
 using namespace jmac;
@@ -862,6 +864,441 @@ __global__ __launch_bounds__(kBlock) void row_normalize_drop_bwd_rows_kernel(con
     }
 }
 
+// ---- fused row passes of the encoder node's completion chain (jmac_amd/encoder.py, FUSE_ROW_PASSES) ---------------------------------
+// The node runs its entities in class order (a row permutation) and normalises + drops what it hands from layer to layer; run as
+// separate launches, four of those passes only re-read a [N, d] table the launch before has just written.  The forms below keep the
+// *_rows layout above (a wave holds R rows, lanes hold column chunks `lane` and `lane + 64`: d <= 512; every load of a row group is
+// issued before its first use) and take an optional int64 row map `map` (class-order row -> caller's row; entries in [0, N)):
+//   rows_normalize_drop_fwd      x[map[r]] -> a copy in class order, normalise + dropout, inv          (gather + normalise)
+//   bn_tanh_normalize_drop_fwd   BatchNorm apply + tanh -> y[r], y[map[r]], normalise + dropout of the row in registers, inv
+//   bn_bwd_{partial,apply}_adj   BatchNorm + tanh backward whose incoming gradient is the normalise/dropout ADJOINT of g, formed per
+//                                row from y (the adjoint's x), inv and the draws -- never stored; gy2 read as gy2[map[r]]
+//                                (the partial pass deals rows to waves as bn_bwd_partial_kernel deals them to threads: same sums)
+//   row_normalize_drop_bwd_scatter   the adjoint + add[r], stored (or accumulated) to dst[map[r]]       (adjoint + scatter)
+// Dropout is the SEED form or none.  The Philox index stays (class-order row, chunk), the per-lane summation order and the DPP chains
+// those of the *_rows kernels, the adjoint is contracted as the separate launch of that row count contracts it
+// (normalize_drop_adjoint_rows) and the BatchNorm backward's column sums keep their association: the bits of the separate launches.
+constexpr int kFuseRows = 4;             // rows per wave: one or two tables in flight
+constexpr int kFuseBwdRows = 2;          // ... four tables in flight
+
+__device__ __forceinline__ uint2 drop_key(const DropSrc& ds, bool seeded) {
+    if (!seeded) return make_uint2(0u, 0u);
+    const uint64_t sd = (uint64_t)ds.seed[0];
+    return make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
+}
+
+// normalise + dropout of R rows held in registers (v: zero on lanes past the row) -> y rows, inv; rows r0 + u >= N are skipped
+template <bool SEED, int R>
+__device__ __forceinline__ void normalize_drop_store_rows(const DropSrc& ds, uint2 key, int64_t r0, int64_t N, int D4, const int (&cc)[2],
+                                                          const bool (&ok)[2], float eps, const float4 (&v)[R][2],
+                                                          float* __restrict__ y, int64_t ldy, float* __restrict__ inv) {
+    float ss[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        ss[u] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const float4 q = v[u][k];
+            ss[u] = fmaf(q.x, q.x, fmaf(q.y, q.y, fmaf(q.z, q.z, fmaf(q.w, q.w, ss[u]))));
+        }
+    }
+    wave_sum_n<R>(ss);
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        const int64_t r = r0 + u;
+        if (r >= N) break;                                     // wave-uniform
+        const float iv = 1.f / fmaxf(sqrtf(ss[u]), eps);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (!ok[k]) continue;
+            float4 q = v[u][k];
+            q.x *= iv; q.y *= iv; q.z *= iv; q.w *= iv;
+            if (SEED) {
+                const float4 m = drop_factors<true>(ds, key, r, cc[k], D4);
+                q.x *= m.x; q.y *= m.y; q.z *= m.z; q.w *= m.w;
+            }
+            st4(y + r * ldy + cc[k] * 4, q);
+        }
+        if (lane_id() == 0) inv[r] = iv;
+    }
+}
+
+// q <- q m - xn (q m . xn), xn = v inv: the normalise/dropout adjoint of R rows held in registers, up to its last factor inv
+// (adjoint_scale below); row[u]: their class-order rows, for the draws; v and q come back zero on lanes past the row.
+// The launches these fused forms replace leave the contraction of this expression to the compiler, which fuses it one way in
+// row_normalize_drop_bwd_rows_kernel (ROWFORM: what drop_bwd launches from kDropRowsMinN rows on) and another way in
+// row_normalize_drop_bwd_kernel; so that a fused launch reproduces the bits of the launch it replaces at every N, both ways are
+// written out here (explicit fmaf, no further contraction):
+//   ROWFORM   s = fma(-xn, dot, q m)            gx = inv s        accumulating: gx = fma(inv, s, old)
+//   otherwise s = fma(m, q, -(xn dot))  (no dropout: fma(-xn, dot, q))    gx = inv s        accumulating: gx = inv s + old
+template <bool SEED, bool ROWFORM, int R>
+__device__ __forceinline__ void normalize_drop_adjoint_rows(const DropSrc& ds, uint2 key, const int64_t (&row)[R], int D4,
+                                                            const int (&cc)[2], const bool (&ok)[2], float eps, const float (&iv)[R],
+                                                            float4 (&v)[R][2], float4 (&q)[R][2]) {
+#pragma clang fp contract(off)
+    float dot[R];
+    float4 m[R][2];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        dot[u] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            float4 b = q[u][k];
+            if (!ok[k]) {
+                b = q[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else if (SEED) {
+                m[u][k] = drop_factors<true>(ds, key, row[u], cc[k], D4);
+                b.x *= m[u][k].x; b.y *= m[u][k].y; b.z *= m[u][k].z; b.w *= m[u][k].w;
+                if (ROWFORM) q[u][k] = b;
+            }
+            const float4 a = v[u][k];
+            dot[u] = fmaf(b.x, a.x * iv[u], fmaf(b.y, a.y * iv[u], fmaf(b.z, a.z * iv[u], fmaf(b.w, a.w * iv[u], dot[u]))));
+        }
+    }
+    wave_sum_n<R>(dot);
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        const float d_ = iv[u] * eps >= 1.f ? 0.f : dot[u];       // ||x|| <= eps: y = x / eps, no radial term
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (!ok[k]) continue;
+            const float4 a = v[u][k], b = q[u][k];
+            float4 o;
+            if (ROWFORM || !SEED) {
+                o.x = fmaf(-(a.x * iv[u]), d_, b.x); o.y = fmaf(-(a.y * iv[u]), d_, b.y);
+                o.z = fmaf(-(a.z * iv[u]), d_, b.z); o.w = fmaf(-(a.w * iv[u]), d_, b.w);
+            } else {
+                o.x = fmaf(m[u][k].x, b.x, -(a.x * iv[u] * d_)); o.y = fmaf(m[u][k].y, b.y, -(a.y * iv[u] * d_));
+                o.z = fmaf(m[u][k].z, b.z, -(a.z * iv[u] * d_)); o.w = fmaf(m[u][k].w, b.w, -(a.w * iv[u] * d_));
+            }
+            q[u][k] = o;
+        }
+    }
+}
+// the adjoint's last factor, and the table an accumulating launch adds (see above)
+__device__ __forceinline__ float4 adjoint_scale(float iv, float4 s) {
+#pragma clang fp contract(off)
+    return make_float4(iv * s.x, iv * s.y, iv * s.z, iv * s.w);
+}
+template <bool ROWFORM>
+__device__ __forceinline__ float4 adjoint_scale_add(float iv, float4 s, float4 p) {
+#pragma clang fp contract(off)
+    if (ROWFORM) return make_float4(fmaf(iv, s.x, p.x), fmaf(iv, s.y, p.y), fmaf(iv, s.z, p.z), fmaf(iv, s.w, p.w));
+    return make_float4(iv * s.x + p.x, iv * s.y + p.y, iv * s.z + p.z, iv * s.w + p.w);
+}
+__device__ __forceinline__ float4 add4(float4 a, float4 b) {
+#pragma clang fp contract(off)
+    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+
+template <bool SEED, int R>
+__global__ __launch_bounds__(kBlock) void rows_normalize_drop_fwd_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                         const int64_t* __restrict__ map, int64_t N, int D4, float eps,
+                                                                         DropSrc ds, float* __restrict__ xr, int64_t ldxr,
+                                                                         float* __restrict__ y, int64_t ldy, float* __restrict__ inv) {
+    const int lane = lane_id();
+    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const uint2 key = drop_key(ds, SEED);
+    const int cc[2] = {lane, lane + 64};
+    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
+    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+        float4 v[R][2];
+        int64_t s[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int64_t r = r0 + u < N ? r0 + u : N - 1;
+            s[u] = map ? map[r] : r;
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) v[u][k] = ld4(x + s[u] * ldx + (ok[k] ? cc[k] : 0) * 4);
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (!ok[k]) v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                else if (xr && r0 + u < N) st4(xr + (r0 + u) * ldxr + cc[k] * 4, v[u][k]);
+            }
+        }
+        normalize_drop_store_rows<SEED, R>(ds, key, r0, N, D4, cc, ok, eps, v, y, ldy, inv);
+    }
+}
+
+template <bool SEED, int R>
+__global__ __launch_bounds__(kBlock) void bn_tanh_normalize_drop_fwd_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int D4,
+                                                                            const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                            float* __restrict__ y, int64_t ldy,
+                                                                            const int64_t* __restrict__ map, float* __restrict__ yr,
+                                                                            int64_t ldyr, float eps, DropSrc ds, float* __restrict__ yn,
+                                                                            int64_t ldyn, float* __restrict__ inv) {
+    const int lane = lane_id();
+    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const uint2 key = drop_key(ds, SEED);
+    const int cc[2] = {lane, lane + 64};
+    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
+    float4 mu[2], is[2], w[2], b[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = (ok[k] ? cc[k] : 0) * 4;
+        mu[k] = ld4(mean + c); is[k] = ld4(invstd + c); w[k] = ld4(weight + c); b[k] = ld4(bias + c);
+    }
+    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+        float4 v[R][2];
+        int64_t s[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int64_t r = r0 + u < N ? r0 + u : N - 1;
+            s[u] = map ? map[r] : r;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) v[u][k] = ld4(x + r * ldx + (ok[k] ? cc[k] : 0) * 4);
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (!ok[k]) {
+                    v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    continue;
+                }
+                float4 o;
+                o.x = tanhf(fmaf((v[u][k].x - mu[k].x) * is[k].x, w[k].x, b[k].x));
+                o.y = tanhf(fmaf((v[u][k].y - mu[k].y) * is[k].y, w[k].y, b[k].y));
+                o.z = tanhf(fmaf((v[u][k].z - mu[k].z) * is[k].z, w[k].z, b[k].z));
+                o.w = tanhf(fmaf((v[u][k].w - mu[k].w) * is[k].w, w[k].w, b[k].w));
+                v[u][k] = o;
+                if (r0 + u < N) {
+                    st4(y + (r0 + u) * ldy + cc[k] * 4, o);
+                    if (yr) st4(yr + s[u] * ldyr + cc[k] * 4, o);   // the same row at its place in the caller's order
+                }
+            }
+        }
+        normalize_drop_store_rows<SEED, R>(ds, key, r0, N, D4, cc, ok, eps, v, yn, ldyn, inv);
+    }
+}
+
+// one element of the BatchNorm + tanh backward (gz = g (1 - y^2), xhat = (x - mean) invstd), written out as the compiler contracts
+// bn_bwd_partial_kernel / bn_bwd_apply_kernel -- in particular both passes form gz the same way, so that a one-row batch gets the
+// exact zero it must
+__device__ __forceinline__ void bn_bwd_sums_elem(float g, float y, float x, float mu, float is, float& s1, float& s2) {
+#pragma clang fp contract(off)
+    const float om = fmaf(-y, y, 1.f), gz = om * g;
+    s1 = fmaf(om, g, s1);
+    s2 = fmaf(gz, (x - mu) * is, s2);
+}
+__device__ __forceinline__ float bn_bwd_apply_elem(float g, float y, float x, float mu, float is, float w, float gw, float gb,
+                                                   int training, float invn) {
+#pragma clang fp contract(off)
+    const float gz = fmaf(-y, y, 1.f) * g;
+    if (!training) return w * is * gz;
+    return w * is * (gz - invn * fmaf((x - mu) * is, gw, gb));
+}
+
+// The column sums keep bn_bwd_partial_kernel's association, so that gweight / gbias (and with them gx) come out bit for bit: a block
+// owns the rows that kernel's block owns -- rpb = kBlock / D4 row slots, slot `rsub` of block b holding rows (b rpb + rsub) + k (grid
+// rpb), k = 0, 1, ... summed in that order -- a wave takes the slots wave, wave + waves, ... one after the other (R consecutive k in
+// flight), and the slots are added in slot order at the end.  Launched with 64 min(rpb, 4) threads (>= D4) and stat_smem(D4) bytes.
+template <bool SEED, bool ROWFORM, int R>
+__global__ __launch_bounds__(kBlock) void bn_bwd_partial_adj_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ y,
+                                                                    int64_t ldy, const float* __restrict__ g, int64_t ldg,
+                                                                    const float* __restrict__ inv, DropSrc ds, float eps,
+                                                                    const float* __restrict__ gy2, int64_t ldgy2,
+                                                                    const int64_t* __restrict__ map, int64_t N, int D4,
+                                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                    float* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float4* red = reinterpret_cast<float4*>(smem);   // [2][rpb][D4]
+    const int rpb = kBlock / D4;                      // >= 2 (D4 <= 128)
+    const int lane = lane_id(), wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
+    const uint2 key = drop_key(ds, SEED);
+    const int cc[2] = {lane, lane + 64};
+    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
+    float4 mu[2], is[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = (ok[k] ? cc[k] : 0) * 4;
+        mu[k] = ld4(mean + c); is[k] = ld4(invstd + c);
+    }
+    const int64_t stride = (int64_t)gridDim.x * rpb;
+    for (int rsub = wv; rsub < rpb; rsub += nwv) {
+        float4 s1[2] = {f4zero(), f4zero()}, s2[2] = {f4zero(), f4zero()};
+        for (int64_t rb = (int64_t)blockIdx.x * rpb + rsub; rb < N; rb += stride * R) {
+            float4 xv[R][2], yv[R][2], q[R][2], g2[R][2];
+            float iv[R];
+            int64_t row[R], s[R];
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                row[u] = rb + u * stride < N ? rb + u * stride : N - 1;
+                s[u] = map ? map[row[u]] : row[u];
+            }
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                iv[u] = inv[row[u]];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int c = (ok[k] ? cc[k] : 0) * 4;
+                    xv[u][k] = ld4(x + row[u] * ldx + c);
+                    yv[u][k] = ld4(y + row[u] * ldy + c);
+                    q[u][k] = ld4(g + row[u] * ldg + c);
+                    if (gy2) g2[u][k] = ld4(gy2 + s[u] * ldgy2 + c);
+                }
+            }
+            normalize_drop_adjoint_rows<SEED, ROWFORM, R>(ds, key, row, D4, cc, ok, eps, iv, yv, q);
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                if (rb + u * stride >= N) break;                   // wave-uniform
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    if (!ok[k]) continue;
+                    float4 gg = adjoint_scale(iv[u], q[u][k]);
+                    if (gy2) gg = add4(gg, g2[u][k]);
+                    const float4 yy = yv[u][k], xx = xv[u][k];
+                    bn_bwd_sums_elem(gg.x, yy.x, xx.x, mu[k].x, is[k].x, s1[k].x, s2[k].x);
+                    bn_bwd_sums_elem(gg.y, yy.y, xx.y, mu[k].y, is[k].y, s1[k].y, s2[k].y);
+                    bn_bwd_sums_elem(gg.z, yy.z, xx.z, mu[k].z, is[k].z, s1[k].z, s2[k].z);
+                    bn_bwd_sums_elem(gg.w, yy.w, xx.w, mu[k].w, is[k].w, s1[k].w, s2[k].w);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (ok[k]) {
+                red[(0 * rpb + rsub) * D4 + cc[k]] = s1[k];
+                red[(1 * rpb + rsub) * D4 + cc[k]] = s2[k];
+            }
+        }
+    }
+    __syncthreads();
+    const int tid = threadIdx.x;
+    if (tid < D4) {
+        float4 a1 = red[tid], a2 = red[rpb * D4 + tid];
+        for (int q = 1; q < rpb; ++q) {
+            const float4 b1 = red[q * D4 + tid], b2 = red[(rpb + q) * D4 + tid];
+            a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
+            a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
+        }
+        st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + tid * 4, a1);
+        st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + tid * 4, a2);
+    }
+}
+
+template <bool SEED, bool ROWFORM, int R>
+__global__ __launch_bounds__(kBlock) void bn_bwd_apply_adj_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ y,
+                                                                  int64_t ldy, const float* __restrict__ g, int64_t ldg,
+                                                                  const float* __restrict__ inv, DropSrc ds, float eps,
+                                                                  const float* __restrict__ gy2, int64_t ldgy2,
+                                                                  const int64_t* __restrict__ map, int64_t N, int D4,
+                                                                  const float* __restrict__ weight, const float* __restrict__ mean,
+                                                                  const float* __restrict__ invstd, const float* __restrict__ gweight,
+                                                                  const float* __restrict__ gbias, int training, float invn,
+                                                                  float* __restrict__ gx, int64_t ldgx) {
+    const int lane = lane_id();
+    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const uint2 key = drop_key(ds, SEED);
+    const int cc[2] = {lane, lane + 64};
+    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
+    float4 mu[2], is[2], w[2], gw[2], gb[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = (ok[k] ? cc[k] : 0) * 4;
+        mu[k] = ld4(mean + c); is[k] = ld4(invstd + c); w[k] = ld4(weight + c);
+        gw[k] = training ? ld4(gweight + c) : f4zero(); gb[k] = training ? ld4(gbias + c) : f4zero();
+    }
+    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+        float4 xv[R][2], yv[R][2], q[R][2], g2[R][2];
+        float iv[R];
+        int64_t row[R], s[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            row[u] = r0 + u < N ? r0 + u : N - 1;
+            s[u] = map ? map[row[u]] : row[u];
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            iv[u] = inv[row[u]];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int c = (ok[k] ? cc[k] : 0) * 4;
+                xv[u][k] = ld4(x + row[u] * ldx + c);
+                yv[u][k] = ld4(y + row[u] * ldy + c);
+                q[u][k] = ld4(g + row[u] * ldg + c);
+                if (gy2) g2[u][k] = ld4(gy2 + s[u] * ldgy2 + c);
+            }
+        }
+        normalize_drop_adjoint_rows<SEED, ROWFORM, R>(ds, key, row, D4, cc, ok, eps, iv, yv, q);
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            if (r0 + u >= N) break;                                // wave-uniform
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (!ok[k]) continue;
+                float4 gg = adjoint_scale(iv[u], q[u][k]);
+                if (gy2) gg = add4(gg, g2[u][k]);
+                const float4 yy = yv[u][k], xx = xv[u][k];
+                float4 o;
+#define JMAC_BN_BWD(comp)                                                                                                       \
+                o.comp = bn_bwd_apply_elem(gg.comp, yy.comp, xx.comp, mu[k].comp, is[k].comp, w[k].comp, gw[k].comp, gb[k].comp, \
+                                           training, invn);
+                JMAC_BN_BWD(x) JMAC_BN_BWD(y) JMAC_BN_BWD(z) JMAC_BN_BWD(w)
+#undef JMAC_BN_BWD
+                st4(gx + (r0 + u) * ldgx + cc[k] * 4, o);
+            }
+        }
+    }
+}
+
+template <bool SEED, bool ROWFORM, int R>
+__global__ __launch_bounds__(kBlock) void row_normalize_drop_bwd_scatter_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                                const float* __restrict__ inv, DropSrc ds,
+                                                                                const float* __restrict__ g, int64_t ldg,
+                                                                                const float* __restrict__ add, int64_t ldadd,
+                                                                                const int64_t* __restrict__ map, int64_t N, int D4,
+                                                                                float eps, float* __restrict__ dst, int64_t lddst,
+                                                                                int accumulate) {
+    const int lane = lane_id();
+    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const uint2 key = drop_key(ds, SEED);
+    const int cc[2] = {lane, lane + 64};
+    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
+    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+        float4 v[R][2], q[R][2], p[R][2], old[R][2];
+        float iv[R];
+        int64_t row[R], s[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            row[u] = r0 + u < N ? r0 + u : N - 1;
+            s[u] = map ? map[row[u]] : row[u];
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            iv[u] = inv[row[u]];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int c = (ok[k] ? cc[k] : 0) * 4;
+                v[u][k] = ld4(x + row[u] * ldx + c);
+                q[u][k] = ld4(g + row[u] * ldg + c);
+                if (add) p[u][k] = ld4(add + row[u] * ldadd + c);
+                if (accumulate) old[u][k] = ld4(dst + s[u] * lddst + c);
+            }
+        }
+        normalize_drop_adjoint_rows<SEED, ROWFORM, R>(ds, key, row, D4, cc, ok, eps, iv, v, q);
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            if (r0 + u >= N) break;                                // wave-uniform
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (!ok[k]) continue;
+                float4 o = add ? adjoint_scale_add<ROWFORM>(iv[u], q[u][k], p[u][k]) : adjoint_scale(iv[u], q[u][k]);
+                if (accumulate) o = add4(o, old[u][k]);
+                st4(dst + s[u] * lddst + cc[k] * 4, o);
+            }
+        }
+    }
+}
+
 constexpr int kDropRows = 4;             // rows per wave of the *_rows forms
 constexpr int64_t kDropRowsMinN = 2048;  // below this the one-row-per-wave forms have more waves to hide latency with
 
@@ -1046,6 +1483,145 @@ int jmac_row_normalize_dropseed_bwd_f32(const float* x, int64_t ldx, const float
     if (int rc = seeded_src(seed, p_drop, ds)) return rc;
     return drop_bwd(x, ldx, inv, ds, true, g, ldg, N, d, eps, gx, ldgx, accumulate, stream);
 }
+
+// ---- fused row passes (kernels: "fused row passes of the encoder node's completion chain" above) --------------------------------
+// seed NULL: no dropout
+static int fused_src(const int64_t* seed, float p_drop, DropSrc& ds) {
+    if (seed) return seeded_src(seed, p_drop, ds);
+    ds = DropSrc{nullptr, 0, nullptr, 0u, 1.f};
+    return JMAC_OK;
+}
+static bool aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t a = 0;
+    for (const void* p : ps) a |= (uintptr_t)p;
+    return (a & 15) == 0;
+}
+static unsigned rows_grid(int64_t N, int R) {                      // a wave per R rows, kBlock / 64 waves per block
+    int64_t rb = ((N + R - 1) / R + kBlock / 64 - 1) / (kBlock / 64);
+    return (unsigned)(rb > 8192 ? 8192 : rb);
+}
+#define JMAC_LAUNCH_SEEDED(kernel, R, grid, st, ...)                                                                      \
+    do {                                                                                                                  \
+        if (ds.seed) hipLaunchKernelGGL((kernel<true, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);                 \
+        else hipLaunchKernelGGL((kernel<false, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);                        \
+    } while (0)
+// ... and the backward forms: the adjoint as the separate launch forms it at this N (normalize_drop_adjoint_rows)
+#define JMAC_LAUNCH_ADJ(kernel, R, grid, st, ...)                                                                         \
+    do {                                                                                                                  \
+        const bool rowform = N >= kDropRowsMinN;                                                                          \
+        if (ds.seed && rowform) hipLaunchKernelGGL((kernel<true, true, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); \
+        else if (ds.seed) hipLaunchKernelGGL((kernel<true, false, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);     \
+        else if (rowform) hipLaunchKernelGGL((kernel<false, true, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);     \
+        else hipLaunchKernelGGL((kernel<false, false, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);                 \
+    } while (0)
+
+int jmac_rows_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, const int64_t* row_map, int64_t N, int64_t d, float eps,
+                                         const int64_t* seed, float p_drop, float* x_rows, int64_t ldxr, float* y, int64_t ldy,
+                                         float* inv, jmac_stream_t stream) {
+    DropSrc ds;
+    if (int rc = fused_src(seed, p_drop, ds)) return rc;
+    if (N < 0) return JMAC_EINVAL;
+    if (d <= 0 || d > 512 || d % 4 || ldx % 4 || ldy % 4 || (x_rows && ldxr % 4)) return JMAC_EDIM;
+    if (N == 0) return JMAC_OK;
+    if (!x || !y || !inv) return JMAC_EINVAL;
+    if (!aligned16({x, y, x_rows})) return JMAC_EDIM;
+    JMAC_LAUNCH_SEEDED(rows_normalize_drop_fwd_kernel, kFuseRows, rows_grid(N, kFuseRows), (hipStream_t)stream, x, ldx, row_map, N,
+                       (int)(d / 4), eps, ds, x_rows, ldxr, y, ldy, inv);
+    return (int)hipGetLastError();
+}
+
+int jmac_bn_tanh_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, int64_t N, int64_t d, const float* weight, const float* bias,
+                                            float* running_mean, float* running_var, int32_t training, float momentum, float eps,
+                                            float* y, int64_t ldy, const int64_t* row_map, float* y_rows, int64_t ldyr, float norm_eps,
+                                            const int64_t* seed, float p_drop, float* yn, int64_t ldyn, float* inv, float* save_mean,
+                                            float* save_invstd, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    DropSrc ds;
+    if (int rc = fused_src(seed, p_drop, ds)) return rc;
+    if (N < 0 || !weight || !bias || !save_mean || !save_invstd || (row_map == nullptr) != (y_rows == nullptr)) return JMAC_EINVAL;
+    if (d <= 0 || d > 512 || d % 4 || ldx % 4 || ldy % 4 || ldyn % 4 || (y_rows && ldyr % 4)) return JMAC_EDIM;
+    if (N == 0) return JMAC_OK;
+    if (!x || !y || !yn || !inv) return JMAC_EINVAL;
+    if (!aligned16({x, y, y_rows, yn, weight, bias, save_mean, save_invstd})) return JMAC_EDIM;
+    hipStream_t st = (hipStream_t)stream;
+    const int D4 = (int)(d / 4);
+    if (training) {                                              // the statistics launches of jmac_bn_tanh_fwd2_f32
+        if (!ws || ws_bytes < jmac_bn_tanh_workspace_bytes(N, d)) return JMAC_EWORKSPACE;
+        float* partial = (float*)ws;
+        const unsigned g = stat_grid(N, D4);
+        hipLaunchKernelGGL(col_stats_partial_kernel, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, N, D4, partial);
+        hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((unsigned)((d + RF_COLS - 1) / RF_COLS)), dim3(1024), 0, st, partial,
+                           (int)g, x, N, (int)d, eps, momentum, running_mean, running_var, save_mean, save_invstd);
+    } else {
+        if (!running_mean || !running_var) return JMAC_EINVAL;
+        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, running_mean, running_var,
+                           (int)d, eps, save_mean, save_invstd);
+    }
+    JMAC_LAUNCH_SEEDED(bn_tanh_normalize_drop_fwd_kernel, kFuseRows, rows_grid(N, kFuseRows), st, x, ldx, N, D4, weight, bias,
+                       (const float*)save_mean, (const float*)save_invstd, y, ldy, row_map, y_rows, ldyr, norm_eps, ds, yn, ldyn, inv);
+    return (int)hipGetLastError();
+}
+
+int jmac_bn_tanh_bwd_normadj_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, const float* inv, const float* g,
+                                 int64_t ldg, float norm_eps, const int64_t* seed, float p_drop, const float* gy2, int64_t ldgy2,
+                                 const int64_t* row_map, int64_t N, int64_t d, const float* weight, const float* save_mean,
+                                 const float* save_invstd, int32_t training, float* gx, int64_t ldgx, float* gweight, float* gbias,
+                                 void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    DropSrc ds;
+    if (int rc = fused_src(seed, p_drop, ds)) return rc;
+    if (N < 0 || !weight || !save_mean || !save_invstd || !gweight || !gbias) return JMAC_EINVAL;
+    if (d <= 0 || d > 512 || d % 4 || ldx % 4 || ldy % 4 || ldg % 4 || ldgx % 4 || (gy2 && ldgy2 % 4)) return JMAC_EDIM;
+    if (!ws || ws_bytes < jmac_bn_tanh_workspace_bytes(N, d)) return JMAC_EWORKSPACE;
+    if (!aligned16({x, y, g, gy2, gx, weight, save_mean, save_invstd, gweight, gbias, ws})) return JMAC_EDIM;
+    hipStream_t st = (hipStream_t)stream;
+    const int D4 = (int)(d / 4);
+    float* partial = (float*)ws;
+    unsigned pg = 0;
+    if (N > 0) {
+        if (!x || !y || !inv || !g || !gx) return JMAC_EINVAL;
+        pg = stat_grid(N, D4);                                    // bn_bwd_partial_kernel's blocks and row slots: the same sums
+        const int rpb = kBlock / D4;
+        const unsigned threads = 64u * (unsigned)(rpb < kBlock / 64 ? rpb : kBlock / 64);
+        const bool rowform = N >= kDropRowsMinN;
+#define JMAC_PARTIAL(SD, RF)                                                                                                      \
+        hipLaunchKernelGGL((bn_bwd_partial_adj_kernel<SD, RF, kFuseBwdRows>), dim3(pg), dim3(threads), stat_smem(D4), st, x, ldx, \
+                           y, ldy, g, ldg, inv, ds, norm_eps, gy2, ldgy2, row_map, N, D4, save_mean, save_invstd, partial)
+        if (ds.seed && rowform) JMAC_PARTIAL(true, true);
+        else if (ds.seed) JMAC_PARTIAL(true, false);
+        else if (rowform) JMAC_PARTIAL(false, true);
+        else JMAC_PARTIAL(false, false);
+#undef JMAC_PARTIAL
+    }
+    if (gweight == gbias + d) {                  // [gbias | gweight] contiguous: the reduction writes them directly
+        launch_reduce_rows(partial, (int)pg, (int)(2 * d), 1.f, gbias, st);
+    } else {
+        float* sums = partial + (size_t)kStatBlocks * 2 * d;
+        launch_reduce_rows(partial, (int)pg, (int)(2 * d), 1.f, sums, st);
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, sums, (int)d, gweight, gbias);
+    }
+    if (N > 0)
+        JMAC_LAUNCH_ADJ(bn_bwd_apply_adj_kernel, kFuseBwdRows, rows_grid(N, kFuseBwdRows), st, x, ldx, y, ldy, g, ldg, inv, ds,
+                           norm_eps, gy2, ldgy2, row_map, N, D4, weight, save_mean, save_invstd, (const float*)gweight,
+                           (const float*)gbias, training ? 1 : 0, 1.f / (float)N, gx, ldgx);
+    return (int)hipGetLastError();
+}
+
+int jmac_row_normalize_dropseed_bwd_rows_f32(const float* x, int64_t ldx, const float* inv, const int64_t* seed, float p_drop,
+                                             const float* g, int64_t ldg, const float* add, int64_t ldadd, const int64_t* row_map,
+                                             int64_t N, int64_t d, float eps, float* dst, int64_t lddst, int32_t accumulate,
+                                             jmac_stream_t stream) {
+    DropSrc ds;
+    if (int rc = fused_src(seed, p_drop, ds)) return rc;
+    if (N < 0) return JMAC_EINVAL;
+    if (d <= 0 || d > 512 || d % 4 || ldx % 4 || ldg % 4 || lddst % 4 || (add && ldadd % 4)) return JMAC_EDIM;
+    if (N == 0) return JMAC_OK;
+    if (!x || !inv || !g || !dst) return JMAC_EINVAL;
+    if (!aligned16({x, g, add, dst})) return JMAC_EDIM;
+    JMAC_LAUNCH_ADJ(row_normalize_drop_bwd_scatter_kernel, kFuseBwdRows, rows_grid(N, kFuseBwdRows), (hipStream_t)stream, x, ldx,
+                       inv, ds, g, ldg, add, ldadd, row_map, N, (int)(d / 4), eps, dst, lddst, accumulate ? 1 : 0);
+    return (int)hipGetLastError();
+}
+#undef JMAC_LAUNCH_SEEDED
+#undef JMAC_LAUNCH_ADJ
 
 // ---- segmented BatchNorm + tanh (block-batched encoder: several KGs in one launch set) ------------------------------
 static int make_seg(int32_t nblocks, const int64_t* blk_ptr, const int32_t* order, int D4, SegTab& s) {

@@ -151,16 +151,22 @@ class RowBlocks:
         self.c_order = (C.c_int32 * self.nb)(*self.order)
 
 
-def _bn_fwd(x, bn, training, y, y2=None, seg=None):
+def _bn_fwd(x, bn, training, y, y2=None, seg=None, norm=None):
     """tanh(BatchNorm1d(x)) into y (and y2), nn.BatchNorm1d bookkeeping included (src/jmac_model.py:52).  ``seg`` (RowBlocks,
     more than one block, batch statistics): every block of rows is normalised with ITS statistics and the running estimates
-    move once per block, as one forward_base call per KG leaves them (src/jmac_model.py:325-326)."""
+    move once per block, as one forward_base call per KG leaves them (src/jmac_model.py:325-326).  ``norm`` (FUSE_ROW_PASSES; no y2,
+    one block): the apply pass also writes normalise + dropout of y into ``norm.yn`` and y in the caller's order into ``norm.y_rows``
+    (``norm.row_map``); it leaves ``norm.inv`` behind."""
     use_batch = bool(training or not bn.track_running_stats)
     if training and bn.track_running_stats:
         if _TRACKERS is not None:
             _TRACKERS.append(bn.num_batches_tracked)           # the encoder node bumps its layers' counters in ONE launch
         else:
             bn.num_batches_tracked.add_(seg.nb if seg is not None else 1)
+    if norm is not None:
+        mean, invstd, norm.inv = ops.bn_tanh_norm_fwd_raw(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch,
+                                                          bn.momentum, bn.eps, y, norm.yn, norm.drop, norm.row_map, norm.y_rows)
+        return mean, invstd, use_batch
     mean, invstd = ops.bn_tanh_fwd_raw(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch, bn.momentum, bn.eps,
                                        y, y2, seg)
     return mean, invstd, use_batch
@@ -204,6 +210,56 @@ def _norm_drop_bwd(x, inv, drop, g, gx, accumulate):
     check(lib().jmac_row_normalize_drop_bwd_f32(ptr(x), x.stride(0), ptr(inv), ptr(mask), d, scale, ptr(g), g.stride(0), N, d,
                                                 1e-12, ptr(gx), gx.stride(0), 1 if accumulate else 0, stream()),
           "jmac_row_normalize_drop_bwd_f32")
+
+
+# ---- fused row passes ----------------------------------------------------------------------------------------------------------------
+# forward_name's completion chain normalises + drops E and c1 on their way into the cat buffers, and (ACTIVE_ROWS) moves both between
+# the caller's entity order and the class order.  As separate launches, four of those passes only re-read a [N, d] table the launch
+# before has just written (the E gather, the normalise behind conv1_completion's BatchNorm, its adjoint in front of that BatchNorm's
+# backward, the final scatter of dE) and two move a table its only consumer can read through the row map (c1 out, g_c1 in).  Fused
+# (norm.hip, "fused row passes"): gather + normalise; BatchNorm apply + tanh + normalise, writing c1 in both orders; a BatchNorm
+# backward that forms the adjoint per row and reads g_c1 through the map; adjoint + dE + scatter.  Four launches and ~155 MB per
+# DBP-5L-size step less, and the bits of the separate launches (tests/test_gpu_row_fusions.py).
+# Kept on the separate launches: stacked KGs (seg.nb > 1: per-block statistics, and no class order either), mask-form dropout
+# (the node itself always draws from seeds), bf16 tables (no backward), d > 512 (a wave holds whole rows), a backward that is itself
+# recorded (create_graph), a backward without g_align (no adjoint to form), and the op-by-op path in jmac_amd.model.
+FUSE_ROW_PASSES = True        # tests / A-B: False runs the separate launches
+
+
+def _fuse_rows_ok(cfg, d) -> bool:
+    return bool(FUSE_ROW_PASSES and d <= 512 and cfg.table_dtype == torch.float32 and (cfg.seg is None or cfg.seg.nb == 1))
+
+
+def _seed_drop(p_drop, training, seed):
+    """The SEED-form dropout state _norm_drop_fwd would return for these settings (None: no dropout)."""
+    return ("seed", seed, float(p_drop)) if (training and p_drop > 0.0 and seed is not None) else None
+
+
+def _gather_norm_drop_fwd(x, row_map, p_drop, training, y, seed=None):
+    """_gather_rows([x], row_map) and _norm_drop_fwd of the result in one launch -> (x[row_map], inv, drop)."""
+    N, d = x.shape
+    x = x if x.stride(-1) == 1 else x.contiguous()
+    xr, inv = _empty(x.device, N, d), _empty(x.device, max(N, 1))
+    drop = _seed_drop(p_drop, training, seed)
+    sp, p = ops._seed_args(drop)
+    check(lib().jmac_rows_normalize_dropseed_fwd_f32(ptr(x), x.stride(0), ptr(row_map), N, d, 1e-12, sp, p, ptr(xr), xr.stride(0), ptr(y),
+                                                     y.stride(0), ptr(inv), stream()), "jmac_rows_normalize_dropseed_fwd_f32")
+    return xr, inv, drop
+
+
+def _norm_drop_bwd_scatter(x, inv, drop, g, add, row_map, dst=None):
+    """_norm_drop_bwd(x, inv, drop, g, add, accumulate) and the scatter of the sum to ``dst[row_map[r]]`` in one launch (``dst``
+    given: accumulate onto it; else a fresh table)."""
+    N, d = x.shape
+    acc = dst is not None
+    if dst is None:
+        dst = _empty(x.device, N, d)
+    sp, p = ops._seed_args(drop)
+    check(lib().jmac_row_normalize_dropseed_bwd_rows_f32(ptr(x), x.stride(0), ptr(inv), sp, p, ptr(g), g.stride(0), ptr(add),
+                                                         add.stride(0) if add is not None else 0, ptr(row_map), N, d, 1e-12, ptr(dst),
+                                                         dst.stride(0), 1 if acc else 0, stream()),
+          "jmac_row_normalize_dropseed_bwd_rows_f32")
+    return dst
 
 
 _TRACKERS = None      # list while an encoder node's forward runs: the num_batches_tracked buffers to bump at its end
@@ -309,8 +365,10 @@ COMPACT_RELATIONS = True      # tests / A-B: False runs every relation-side prod
 # encoder node orders the entities BY CLASS inside itself -- [destination only | destination and source | source only | neither]
 # -- which makes the destinations rows [0, nD) and the sources rows [s0, s1): three row-range products per projection instead of
 # one full one.  The permutation never leaves the node: its inputs are gathered into class order on the way in, its outputs and
-# input gradients gathered back on the way out (jmac_rows_{compact,expand}_f32: one launch each), the graph is re-indexed once
-# per graph (cached on it).  P rows of non-destinations / Q rows of non-sources are never written and never read.
+# input gradients gathered back on the way out (jmac_rows_{compact,expand}_f32: one launch each -- with FUSE_ROW_PASSES, below,
+# only align_out and g_align still move that way: E, c1, g_c1 and dE go through the row map inside the normalise / BatchNorm
+# kernels that read or write them anyway), the graph is re-indexed once per graph (cached on it).  P rows of non-destinations /
+# Q rows of non-sources are never written and never read.
 ACTIVE_ROWS = True            # tests / A-B: False keeps the entity order and the full products
 ACTIVE_ROWS_MAX_FRACTION = 0.85   # taken only where (destinations + sources) / 2N is below this: the copies must pay for themselves
 ACTIVE_ROWS_MIN_N = 4096
@@ -593,7 +651,7 @@ _DEFER = object()
 
 
 def _layer_fwd(lay, X, wc, RR, a, graph, training, y, y2=None, table_dtype=torch.float32, seg=None, compact=False, rows=None,
-               agg=None):
+               agg=None, norm=None):
     """Node side of one RelationAwareLayer (src/jmac_model.py:44-52) given its relation tables: state for the backward.
     ``table_dtype`` bf16 (inference form, no backward: BASELINE config 3): the [P|Q|Z] table comes out of a bf16 GEMM and the
     relation table is rounded to bf16; the aggregation gathers half the bytes, its arithmetic and everything after it is fp32."""
@@ -630,24 +688,29 @@ def _layer_fwd(lay, X, wc, RR, a, graph, training, y, y2=None, table_dtype=torch
     if agg is None:                                     # the self loop is the last relation row
         agg = ops.rel_attn_split_fwd_raw(*ops.pqz_views(PQZ), RR, a, graph, slope, 0.5, RR.shape[0] - 1, 0, compact=compact)
     pre, smax, sden = agg
-    mean, invstd, use_batch = _bn_fwd(pre, lay.bn, training, y, y2, seg)
+    mean, invstd, use_batch = _bn_fwd(pre, lay.bn, training, y, y2, seg, norm)
     return SimpleNamespace(X=X, wc=wc, RR=RR, a=a, PQZ=PQZ, pre=pre, smax=smax, sden=sden, y=y, mean=mean, invstd=invstd,
                            use_batch=use_batch, slope=slope, bn_weight=lay.bn.weight, seg=seg, compact=compact, rows=rows)
 
 
-def _layer_finish(lay, part, agg, training, y, y2=None, seg=None, compact=False, rows=None):
+def _layer_finish(lay, part, agg, training, y, y2=None, seg=None, compact=False, rows=None, norm=None):
     """Second half of _layer_fwd for a layer whose tables were built with ``agg=_DEFER`` and aggregated by the caller."""
     pre, smax, sden = agg
-    mean, invstd, use_batch = _bn_fwd(pre, lay.bn, training, y, y2, seg)
+    mean, invstd, use_batch = _bn_fwd(pre, lay.bn, training, y, y2, seg, norm)
     return SimpleNamespace(X=part.X, wc=part.wc, RR=part.RR, a=part.a, PQZ=part.PQZ, pre=pre, smax=smax, sden=sden, y=y, mean=mean,
                            invstd=invstd, use_batch=use_batch, slope=part.slope, bn_weight=lay.bn.weight, seg=seg, compact=compact,
                            rows=rows)
 
 
-def _layer_bwd(st, graph, gy, gy2, dX, dX_accumulate):
+def _layer_bwd(st, graph, gy, gy2, dX, dX_accumulate, adj=None):
     """Backward of _layer_fwd.  dX: destination of the input gradient (None: not needed).  Returns dRR, dwc (node part),
-    da, gbw."""
-    gpre, gbw = _bn_bwd(st.pre, st.y, gy, gy2, st.bn_weight, st.mean, st.invstd, st.use_batch, st.seg)
+    da, gbw.  ``adj`` (FUSE_ROW_PASSES, instead of gy): gy is the normalise + dropout adjoint of ``adj.g`` (state ``adj.inv``,
+    ``adj.drop``), formed inside the BatchNorm backward; gy2 is in the caller's row order (``adj.row_map``)."""
+    if adj is not None:
+        gpre, gbw = ops.bn_tanh_bwd_normadj_raw(st.pre, st.y, adj.inv, adj.drop, adj.g, gy2, adj.row_map, st.bn_weight, st.mean,
+                                                st.invstd, st.use_batch)
+    else:
+        gpre, gbw = _bn_bwd(st.pre, st.y, gy, gy2, st.bn_weight, st.mean, st.invstd, st.use_batch, st.seg)
     dPQZ = _empty(st.PQZ.device, *st.PQZ.shape)
     _, _, dRR, da = ops.rel_attn_split_bwd_raw(*ops.pqz_views(st.PQZ), st.RR, st.a, graph, st.slope, 0.5, st.RR.shape[0] - 1, 0,
                                                st.pre, st.smax, st.sden, gpre, compact=st.compact, dPQZ=dPQZ)
@@ -855,14 +918,14 @@ class _RelCompGrad:
         return outs[:len(others)], _plus(own, self.extra)
 
 
-def _completion_layer_bwd(t, c1, graph, gy, gy2, g_E0, take=True):
+def _completion_layer_bwd(t, c1, graph, gy, gy2, g_E0, take=True, adj=None):
     """conv1_completion's node side in a backward -> (dE, what is left of g_E0 for the caller to add, _layer_bwd's results).  dE is
     the layer-0 loss gradient's buffer where it may be taken over (``take`` False: the caller does, later), else a fresh one."""
     sc = SimpleNamespace(**vars(t.sc))                                   # c1 is an output: never stored on ctx.t (reference cycle)
     sc.y = c1
     taken = _take_grad(g_E0, c1.shape) if take else None
     dE = taken if taken is not None else _empty(c1.device, *c1.shape)
-    return dE, (g_E0 if taken is None else None), _layer_bwd(sc, graph, gy, gy2, dE, taken is not None)
+    return dE, (g_E0 if taken is None else None), _layer_bwd(sc, graph, gy, gy2, dE, taken is not None, adj)
 
 
 # ---- forward_name ---------------------------------------------------------------------------------------------------------
@@ -958,10 +1021,12 @@ class _EncoderName(torch.autograd.Function):
         # active rows: inside the node the entities are in CLASS order (_RowOrder) -- E_n / info_n are the inputs gathered into it,
         # the graph is the re-indexed one, the projections run on row ranges; outputs are gathered back at the end
         t.ro = ro = _row_order(cfg, graph, N)
+        t.fuse = fuse = _fuse_rows_ok(cfg, d)     # FUSE_ROW_PASSES: the gathers / normalise passes ride in their neighbours' launches
         E_n, info_n = E, info
         if ro is not None:
             graph = ro.graph
-            (E_n,) = _gather_rows([E], ro.old_of_new)
+            if not fuse:                          # (fused: by the normalise launch below)
+                (E_n,) = _gather_rows([E], ro.old_of_new)
             info_n = ro.info_rows(info)
         # :177 + :180  cat(comp0, info @ name_linear) @ U11  ==  cat(comp0, info) @ [U11_top ; name_linear @ U11_bottom]
         t.w = _empty(dev, d + di, d)
@@ -993,12 +1058,19 @@ class _EncoderName(torch.autograd.Function):
         seeds = (seeds[1] if seeds is not None                     # (no persistent state, e.g. a first call inside a capture: drawn here)
                  else (torch.empty(2, dtype=torch.int64, device=dev).random_() if training and p_drop > 0.0 else None))
         sd = (lambda i: seeds[i:i + 1]) if seeds is not None else (lambda i: None)
-        t.inv0, t.drop0 = _norm_drop_fwd(E_n, p_drop, training, t.cat0[:, :d], seed=sd(0))                # :179
+        if fuse and ro is not None:
+            E_n, t.inv0, t.drop0 = _gather_norm_drop_fwd(E, ro.old_of_new, p_drop, training, t.cat0[:, :d], seed=sd(0))   # :179
+        else:
+            t.inv0, t.drop0 = _norm_drop_fwd(E_n, p_drop, training, t.cat0[:, :d], seed=sd(0))            # :179
         align0 = t.catA[:, :d]
         torch.mm(t.cat0, t.w, out=align0)                                                       # :180
         a_att = [p[4].reshape(-1) for p in (pa, pc, p2)]
         seg = cfg.seg
         c1 = _empty(dev, N, d)
+        # fused: conv1_completion's BatchNorm apply also writes normalise + dropout of c1 into cat1 (:191) and c1 in the caller's order
+        c1_out = _empty(dev, N, d) if (fuse and ro is not None) else None
+        norm = (SimpleNamespace(yn=t.cat1[:, :d], drop=_seed_drop(p_drop, training, sd(1)), y_rows=c1_out,
+                                row_map=ro.old_of_new if ro is not None else None, inv=None) if fuse else None)
         if PAIR_LAUNCHES and cfg.table_dtype == torch.float32:
             # conv1_alignment (:183) and conv1_completion (:190) do not depend on each other and share the graph: their tables first,
             # then BOTH aggregations as one launch (jmac_rel_attn_aggregate_fwd_jobs_f32), then each layer's BatchNorm + tanh
@@ -1006,20 +1078,26 @@ class _EncoderName(torch.autograd.Function):
             pc_ = _layer_fwd(lc, E_n, t.wc[1], t.chc.RR, a_att[1], graph, training, None, rows=ro, agg=_DEFER)
             ra, rc_ = _agg_fwd_pair([(pa_.PQZ, pa_.RR, pa_.a, pa_.slope), (pc_.PQZ, pc_.RR, pc_.a, pc_.slope)], graph, compact=t.rc.on)
             t.sa = _layer_finish(la, pa_, ra, training, t.catA[:, d:2 * d], t.cat1[:, d:], seg=seg, compact=t.rc.on, rows=ro)
-            t.sc = _layer_finish(lc, pc_, rc_, training, c1, seg=seg, compact=t.rc.on, rows=ro)
+            t.sc = _layer_finish(lc, pc_, rc_, training, c1, seg=seg, compact=t.rc.on, rows=ro, norm=norm)
         else:
             t.sa = _layer_fwd(la, align0, t.wc[0], t.cha.RR, a_att[0], graph, training, t.catA[:, d:2 * d], t.cat1[:, d:],
                               table_dtype=cfg.table_dtype, seg=seg, compact=t.rc.on, rows=ro)                           # :183
             t.sc = _layer_fwd(lc, E_n, t.wc[1], t.chc.RR, a_att[1], graph, training, c1, table_dtype=cfg.table_dtype, seg=seg,
-                              compact=t.rc.on, rows=ro)                              # :190
-        t.inv1, t.drop1 = _norm_drop_fwd(c1, p_drop, training, t.cat1[:, :d], seed=sd(1))                 # :191
+                              compact=t.rc.on, rows=ro, norm=norm)                   # :190
+        if norm is not None:
+            t.inv1, t.drop1 = norm.inv, norm.drop                                                         # :191
+        else:
+            t.inv1, t.drop1 = _norm_drop_fwd(c1, p_drop, training, t.cat1[:, :d], seed=sd(1))             # :191
         t.a_in = torch.mm(t.cat1, U21)                                                          # :192
         t.s2 = _layer_fwd(l2, t.a_in, t.wc[2], t.ch2.RR, a_att[2], graph, training, t.catA[:, 2 * d:],
                           table_dtype=cfg.table_dtype, seg=seg, compact=t.rc.on, rows=ro)                               # :197
         align_out = torch.mm(t.catA, Wall)                                                      # :203
         if ro is not None:                                   # back into the caller's entity order (one launch for both outputs)
             t.E_n, t.c1_n = E_n, c1                          # class-order tensors the backward reads (neither is an output)
-            align_out, c1 = _gather_rows([align_out, c1], ro.new_of_old)
+            if c1_out is not None:
+                (align_out,), c1 = _gather_rows([align_out], ro.new_of_old), c1_out
+            else:
+                align_out, c1 = _gather_rows([align_out, c1], ro.new_of_old)
         if CAPTURE is not None:
             back = (lambda x: x[ro.new_of_old]) if ro is not None else (lambda x: x.clone())
             rel_a_in = torch.mm(F.leaky_relu(torch.mm(Ra.detach(), L11u.detach()), mslope), L12u.detach())   # (:196) on all rows
@@ -1047,14 +1125,18 @@ class _EncoderName(torch.autograd.Function):
         dev = E.device
         have_align = g_align is not None
         have_c = have_align or g_c1 is not None
+        # fused row passes: not in a backward that is itself recorded; conv1_completion's BatchNorm backward forms the adjoint
+        # of d c1n itself (``adj``) where there is one, i.e. with g_align
+        fuse = t.fuse and not torch.is_grad_enabled()
+        adj_c = fuse and have_align
         if ro is not None and have_c:                        # the incoming gradients into class order: one launch
-            gin = [g for g in (g_align, g_c1) if g is not None]
+            gin = [g for g in (g_align, None if adj_c else g_c1) if g is not None]      # (adj_c: g_c1 is read through the row map)
             gout = _gather_rows(gin, ro.old_of_new)
             if g_align is not None:
                 g_align = gout[0]
-            if g_c1 is not None:
+            if g_c1 is not None and not adj_c:
                 g_c1 = gout[-1]
-        dE = dRa = None
+        dE = dRa = e_adj = None
         dRc = g_Rc0                                          # (no gradient into this node's relation side: passed on as it came)
         dWall = dU21 = dU11 = dNL = gL11 = gL12 = gL11u = gL12u = None
         ga = gc = g2 = [None] * 8
@@ -1070,15 +1152,18 @@ class _EncoderName(torch.autograd.Function):
             dU21 = torch.mm(t.cat1.t(), d_ain)
         # conv1_completion: gradient of c1 = normalise/dropout adjoint of d c1n (+ the loss' own gradient)
         if have_c:
-            gy, gy2 = None, None
+            gy, gy2, adj = None, None, None
             if have_align:
-                gy = _empty(dev, N, d)
-                _norm_drop_bwd(c1_y, t.inv1, t.drop1, dcat1[:, :d], gy, False)
                 gy2 = g_c1.contiguous() if g_c1 is not None else None
+                if adj_c:
+                    adj = SimpleNamespace(inv=t.inv1, drop=t.drop1, g=dcat1[:, :d], row_map=ro.old_of_new if ro is not None else None)
+                else:
+                    gy = _empty(dev, N, d)
+                    _norm_drop_bwd(c1_y, t.inv1, t.drop1, dcat1[:, :d], gy, False)
             else:
                 gy = g_c1.contiguous()
             # the layer-0 loss gradient: this node's input gradient goes on top of it (class order: at the very end, below)
-            dE, g_E0, (dRRc, dwcc, dac, gbwc) = _completion_layer_bwd(t, c1_y, graph, gy, gy2, g_E0, take=ro is None)
+            dE, g_E0, (dRRc, dwcc, dac, gbwc) = _completion_layer_bwd(t, c1_y, graph, gy, gy2, g_E0, take=ro is None, adj=adj)
         if have_align:
             # conv1_alignment: its output fed cat1 and catA -> two gradient sources; its input is align0 = catA[:, :d]
             d_align0 = dcatA[:, :d]
@@ -1088,7 +1173,10 @@ class _EncoderName(torch.autograd.Function):
             t.cat0_lease.check()
             dw = torch.mm(t.cat0.t(), d_align0)                                  # [d+di, d]
             t.cat0_lease.release()                                               # last reader of cat0
-            _norm_drop_bwd(E_x, t.inv0, t.drop0, d_comp0, dE, True)
+            if fuse and ro is not None:
+                e_adj = d_comp0                                                  # (with the scatter at the very end)
+            else:
+                _norm_drop_bwd(E_x, t.inv0, t.drop0, d_comp0, dE, True)
             dU11 = _empty(dev, 2 * d, d)                                         # [:d] <- dw[:d] by the unpack launch below
             dNL = _empty(dev, di, d)
             levels[0].extend([gemm_task(dw[d:], U11[d:], dNL, tb=True, defer=True), gemm_task(NL, dw[d:], dU11[d:], ta=True, defer=True)])
@@ -1118,7 +1206,10 @@ class _EncoderName(torch.autograd.Function):
         t.cat0_lease.release()
         if ro is not None and dE is not None:          # class order -> the caller's, onto the layer-0 loss gradient where it may
             taken = _take_grad(g_E0, (N, d))
-            dE = _scatter_rows(dE, ro.pos32, dst=taken)
+            if e_adj is not None:                      # + the normalise adjoint of d comp0, in the same launch
+                dE = _norm_drop_bwd_scatter(E_x, t.inv0, t.drop0, e_adj, dE, ro.old_of_new, dst=taken)
+            else:
+                dE = _scatter_rows(dE, ro.pos32, dst=taken)
             if taken is not None:
                 g_E0 = None
         dE = _plus(dE, g_E0)                           # a layer-0 gradient this backward could not take over: added here

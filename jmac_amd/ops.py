@@ -355,6 +355,56 @@ def bn_tanh_bwd_raw(x, y, gy, gy2, weight, mean, invstd, training: bool, seg=Non
     return gx, gbw
 
 
+def _seed_args(drop):
+    """(seed pointer, p_drop) of a SEED-form dropout state ``("seed", tensor, p_drop)`` or None (no dropout)."""
+    if drop is None:
+        return None, 0.0
+    if drop[0] != "seed":
+        raise ValueError("the fused row passes draw from a device seed (mask-form dropout keeps the separate launches)")
+    return ptr(drop[1]), float(drop[2])
+
+
+def bn_tanh_norm_fwd_raw(x, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float, y, yn, drop,
+                         row_map=None, y_rows=None):
+    """bn_tanh_fwd_raw whose apply pass also writes F.normalize + dropout of the output rows into ``yn`` (a cat operand) and, with a
+    ``row_map`` (int64 [N]), row r to ``y_rows[row_map[r]]``: jmac_bn_tanh_normalize_dropseed_fwd_f32 -> (save_mean, save_invstd,
+    inv).  ``drop``: ("seed", tensor, p_drop) or None."""
+    L = lib()
+    N, d = x.shape
+    dev = x.device
+    mean = torch.empty(d, dtype=torch.float32, device=dev)
+    invstd = torch.empty(d, dtype=torch.float32, device=dev)
+    inv = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+    seed, p_drop = _seed_args(drop)
+    ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
+    ws = workspace(ws_bytes, dev)
+    check(L.jmac_bn_tanh_normalize_dropseed_fwd_f32(ptr(x), x.stride(0), N, d, ptr(weight), ptr(bias), ptr(running_mean),
+                                                    ptr(running_var), 1 if training else 0, float(momentum), float(eps), ptr(y),
+                                                    y.stride(0), ptr(row_map), ptr(y_rows), y_rows.stride(0) if y_rows is not None else 0,
+                                                    1e-12, seed, p_drop, ptr(yn), yn.stride(0), ptr(inv), ptr(mean), ptr(invstd),
+                                                    ptr(ws), ws_bytes, stream()), "jmac_bn_tanh_normalize_dropseed_fwd_f32")
+    return mean, invstd, inv
+
+
+def bn_tanh_bwd_normadj_raw(x, y, inv, drop, g, gy2, row_map, weight, mean, invstd, training: bool):
+    """bn_tanh_bwd_raw whose first incoming gradient is the normalise + dropout adjoint of ``g`` (rows of a cat adjoint; the
+    adjoint's x is ``y``), formed per row inside both passes instead of being written as a table; ``gy2`` (may be None) is read
+    through ``row_map`` (may be None): jmac_bn_tanh_bwd_normadj_f32 -> gx [N, d], [grad bias | grad weight] [2d]."""
+    L = lib()
+    N, d = x.shape
+    dev = x.device
+    gx = torch.empty((N, d), dtype=torch.float32, device=dev)
+    gbw = torch.empty(2 * d, dtype=torch.float32, device=dev)
+    seed, p_drop = _seed_args(drop)
+    ws_bytes = int(L.jmac_bn_tanh_workspace_bytes(N, d))
+    ws = workspace(ws_bytes, dev)
+    check(L.jmac_bn_tanh_bwd_normadj_f32(ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(inv), ptr(g), g.stride(0), 1e-12, seed, p_drop,
+                                         ptr(gy2), gy2.stride(0) if gy2 is not None else 0, ptr(row_map), N, d, ptr(weight), ptr(mean),
+                                         ptr(invstd), 1 if training else 0, ptr(gx), d, gbw.data_ptr() + d * 4, ptr(gbw), ptr(ws),
+                                         ws_bytes, stream()), "jmac_bn_tanh_bwd_normadj_f32")
+    return gx, gbw
+
+
 class _BnTanh(torch.autograd.Function):
     """tanh(BatchNorm1d(x)) with nn.BatchNorm1d semantics (src/jmac_model.py:52)."""
 
