@@ -517,6 +517,21 @@ int jmac_sim_softmax_stats_f32(const float* A, int64_t lda, const float* B, int6
                                int32_t* col_arg, float* col_sum, float* col_ent, void* ws, size_t ws_bytes,
                                jmac_stream_t stream);
 
+/* Log-sum-exp of S = A B^T (n1 x n2) with additive offsets, without the matrix (the half-steps of log-domain Sinkhorn):
+ *   row_out[i] = row_shift - log sum_j exp(scale S[i,j] + col_add[j])
+ *   col_out[j] = col_shift - log sum_i exp(scale S[i,j] + row_add[i])
+ * S is jmac_sim_matrix_f32's fp32-MFMA product, bit for bit, reduced in the product kernel's epilogue and never written.  A logit
+ * is fma(scale, s, add); every 64-element part takes its maximum exactly before any exponential.  col_add [n2] / row_add [n1]
+ * may be NULL (= 0); the offsets must be finite (the caller vouches), scale > 0.  row_out / col_out may be NULL: that side is
+ * not reduced at all (no partials, no epilogue work); at least one must be given.  An output may not alias an offset vector the
+ * same call reads.  The workspace holds the partials, [ceil(n2/64)][n1] and [ceil(n1/64)][n2] float2 -- O((n1 + n2) n / 64),
+ * never n1 * n2 -- written once and merged in ascending part order: bitwise reproducible, independent of the grid, the tile
+ * walk and the device's CU count; a one-sided call gives the bits of the two-sided one.  lda, ldb, d % 4 == 0 (JMAC_EDIM). */
+size_t jmac_sim_lse_workspace_bytes(int64_t n1, int64_t n2);
+int jmac_sim_lse_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, float scale,
+                     const float* col_add, const float* row_add, float row_shift, float col_shift, float* row_out,
+                     float* col_out, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
 /* Softmax of an existing score matrix S [n1,n2] (row-major) with rows in `row_mask` and columns in `col_mask` (uint8, 1 = keep;
  * NULL mask = keep all) left as they are and every other entry replaced by `fill` (train.py:252-257: fill = -1), all scaled by
  * `scale`, then

@@ -147,6 +147,8 @@ _SIGS = {
     "jmac_softmax_entropy_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, f32, vp, vp, vp, sz, vp]),
     "jmac_sim_softmax_stats_workspace_bytes": (sz, [i64, i64]),
     "jmac_sim_softmax_stats_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "jmac_sim_lse_workspace_bytes": (sz, [i64, i64]),
+    "jmac_sim_lse_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, f32, vp, vp, f32, f32, vp, vp, vp, sz, vp]),
     "jmac_row_softmax_f32": (C.c_int, [vp, i64, i64, i64, vp, vp, f32, f32, vp, i64, vp, vp]),
     "jmac_col_softmax_workspace_bytes": (sz, [i64, i64]),
     "jmac_col_softmax_f32": (C.c_int, [vp, i64, i64, i64, vp, vp, f32, f32, vp, i64, vp, vp, sz, vp]),

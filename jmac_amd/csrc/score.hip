@@ -10,6 +10,8 @@
 //  * jmac_softmax_entropy_f32, jmac_row_softmax_f32                      train.py:241-257
 //  * jmac_sim_softmax_stats_f32  the same softmax's maxima, arg-maxima, sums and entropies per row and per column from the
 //                                product's epilogue, the matrix never written                   train.py:160-169, 231-259
+//  * jmac_sim_lse_f32            log-sum-exp of scale S + offsets per row and per column from the same epilogue: the half-steps
+//                                of log-domain Sinkhorn (no counterpart in the reference's sim())
 //
 // L1 distance is |a-b| accumulation: not a contraction, so it runs on the VALU (register-tiled through
 // LDS); the similarity matrices are contractions and run on the matrix cores with the fp32-input MFMA
@@ -666,12 +668,25 @@ struct SimViable : SimCsls {
     const int32_t* row_id;               // [M] the suitor id of row m (the rows are a gathered subset): the tie-break of the word
     const unsigned long long* best;      // [n_off + N] the reviewers' words, 0 = free
 };
-constexpr int SG_CSLS_COUNT = 1, SG_CSLS_FILTER = 2, SG_CSLS_VIABLE = 3;
+// CSLS = SG_LSE: the scores are not stored; every wave reduces its 64 x 64 part to partial log-sum-exps with additive offsets
+// (jmac_sim_lse_f32: the half-steps of a log-domain Sinkhorn iteration).  Per row and 64-column part (max z, sum e^(z - max z)) of
+// z = fma(scale, S[m, n], col_add[n]); per column and 64-row part the same of z = fma(scale, S[m, n], row_add[m]).  The SimStats
+// scheme otherwise: exact part maxima, partials addressed by the part's position, plain stores, merged in ascending order by
+// sim_lse_merge_kernel; reductions in registers.  A side whose partial pointer is NULL is skipped.  128 x 128 tile only.
+struct SimLse {
+    float2* rpart;           // [ceil(N / 64)][M] (max z, l); NULL: no row side
+    float2* cpart;           // [ceil(M / 64)][N] (max z, l); NULL: no column side
+    const float* col_add;    // [N] added to the logits of the row side; NULL: 0
+    const float* row_add;    // [M] added to the logits of the column side; NULL: 0
+    float scale;             // > 0
+};
+constexpr int SG_CSLS_COUNT = 1, SG_CSLS_FILTER = 2, SG_CSLS_VIABLE = 3, SG_LSE = 4;
 template <bool STATS, int CSLS = 0> struct SgExt { typedef SimFilter type; };
 template <> struct SgExt<true, 0> { typedef SimStats type; };
 template <> struct SgExt<false, SG_CSLS_COUNT> { typedef SimCsls type; };
 template <> struct SgExt<false, SG_CSLS_FILTER> { typedef SimCsls type; };
 template <> struct SgExt<false, SG_CSLS_VIABLE> { typedef SimViable type; };
+template <> struct SgExt<false, SG_LSE> { typedef SimLse type; };
 
 // the DPP-selected lane's v (old = 0 with bound_ctrl: every source lane of the controls used here exists; ROWS: rows written)
 template <int CTRL, int ROWS = 0xF>
@@ -721,6 +736,9 @@ __device__ __forceinline__ void sg_exp_term(float s, float mx, float scale, floa
     t = fmaf(e, x, t);
 }
 
+// e^(z - max z) of one logit of the log-sum-exp epilogue; an excluded element (z = -inf, or the whole part excluded: NaN) gives 0
+__device__ __forceinline__ float sg_lse_term(float z, float mx) { return fast_exp(fmaxf(z - mx, -1e30f)); }
+
 template <bool FILTER, int WJ, bool STATS = false, int CSLS = 0>
 __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                           int64_t ldb, int M, int N, int d, float* __restrict__ C, int64_t ldc,
@@ -728,9 +746,10 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
                                                           typename SgExt<STATS, CSLS>::type ext) {
     static_assert(!(STATS && (FILTER || WJ != 2)), "the statistics epilogue is written for the plain 128 x 128 tile");
     static_assert(CSLS == 0 || (!STATS && FILTER == (CSLS == SG_CSLS_FILTER || CSLS == SG_CSLS_VIABLE)), "CSLS: the count form or a filter form");
+    static_assert(CSLS != SG_LSE || WJ == 2, "the log-sum-exp epilogue is written for the plain 128 x 128 tile");
     constexpr bool VIABLE = CSLS == SG_CSLS_VIABLE;
     const auto& flt = [&]() -> const auto& {
-        if constexpr (CSLS != 0) return ext.f;
+        if constexpr (CSLS != 0 && CSLS != SG_LSE) return ext.f;
         else return ext;
     }();
     (void)flt;
@@ -972,6 +991,80 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
                         : "s"(c0), "n"(rbase), "s"(c1), "n"(rbase + 4));
                 }
             if (hits != 0 && m0 + wm * 64 + lane < M) atomicAdd(ext.rank + m0 + wm * 64 + lane, hits);      // rows >= M: no such row
+        } else if constexpr (CSLS == SG_LSE) {
+            const float scale = ext.scale;
+            const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
+            const int ncol[2] = {ncol0 + r, ncol0 + 32 + r};
+            const int mlim = M - mrow0 - 4 * h;                       // row (i, reg) of this lane is inside iff its base < mlim
+            // elements outside the matrix become -inf, and so do their logits (scale > 0, finite offsets): as in STATS below
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) {
+                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                        const unsigned inside = (unsigned)(rbase - mlim) & (unsigned)(ncol[j] - N) & 0x80000000u;
+                        acc[i][j][reg] = fminf(acc[i][j][reg], __uint_as_float(0xff800000u ^ inside));
+                    }
+            // rows: (i, reg) is one row per half-wave; the lane's two columns carry their offsets.  Lane 16 of the half stores.
+            if (ext.rpart != nullptr) {
+                const float ca0 = ext.col_add ? ext.col_add[min(ncol[0], N - 1)] : 0.f;
+                const float ca1 = ext.col_add ? ext.col_add[min(ncol[1], N - 1)] : 0.f;
+                float2* const rdst = ext.rpart + (int64_t)(ncol0 >> 6) * M + mrow0 + 4 * h;
+                const bool rstore = r == 16 && ncol0 < N;             // (a part wholly outside the matrix does not exist)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) {
+                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                        const float z0 = fmaf(scale, acc[i][0][reg], ca0), z1 = fmaf(scale, acc[i][1][reg], ca1);
+                        const float mx = sg_half_max(sg_max(z0, z1));
+                        float l = sg_lse_term(z0, mx) + sg_lse_term(z1, mx);
+                        l = sg_half_sum_upper(l);
+                        if (rstore && rbase < mlim) rdst[rbase] = make_float2(mx, l);
+                        if (reg & 1) __builtin_amdgcn_sched_barrier(0);      // two rows' chains interleave, no more
+                    }
+            }
+            // columns: a lane holds 32 rows of its column per j, the other half-wave the other 32.  The rows' offsets: ONE
+            // coalesced load (lane l <-> row l of the wave's 64 rows), read out per accumulator row as in the count epilogue; the
+            // logits replace the scores in place (the row side is done with them).
+            if (ext.cpart != nullptr) {
+                float radd = ext.row_add ? ext.row_add[min(mrow0 + lane, M - 1)] : 0.f;
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) {
+                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                        const float a0 = bcast_f(radd, rbase), a1 = bcast_f(radd, rbase + 4);
+                        const float av = h ? a1 : a0;
+                        acc[i][0][reg] = fmaf(scale, acc[i][0][reg], av);
+                        acc[i][1][reg] = fmaf(scale, acc[i][1][reg], av);
+                    }
+                float cm[2], cl[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    float mx = -INFINITY;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) mx = sg_max(mx, acc[i][j][reg]);
+                    float lo, hi;
+                    sg_halves(mx, lo, hi);
+                    mx = sg_max(lo, hi);
+                    float l = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) l += sg_lse_term(acc[i][j][reg], mx);
+                    sg_halves(l, lo, hi);
+                    cl[j] = lo + hi;
+                    cm[j] = mx;
+                }
+                // the lower half-wave stores the columns of j = 0, the upper half those of j = 1
+                const int col = h ? ncol[1] : ncol[0];
+                if (col < N && mrow0 < M) ext.cpart[(int64_t)(mrow0 >> 6) * N + col] = make_float2(h ? cm[1] : cm[0], h ? cl[1] : cl[0]);
+            }
         } else if constexpr (STATS) {
             const float scale = flt.scale;
             const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
@@ -2203,7 +2296,7 @@ int launch_sim_epi(const float* A, int64_t lda, const float* B, int64_t ldb, int
     if (d % 4) return JMAC_EDIM;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if constexpr (!STATS) {
+    if constexpr (!STATS && CSLS != SG_LSE) {
         bool wide = SG_FORCE_WJ == 4;
         if (CSLS != 0 || SG_FORCE_WJ == 0) {
             const SimGeom<2> g2(M, N);
@@ -2251,6 +2344,11 @@ template <int CSLS>
 int launch_sim_csls(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimCsls& cx,
                     hipStream_t st) {
     return launch_sim_epi<CSLS == SG_CSLS_FILTER, false, CSLS>(A, lda, B, ldb, M, N, d, nullptr, 0, st, cx);
+}
+
+int launch_sim_lse(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimLse& lx,
+                   hipStream_t st) {
+    return launch_sim_epi<false, false, SG_LSE>(A, lda, B, ldb, M, N, d, nullptr, 0, st, lx);
 }
 
 // 64 rows (blocks [0, row_blocks)) or 64 columns (the blocks behind them) per block.  Wave g combines the g-th quarter of a
@@ -2323,6 +2421,55 @@ __global__ __launch_bounds__(kBlock) void sim_stats_merge_kernel(const float4* _
     if (oarg) oarg[e] = s.arg;
     if (osum) osum[e] = s.z;
     if (oent) oent[e] = logf(s.z) - s.y / s.z;
+}
+
+// The log-sum-exp partials' merge, in sim_stats_merge_kernel's shape: 64 lines per block, wave g walks the g-th quarter of a line's
+// parts in ascending order (loads four ahead), wave 0 combines the quarters in order; out = shift - log sum e^z = shift - (m + log l).
+struct LseState {
+    float m = -INFINITY, l = 0.f;
+    __device__ __forceinline__ void push(float pm, float pl) {
+        if (!(pl > 0.f)) return;                                   // nothing behind this partial
+        const float mn = fmaxf(m, pm);
+        l = expf(m - mn) * l + expf(pm - mn) * pl;
+        m = mn;
+    }
+};
+__global__ __launch_bounds__(kBlock) void sim_lse_merge_kernel(const float2* __restrict__ rpart, const float2* __restrict__ cpart, int n1,
+                                                               int n2, int row_blocks, float row_shift, float col_shift,
+                                                               float* __restrict__ row_out, float* __restrict__ col_out) {
+    __shared__ float sh[SM_G][2][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const bool rows = (int)blockIdx.x < row_blocks;
+    const int e = ((int)blockIdx.x - (rows ? 0 : row_blocks)) * 64 + lane;
+    const int n = rows ? n1 : n2, parts = ((rows ? n2 : n1) + 63) / 64;
+    const int per = (parts + SM_G - 1) / SM_G, p0 = g * per, p1 = min(parts, p0 + per);
+    const int ec = min(e, n - 1);
+    const float2* const part = rows ? rpart : cpart;
+    LseState s;
+    for (int pb = p0; pb < p1; pb += 4) {
+        float2 q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = part[(int64_t)min(pb + k, p1 - 1) * n + ec];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (pb + k < p1) s.push(q[k].x, q[k].y);
+    }
+    sh[g][0][lane] = s.m;
+    sh[g][1][lane] = s.l;
+    __syncthreads();
+    if (g != 0 || e >= n) return;
+    for (int q = 1; q < SM_G; ++q) s.push(sh[q][0][lane], sh[q][1][lane]);
+    (rows ? row_out : col_out)[e] = (rows ? row_shift : col_shift) - (s.m + logf(s.l));
+}
+
+struct SlWs { size_t rpart, cpart, total; };
+SlWs sl_layout(int64_t n1, int64_t n2) {
+    SlWs w{};
+    size_t off = 0;
+    w.rpart = off; off += align_up((size_t)((n2 + 63) / 64) * (size_t)n1 * 8);
+    w.cpart = off; off += align_up((size_t)((n1 + 63) / 64) * (size_t)n2 * 8);
+    w.total = off + 256;
+    return w;
 }
 
 struct SsWs { size_t rpart, cpart, cbest, total; };
@@ -2748,6 +2895,35 @@ int jmac_sim_softmax_stats_f32(const float* A, int64_t lda, const float* B, int6
     const int rb = want_rows ? (int)((n1 + 63) / 64) : 0, cb = want_cols ? (int)((n2 + 63) / 64) : 0;
     hipLaunchKernelGGL(sim_stats_merge_kernel, dim3((unsigned)(rb + cb)), dim3(kBlock), 0, st, sx.rpart, sx.cpart, sx.cbest, (int)n1,
                        (int)n2, scale, rb, row_max, row_arg, row_sum, row_ent, col_max, col_arg, col_sum, col_ent);
+    return (int)hipGetLastError();
+}
+
+size_t jmac_sim_lse_workspace_bytes(int64_t n1, int64_t n2) {
+    if (n1 < 0 || n2 < 0) return 0;
+    return sl_layout(n1, n2).total;
+}
+
+int jmac_sim_lse_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, float scale,
+                     const float* col_add, const float* row_add, float row_shift, float col_shift, float* row_out, float* col_out,
+                     void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (n1 < 0 || n2 < 0 || d <= 0 || !(scale > 0.f)) return JMAC_EINVAL;
+    if (n1 == 0 || n2 == 0) return JMAC_OK;
+    if (!A || !B || !(row_out || col_out)) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
+    if (n1 >= INT32_MAX || n2 >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_sim_lse_workspace_bytes(n1, n2)) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const SlWs w = sl_layout(n1, n2);
+    SimLse lx{};
+    lx.rpart = row_out ? (float2*)((char*)ws + w.rpart) : nullptr;
+    lx.cpart = col_out ? (float2*)((char*)ws + w.cpart) : nullptr;
+    lx.col_add = col_add;
+    lx.row_add = row_add;
+    lx.scale = scale;
+    if (int rc = launch_sim_lse(A, lda, B, ldb, n1, n2, d, lx, st)) return rc;
+    const int rb = row_out ? (int)((n1 + 63) / 64) : 0, cb = col_out ? (int)((n2 + 63) / 64) : 0;
+    hipLaunchKernelGGL(sim_lse_merge_kernel, dim3((unsigned)(rb + cb)), dim3(kBlock), 0, st, lx.rpart, lx.cpart, (int)n1, (int)n2, rb,
+                       row_shift, col_shift, row_out, col_out);
     return (int)hipGetLastError();
 }
 

@@ -272,6 +272,40 @@ def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGr
     return precision, stats
 
 
+@torch.no_grad()
+def evaluate_sinkhorn_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, scale=50.0, iters=10,
+                                top_k=(1, 5, 10), stable_k=None):
+    """``evaluate_alignment`` under the Sinkhorn plan of the test pairs instead of CSLS (no counterpart in the reference): the
+    pairs' embeddings are selected as there, scoring.sinkhorn_terms gives the rescoring terms (2 ``iters`` products, no
+    len(pairs)^2 matrix) and scoring.alignment_ranks the ranks.  ``args.eval_metric`` ('cosine', 'inner'; 'manhattan' is not
+    built) and ``args.eval_norm`` as there.  Returns (top_k, hits [%], mr, mrr); with ``stable_k`` a fifth entry, the one-to-one
+    precision [%] of scoring.stable_alignment (k = ``stable_k``) under the same terms, as ``evaluate_stable_alignment`` counts it."""
+    (ei1, et1), (ei2, et2) = graphs
+    b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
+    b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
+    metric, norm = getattr(args, "eval_metric", "cosine"), bool(getattr(args, "eval_norm", False))
+    if metric == "manhattan":
+        raise NotImplementedError("evaluate_sinkhorn_alignment: metric 'manhattan' is not built ('cosine' and 'inner' are)")
+    was_training = model.training
+    model.eval()
+    (a1, _), (a2, _) = model.get_emb_blocks([b1, b2], on_device=True)
+    model.train(was_training)
+    pairs = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    scoring.check_index_range(pairs[:, 0], a1.shape[0], "pairs[:, 0]")
+    scoring.check_index_range(pairs[:, 1], a2.shape[0], "pairs[:, 1]")
+    p = torch.from_numpy(pairs).to(a1.device)
+    e1, e2 = a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1])
+    terms = scoring.sinkhorn_terms(e1, e2, scale, iters, metric, norm)
+    gold = torch.arange(e1.shape[0], device=e1.device, dtype=torch.int32)
+    out = scoring._rank_summary(scoring.alignment_ranks(e1, e2, gold, 1, metric, norm, terms=terms), top_k)
+    if stable_k is None:
+        return out
+    match1, _, _ = scoring.stable_alignment(e1, e2, min(int(stable_k), len(pairs)), 1, metric, norm, terms=terms)
+    matched = match1 >= 0
+    hits = (match1 == torch.arange(match1.numel(), device=match1.device)) & matched
+    return (*out, 100.0 * float(hits.sum().item()) / max(1, int(matched.sum().item())))
+
+
 def train_epoch(model: JMAC, kgs: Dict[str, KnowledgeGraph], seeds_train: Dict[Tuple[str, str], np.ndarray],
                 seeds_test: Dict[Tuple[str, str], np.ndarray], opt_c, opt_a, args, state: dict, refresh: bool,
                 generator=None) -> List[dict]:

@@ -368,6 +368,49 @@ def sim_softmax_stats(a: torch.Tensor, b: torch.Tensor, scale: float = 20.0, col
     return SoftmaxStats(*(r + c))
 
 
+def _sim_lse_call(a, b, scale, col_add, row_add, row_shift, col_shift, row_out, col_out, ws, ws_bytes):
+    """One jmac_sim_lse_f32 launch on prepared operands (``_rows16``) and caller-held vectors and workspace."""
+    d = a.shape[1]
+    check(lib().jmac_sim_lse_f32(ptr(a), d, ptr(b), d, a.shape[0], b.shape[0], d, float(scale), ptr(col_add), ptr(row_add),
+                                 float(row_shift), float(col_shift), ptr(row_out), ptr(col_out), ptr(ws), ws_bytes, stream()),
+          "jmac_sim_lse_f32")
+
+
+def _offsets(v, n: int, what: str, dev):
+    if v is None:
+        return None
+    v = v.contiguous()
+    if v.shape != (n,) or v.dtype != torch.float32 or v.device != dev:
+        raise ValueError("%s must be an fp32 vector of %d entries on the operands' device" % (what, n))
+    return v
+
+
+def sim_lse(a: torch.Tensor, b: torch.Tensor, scale: float, col_add=None, row_add=None, row_shift: float = 0.0,
+            col_shift: float = 0.0, rows: bool = True, cols: bool = True):
+    """``(row_out | None, col_out | None)`` of S = a @ b.T, which is never written (jmac_sim_lse_f32):
+    ``row_out[i] = row_shift - log sum_j exp(scale S[i, j] + col_add[j])`` and
+    ``col_out[j] = col_shift - log sum_i exp(scale S[i, j] + row_add[i])``; an absent offset vector is 0, the given ones must be
+    finite.  A side that is not asked for (``rows`` / ``cols``) costs no epilogue work; the other side's bits do not change."""
+    require_device(a, b)
+    a, b = _rows16(a), _rows16(b)
+    n1, n2 = a.shape[0], b.shape[0]
+    if n1 == 0 or n2 == 0:
+        raise ValueError("sim_lse: empty operand")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("sim_lse: the operands disagree in width")
+    if not (rows or cols):
+        raise ValueError("sim_lse: at least one of rows / cols")
+    if not scale > 0:
+        raise ValueError("sim_lse: scale must be positive")
+    dev = a.device
+    col_add, row_add = _offsets(col_add, n2, "col_add", dev), _offsets(row_add, n1, "row_add", dev)
+    row_out = torch.empty(n1, dtype=torch.float32, device=dev) if rows else None
+    col_out = torch.empty(n2, dtype=torch.float32, device=dev) if cols else None
+    ws_bytes = int(lib().jmac_sim_lse_workspace_bytes(n1, n2))
+    _sim_lse_call(a, b, scale, col_add, row_add, row_shift, col_shift, row_out, col_out, workspace(ws_bytes, dev), ws_bytes)
+    return row_out, col_out
+
+
 def _best_with_constant(x: torch.Tensor, l: torch.Tensor, arg: torch.Tensor, index_of: torch.Tensor, c: int, first_masked: int,
                         fill: float, scale: float):
     """Largest softmax entry and its index for lines of the masked matrix: ``x`` / ``l`` / ``arg`` are the maximum, the sum
@@ -555,6 +598,62 @@ def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int, metric: str = "inn
     return r1, r2
 
 
+def sinkhorn_potentials(emb1: torch.Tensor, emb2: torch.Tensor, scale: float = 50.0, iters: int = 10, metric: str = "cosine",
+                        normalize: bool = False, tol: Optional[float] = None):
+    """``(f fp32 [n1], g fp32 [n2], stats)``: the potentials of the log-domain Sinkhorn plan with uniform marginals,
+    ``log P[i, j] = scale S[i, j] + f[i] + g[j]`` for S = the similarity of ``alignment_sim`` ('cosine', 'inner'), without the
+    n1 x n2 matrix.  From f = g = 0, ``iters`` times  f <- -log n1 - LSE_j(scale S + g),  g <- -log n2 - LSE_i(scale S + f): every
+    half-step is ONE jmac_sim_lse_f32 launch that writes f or g in place of the old one (the shifts carry the marginals), so an
+    iteration is two full products and no element-wise launch.  The run ends on a g update: the column sums of P are 1 / n2 to
+    rounding.  ``stats``: iters (done) and residual = max_i |f_new - f_old| of the last row step.  ``tol``: stop after the first
+    iteration whose residual is <= tol (one host read per iteration; a default run has none)."""
+    if _l1_metric(metric):
+        raise NotImplementedError("sinkhorn_potentials: metric 'manhattan' is not built ('cosine' and 'inner' are)")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError("sinkhorn_potentials: iters must be at least 1")
+    if not scale > 0:
+        raise ValueError("sinkhorn_potentials: scale must be positive")
+    require_device(emb1, emb2)
+    a, b = _alignment_operands(emb1, emb2, metric, normalize)
+    a, b = _rows16(a.detach()), _rows16(b.detach())
+    n1, n2 = a.shape[0], b.shape[0]
+    if n1 == 0 or n2 == 0:
+        raise ValueError("sinkhorn_potentials: empty operand")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("the two embedding tables disagree in width")
+    dev = a.device
+    f, f_old = torch.zeros(n1, dtype=torch.float32, device=dev), torch.zeros(n1, dtype=torch.float32, device=dev)
+    g = torch.zeros(n2, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib().jmac_sim_lse_workspace_bytes(n1, n2))
+    ws = workspace(ws_bytes, dev)
+    row_shift, col_shift = -float(np.log(n1)), -float(np.log(n2))
+    done, residual = 0, None
+    for _ in range(iters):
+        f, f_old = f_old, f                                            # the row step writes the buffer of two steps ago
+        _sim_lse_call(a, b, scale, g, None, row_shift, 0.0, f, None, ws, ws_bytes)
+        # g is read by nothing in its own launch (the column side adds f): written in place
+        _sim_lse_call(a, b, scale, None, f, 0.0, col_shift, None, g, ws, ws_bytes)
+        done += 1
+        if tol is not None:
+            residual = float((f - f_old).abs().max().item())
+            if residual <= tol:
+                break
+    if residual is None:
+        residual = float((f - f_old).abs().max().item())
+    return f, g, {"iters": done, "residual": residual}
+
+
+def sinkhorn_terms(emb1: torch.Tensor, emb2: torch.Tensor, scale: float = 50.0, iters: int = 10, metric: str = "cosine",
+                   normalize: bool = False, tol: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(r1, r2) = (-(2 / scale) f, -(2 / scale) g)`` of ``sinkhorn_potentials``: with them the rescored value the alignment
+    kernels decide on, ``c = 2 S - r1 - r2``, is ``(2 / scale) log P`` -- ranks, top-k and the stable matching under the Sinkhorn
+    plan come from ``alignment_ranks`` / ``alignment_topk`` / ``stable_alignment(..., csls_k=<any positive>, terms=(r1, r2))``."""
+    f, g, _ = sinkhorn_potentials(emb1, emb2, scale, iters, metric, normalize, tol)
+    w = -2.0 / float(scale)
+    return f * w, g * w
+
+
 def _csls_operands(emb1, emb2, csls_k, metric, normalize, terms):
     require_device(emb1, emb2)
     a, b = _alignment_operands(emb1, emb2, metric, normalize)
@@ -577,7 +676,8 @@ def alignment_ranks(emb1: torch.Tensor, emb2: torch.Tensor, gold, csls_k: int = 
     (descending, ties -> lower index first) == ``csls_rank(sim_matrix(..), csls_k, gold)`` (``csls_k = 0``:
     ``filtered_rank(sim_matrix(..), gold, descending=True)``) bit for bit, without the n1 x n2 matrix: the count runs in the
     product's epilogue (``metric="manhattan"``: in the L1 tile kernel's, against ``1 - l1_scores``).  ``terms``: ``csls_terms`` of the
-    same operands and metric, if the caller has them already."""
+    same operands and metric, if the caller has them already -- or ``sinkhorn_terms``: the ranks are then those under the
+    Sinkhorn plan (any positive ``csls_k``)."""
     a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
     n1, d = a.shape
     n2 = b.shape[0]
