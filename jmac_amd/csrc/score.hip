@@ -2492,6 +2492,36 @@ int launch_topk(const float* S, int64_t lds, int64_t L, int64_t N, int32_t k, fl
 
 }  // namespace
 
+// the tile kernel with epilogue EPI over the first ncols columns of a's tables
+template <typename TT, int EPI>
+static void launch_link_tile(const LinkRankArgs& a, bool vec, int64_t ncols, hipStream_t st) {
+    dim3 grid((unsigned)((ncols + L1_T - 1) / L1_T), (unsigned)((a.B + L1_T - 1) / L1_T));
+    if (vec) hipLaunchKernelGGL((link_rank_tile_kernel<TT, true, EPI>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((link_rank_tile_kernel<TT, false, EPI>), grid, dim3(kBlock), 0, st, a);
+}
+
+// what jmac_linkpred_rank_* and jmac_linkpred_topk_* fill of LinkRankArgs alike: sizes, layer tables, sign, queries and the known-tail
+// index.  vec: whether the tile kernel may take its vector form, which issues 4-element loads (16 B fp32, 8 B bf16) -- every table's
+// leading dimension AND base pointer must allow it
+template <typename TT>
+static int link_args(LinkRankArgs& a, bool& vec, const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                     int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d) {
+    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
+    vec = d % 4 == 0;
+    for (int l = 0; l < n_layers; ++l) {
+        if (!layers[l].ent || !layers[l].rel || !layers[l].table) return JMAC_EINVAL;
+        a.ent[l] = layers[l].ent; a.rel[l] = layers[l].rel; a.tab[l] = layers[l].table;
+        a.ld_ent[l] = layers[l].ld_ent; a.ld_rel[l] = layers[l].ld_rel; a.ld_tab[l] = layers[l].ld_table;
+        if (a.ld_tab[l] % 4 || ((uintptr_t)a.tab[l] % (4 * sizeof(TT)))) vec = false;
+    }
+    a.sign = pred_head ? -1.f : 1.f;
+    a.h = h; a.r = r;
+    if (index) {
+        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
+    }
+    return JMAC_OK;
+}
+
 template <typename TT>
 static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
                             const int32_t* gold, const int32_t* filt_ptr, const int32_t* filt_idx, const jmac_tail_index_t* index,
@@ -2503,20 +2533,9 @@ static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, c
     if (B >= INT32_MAX || N >= INT32_MAX || d > 512) return JMAC_ERANGE;
     if (!ws || ws_bytes < jmac_linkpred_rank_workspace_bytes(B, d, n_layers)) return JMAC_EWORKSPACE;
     LinkRankArgs a{};
-    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
-    bool vec = d % 4 == 0;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!layers[l].ent || !layers[l].rel || !layers[l].table) return JMAC_EINVAL;
-        a.ent[l] = layers[l].ent; a.rel[l] = layers[l].rel; a.tab[l] = layers[l].table;
-        a.ld_ent[l] = layers[l].ld_ent; a.ld_rel[l] = layers[l].ld_rel; a.ld_tab[l] = layers[l].ld_table;
-        // the vector form issues 4-element loads (16 B fp32, 8 B bf16): leading dimension AND base pointer must allow it
-        if (a.ld_tab[l] % 4 || ((uintptr_t)a.tab[l] % (4 * sizeof(TT)))) vec = false;
-    }
-    a.sign = pred_head ? -1.f : 1.f;
-    a.h = h; a.r = r; a.gold = gold; a.filt_ptr = filt_ptr; a.filt_idx = filt_idx;
-    if (index) {
-        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
-    }
+    bool vec;
+    a.gold = gold; a.filt_ptr = filt_ptr; a.filt_idx = filt_idx;            // the per-batch CSR: an index takes its place
+    if (int rc = link_args<TT>(a, vec, layers, n_layers, h, r, pred_head, index, B, N, d)) return rc;
     a.gs = (float*)ws;
     a.er = (char*)ws + align_up((size_t)B * 4);
     a.rank = rank;
@@ -2527,9 +2546,7 @@ static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, c
     const size_t shm = (size_t)(W + a.rows * (W + 1)) * sizeof(float);
     if (index) hipLaunchKernelGGL((link_rank_prep_kernel<TT, true>), dim3((unsigned)B), dim3(kBlock), shm, st, a);
     else hipLaunchKernelGGL((link_rank_prep_kernel<TT, false>), dim3((unsigned)B), dim3(kBlock), shm, st, a);
-    dim3 grid((unsigned)((N + L1_T - 1) / L1_T), (unsigned)((B + L1_T - 1) / L1_T));
-    if (vec) hipLaunchKernelGGL((link_rank_tile_kernel<TT, true>), grid, dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL((link_rank_tile_kernel<TT, false>), grid, dim3(kBlock), 0, st, a);
+    launch_link_tile<TT, LR_COUNT>(a, vec, N, st);
     return (int)hipGetLastError();
 }
 
@@ -2628,7 +2645,9 @@ int jmac_sim_matrix_f32(const float* A, int64_t lda, const float* B, int64_t ldb
     return launch_sim(A, lda, B, ldb, M, N, d, C, ldc, (hipStream_t)stream);
 }
 
-// fused similarity + running top-k: used when the matrix is wide enough for the column sample to pay
+}  // extern "C"
+
+// ---- the two-stage row top-k every fused form runs: used when the matrix is wide enough for the column sample to pay ----
 constexpr int ST_CAP = TK_CAP;            // candidates kept per row
 constexpr int ST_KMAX = 64;
 constexpr int64_t ST_MIN_N = 8192;
@@ -2637,78 +2656,90 @@ static inline int64_t st_sample(int64_t N) {
     int64_t ns = N / 12 > 2048 ? N / 12 : 2048;            // expected candidates per row ~ k * N / Ns <= 12k (cap: 1024)
     return (ns + 127) / 128 * 128;
 }
-// a row's candidate list and its sample's k best: the part of the workspace the fused forms share (off: running offset)
-struct CandWs { size_t val0, idx0, cnt, cval, cidx; };
-static CandWs cand_layout(size_t& off, int64_t rows, int64_t k) {
-    CandWs c{};
-    c.val0 = off; off += align_up((size_t)rows * (size_t)k * 4);
-    c.idx0 = off; off += align_up((size_t)rows * (size_t)k * 4);
-    c.cnt = off;  off += align_up((size_t)rows * 4);
-    c.cval = off; off += align_up((size_t)rows * ST_CAP * 4);
-    c.cidx = off; off += align_up((size_t)rows * ST_CAP * 4);
-    return c;
-}
-struct StWs { size_t s0; CandWs c; size_t total; };
+// the fused workspace: the sample's scores at offset 0, its k best per row, every row's candidate list
+struct StWs { size_t val0, idx0, cnt, cval, cidx, total; };
 static StWs st_layout(int64_t L, int64_t N, int64_t k) {
     StWs w{};
-    size_t off = 0;
-    w.s0 = off;   off += align_up((size_t)L * (size_t)st_sample(N) * 4);
-    w.c = cand_layout(off, L, k);
+    size_t off = align_up((size_t)L * (size_t)st_sample(N) * 4);
+    w.val0 = off; off += align_up((size_t)L * (size_t)k * 4);
+    w.idx0 = off; off += align_up((size_t)L * (size_t)k * 4);
+    w.cnt = off;  off += align_up((size_t)L * 4);
+    w.cval = off; off += align_up((size_t)L * ST_CAP * 4);
+    w.cidx = off; off += align_up((size_t)L * ST_CAP * 4);
     w.total = off + 256;
     return w;
 }
 
-// jmac_sim_topk_f32 (r1 == nullptr) and jmac_sim_csls_topk_f32: every step works on c = csls_value(S, r1, r2), or on S itself
-// best != nullptr (jmac_sim_csls_topk_viable_f32): of the columns n with tk_pack(c(m, n), row_id[m]) > best[n] only -- one more
-// predicate in each stage; a row with fewer than k of them ends in (idx -1, val -inf)
+// One driver for every score source -- the similarity product, the Manhattan alignment, link prediction.  It owns the scheme: the
+// narrow / fused decision, the workspace carving, the sample pass, the row passes, the candidate counters, the filter pass, the
+// select.  A source scores L rows against N columns (larger is better) and supplies what differs:
+//   store(S, ldS, n) -> rc      the scores of the first n columns at (S, ldS), rescored / masked in place
+//   filter(f) -> rc             its filter epilogue over the columns from f.n_off: what reaches f.tau is appended to f's lists
+//   select(f, val0, idx0)       its select kernel: the k best of every list and of the sample (val0, idx0); an overflowing row recomputes
+//   finish                      the kernel the narrow exit runs over (val, idx, L * k) behind the row pass, or nullptr
+// wb: the workspace behind the source's own prefix, laid out as st_layout says; ld_narrow: the row stride of the narrow matrix.
+template <class Store, class Filter, class Select, class Finish>
+static int topk_drive(int64_t L, int64_t N, int32_t k, float* val, int32_t* idx, char* wb, int64_t ld_narrow, hipStream_t st,
+                      Store store, Filter filter, Select select, Finish finish) {
+    float* S = (float*)wb;                                   // either layout begins with the stored scores
+    if (!st_fused(N, k)) {                                   // narrow matrices: every score, then the row pass
+        if (int rc = store(S, ld_narrow, N)) return rc;
+        if (int rc = launch_topk(S, ld_narrow, L, N, k, val, idx, st)) return rc;
+        if (finish) hipLaunchKernelGGL(finish, dim3((unsigned)((L * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, val, idx, L * k);
+        return (int)hipGetLastError();
+    }
+    // 1. tau[m] = k-th best score of row m among the first Ns columns: a bound of the row's final k-th score
+    const StWs w = st_layout(L, N, k);
+    const int64_t Ns = st_sample(N);
+    float* val0 = (float*)(wb + w.val0);
+    int32_t* idx0 = (int32_t*)(wb + w.idx0);
+    if (int rc = store(S, Ns, Ns)) return rc;
+    if (int rc = launch_topk(S, Ns, L, Ns, k, val0, idx0, st)) return rc;
+    // 2. the REMAINING columns with the filtering epilogue: candidates instead of the matrix
+    SimFilter f{};
+    f.tau = val0 + (k - 1); f.tau_stride = k;
+    f.cnt = (int*)(wb + w.cnt); f.cval = (float*)(wb + w.cval); f.cidx = (int*)(wb + w.cidx); f.cap = ST_CAP; f.n_off = (int)Ns;
+    if (hipMemsetAsync(f.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
+    if (int rc = filter(f)) return rc;
+    // 3. the k best of every candidate list (+ the sample's k best)
+    select(f, val0, idx0);
+    return (int)hipGetLastError();
+}
+
+// the similarity product as the source.  jmac_sim_topk_f32 (r1 == nullptr) and jmac_sim_csls_topk_f32: every step works on
+// c = csls_value(S, r1, r2), or on S itself.  best != nullptr (jmac_sim_csls_topk_viable_f32): of the columns n with
+// tk_pack(c(m, n), row_id[m]) > best[n] only -- one more predicate in each stage; a row with fewer than k of them ends in (idx -1, val -inf)
 static int sim_topk_impl(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
                          const float* r2, int32_t k, float* val, int32_t* idx, void* ws, hipStream_t st,
                          const int32_t* row_id = nullptr, const unsigned long long* best = nullptr) {
-    // the product of A with B's first n rows, stored (and rescored, and masked) in the workspace
-    auto scores = [&](float* S, int64_t n) -> int {
-        if (int rc = launch_sim(A, lda, B, ldb, L, n, d, S, n, st)) return rc;
-        if (best) hipLaunchKernelGGL(viable_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2, row_id, best);
-        else if (r1) hipLaunchKernelGGL(csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2);
-        return 0;
-    };
-    if (!st_fused(N, k)) {                                   // narrow matrices: scores to the workspace, then the row pass
-        float* S = (float*)ws;
-        if (int rc = scores(S, N)) return rc;
-        if (int rc = launch_topk(S, N, L, N, k, val, idx, st)) return rc;
-        if (best)
-            hipLaunchKernelGGL(viable_topk_finish_kernel, dim3((unsigned)((L * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, val, idx, L * k);
-        return (int)hipGetLastError();
-    }
-    // 1. tau[m] = k-th largest score of row m among the first Ns columns: a lower bound of the row's final k-th score
-    const StWs w = st_layout(L, N, k);
-    char* wb = (char*)ws;
-    const int64_t Ns = st_sample(N);
-    float* S0 = (float*)(wb + w.s0);
-    float* val0 = (float*)(wb + w.c.val0);
-    int32_t* idx0 = (int32_t*)(wb + w.c.idx0);
-    if (int rc = scores(S0, Ns)) return rc;
-    if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, idx0, st)) return rc;
-    // 2. the product over the REMAINING columns with the filtering epilogue: candidates instead of the matrix
-    SimViable cx{};
-    cx.r1 = r1; cx.r2 = r2; cx.row_id = row_id; cx.best = best;
-    SimFilter& f = cx.f;
-    f.tau = val0 + (k - 1); f.tau_stride = k;
-    f.cnt = (int*)(wb + w.c.cnt); f.cval = (float*)(wb + w.c.cval); f.cidx = (int*)(wb + w.c.cidx); f.cap = ST_CAP;
-    f.n_off = (int)Ns;
-    if (hipMemsetAsync(f.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
-    if (int rc = best ? launch_sim_epi<true, false, SG_CSLS_VIABLE>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, nullptr, 0, st, cx)
-                 : r1 ? launch_sim_csls<SG_CSLS_FILTER>(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, cx, st)
-                      : launch_sim(A, lda, B + Ns * ldb, ldb, L, N - Ns, d, nullptr, 0, st, &f))
-        return rc;
-    // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes (and rescores)
-    if (best)
-        hipLaunchKernelGGL(cand_select_viable_kernel<false>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt,
-                           f.cval, f.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2, row_id, best);
-    else
-        hipLaunchKernelGGL(r1 ? cand_select_kernel<true> : cand_select_kernel<false>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb,
-                           (int)N, (int)d, (int)k, f.cnt, f.cval, f.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2);
-    return (int)hipGetLastError();
+    const dim3 rows((unsigned)L), block(kBlock);
+    return topk_drive(L, N, k, val, idx, (char*)ws, N, st,
+        [&](float* S, int64_t ldS, int64_t n) -> int {       // the product of A with B's first n rows
+            if (int rc = launch_sim(A, lda, B, ldb, L, n, d, S, ldS, st)) return rc;
+            if (best) hipLaunchKernelGGL(viable_inplace_kernel, rows, block, 0, st, S, ldS, (int)n, r1, r2, row_id, best);
+            else if (r1) hipLaunchKernelGGL(csls_inplace_kernel, rows, block, 0, st, S, ldS, (int)n, r1, r2);
+            return 0;
+        },
+        [&](const SimFilter& f) -> int {
+            SimViable cx{};
+            cx.f = f; cx.r1 = r1; cx.r2 = r2; cx.row_id = row_id; cx.best = best;
+            const float* Br = B + f.n_off * ldb;
+            return best ? launch_sim_epi<true, false, SG_CSLS_VIABLE>(A, lda, Br, ldb, L, N - f.n_off, d, nullptr, 0, st, cx)
+                   : r1 ? launch_sim_csls<SG_CSLS_FILTER>(A, lda, Br, ldb, L, N - f.n_off, d, cx, st)
+                        : launch_sim(A, lda, Br, ldb, L, N - f.n_off, d, nullptr, 0, st, &f);
+        },
+        [&](const SimFilter& f, const float* val0, const int32_t* idx0) {      // an overflowing row recomputes (and rescores)
+            if (best)
+                hipLaunchKernelGGL(cand_select_viable_kernel<false>, rows, block, 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt, f.cval,
+                                   f.cidx, f.cap, val0, idx0, val, idx, r1, r2, row_id, best);
+            else
+                hipLaunchKernelGGL(r1 ? cand_select_kernel<true> : cand_select_kernel<false>, rows, block, 0, st, A, lda, B, ldb, (int)N, (int)d,
+                                   (int)k, f.cnt, f.cval, f.cidx, f.cap, val0, idx0, val, idx, r1, r2);
+        },
+        best ? viable_topk_finish_kernel : nullptr);
 }
+
+extern "C" {
 
 size_t jmac_sim_topk_workspace_bytes(int64_t L, int64_t N, int32_t k) {
     if (L < 0 || N < 0 || k <= 0) return 0;
@@ -2736,32 +2767,34 @@ int jmac_sim_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, 
 
 }  // extern "C"
 
-// ---- link-prediction top-k: jmac_sim_topk_f32's scheme around the L1 tile loop -------------------------------------------
-struct LtWs { size_t er, rng, s0; CandWs c; size_t total; int64_t ldS; };
+// ---- link-prediction top-k: the L1 tile loop over prepared query rows as the source ---------------------------------------------
+// the prefix (query rows, index ranges), then jmac_sim_topk_f32's workspace for B rows; narrow: rows padded to 4 elements
+struct LtWs { size_t er, rng, tail, total; int64_t ld_narrow; };
 static LtWs lt_layout(int64_t B, int64_t N, int64_t d, int64_t nl, int64_t k) {
     LtWs w{};
     size_t off = 0;
     w.er = off;  off += align_up((size_t)nl * (size_t)B * (size_t)((d + 3) / 4 * 4) * 4);
     w.rng = off; off += align_up((size_t)B * 8);
-    if (!st_fused(N, k)) {                                    // narrow tables: the [B, N] scores, then the row pass
-        w.ldS = (N + 3) / 4 * 4;
-        w.s0 = off; off += align_up((size_t)B * (size_t)w.ldS * 4);
-    } else {                                                  // sample scores + candidate lists: no B x N buffer
-        w.ldS = st_sample(N);
-        w.s0 = off;   off += align_up((size_t)B * (size_t)w.ldS * 4);
-        w.c = cand_layout(off, B, k);
-    }
-    w.total = off + 256;
+    w.tail = off;
+    w.ld_narrow = (N + 3) / 4 * 4;
+    w.total = off + (st_fused(N, k) ? st_layout(B, N, k).total : align_up((size_t)B * (size_t)w.ld_narrow * 4) + 256);
     return w;
 }
 
-template <typename TT, int EPI>
-static void launch_link_tile(const LinkRankArgs& a, bool vec, int64_t ncols, hipStream_t st) {
-    dim3 grid((unsigned)((ncols + L1_T - 1) / L1_T), (unsigned)((a.B + L1_T - 1) / L1_T));
-    if (vec) hipLaunchKernelGGL((link_rank_tile_kernel<TT, true, EPI>), grid, dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL((link_rank_tile_kernel<TT, false, EPI>), grid, dim3(kBlock), 0, st, a);
+// the tile kernel's STORE epilogue over the first n columns, and a with the filter epilogues' thresholds and candidate lists (S and
+// ldS stay unset there: only the STORE epilogue reads them)
+template <typename TT>
+static void launch_link_store(LinkRankArgs a, bool vec, float* S, int64_t ldS, int64_t n, hipStream_t st) {
+    a.N = (int32_t)n; a.S = S; a.ldS = ldS; a.n_off = 0;
+    launch_link_tile<TT, LR_STORE>(a, vec, n, st);
+}
+static LinkRankArgs link_filter_args(LinkRankArgs a, const SimFilter& f) {
+    a.ntau = f.tau; a.tau_stride = (int32_t)f.tau_stride; a.cap = f.cap;
+    a.cnt = f.cnt; a.cval = f.cval; a.cidx = f.cidx; a.n_off = f.n_off;
+    return a;
 }
 
+// the scores are -dist; the index's listed tails are masked in the stored scores and skipped by the filter and the select
 template <typename TT>
 static int launch_link_topk(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
                             const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k, float* val, int32_t* idx,
@@ -2775,56 +2808,32 @@ static int launch_link_topk(const jmac_link_layer_t* layers, int32_t n_layers, c
     if (B >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
     if (!ws || ws_bytes < jmac_linkpred_topk_workspace_bytes(B, N, d, n_layers, k)) return JMAC_EWORKSPACE;
     LinkRankArgs a{};
-    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
-    bool vec = d % 4 == 0;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!layers[l].ent || !layers[l].rel || !layers[l].table) return JMAC_EINVAL;
-        a.ent[l] = layers[l].ent; a.rel[l] = layers[l].rel; a.tab[l] = layers[l].table;
-        a.ld_ent[l] = layers[l].ld_ent; a.ld_rel[l] = layers[l].ld_rel; a.ld_tab[l] = layers[l].ld_table;
-        if (a.ld_tab[l] % 4 || ((uintptr_t)a.tab[l] % (4 * sizeof(TT)))) vec = false;
-    }
+    bool vec;
+    if (int rc = link_args<TT>(a, vec, layers, n_layers, h, r, pred_head, index, B, N, d)) return rc;
     const int64_t W = (int64_t)n_layers * a.dq;
     if (W + 1 > 60 * 1024 / 4 - W) return JMAC_ERANGE;         // jmac_linkpred_rank_*'s LDS limit
-    a.sign = pred_head ? -1.f : 1.f;
-    a.h = h; a.r = r;
     const LtWs w = lt_layout(B, N, d, n_layers, k);
     char* wb = (char*)ws;
     a.er = wb + w.er;
     a.rng = (int2*)(wb + w.rng);
-    float* S0 = (float*)(wb + w.s0);
-    // 1. the query rows and every query's range in the index
-    if (index) {
-        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
-        hipLaunchKernelGGL((link_rank_prep_kernel<TT, true, false>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a);
-    } else {
-        hipLaunchKernelGGL((link_rank_prep_kernel<TT, false, false>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a);
-    }
-    a.S = S0; a.ldS = w.ldS; a.n_off = 0;
-    if (!st_fused(N, k)) {
-        launch_link_tile<TT, LR_STORE>(a, vec, N, st);
-        if (index) hipLaunchKernelGGL(link_mask_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, S0, w.ldS, (int)N, a.rng, a.filt_idx);
-        if (int rc = launch_topk(S0, w.ldS, B, N, k, val, idx, st)) return rc;
-        hipLaunchKernelGGL(link_topk_finish_kernel, dim3((unsigned)((B * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, val, idx, B * k);
-        return (int)hipGetLastError();
-    }
-    // 2. tau_b = k-th smallest unlisted distance among the first Ns columns: an upper bound of the row's final k-th distance
-    const int64_t Ns = w.ldS;
-    float* val0 = (float*)(wb + w.c.val0);
-    int32_t* idx0 = (int32_t*)(wb + w.c.idx0);
-    LinkRankArgs as = a;
-    as.N = (int32_t)Ns;
-    launch_link_tile<TT, LR_STORE>(as, vec, Ns, st);
-    if (index) hipLaunchKernelGGL(link_mask_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, S0, Ns, (int)Ns, a.rng, a.filt_idx);
-    if (int rc = launch_topk(S0, Ns, B, Ns, k, val0, idx0, st)) return rc;
-    // 3. the remaining columns with the filtering epilogue: candidates instead of the matrix
-    a.ntau = val0 + (k - 1); a.tau_stride = k; a.cap = ST_CAP;
-    a.cnt = (int32_t*)(wb + w.c.cnt); a.cval = (float*)(wb + w.c.cval); a.cidx = (int32_t*)(wb + w.c.cidx);
-    a.n_off = (int32_t)Ns;
-    if (hipMemsetAsync(a.cnt, 0, (size_t)B * 4, st) != hipSuccess) return (int)hipGetLastError();
-    launch_link_tile<TT, LR_FILTER>(a, vec, N - Ns, st);
-    // 4. the k best unlisted of every candidate list (+ the sample's k best)
-    hipLaunchKernelGGL((link_select_kernel<TT>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a, (int)k, val0, idx0, val, idx);
-    return (int)hipGetLastError();
+    // the query rows and every query's range in the index
+    if (index) hipLaunchKernelGGL((link_rank_prep_kernel<TT, true, false>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a);
+    else hipLaunchKernelGGL((link_rank_prep_kernel<TT, false, false>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, a);
+    return topk_drive(B, N, k, val, idx, wb + w.tail, w.ld_narrow, st,
+        [&](float* S, int64_t ldS, int64_t n) -> int {
+            launch_link_store<TT>(a, vec, S, ldS, n, st);
+            if (index) hipLaunchKernelGGL(link_mask_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, S, ldS, (int)n, a.rng, a.filt_idx);
+            return 0;
+        },
+        [&](const SimFilter& f) -> int {
+            launch_link_tile<TT, LR_FILTER>(link_filter_args(a, f), vec, N - f.n_off, st);
+            return 0;
+        },
+        [&](const SimFilter& f, const float* val0, const int32_t* idx0) {
+            hipLaunchKernelGGL((link_select_kernel<TT>), dim3((unsigned)B), dim3(kBlock), (size_t)W * 4, st, link_filter_args(a, f), (int)k, val0,
+                               idx0, val, idx);
+        },
+        link_topk_finish_kernel);
 }
 
 extern "C" {
@@ -3035,55 +3044,15 @@ size_t jmac_sim_csls_rank_workspace_bytes(int64_t n1, int64_t n2) {
     return align_up((size_t)n1 * 4) + 256;                   // the rows' gold values: nothing grows with n2
 }
 
-int jmac_sim_csls_rank_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, const float* r1,
-                           const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    if (n1 < 0 || n2 <= 0 || d <= 0 || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
-    if (n1 == 0) return JMAC_OK;
-    if (!A || !B || !gold || !rank) return JMAC_EINVAL;
-    if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
-    if (n1 >= INT32_MAX || n2 >= INT32_MAX) return JMAC_ERANGE;
-    if (!ws || ws_bytes < jmac_sim_csls_rank_workspace_bytes(n1, n2)) return JMAC_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    SimCsls cx{};
-    cx.r1 = r1; cx.r2 = r2; cx.gval = (float*)ws; cx.gold = gold; cx.rank = rank;
-    hipLaunchKernelGGL(csls_gold_kernel, dim3((unsigned)((n1 + 32 * (kBlock / 64) - 1) / (32 * (kBlock / 64)))), dim3(kBlock), 0, st, A, lda,
-                       B, ldb, (int)n1, (int)d, r1, r2, gold, (float*)ws, rank);
-    return launch_sim_csls<SG_CSLS_COUNT>(A, lda, B, ldb, n1, n2, d, cx, st);
-}
-
 size_t jmac_sim_csls_topk_workspace_bytes(int64_t L, int64_t N, int32_t k) {
     return jmac_sim_topk_workspace_bytes(L, N, k);            // the same layout: r1 / r2 are the caller's
 }
 
-int jmac_sim_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
-                           const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
-    if (L == 0) return JMAC_OK;
-    if (!A || !B || !idx) return JMAC_EINVAL;
-    if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
-    if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
-    if (!ws || ws_bytes < jmac_sim_csls_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
-    return sim_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream);      // r1 == NULL: c = S, jmac_sim_topk_f32's bits
-}
-
-int jmac_sim_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
-                                  const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k, float* val, int32_t* idx,
-                                  void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
-    if (L == 0) return JMAC_OK;
-    if (!A || !B || !row_id || !best || !val || !idx) return JMAC_EINVAL;
-    if (lda % 4 || ldb % 4 || d % 4) return JMAC_EDIM;
-    if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
-    if (!ws || ws_bytes < jmac_sim_csls_topk_workspace_bytes(L, N, k)) return JMAC_EWORKSPACE;
-    return sim_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream, row_id,
-                         reinterpret_cast<const unsigned long long*>(best));
-}
-
 }  // extern "C"
 
-// ---- Manhattan alignment: sim_topk_impl's steps around the L1 tile loop ------------------------------------------------------
-// s = 1 - dist(A_m, B_n) (similarity.py:47-49), c = csls_value(s, r1, r2) or s; the tile kernel reads its query rows straight from A
-// (one layer, er = A), so dist carries jmac_l1_score_f32's bits.
+// ---- alignment top-k and ranks: the similarity product (cosine, inner) or the L1 tile loop (Manhattan) as the source ----------------
+// Manhattan: s = 1 - dist(A_m, B_n) (similarity.py:47-49), c = csls_value(s, r1, r2) or s; the tile kernel reads its query rows straight
+// from A (one layer, er = A), so dist carries jmac_l1_score_f32's bits.
 static bool l1_align_args(LinkRankArgs& a, const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d,
                           const float* r1, const float* r2) {
     a.nl = 1; a.B = (int32_t)L; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)lda;
@@ -3094,53 +3063,98 @@ static bool l1_align_args(LinkRankArgs& a, const float* A, int64_t lda, const fl
 }
 
 static int l1_topk_impl(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
-                        const float* r2, int32_t k, float* val, int32_t* idx, void* ws, hipStream_t st,
-                        const int32_t* row_id = nullptr, const unsigned long long* best = nullptr) {
+                        const float* r2, int32_t k, float* val, int32_t* idx, void* ws, hipStream_t st, const int32_t* row_id,
+                        const unsigned long long* best) {
     LinkRankArgs a{};
     const bool vec = l1_align_args(a, A, lda, B, ldb, L, N, d, r1, r2);
     a.row_id = row_id; a.best = best;
-    // c over B's first n rows, stored in the workspace: the tile kernel's -dist slab, rescored (and masked) in place
-    auto scores = [&](float* S, int64_t n) {
-        LinkRankArgs as = a;
-        as.N = (int32_t)n; as.S = S; as.ldS = n; as.n_off = 0;
-        launch_link_tile<float, LR_STORE>(as, vec, n, st);
-        hipLaunchKernelGGL(l1_csls_inplace_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, S, n, (int)n, r1, r2, row_id, best);
-    };
-    if (!st_fused(N, k)) {
-        float* S = (float*)ws;
-        scores(S, N);
-        if (int rc = launch_topk(S, N, L, N, k, val, idx, st)) return rc;
-        if (best)
-            hipLaunchKernelGGL(viable_topk_finish_kernel, dim3((unsigned)((L * k + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, val, idx, L * k);
-        return (int)hipGetLastError();
+    const dim3 rows((unsigned)L), block(kBlock);
+    return topk_drive(L, N, k, val, idx, (char*)ws, N, st,
+        [&](float* S, int64_t ldS, int64_t n) -> int {       // the tile kernel's -dist slab, rescored (and masked) in place
+            launch_link_store<float>(a, vec, S, ldS, n, st);
+            hipLaunchKernelGGL(l1_csls_inplace_kernel, rows, block, 0, st, S, ldS, (int)n, r1, r2, row_id, best);
+            return 0;
+        },
+        [&](const SimFilter& f) -> int {
+            if (best) launch_link_tile<float, LR_CSLS_VIABLE>(link_filter_args(a, f), vec, N - f.n_off, st);
+            else launch_link_tile<float, LR_CSLS_FILTER>(link_filter_args(a, f), vec, N - f.n_off, st);
+            return 0;
+        },
+        [&](const SimFilter& f, const float* val0, const int32_t* idx0) {
+            if (best)
+                hipLaunchKernelGGL(cand_select_viable_kernel<true>, rows, block, 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt, f.cval,
+                                   f.cidx, f.cap, val0, idx0, val, idx, r1, r2, row_id, best);
+            else
+                hipLaunchKernelGGL((cand_select_kernel<false, true>), rows, block, 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, f.cnt, f.cval,
+                                   f.cidx, f.cap, val0, idx0, val, idx, r1, r2);
+        },
+        best ? viable_topk_finish_kernel : nullptr);
+}
+
+// jmac_{sim,l1}_csls_topk{,_viable}_f32: one argument check, then the source.  ALIGN_L1: the Manhattan forms take any d and need lda
+// to be the tile kernel's int32 row stride; TOPK_VIABLE: row_id and best are arguments; val may be NULL in the plain similarity form only.
+enum AlignMetric { ALIGN_SIM, ALIGN_L1 };
+enum TopkForm { TOPK_PLAIN, TOPK_VIABLE };
+static int csls_topk_entry(AlignMetric metric, TopkForm form, const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d,
+                           const float* r1, const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k, float* val,
+                           int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (L == 0) return JMAC_OK;
+    const bool l1 = metric == ALIGN_L1, viable = form == TOPK_VIABLE;
+    if (!A || !B || !idx || (!val && (l1 || viable)) || (viable && (!row_id || !best))) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || (!l1 && d % 4)) return JMAC_EDIM;
+    if (L >= INT32_MAX || N >= INT32_MAX || (l1 && lda >= INT32_MAX)) return JMAC_ERANGE;
+    if (!ws || ws_bytes < (l1 ? jmac_l1_csls_topk_workspace_bytes(L, N, d, k) : jmac_sim_csls_topk_workspace_bytes(L, N, k))) return JMAC_EWORKSPACE;
+    const auto* words = reinterpret_cast<const unsigned long long*>(best);
+    return l1 ? l1_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream, row_id, words)
+              : sim_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream, row_id, words);     // r1 == NULL: c = S
+}
+
+// jmac_{sim,l1}_csls_rank_f32: the same for the ranks -- the gold values, then the count epilogue over all columns
+static int csls_rank_entry(AlignMetric metric, const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                           const float* r1, const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes,
+                           jmac_stream_t stream) {
+    if (n1 < 0 || n2 <= 0 || d <= 0 || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (n1 == 0) return JMAC_OK;
+    const bool l1 = metric == ALIGN_L1;
+    if (!A || !B || !gold || !rank) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || (!l1 && d % 4)) return JMAC_EDIM;
+    if (n1 >= INT32_MAX || n2 >= INT32_MAX || (l1 && lda >= INT32_MAX)) return JMAC_ERANGE;
+    if (!ws || ws_bytes < (l1 ? jmac_l1_csls_rank_workspace_bytes(n1, n2) : jmac_sim_csls_rank_workspace_bytes(n1, n2))) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (!l1) {
+        SimCsls cx{};
+        cx.r1 = r1; cx.r2 = r2; cx.gval = (float*)ws; cx.gold = gold; cx.rank = rank;
+        hipLaunchKernelGGL(csls_gold_kernel, dim3((unsigned)((n1 + 32 * (kBlock / 64) - 1) / (32 * (kBlock / 64)))), dim3(kBlock), 0, st, A, lda,
+                           B, ldb, (int)n1, (int)d, r1, r2, gold, (float*)ws, rank);
+        return launch_sim_csls<SG_CSLS_COUNT>(A, lda, B, ldb, n1, n2, d, cx, st);
     }
-    // 1. tau[m] = k-th largest c of row m among the first Ns columns
-    const StWs w = st_layout(L, N, k);
-    char* wb = (char*)ws;
-    const int64_t Ns = st_sample(N);
-    float* S0 = (float*)(wb + w.s0);
-    float* val0 = (float*)(wb + w.c.val0);
-    int32_t* idx0 = (int32_t*)(wb + w.c.idx0);
-    scores(S0, Ns);
-    if (int rc = launch_topk(S0, Ns, L, Ns, k, val0, idx0, st)) return rc;
-    // 2. the remaining columns with the filtering epilogue
-    a.ntau = val0 + (k - 1); a.tau_stride = k; a.cap = ST_CAP;
-    a.cnt = (int32_t*)(wb + w.c.cnt); a.cval = (float*)(wb + w.c.cval); a.cidx = (int32_t*)(wb + w.c.cidx);
-    a.n_off = (int32_t)Ns;
-    if (hipMemsetAsync(a.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
-    if (best) launch_link_tile<float, LR_CSLS_VIABLE>(a, vec, N - Ns, st);
-    else launch_link_tile<float, LR_CSLS_FILTER>(a, vec, N - Ns, st);
-    // 3. the k best of every candidate list (+ the sample's k best); an overflowing row recomputes
-    if (best)
-        hipLaunchKernelGGL(cand_select_viable_kernel<true>, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k,
-                           a.cnt, a.cval, a.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2, row_id, best);
-    else
-        hipLaunchKernelGGL((cand_select_kernel<false, true>), dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k,
-                           a.cnt, a.cval, a.cidx, ST_CAP, val0, (const int32_t*)idx0, val, idx, r1, r2);
+    LinkRankArgs a{};
+    const bool vec = l1_align_args(a, A, lda, B, ldb, n1, n2, d, r1, r2);
+    a.gs = (float*)ws; a.gold = gold; a.rank = rank;
+    hipLaunchKernelGGL(l1_csls_gold_kernel, dim3((unsigned)((n1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, A, lda, B, ldb, (int)n1, (int)d,
+                       r1, r2, gold, a.gs, rank);
+    launch_link_tile<float, LR_CSLS_COUNT>(a, vec, n2, st);
     return (int)hipGetLastError();
 }
 
 extern "C" {
+
+int jmac_sim_csls_rank_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, const float* r1,
+                           const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return csls_rank_entry(ALIGN_SIM, A, lda, B, ldb, n1, n2, d, r1, r2, gold, rank, ws, ws_bytes, stream);
+}
+
+int jmac_sim_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                           const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return csls_topk_entry(ALIGN_SIM, TOPK_PLAIN, A, lda, B, ldb, L, N, d, r1, r2, nullptr, nullptr, k, val, idx, ws, ws_bytes, stream);
+}
+
+int jmac_sim_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                                  const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k, float* val, int32_t* idx,
+                                  void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return csls_topk_entry(ALIGN_SIM, TOPK_VIABLE, A, lda, B, ldb, L, N, d, r1, r2, row_id, best, k, val, idx, ws, ws_bytes, stream);
+}
 
 size_t jmac_l1_csls_topk_workspace_bytes(int64_t L, int64_t N, int64_t d, int32_t k) {
     if (d <= 0) return 0;
@@ -3149,26 +3163,13 @@ size_t jmac_l1_csls_topk_workspace_bytes(int64_t L, int64_t N, int64_t d, int32_
 
 int jmac_l1_csls_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
                           const float* r2, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
-    if (L == 0) return JMAC_OK;
-    if (!A || !B || !val || !idx) return JMAC_EINVAL;
-    if (lda % 4 || ldb % 4) return JMAC_EDIM;
-    if (L >= INT32_MAX || N >= INT32_MAX || lda >= INT32_MAX) return JMAC_ERANGE;
-    if (!ws || ws_bytes < jmac_l1_csls_topk_workspace_bytes(L, N, d, k)) return JMAC_EWORKSPACE;
-    return l1_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream);
+    return csls_topk_entry(ALIGN_L1, TOPK_PLAIN, A, lda, B, ldb, L, N, d, r1, r2, nullptr, nullptr, k, val, idx, ws, ws_bytes, stream);
 }
 
 int jmac_l1_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
                                  const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k, float* val, int32_t* idx,
                                  void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > ST_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
-    if (L == 0) return JMAC_OK;
-    if (!A || !B || !row_id || !best || !val || !idx) return JMAC_EINVAL;
-    if (lda % 4 || ldb % 4) return JMAC_EDIM;
-    if (L >= INT32_MAX || N >= INT32_MAX || lda >= INT32_MAX) return JMAC_ERANGE;
-    if (!ws || ws_bytes < jmac_l1_csls_topk_workspace_bytes(L, N, d, k)) return JMAC_EWORKSPACE;
-    return l1_topk_impl(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, (hipStream_t)stream, row_id,
-                        reinterpret_cast<const unsigned long long*>(best));
+    return csls_topk_entry(ALIGN_L1, TOPK_VIABLE, A, lda, B, ldb, L, N, d, r1, r2, row_id, best, k, val, idx, ws, ws_bytes, stream);
 }
 
 size_t jmac_l1_csls_rank_workspace_bytes(int64_t n1, int64_t n2) {
@@ -3177,20 +3178,7 @@ size_t jmac_l1_csls_rank_workspace_bytes(int64_t n1, int64_t n2) {
 
 int jmac_l1_csls_rank_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d, const float* r1,
                           const float* r2, const int32_t* gold, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
-    if (n1 < 0 || n2 <= 0 || d <= 0 || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
-    if (n1 == 0) return JMAC_OK;
-    if (!A || !B || !gold || !rank) return JMAC_EINVAL;
-    if (lda % 4 || ldb % 4) return JMAC_EDIM;
-    if (n1 >= INT32_MAX || n2 >= INT32_MAX || lda >= INT32_MAX) return JMAC_ERANGE;
-    if (!ws || ws_bytes < jmac_l1_csls_rank_workspace_bytes(n1, n2)) return JMAC_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    LinkRankArgs a{};
-    const bool vec = l1_align_args(a, A, lda, B, ldb, n1, n2, d, r1, r2);
-    a.gs = (float*)ws; a.gold = gold; a.rank = rank;
-    hipLaunchKernelGGL(l1_csls_gold_kernel, dim3((unsigned)((n1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, A, lda, B, ldb, (int)n1, (int)d,
-                       r1, r2, gold, a.gs, rank);
-    launch_link_tile<float, LR_CSLS_COUNT>(a, vec, n2, st);
-    return (int)hipGetLastError();
+    return csls_rank_entry(ALIGN_L1, A, lda, B, ldb, n1, n2, d, r1, r2, gold, rank, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

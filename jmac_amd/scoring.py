@@ -560,21 +560,33 @@ def alignment_sim(embed1: torch.Tensor, embed2: torch.Tensor, metric: str = "cos
 CSLS_KMAX = 64
 
 
-def _l1_topk(a: torch.Tensor, b: torch.Tensor, k: int, r1=None, r2=None, row_id=None, best=None):
-    """(idx int32 [n1, k], val fp32 [n1, k]) of jmac_l1_csls_topk_f32 / _viable_f32 on prepared operands (``_rows16``)."""
+def _check_k(who: str, k, n2: int) -> int:
+    k = int(k)
+    if not 1 <= k <= CSLS_KMAX or k > n2:
+        raise ValueError("%s: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (who, k, n2))
+    return k
+
+
+def _topk_bytes(metric: str, rows: int, n2: int, d: int, k: int) -> int:
+    """Workspace bytes of the fused top-k of ``rows`` rows on the machine ``metric`` runs on."""
+    if _l1_metric(metric):
+        return int(lib().jmac_l1_csls_topk_workspace_bytes(rows, n2, d, k))
+    return int(lib().jmac_sim_csls_topk_workspace_bytes(rows, n2, k))
+
+
+def _csls_topk(a: torch.Tensor, b: torch.Tensor, k: int, r1=None, r2=None, metric: str = "inner", row_id=None, best=None, ws=None):
+    """(idx int32 [n1, k], val fp32 [n1, k]) of jmac_{sim,l1}_csls_topk_f32 -- with ``best`` (and ``row_id``) of the _viable_f32 form --
+    on prepared operands (``_rows16``).  ``ws``: a caller-held workspace of at least ``_topk_bytes`` bytes, whose head is used."""
     n1, d = a.shape
     n2 = b.shape[0]
     idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
     val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
-    L = lib()
-    ws_bytes = int(L.jmac_l1_csls_topk_workspace_bytes(n1, n2, d, k))
-    ws = workspace(ws_bytes, a.device)
-    if best is None:
-        check(L.jmac_l1_csls_topk_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
-                                      stream()), "jmac_l1_csls_topk_f32")
-    else:
-        check(L.jmac_l1_csls_topk_viable_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(row_id), ptr(best), k, ptr(val),
-                                             ptr(idx), ptr(ws), ws_bytes, stream()), "jmac_l1_csls_topk_viable_f32")
+    ws_bytes = _topk_bytes(metric, n1, n2, d, k)
+    ws = workspace(ws_bytes, a.device) if ws is None else ws
+    name = ("jmac_l1_csls_topk" if _l1_metric(metric) else "jmac_sim_csls_topk") + ("_f32" if best is None else "_viable_f32")
+    viable = () if best is None else (ptr(row_id), ptr(best))
+    check(getattr(lib(), name)(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), *viable, k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
+                               stream()), name)
     return idx, val
 
 
@@ -592,7 +604,7 @@ def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int, metric: str = "inn
     if _l1_metric(metric):
         require_device(a, b)
         a, b = _rows16(a.detach()), _rows16(b.detach())
-        return _l1_topk(a, b, csls_k)[1].mean(1), _l1_topk(b, a, csls_k)[1].mean(1)
+        return _csls_topk(a, b, csls_k, metric=metric)[1].mean(1), _csls_topk(b, a, csls_k, metric=metric)[1].mean(1)
     r1 = sim_topk(a, b, csls_k, return_values=True)[1].mean(1)
     r2 = sim_topk(b, a, csls_k, return_values=True)[1].mean(1)
     return r1, r2
@@ -701,21 +713,7 @@ def alignment_topk(emb1: torch.Tensor, emb2: torch.Tensor, k: int, csls_k: int =
     under ``alignment_sim(.., csls_k)``, best first (ties -> lower index first) == ``row_topk(alignment_sim(..), k)`` bit for
     bit, without the n1 x n2 matrix (greedy_alignment's alignment_rest, alignment.py:10-112, is column 0).  1 <= k <= 64."""
     a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
-    n1, d = a.shape
-    n2 = b.shape[0]
-    k = int(k)
-    if not 1 <= k <= 64 or k > n2:
-        raise ValueError("alignment_topk: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
-    if _l1_metric(metric):
-        idx, val = _l1_topk(a, b, k, r1, r2)
-        return idx.to(torch.int64), val
-    idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
-    val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
-    L = lib()
-    ws_bytes = int(L.jmac_sim_csls_topk_workspace_bytes(n1, n2, k))
-    ws = workspace(ws_bytes, a.device)
-    check(L.jmac_sim_csls_topk_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
-                                   stream()), "jmac_sim_csls_topk_f32")
+    idx, val = _csls_topk(a, b, _check_k("alignment_topk", k, b.shape[0]), r1, r2, metric)
     return idx.to(torch.int64), val
 
 
@@ -752,9 +750,7 @@ def _candidate_lists(idx: torch.Tensor, val: torch.Tensor, n2: int, what: str):
     require_device(idx, val)
     if idx.dim() != 2 or idx.shape != val.shape or val.dtype != torch.float32:
         raise ValueError("%s: idx and val must be [n1, k] tensors, val fp32" % what)
-    k = idx.shape[1]
-    if not 1 <= k <= 64 or k > int(n2):
-        raise ValueError("%s: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (what, k, int(n2)))
+    _check_k(what, idx.shape[1], int(n2))
     return idx.to(torch.int32).contiguous(), val.contiguous()
 
 
@@ -776,11 +772,8 @@ def alignment_topk_viable(emb1: torch.Tensor, emb2: torch.Tensor, k: int, best: 
     a deferred-acceptance run, 0 = free).  ``row_id`` (default 0 .. n1-1) names the suitor each row stands for.  A row with fewer
     than k such columns ends in (idx -1, val -inf).  With ``best`` all zero this is ``alignment_topk`` bit for bit."""
     a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
-    n1, d = a.shape
-    n2 = b.shape[0]
-    k = int(k)
-    if not 1 <= k <= 64 or k > n2:
-        raise ValueError("alignment_topk_viable: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
+    n1, n2 = a.shape[0], b.shape[0]
+    k = _check_k("alignment_topk_viable", k, n2)
     require_device(best)
     if best.dtype != torch.int64 or best.shape != (n2,):
         raise ValueError("best must be an int64 vector of n2 words")
@@ -788,32 +781,13 @@ def alignment_topk_viable(emb1: torch.Tensor, emb2: torch.Tensor, k: int, best: 
         torch.as_tensor(row_id, device=a.device).to(torch.int32).contiguous()
     if rid.shape != (n1,):
         raise ValueError("row_id must have one entry per row of emb1")
-    if _l1_metric(metric):
-        idx, val = _l1_topk(a, b, k, r1, r2, rid, best.contiguous())
-        return idx.to(torch.int64), val
-    idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
-    val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
-    L = lib()
-    ws_bytes = int(L.jmac_sim_csls_topk_workspace_bytes(n1, n2, k))
-    ws = workspace(ws_bytes, a.device)
-    check(L.jmac_sim_csls_topk_viable_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(rid), ptr(best.contiguous()), k,
-                                          ptr(val), ptr(idx), ptr(ws), ws_bytes, stream()), "jmac_sim_csls_topk_viable_f32")
+    idx, val = _csls_topk(a, b, k, r1, r2, metric, rid, best.contiguous())
     return idx.to(torch.int64), val
 
 
-def _topk_entry_points(metric: str, d: int):
-    """(workspace_bytes(rows, n2, k), top-k, viable top-k) of the machine ``metric`` runs on; the two take the same arguments."""
-    L = lib()
-    if _l1_metric(metric):
-        return (lambda rows, n2, k: int(L.jmac_l1_csls_topk_workspace_bytes(rows, n2, d, k)),
-                (L.jmac_l1_csls_topk_f32, "jmac_l1_csls_topk_f32"), (L.jmac_l1_csls_topk_viable_f32, "jmac_l1_csls_topk_viable_f32"))
-    return (lambda rows, n2, k: int(L.jmac_sim_csls_topk_workspace_bytes(rows, n2, k)),
-            (L.jmac_sim_csls_topk_f32, "jmac_sim_csls_topk_f32"), (L.jmac_sim_csls_topk_viable_f32, "jmac_sim_csls_topk_viable_f32"))
-
-
-def _refill_chunk_rows(n1: int, n2: int, d: int, k: int, ws_bytes: int, topk_bytes) -> int:
+def _refill_chunk_rows(metric: str, n1: int, n2: int, d: int, k: int, ws_bytes: int) -> int:
     """Most rows L whose top-k workspace AND gathered operand rows fit ``ws_bytes`` together (both grow linearly with L)."""
-    need = lambda rows: topk_bytes(rows, n2, k) + rows * d * 4 + 256      # noqa: E731
+    need = lambda rows: _topk_bytes(metric, rows, n2, d, k) + rows * d * 4 + 256      # noqa: E731
     rows = n1
     while rows > 1 and need(rows) > ws_bytes:
         rows = max(1, min(rows - 1, rows * ws_bytes // need(rows)))
@@ -835,17 +809,11 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
     a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
     n1, d = a.shape
     n2 = b.shape[0]
-    k = int(k)
-    if not 1 <= k <= 64 or k > n2:
-        raise ValueError("stable_alignment: k must lie in [1, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
-    dev = a.device
-    topk_bytes, (topk, topk_name), (viable, viable_name) = _topk_entry_points(metric, d)
-    idx = torch.empty((n1, k), dtype=torch.int32, device=dev)
-    val = torch.empty((n1, k), dtype=torch.float32, device=dev)
+    k = _check_k("stable_alignment", k, n2)
     # one workspace for every top-k of the run; a refill's gathered rows of `a` live in its tail
-    ws_bytes = max(topk_bytes(n1, n2, k), topk_bytes(1, n2, k) + d * 4 + 256)
-    ws = workspace(ws_bytes, dev)
-    check(topk(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), k, ptr(val), ptr(idx), ptr(ws), ws_bytes, stream()), topk_name)
+    ws_bytes = max(_topk_bytes(metric, n1, n2, d, k), _topk_bytes(metric, 1, n2, d, k) + d * 4 + 256)
+    ws = workspace(ws_bytes, a.device)
+    idx, val = _csls_topk(a, b, k, r1, r2, metric, ws=ws)
     st = _StableState(idx, val, n2)
     refills = proposals = 0
     complete = True
@@ -859,21 +827,15 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
             complete = False
             break
         ids = st.exhausted_ids(exhausted)
-        chunk = chunk or _refill_chunk_rows(n1, n2, d, k, ws_bytes, topk_bytes)
+        chunk = chunk or _refill_chunk_rows(metric, n1, n2, d, k, ws_bytes)
         for lo in range(0, exhausted, chunk):
             rid = ids[lo:lo + chunk].contiguous()
             rows = rid.numel()
             sel = rid.to(torch.int64)
-            top_bytes = topk_bytes(rows, n2, k)
             sub = ws[ws_bytes - rows * d * 4:].view(torch.float32).view(rows, d)       # (ws_bytes and the offset: multiples of 16)
             torch.index_select(a, 0, sel, out=sub)
             r1s = r1.index_select(0, sel) if r1 is not None else None
-            nidx = torch.empty((rows, k), dtype=torch.int32, device=dev)
-            nval = torch.empty((rows, k), dtype=torch.float32, device=dev)
-            check(viable(ptr(sub), d, ptr(b), d, rows, n2, d, ptr(r1s), ptr(r2), ptr(rid), ptr(st.best), k, ptr(nval), ptr(nidx), ptr(ws),
-                         top_bytes, stream()), viable_name)
-            idx[sel] = nidx
-            val[sel] = nval
+            idx[sel], val[sel] = _csls_topk(sub, b, k, r1s, r2, metric, rid, st.best, ws)       # the workspace's head
             st.ptr[sel] = 0
         refills += 1
     m1 = st.match1.to(torch.int64)

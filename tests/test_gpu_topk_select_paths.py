@@ -3,11 +3,12 @@
 A row of a fused top-k takes one of three exits: its candidate list fits (sort the list); the list overflows but the bins at and
 above the one that holds the k-th best fit the LDS list (two recomputing passes, then the sort); even those overflow (arg-max
 rounds).  The first and the last are reached by the tests of the three callers; the inputs here are built for the middle one,
-and every test ASSERTS from a materialised matrix that its rows take it, per row:
+and every test of it ASSERTS from a materialised matrix that its rows take it, per row:
   A  more than 1024 - k of the columns past the sample (the first 2048 columns at N = 8192) reach the row's k-th best sample
      score, so the list of 1024 overflows;
   B  the 12-bit bin of the row's k-th best score holds, together with the bins above it, at most 1024 elements.
-The last test pins the byte counts of the three workspace functions (it needs no GPU)."""
+test_narrow_fused_seam runs every source on both sides of the driver's one narrow / fused decision.  The last test pins the byte
+counts of the workspace functions (it needs no GPU)."""
 import numpy as np
 import pytest
 import torch
@@ -109,6 +110,49 @@ def test_linkpred_topk_two_pass_recompute_with_listed_tails(bf16):
     assert ridx[0, 0] == NS and ridx[1, 0] == NS + 2
 
 
+@pytest.fixture(scope="module")
+def seam_rows():
+    gen = torch.Generator().manual_seed(11)
+    unit = lambda n: torch.nn.functional.normalize(torch.randn(n, 16, generator=gen), dim=1)       # noqa: E731
+    return unit(10).cuda(), unit(N).cuda(), torch.randn(3, 16, generator=gen).cuda()
+
+
+def _same(got, want):
+    """(idx, val) pairs, bit for bit"""
+    return torch.equal(got[0], want[0]) and torch.equal(got[1].view(torch.int32), want[1].view(torch.int32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [N - 1, N])
+def test_narrow_fused_seam(seam_rows, n):
+    """N = 8191 stores the scores and runs the row pass, N = 8192 is the first fused shape (k = 64 <= 64; k = 65 is narrow again):
+    every source's fused form against the stored path, bit for bit, on both sides of the decision.  Five query rows; the CSLS terms
+    (csls_k = 10 needs ten rows) are those of ten rows, of which the queries are the first five."""
+    from jmac_amd import scoring
+    from jmac_amd.sampling import TrueTailIndex
+    a10, b, rel = seam_rows[0], seam_rows[1][:n].contiguous(), seam_rows[2]
+    a = a10[:5].contiguous()
+    k = 64
+    for kk in [k] + ([k + 1] if n == N else []):
+        rval, ridx = scoring.row_topk(scoring.sim_matrix(a, b), kk)
+        assert _same(scoring.sim_topk(a, b, kk, return_values=True), (ridx, rval)), kk
+    for metric in ("inner", "manhattan"):
+        rval, ridx = scoring.row_topk(scoring.alignment_sim(a10, b, metric, csls_k=10)[:5], k)
+        r1, r2 = scoring.csls_terms(a10, b, 10, metric)
+        got = scoring.alignment_topk(a, b, k, csls_k=10, metric=metric, terms=(r1[:5], r2))
+        assert _same(got, (ridx, rval)), metric
+        free = torch.zeros(n, dtype=torch.int64, device="cuda")
+        assert _same(scoring.alignment_topk_viable(a, b, k, free, csls_k=10, metric=metric, terms=(r1[:5], r2)), got), metric
+    # link prediction: one fp32 layer, whose fused distance has the stored l1_scores' bits; the lists reach into both column ranges
+    h, r = np.array([0, 7, n - 1, 4000, 7]), np.array([0, 1, 2, 0, 2])
+    tt = {(0, 0): np.array([0, 3, NS - 1, NS, n - 1]), (7, 2): np.array([5000]), (9, 1): np.array([1])}
+    dist = scoring.linkpred_dist([b], [rel], h, r).cpu().numpy()
+    ridx, rval = linkpred_ref.topk(dist, k, linkpred_ref.listed_mask(h, r, tt, n))
+    idx, val = scoring.linkpred_topk([b], [rel], h, r, k, index=TrueTailIndex.from_dict(tt, "cuda"))
+    assert (idx.cpu().numpy() == ridx).all()
+    assert (val.cpu().numpy().view(np.int32) == rval.astype(np.float32).view(np.int32)).all()
+
+
 def test_topk_workspace_sizes_are_unchanged():
     """The byte counts the library returned before the candidate-list layout became one struct (L / B, N, [d, layers,] k)."""
     from jmac_amd import _lib
@@ -118,6 +162,9 @@ def test_topk_workspace_sizes_are_unchanged():
     for shape, want in sim.items():
         assert L.jmac_sim_topk_workspace_bytes(*shape) == want, shape
         assert L.jmac_sim_csls_topk_workspace_bytes(*shape) == want, shape
+        rows, n, k = shape
+        assert L.jmac_l1_csls_topk_workspace_bytes(rows, n, 32, k) == want, shape                        # the sim value for any d > 0
+        assert L.jmac_l1_csls_topk_workspace_bytes(rows, n, 0, k) == 0, shape
     link = {(9, 70, 7, 3, 10): 4352, (40, 4000, 64, 1, 64): 651008,                                    # narrow
             (70, 9000, 30, 2, 10): 1171968, (96, 20000, 64, 1, 64): 1648128, (2, 8192, 8, 1, 10): 34304,
             (5, 8192, 13, 2, 3): 83968}                                                                # d % 4 != 0, fused
