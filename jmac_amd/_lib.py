@@ -189,6 +189,8 @@ _SIGS = {
 
 # entry points of libjmac_hip_testing.so only (include/jmac_hip_testing.h)
 _TESTING_SIGS = {
+    "jmac_rel_attn_aggregate_fwd_lanes64_f32": _SIGS["jmac_rel_attn_aggregate_fwd_f32"],
+    "jmac_rel_attn_aggregate_fwd_lanes64_bf16_padded": _SIGS["jmac_rel_attn_aggregate_fwd_bf16_padded"],
     "jmac_gemm_nt_x3_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, i64, vp]),
 }
 
@@ -227,8 +229,9 @@ _tlib: Optional[C.CDLL] = None
 
 
 def testing_lib() -> C.CDLL:
-    """libjmac_hip_testing.so: the same library with the ATOMIC aggregation backward compiled in (mode 0) -- an independent
-    second implementation for the parity tests.  Nothing on the product path calls this."""
+    """libjmac_hip_testing.so: the same library with the ATOMIC aggregation backward compiled in (mode 0) and the forward entry
+    points held to the 64-lane kernels -- independent second implementations for the parity tests.  Nothing on the product
+    path calls this."""
     global _tlib
     if _tlib is None:
         path = os.path.join(_HERE, "libjmac_hip_testing.so")

@@ -12,7 +12,6 @@
 // wave; logits are reduced across the wave with DPP + permlane swaps; the softmax is online (running
 // max / denominator), so each edge row is read exactly once.  The relation table [Rq|Rz] stays
 // L2-resident.  HBM-bound by design: see DESIGN.md for the byte model.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -24,10 +23,7 @@ namespace {
 constexpr int kBlock = 256;            // 4 waves
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kPersistBlocks = 2048;   // 256 CUs x 8
-#ifndef JMAC_EMPTY_PACK
-#define JMAC_EMPTY_PACK 4
-#endif
-constexpr int kEmptyPack = JMAC_EMPTY_PACK;          // empty segments handled by one wave of the forward kernel
+constexpr int kEmptyPack = 4;          // empty segments handled by one wave of the forward kernel
 // (non-temporal gathers were measured and rejected: 13.4 vs 12.3 ms on config 4, 36 vs 26 us on ja)
 
 // IGroupLP pipeline for the machine scheduler: first the group's n vector-memory reads, then the vector ALU work.
@@ -106,14 +102,6 @@ __device__ __forceinline__ float4 sel4(bool c, float4 a) { return c ? a : f4zero
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-#ifndef JMAC_FWD_WPE
-#define JMAC_FWD_WPE 0
-#endif
-#if JMAC_FWD_WPE
-#define JMAC_FWD_ATTR __attribute__((amdgpu_waves_per_eu(JMAC_FWD_WPE, JMAC_FWD_WPE)))
-#else
-#define JMAC_FWD_ATTR
-#endif
 // bid / nblk: the block's index and the block count of ITS job (one launch may carry two independent jobs: below)
 template <int NCH, int U, int D4T, typename TT>
 __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bid, const int nblk) {
@@ -484,7 +472,7 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
 }
 
 template <int NCH, int U, int D4T, typename TT>
-__global__ __launch_bounds__(kBlock) JMAC_FWD_ATTR void rel_attn_fwd_kernel(FwdArgs a) {
+__global__ __launch_bounds__(kBlock) void rel_attn_fwd_kernel(FwdArgs a) {
     rel_attn_fwd_body<NCH, U, D4T, TT>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
@@ -496,7 +484,7 @@ __global__ __launch_bounds__(kBlock) JMAC_FWD_ATTR void rel_attn_fwd_kernel(FwdA
 // copy fetched from the kernarg segment at a run-time offset) loses the "kernel arguments point to global memory" inference --
 // 90 flat_loads instead of global_loads in the ISA, each counted on two wait counters.
 template <int NCH, int U, int D4T, typename TT>
-__global__ __launch_bounds__(kBlock) JMAC_FWD_ATTR void rel_attn_fwd_jobs_kernel(FwdArgs a0, FwdArgs a1, int g0) {
+__global__ __launch_bounds__(kBlock) void rel_attn_fwd_jobs_kernel(FwdArgs a0, FwdArgs a1, int g0) {
     if ((int)blockIdx.x < g0)                                         // block-uniform
         rel_attn_fwd_body<NCH, U, D4T, TT>(a0, (int)blockIdx.x, g0);
     else
@@ -521,11 +509,6 @@ template <> struct HwElem<float> { static constexpr int CH = 4; };
 template <> struct HwElem<bf16_t> { static constexpr int CH = 8; };
 template <int CH> struct VF { float v[CH]; };
 __device__ __forceinline__ uint4 ld16(const void* p) { return *reinterpret_cast<const uint4*>(p); }
-typedef unsigned jmac_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ld16_nt(const void* p) {   // streaming: the line is first in line for eviction from L2
-    const jmac_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const jmac_u32x4*>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
 template <typename TT> __device__ __forceinline__ VF<HwElem<TT>::CH> hw_cvt(uint4 r);
 template <> __device__ __forceinline__ VF<4> hw_cvt<float>(uint4 r) {
     VF<4> o;
@@ -570,12 +553,10 @@ __device__ __forceinline__ float halves_meet(float a, float b) {
     return a + b;
 }
 
-// HOT > 0 (experiment, JMAC_FWD_HOT=1: north_star's "LDS-staged relation tiles"): rows 0 .. HOT-1 of [Rq|Rz] -- the hottest
-// relations when the ids are ordered by frequency -- are staged in LDS once per workgroup; an edge of such a relation reads its
-// relation chunks from LDS (its global load is pointed at row 0, an L1 hit), the Zipf tail keeps its L2 / Infinity-Cache path.
-// PIPE: 0 = load / reduce in turn (one wave per item); 12 = two groups' gathers in flight, uniform issue (the persistent form);
-// 2 = two groups, conditional issue (A/B knob).  One pair of edges per group (GP = 1: two pairs measured 8.94 against 6.66 ms)
-template <int DC, int PIPE, typename TT, int HOT = 0, int NT = 0>
+// One form: two groups' gathers in flight per wave, uniform issue (below).  One pair of edges per group (GP = 1: two pairs
+// measured 8.94 against 6.66 ms).  The forms measured against it and closed -- LDS-staged hot relation rows, streaming [Q|Z]
+// gathers, a guarded two-deep and a load / reduce in turn pipeline -- are recorded in profiles/HISTORY.md.
+template <int DC, typename TT>
 __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
     constexpr int GP = 1;
     constexpr int CH = HwElem<TT>::CH;
@@ -587,7 +568,6 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
     typedef VF<CH> vf;
     __shared__ float coop_acc[kWavesPerBlock][NP][CH][64];
     __shared__ float coop_ml[kWavesPerBlock][2];
-    __shared__ uint4 hot_rows[HOT > 0 ? HOT * 2 * DC : 1];
     const TT* const tP = static_cast<const TT*>(a.P);
     const TT* const tQZ = static_cast<const TT*>(a.QZ);
     const TT* const tRR = static_cast<const TT*>(a.RR);
@@ -632,47 +612,23 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
     }
     // Every load stays RAW (uint4) until its first use: a conversion or a select right behind a load is waited for where it
     // stands, i.e. in front of the gathers that should be in flight together with it (one more round trip per item).
-    // relation table as a buffer resource (HOT only): 32-bit lane offsets, out-of-range lanes are dropped by the range check
-    const auto rr_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<TT*>(tRR), 0, (int)0xFFFFFFF0u, 0x00020000);
-    if constexpr (HOT > 0) {                           // stage the hot relation rows (the table has more than HOT rows: launcher)
-        for (int i = threadIdx.x; i < HOT * 2 * DC; i += kBlock)
-            hot_rows[i] = ld16(tRR + (int64_t)(i / (2 * DC)) * a.ldrr + (i % (2 * DC)) * CH);
-        __syncthreads();
-    }
     uint4 rlraw[NP];                                   // the loop relation's Rz chunks in the OUTPUT layout: one read per wave
 #pragma unroll
     for (int p = 0; p < NP; ++p) rlraw[p] = ld16(rloop + (oc[p] >= 0 ? oc[p] : 0) * CH);
 
     // ---- online softmax over the entries [item.beg, item.end) of one destination; both halves carry PARTIAL accumulators
     auto edge_loop = [&](const jmac_item_t& item, int my_col, int my_typ, const uint4 (&praw)[KH], float& m, float& l, vf (&acc)[NCH]) {
-        auto issue = [&](const int nb, const int mc, const int mt, const int p0, uint4 (&qr)[GP][NCH], uint4 (&rr)[GP][NCH], int (&th)[GP]) {
+        auto issue = [&](const int nb, const int mc, const int mt, const int p0, uint4 (&qr)[GP][NCH], uint4 (&rr)[GP][NCH]) {
 #pragma unroll
             for (int u = 0; u < GP; ++u) {
                 const int ea = max(min(2 * (p0 + u), nb - 1), 0), eb = max(min(2 * (p0 + u) + 1, nb - 1), 0);
                 const int ja = bcast_i(mc, ea), jb = bcast_i(mc, eb);
                 const int ta = bcast_i(mt, ea), tb = bcast_i(mt, eb);
                 const TT* qrow = tQZ + (int64_t)(upper ? jb : ja) * a.ldqz;
-                const int tsel = upper ? tb : ta;
-                th[u] = -1;
-                const TT* rrow = tRR + (int64_t)tsel * a.ldrr;
-                if constexpr (HOT > 0) {
-                    // hot: the chunks come from LDS and the lane's relation load must cost NOTHING -- pointed at a dummy row (row 0,
-                    // or the lane's own [Q|Z] chunk) it still went to L2 and the kernel ran 2.4 x longer.  A buffer load whose
-                    // offset lies past the descriptor's range is dropped by the range check: no request leaves the CU.
-                    th[u] = tsel < HOT ? tsel : -1;
-                    const unsigned rb = tsel < HOT ? 0xFFFFFFFFu : (unsigned)tsel * (unsigned)(a.ldrr * sizeof(TT));
-#pragma unroll
-                    for (int k = 0; k < NCH; ++k) {
-                        qr[u][k] = ld16(qrow + coff[k]);
-                        const unsigned vo = tsel < HOT ? 0xFFFFFFFFu : rb + (unsigned)(coff[k] * sizeof(TT));
-                        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rr_rsrc, (int)vo, 0, 0);
-                        rr[u][k] = make_uint4(v[0], v[1], v[2], v[3]);
-                    }
-                    continue;
-                }
+                const TT* rrow = tRR + (int64_t)(upper ? tb : ta) * a.ldrr;
 #pragma unroll
                 for (int k = 0; k < NCH; ++k) {
-                    qr[u][k] = NT ? ld16_nt(qrow + coff[k]) : ld16(qrow + coff[k]);
+                    qr[u][k] = ld16(qrow + coff[k]);
                     rr[u][k] = ld16(rrow + coff[k]);
                 }
             }
@@ -680,8 +636,7 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
         // the item's FIRST group of gathers goes out here, in one basic block with the loads of P[i] / Z[i] and ahead of the
         // conversion of P[i]: that conversion waits for P[i] only (the gathers are younger), not the other way round
         uint4 qA[GP][NCH], rA[GP][NCH];
-        int tA[GP];
-        issue(min(64, item.end - item.beg), my_col, my_typ, 0, qA, rA, tA);
+        issue(min(64, item.end - item.beg), my_col, my_typ, 0, qA, rA);
         vf pv[KH];
 #pragma unroll
         for (int k = 0; k < KH; ++k) {
@@ -696,10 +651,10 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
                 const int le = min(lane, nb - 1);
                 my_col = a.col[e0 + le];
                 my_typ = a.etype[e0 + le];
-                issue(nb, my_col, my_typ, 0, qA, rA, tA);
+                issue(nb, my_col, my_typ, 0, qA, rA);
             }
             const int npairs = (nb + 1) >> 1;
-            auto consume = [&](const int p0, const uint4 (&qr)[GP][NCH], const uint4 (&rr)[GP][NCH], const int (&th)[GP]) {
+            auto consume = [&](const int p0, const uint4 (&qr)[GP][NCH], const uint4 (&rr)[GP][NCH]) {
                 vf x[GP][NCH];
                 float part[GP];
 #pragma unroll
@@ -707,16 +662,7 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
                     part[u] = 0.f;
 #pragma unroll
                     for (int k = 0; k < NCH; ++k) {
-                        uint4 rraw = rr[u][k];
-                        if constexpr (HOT > 0) {
-                            const uint4 lv = hot_rows[max(th[u], 0) * (2 * DC) + min(hl + 32 * k, 2 * DC - 1)];
-                            // component-wise: hipcc lowers a ternary over uint4 STRUCTS to two scratch stores and an indexed
-                            // scratch load (48 B of private segment, 2.4 x the kernel's time); on dwords it is v_cndmask
-                            const bool hsel = th[u] >= 0;
-                            rraw.x = hsel ? lv.x : rraw.x; rraw.y = hsel ? lv.y : rraw.y;
-                            rraw.z = hsel ? lv.z : rraw.z; rraw.w = hsel ? lv.w : rraw.w;
-                        }
-                        const vf q = hw_cvt<TT>(qr[u][k]), r = hw_cvt<TT>(rraw);
+                        const vf q = hw_cvt<TT>(qr[u][k]), r = hw_cvt<TT>(rr[u][k]);
 #pragma unroll
                         for (int e = 0; e < CH; ++e) {
                             float d = q.v[e] - r.v[e];
@@ -755,50 +701,26 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
                     }
                 m = mn;
             };
-            if constexpr (PIPE == 12) {
-                // two groups in flight, EVERY path issuing the same loads: a group past the batch's end re-reads the last pair's rows
-                // (an L1 hit; it is never reduced).  The compiler's vmcnt bookkeeping is exact only when all paths into a wait have
-                // issued the same number of loads: behind a conditional issue (the PIPE 2 form below, and the three-deep form this
-                // replaced) it falls back to vmcnt(0) -- the whole pipeline drained once per trip, seen in the ISA; here the waits
-                // count down vmcnt(11) .. vmcnt(6) chunk by chunk while the younger group stays in flight
-                uint4 qB[GP][NCH], rB[GP][NCH];
-                int tB[GP];
-                int p = 0;
-                for (;;) {
-                    issue(nb, my_col, my_typ, p + GP, qB, rB, tB);
-                    __builtin_amdgcn_sched_barrier(0);
-                    consume(p, qA, rA, tA);
-                    __builtin_amdgcn_sched_barrier(0);
-                    p += GP;
-                    if (p >= npairs) break;
-                    issue(nb, my_col, my_typ, p + GP, qA, rA, tA);
-                    __builtin_amdgcn_sched_barrier(0);
-                    consume(p, qB, rB, tB);
-                    __builtin_amdgcn_sched_barrier(0);
-                    p += GP;
-                    if (p >= npairs) break;
-                }
-            } else if constexpr (PIPE == 2) {
-                uint4 qB[GP][NCH], rB[GP][NCH];
-                int tB[GP];
-                for (int p = 0; p < npairs; p += 2 * GP) {
-                    if (p + GP < npairs) issue(nb, my_col, my_typ, p + GP, qB, rB, tB);
-                    __builtin_amdgcn_sched_barrier(0);
-                    consume(p, qA, rA, tA);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (p + GP < npairs) {
-                        if (p + 2 * GP < npairs) issue(nb, my_col, my_typ, p + 2 * GP, qA, rA, tA);
-                        __builtin_amdgcn_sched_barrier(0);
-                        consume(p + GP, qB, rB, tB);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            } else {
-                for (int p = 0; p < npairs; p += GP) {
-                    if (p > 0) issue(nb, my_col, my_typ, p, qA, rA, tA);
-                    __builtin_amdgcn_sched_barrier(0);
-                    consume(p, qA, rA, tA);
-                }
+            // two groups in flight, EVERY path issuing the same loads: a group past the batch's end re-reads the last pair's rows
+            // (an L1 hit; it is never reduced).  The compiler's vmcnt bookkeeping is exact only when all paths into a wait have
+            // issued the same number of loads: behind a conditional issue (the guarded two-deep and three-deep forms this replaced)
+            // it falls back to vmcnt(0) -- the whole pipeline drained once per trip, seen in the ISA; here the waits count down
+            // vmcnt(11) .. vmcnt(6) chunk by chunk while the younger group stays in flight
+            uint4 qB[GP][NCH], rB[GP][NCH];
+            int p = 0;
+            for (;;) {
+                issue(nb, my_col, my_typ, p + GP, qB, rB);
+                __builtin_amdgcn_sched_barrier(0);
+                consume(p, qA, rA);
+                __builtin_amdgcn_sched_barrier(0);
+                p += GP;
+                if (p >= npairs) break;
+                issue(nb, my_col, my_typ, p + GP, qA, rA);
+                __builtin_amdgcn_sched_barrier(0);
+                consume(p, qB, rB);
+                __builtin_amdgcn_sched_barrier(0);
+                p += GP;
+                if (p >= npairs) break;
             }
         }
     };
@@ -1003,9 +925,9 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
     empties(it - n_reg);
 }
 
-template <int DC, int PIPE, typename TT, int HOT = 0, int NT = 0>
+template <int DC, typename TT>
 __global__ __launch_bounds__(kBlock) void rel_attn_fwd_hw_kernel(FwdArgs a) {
-    rel_attn_fwd_hw_body<DC, PIPE, TT, HOT, NT>(a);
+    rel_attn_fwd_hw_body<DC, TT>(a);
 }
 
 // merges the partial (max, denominator, accumulator) triples of destinations that were split: one BLOCK per split
@@ -1699,27 +1621,22 @@ inline int check_dims(int64_t d, int64_t ld0, int64_t ld1, int64_t ld2) {
     return 0;
 }
 
-inline int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
+// blocks that give every work unit (an item, a pack of empty segments) a wave of its own
+inline int64_t unit_blocks(int64_t n_units) {
+    const int64_t need = (n_units + kWavesPerBlock - 1) / kWavesPerBlock;
+    return need < 1 ? 1 : need;
 }
 
+// backward passes B / C: one wave per item up to the persistent grid
 inline unsigned persist_grid(int64_t n_items_max) {
-    static const int cap = env_int("JMAC_GRID", kPersistBlocks);   // tuning knob (debug)
-    int64_t need = (n_items_max + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (need < 1) need = 1;
-    return (unsigned)(need < cap ? need : cap);
+    const int64_t need = unit_blocks(n_items_max);
+    return (unsigned)(need < kPersistBlocks ? need : kPersistBlocks);
 }
 
-// forward: graphs of up to 16k items get one wave per item (measured on the DBP-5L ja shape: 21 us against 24 us
-// with the persistent 2048-block grid -- at that size the kernel is a chain of dependent round trips, not a stream)
-inline unsigned fwd_grid(int64_t n_items_max) {
-    static const int cap = env_int("JMAC_GRID", 0);
-    if (cap > 0) return persist_grid(n_items_max);
-    const int64_t need = (n_items_max + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (need <= 2 * kPersistBlocks) return (unsigned)(need < 1 ? 1 : need);
-    return kPersistBlocks;
-}
+// forward and backward pass A: one wave per unit while that takes at most 2 x kPersistBlocks blocks (graphs of up to 16k items),
+// the persistent grid beyond (measured on the DBP-5L ja shape: 21 us against 24 us with the persistent 2048-block grid -- at
+// that size the kernel is a chain of dependent round trips, not a stream)
+inline unsigned fwd_grid(int64_t blocks) { return (unsigned)(blocks <= 2 * kPersistBlocks ? blocks : kPersistBlocks); }
 
 inline unsigned split_grid(int64_t n_splits_max) {
     if (n_splits_max < 1) n_splits_max = 1;
@@ -1750,21 +1667,45 @@ void launch_reduce_rows(const float* partial, int nparts, int W, float scale, fl
 
 // What launch_rel_attn_fwd decided for one call, for jmac_rel_attn_aggregate_fwd_jobs_f32: a call whose form is the plain
 // small-graph kernel (one wave per item) is NOT launched when a plan is asked for -- the caller pairs two of them in one launch
+enum FwdForm { kFwdLanes64U2, kFwdLanes64U4, kFwdHalfWave };
+
 struct FwdPlan {
     FwdArgs a;
     unsigned grid;
     int nch;
+    FwdForm form;
     bool plain_small, slope01, launched;
     int64_t n_comb;                      // split (non-cooperative) destinations: the combine kernel follows the main launch
 };
 
-// dh: pitch of the halves of a [Q|Z] / [Rq|Rz] row in elements (Q at 0, Z at dh): d, or the padded pitch of the bf16 tables
+// The forward kernel of one call, from its arguments alone.
+template <typename TT>
+static FwdForm fwd_form(const TT* P, int64_t ldp, const TT* QZ, int64_t ldqz, const TT* RR, int64_t ldrr, int64_t dh, int64_t d,
+                        const void* item_edges, int64_t n_items_max, bool slope01, bool half_wave_ok) {
+    // small graphs (one wave per item) are bound by round trips, not by gathers in flight: the 2-edge group
+    // is the faster form there (DBP-5L ja: 20.4 us against 22.6 us).  "Small" is the host's call (jmac_amd/graph.py:
+    // schedules that carry their items' first entries inline, the real el + ja pair step: 1.571 -> 1.527 ms)
+    if (item_edges || n_items_max <= 8 * kPersistBlocks) return kFwdLanes64U2;
+    // half-wave lane map (rel_attn_fwd_hw_kernel): d = 256 / 300 with 16-byte aligned rows and halves
+    constexpr int CHE = 16 / (int)sizeof(TT);                          // elements per 16-byte chunk
+    const bool aligned = ((((uintptr_t)P | (uintptr_t)QZ | (uintptr_t)RR) & 15) == 0) && ldp % CHE == 0 && ldqz % CHE == 0 &&
+                         ldrr % CHE == 0 && dh % CHE == 0;
+    const bool hw_shape = sizeof(TT) == 4 ? ((d == 300 || d == 256) && dh == d) : ((d == 300 && dh == 304) || (d == 256 && dh == 256));
+    // measured (rocprofv3 / HIP events, MI355X): config 4 (persistent grid) bf16 7.53 -> 6.48 ms (0.43 -> 0.50 of the HBM peak),
+    // fp32 10.93 -> 10.45 / 9.67 ms; on the 56 589-entity union (one wave per item) the 64-lane kernel stays ahead
+    // (fp32 116 against 120 us, bf16 87 against 105 us): the small-graph form keeps it
+    return half_wave_ok && slope01 && aligned && hw_shape ? kFwdHalfWave : kFwdLanes64U4;
+}
+
+// dh: pitch of the halves of a [Q|Z] / [Rq|Rz] row in elements (Q at 0, Z at dh): d, or the padded pitch of the bf16 tables.
+// half_wave_ok = false (testing build only): the 64-lane kernels at the widths the half-wave kernel would take
 template <typename TT>
 static int launch_rel_attn_fwd(const TT* P, int64_t ldp, const TT* QZ, int64_t ldqz, const TT* RR, int64_t ldrr, int64_t dh,
                                const float* a_att,
                                const int32_t* col, const int32_t* etype, const jmac_view_t* v, int64_t N, int64_t d, float slope,
                                int32_t loop_rel, int64_t self_off, float out_scale, float* out, int64_t ldo, float* seg_max,
-                               float* seg_den, void* ws, size_t ws_bytes, jmac_stream_t stream, FwdPlan* plan = nullptr) {
+                               float* seg_den, void* ws, size_t ws_bytes, jmac_stream_t stream, FwdPlan* plan = nullptr,
+                               bool half_wave_ok = true) {
     if (plan) *plan = FwdPlan{};
     if (N < 0 || !v || v->n_items_max < 0 || v->n_splits_max < 0) return JMAC_EINVAL;
     if (N == 0) {
@@ -1803,67 +1744,30 @@ static int launch_rel_attn_fwd(const TT* P, int64_t ldp, const TT* QZ, int64_t l
     // (a wave each).  One-wave-per-unit grids cover max(blocks for the cooperative segments, blocks for the rest):
     // block b first does cooperative segment b, then its items.
     const int64_t n_wave_units = n_items_max - n_coop * kWavesPerBlock - n_empty + (n_empty + kEmptyPack - 1) / kEmptyPack;
-    int64_t need = (n_wave_units + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (need < n_coop) need = n_coop;
-    if (need < 1) need = 1;
-    static const int grid_env = env_int("JMAC_GRID", 0);               // tuning knob (debug)
-    unsigned grid;
-    if (grid_env > 0) grid = (unsigned)(need < grid_env ? need : grid_env);
-    else grid = (unsigned)(need <= 2 * kPersistBlocks ? need : kPersistBlocks);
-    // small graphs (one wave per item) are bound by round trips, not by gathers in flight: the 2-edge group
-    // is the faster form there (DBP-5L ja: 20.4 us against 22.6 us).  "Small" is the host's call (jmac_amd/graph.py:
-    // schedules that carry their items' first entries inline, the real el + ja pair step: 1.571 -> 1.527 ms)
-    static const int fwd_u_env = env_int("JMAC_FWD_U", 0);         // tuning knob (debug)
-    const int fwd_u = fwd_u_env ? fwd_u_env : ((v->item_edges || n_items_max <= 8 * kPersistBlocks) ? 2 : 4);
+    const int64_t need = unit_blocks(n_wave_units);
+    const unsigned grid = fwd_grid(need < n_coop ? n_coop : need);
     const bool slope01 = slope >= 0.f && slope <= 1.f;
-    // half-wave lane map (rel_attn_fwd_hw_kernel): d = 256 / 300 with 16-byte aligned rows and halves
-    static const int hw_env = env_int("JMAC_FWD_HW", 1);             // tuning knobs (debug)
-    constexpr int CHE = 16 / (int)sizeof(TT);                          // elements per 16-byte chunk
-    const bool aligned = ((((uintptr_t)P | (uintptr_t)QZ | (uintptr_t)RR) & 15) == 0) && ldp % CHE == 0 && ldqz % CHE == 0 &&
-                         ldrr % CHE == 0 && dh % CHE == 0;
-    const int dc = (int)(dh / CHE);
-    const bool hw_shape = sizeof(TT) == 4 ? ((d == 300 || d == 256) && dh == d) : ((d == 300 && dh == 304) || (d == 256 && dh == 256));
-    static const int hw_small_env = env_int("JMAC_FWD_HW_SMALL", 0);
-    // measured (rocprofv3 / HIP events, MI355X): config 4 (persistent grid) bf16 7.53 -> 6.48 ms (0.43 -> 0.50 of the HBM peak),
-    // fp32 10.93 -> 10.45 / 9.67 ms; on the 56 589-entity union (one wave per item) the 64-lane kernel stays ahead
-    // (fp32 116 against 120 us, bf16 87 against 105 us): the small-graph form keeps it
-    const bool use_hw = hw_env && slope01 && aligned && hw_shape && (fwd_u != 2 || hw_small_env);
+    const FwdForm form = fwd_form(P, ldp, QZ, ldqz, RR, ldrr, dh, d, v->item_edges, n_items_max, slope01, half_wave_ok);
     if (plan) {
-        plan->a = a; plan->grid = grid; plan->nch = nch; plan->slope01 = slope01; plan->n_comb = n_splits_max - n_coop;
-        plan->plain_small = !use_hw && fwd_u == 2 && sizeof(TT) == 4;
+        plan->a = a; plan->grid = grid; plan->nch = nch; plan->form = form; plan->slope01 = slope01;
+        plan->n_comb = n_splits_max - n_coop;
+        plan->plain_small = form == kFwdLanes64U2 && sizeof(TT) == 4;
         if (plan->plain_small) return JMAC_OK;          // the caller launches it (paired with another job where it can)
         plan->launched = true;
     }
-    if (use_hw) {
-        static const int hw_depth_env = env_int("JMAC_FWD_HW_DEPTH", 0);
-        // gathers in flight per wave (persistent form): two groups, EVERY path issuing the same loads (PIPE 12: exact vmcnt waits).
-        // Config 4, MI355X: bf16 6.9 ms with the three-deep conditional form this replaced (one vmcnt(0) per trip in its ISA)
-        // -> 6.1-6.2 ms two- or three-deep uniform (0.47 -> 0.53 of the HBM peak); four-deep conditional 7.2 ms; held to three waves
-        // per SIMD (168 VGPRs) 6.3 ms.  fp32: 10.3 ms either way (the launch moves 62 GB at 6 TB/s: the fabric's rate); the
-        // conditional two-deep form stays selectable (JMAC_FWD_HW_DEPTH=2) for A/B runs.
-        const int depth = fwd_u == 2 ? 0 : (hw_depth_env ? hw_depth_env : 12);
-        // experiments (default off, profiles/r4_pmc_config4_experiments.json): the hottest relation rows (ids 0 .. HOT-1: tables
-        // whose relation ids are ordered by frequency) in LDS; streaming [Q|Z] gathers
-        static const int hot_env = env_int("JMAC_FWD_HOT", 0);
-        static const int nt_env = env_int("JMAC_FWD_NT", 0);
-        constexpr int HOTN = sizeof(TT) == 2 ? 40 : 20;                 // 48 KB of rows either way
-        const bool hot = hot_env && depth == 12 && v->n_items_max > 0 && loop_rel >= HOTN &&
-                         (uint64_t)(loop_rel + 1) * (uint64_t)ldrr * sizeof(TT) < 0xFFFFFFF0ull;
-#define JMAC_HW_LAUNCH(DCv)                                                                                                   \
-        do {                                                                                                                  \
-            if (hot) hipLaunchKernelGGL((rel_attn_fwd_hw_kernel<DCv, 12, TT, HOTN>), dim3(grid), dim3(kBlock), 0, st, a);     \
-            else if (nt_env && depth == 12) hipLaunchKernelGGL((rel_attn_fwd_hw_kernel<DCv, 12, TT, 0, 1>), dim3(grid), dim3(kBlock), 0, st, a); \
-            else if (depth == 12) hipLaunchKernelGGL((rel_attn_fwd_hw_kernel<DCv, 12, TT>), dim3(grid), dim3(kBlock), 0, st, a); \
-            else if (depth == 2) hipLaunchKernelGGL((rel_attn_fwd_hw_kernel<DCv, 2, TT>), dim3(grid), dim3(kBlock), 0, st, a);  \
-            else hipLaunchKernelGGL((rel_attn_fwd_hw_kernel<DCv, 0, TT>), dim3(grid), dim3(kBlock), 0, st, a);                  \
-        } while (0)
+    if (form == kFwdHalfWave) {
+        // gathers in flight per wave: two groups, EVERY path issuing the same loads (exact vmcnt waits).  Config 4, MI355X: bf16
+        // 6.9 ms with the three-deep conditional form this replaced (one vmcnt(0) per trip in its ISA) -> 6.1-6.2 ms two- or
+        // three-deep uniform (0.47 -> 0.53 of the HBM peak); four-deep conditional 7.2 ms; held to three waves per SIMD
+        // (168 VGPRs) 6.3 ms.  fp32: 10.3 ms either way (the launch moves 62 GB at 6 TB/s: the fabric's rate)
+#define JMAC_HW_LAUNCH(DCv) hipLaunchKernelGGL((rel_attn_fwd_hw_kernel<DCv, TT>), dim3(grid), dim3(kBlock), 0, st, a)
         if constexpr (sizeof(TT) == 4) {
-            if (dc == 75) JMAC_HW_LAUNCH(75); else JMAC_HW_LAUNCH(64);
+            if (dh == 300) JMAC_HW_LAUNCH(75); else JMAC_HW_LAUNCH(64);
         } else {
-            if (dc == 38) JMAC_HW_LAUNCH(38); else JMAC_HW_LAUNCH(32);
+            if (dh == 304) JMAC_HW_LAUNCH(38); else JMAC_HW_LAUNCH(32);
         }
 #undef JMAC_HW_LAUNCH
-    } else if (fwd_u == 2) {
+    } else if (form == kFwdLanes64U2) {
         JMAC_DISPATCH_D(a.D4, nch, hipLaunchKernelGGL((rel_attn_fwd_kernel<NCH, 2, D4T, TT>), dim3(grid), dim3(kBlock), 0, st, a));
     } else {
         JMAC_DISPATCH_D(a.D4, nch, hipLaunchKernelGGL((rel_attn_fwd_kernel<NCH, 4, D4T, TT>), dim3(grid), dim3(kBlock), 0, st, a));
@@ -1947,6 +1851,28 @@ int jmac_rel_attn_aggregate_fwd_bf16_padded(const uint16_t* P, int64_t ldp, cons
     return launch_rel_attn_fwd<bf16_t>(P, ldp, QZ, ldqz, RR, ldrr, dh, a_att, col, etype, by_dst, N, d, slope, loop_rel, self_off,
                                        out_scale, out, ldo, seg_max, seg_den, ws, ws_bytes, stream);
 }
+
+#ifdef JMAC_TESTING_BUILD
+// the 64-lane kernels on arguments that the product entry points give to the half-wave kernel (include/jmac_hip_testing.h)
+int jmac_rel_attn_aggregate_fwd_lanes64_f32(const float* P, int64_t ldp, const float* QZ, int64_t ldqz, const float* RR,
+                                            int64_t ldrr, const float* a_att, const int32_t* col, const int32_t* etype,
+                                            const jmac_view_t* by_dst, int64_t N, int64_t d, float slope, int32_t loop_rel,
+                                            int64_t self_off, float out_scale, float* out, int64_t ldo, float* seg_max,
+                                            float* seg_den, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    return launch_rel_attn_fwd<float>(P, ldp, QZ, ldqz, RR, ldrr, d, a_att, col, etype, by_dst, N, d, slope, loop_rel, self_off,
+                                      out_scale, out, ldo, seg_max, seg_den, ws, ws_bytes, stream, nullptr, false);
+}
+
+int jmac_rel_attn_aggregate_fwd_lanes64_bf16_padded(const uint16_t* P, int64_t ldp, const uint16_t* QZ, int64_t ldqz,
+                                                    const uint16_t* RR, int64_t ldrr, int64_t dh, const float* a_att,
+                                                    const int32_t* col, const int32_t* etype, const jmac_view_t* by_dst, int64_t N,
+                                                    int64_t d, float slope, int32_t loop_rel, int64_t self_off, float out_scale,
+                                                    float* out, int64_t ldo, float* seg_max, float* seg_den, void* ws,
+                                                    size_t ws_bytes, jmac_stream_t stream) {
+    return launch_rel_attn_fwd<bf16_t>(P, ldp, QZ, ldqz, RR, ldrr, dh, a_att, col, etype, by_dst, N, d, slope, loop_rel, self_off,
+                                       out_scale, out, ldo, seg_max, seg_den, ws, ws_bytes, stream, nullptr, false);
+}
+#endif
 
 // ---- merge of per-source-chunk partial aggregations (slab-pipelined exchange, jmac_amd/dist.py) --------------------------------
 // Part c is the forward above run on the edges whose SOURCE lies in chunk c (no self loop, out_scale 1): out_c[i] =
@@ -2134,7 +2060,7 @@ static int rel_attn_bwd_impl(const float* P, int64_t ldp, const float* QZ, int64
     a.n_items_max = (int32_t)(by_dst->n_items_max > 0 ? by_dst->n_items_max : 1);
 
     [[maybe_unused]] const int T = 256;                            // (atomic test mode only)
-    const unsigned gridA = fwd_grid(by_dst->n_items_max);          // small graphs: one wave per item, like the forward
+    const unsigned gridA = fwd_grid(unit_blocks(by_dst->n_items_max));          // small graphs: one wave per item, like the forward
     const bool slope01 = slope >= 0.f && slope <= 1.f;
     // column sum of G for the fused self loop (dRz[loop] -= kappa * sum_i G[i]): per-block partials by extra blocks of
     // the pass-A launch, reduced in the last launch
@@ -2156,7 +2082,7 @@ static int rel_attn_bwd_impl(const float* P, int64_t ldp, const float* QZ, int64
         t.nblocks = nparts > 0 ? (int)((d + RT_COLS - 1) / RT_COLS) : 0;
         return t;
     };
-#ifndef JMAC_TEST_ATOMIC_BWD
+#ifndef JMAC_TESTING_BUILD
     // the product library carries the deterministic backward only; the atomic variant (an independent second implementation
     // for the parity tests) is compiled into libjmac_hip_testing.so (csrc/Makefile)
     if (mode == 0) return JMAC_EINVAL;

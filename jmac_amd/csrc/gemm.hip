@@ -711,10 +711,7 @@ int jmac_gemm_trace_buffer(unsigned long long* buf) {
 }
 #endif
 
-static int64_t big_rows() {                          // rows from which a product takes 64x64 tiles (JMAC_GG_TILE64_ROWS: A/B switch)
-    static const int64_t rows = [] { const char* e = getenv("JMAC_GG_TILE64_ROWS"); return e ? (int64_t)atoll(e) : (int64_t)2048; }();
-    return rows;
-}
+constexpr int64_t kBigRows = 2048;                   // rows from which a product takes 64x64 tiles
 
 int jmac_gemm_grouped_f32(const jmac_gemm_task_t* tasks, int32_t n_tasks, jmac_stream_t stream) {
     if (n_tasks < 0 || n_tasks > kMaxTasks || (n_tasks > 0 && !tasks)) return JMAC_EINVAL;
@@ -749,7 +746,7 @@ int jmac_gemm_grouped_f32(const jmac_gemm_task_t* tasks, int32_t n_tasks, jmac_s
         t.vec = ((a_al && (!a_kc || k4)) ? 1 : 0) | ((b_al && (!b_kc || k4)) ? 2 : 0);
         // 64x64 tiles for long tables: A row-major with vector loads, B either K-contiguous (vector loads) or N-contiguous with
         // N % 4 == 0 (ragged column tiles then end on a quad boundary)
-        t.big = (!u.transA && (t.vec & 1) && (t.vec & 2) && (u.transB || u.N % 4 == 0) && u.M >= big_rows() && u.N >= 64) ? 1 : 0;
+        t.big = (!u.transA && (t.vec & 1) && (t.vec & 2) && (u.transB || u.N % 4 == 0) && u.M >= kBigRows && u.N >= 64) ? 1 : 0;
         const int ts = t.big ? 64 : 32;
         t.tiles_n = (int32_t)((u.N + ts - 1) / ts);
         const int64_t nt = (int64_t)((u.M + ts - 1) / ts) * t.tiles_n;

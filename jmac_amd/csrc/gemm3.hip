@@ -15,7 +15,6 @@
 // padded to 80 B: conflict-free ds_read_b128 fragment reads) -> fragments -> MFMA.  One LDS buffer, two barriers per
 // slab, the next slab's global loads in flight across the MFMAs; two blocks per CU so that one block's split (VALU) runs
 // beside the other block's MFMAs (separate pipes).
-#include <cstdlib>
 
 #include "common.h"
 #include "jmac_hip_testing.h"
@@ -209,24 +208,18 @@ int jmac_gemm_nt_x3_f32(const float* A, int64_t lda, const float* B, int64_t ldb
     hipStream_t st = (hipStream_t)stream;
     // tile shape: the kernel is whole blocks of MFMA work on k x 256 resident block slots, so its cost is
     // rounds x work per tile; ragged column blocks are skipped at 32-column granularity
-    static const int force = getenv("JMAC_G3_TILE") ? atoi(getenv("JMAC_G3_TILE")) : 0;      // tuning knob (debug): BM*1000+BN
     int bm = 128, bn = 128;
-    if (force) {
-        bm = force / 1000;
-        bn = force % 1000;
-    } else {
-        double best = 1e300;
-        const int cand[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
-        for (auto& c : cand) {
-            const int64_t tm = (M + c[0] - 1) / c[0], tn = (N + c[1] - 1) / c[1];
-            const int64_t slots = 256 * (c[0] * c[1] >= 128 * 128 ? 3 : (c[0] * c[1] >= 128 * 64 ? 4 : 6));   // blocks per CU (VGPRs / LDS)
-            const int64_t nblk32 = (N + 31) / 32;                                  // column blocks actually computed
-            const double work = (double)c[0] * (double)nblk32 * 32.0 / (double)tn;   // average columns x rows per tile
-            // smaller tiles re-read operands more often and issue fewer MFMAs per fragment: penalise them mildly
-            const double eff = c[0] * c[1] >= 128 * 128 ? 1.0 : (c[0] * c[1] >= 128 * 64 ? 0.9 : 0.8);
-            const double cost = (double)((tm * tn + slots - 1) / slots) * work / eff;
-            if (cost < best) { best = cost; bm = c[0]; bn = c[1]; }
-        }
+    double best = 1e300;
+    const int cand[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
+    for (auto& c : cand) {
+        const int64_t tm = (M + c[0] - 1) / c[0], tn = (N + c[1] - 1) / c[1];
+        const int64_t slots = 256 * (c[0] * c[1] >= 128 * 128 ? 3 : (c[0] * c[1] >= 128 * 64 ? 4 : 6));   // blocks per CU (VGPRs / LDS)
+        const int64_t nblk32 = (N + 31) / 32;                                  // column blocks actually computed
+        const double work = (double)c[0] * (double)nblk32 * 32.0 / (double)tn;   // average columns x rows per tile
+        // smaller tiles re-read operands more often and issue fewer MFMAs per fragment: penalise them mildly
+        const double eff = c[0] * c[1] >= 128 * 128 ? 1.0 : (c[0] * c[1] >= 128 * 64 ? 0.9 : 0.8);
+        const double cost = (double)((tm * tn + slots - 1) / slots) * work / eff;
+        if (cost < best) { best = cost; bm = c[0]; bn = c[1]; }
     }
     const int64_t tiles_m = (M + bm - 1) / bm, tiles_n = (N + bn - 1) / bn;
     if (tiles_m * tiles_n >= INT32_MAX) return JMAC_ERANGE;

@@ -115,9 +115,11 @@ def rel_attn_aggregate(PQZ: torch.Tensor, RR: torch.Tensor, a: torch.Tensor, gra
     return _RelAttnAggregate.apply(PQZ, RR, a, graph, float(slope), int(loop_rel), float(out_scale), int(bwd_mode))
 
 
-def _fwd_call(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int, compact: bool):
+def _fwd_call(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int, compact: bool,
+              lanes64: bool = False):
     """(entry point, arguments, (out, seg_max, seg_den), workspace) of one forward aggregation.  The arguments of the fp32 form
-    without the stream are the fields of an AggFwdJob (jmac_rel_attn_aggregate_fwd_jobs_f32)."""
+    without the stream are the fields of an AggFwdJob (jmac_rel_attn_aggregate_fwd_jobs_f32).  ``lanes64``: the testing
+    build's entry point of the same signature (rel_attn_split_fwd_raw)."""
     if QZ.dtype != P.dtype or RR.dtype != P.dtype:
         raise TypeError("P, QZ and RR must share a dtype")
     N, dh, d = P.shape[0], P.shape[1], int(a.numel())      # dh: half pitch of the table rows; > d for padded bf16 tables
@@ -136,7 +138,10 @@ def _fwd_call(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loo
     ws = workspace(ws_bytes, dev)
     # compact: RR holds the rows of graph.rel_used + the loop row (RelGraph.ensure_rel_compact)
     etype, view = (graph.etype_c, s.view_compact(graph.col, graph.etype_c)) if compact else (graph.etype, s.view())
-    if dh != d:                                         # the padded form takes the half pitch after ldrr
+    if lanes64:                                         # fp32 tables, or bf16 tables in the padded layout (pitch = d where no pad)
+        T = testing_lib()
+        fn, pitch = (T.jmac_rel_attn_aggregate_fwd_lanes64_bf16_padded, (dh,)) if bf16 else (T.jmac_rel_attn_aggregate_fwd_lanes64_f32, ())
+    elif dh != d:                                       # the padded form takes the half pitch after ldrr
         fn, pitch = L.jmac_rel_attn_aggregate_fwd_bf16_padded, (dh,)
     else:
         fn, pitch = (L.jmac_rel_attn_aggregate_fwd_bf16 if bf16 else L.jmac_rel_attn_aggregate_fwd_f32), ()
@@ -147,12 +152,13 @@ def _fwd_call(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loo
 
 
 def rel_attn_split_fwd_raw(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float, loop_rel: int, self_off: int, *,
-                           compact: bool = False):
+                           compact: bool = False, lanes64: bool = False):
     """The forward aggregation without autograd on P [N_dst, dh] and QZ [N_src, 2dh] -- separate tables, or the column views
     of one [P|Q|Z] table (pqz_views): out [N, d] and the per-destination softmax (max, denominator).  d = a.numel(); the half
     pitch dh is d, or bf16_pad(d) for padded bf16 tables.  ``compact``: the edge types and RR's rows are in the compact
-    relation numbering (RelGraph.ensure_rel_compact)."""
-    fn, args, res, ws = _fwd_call(P, QZ, RR, a, graph, slope, out_scale, loop_rel, self_off, compact)
+    relation numbering (RelGraph.ensure_rel_compact).  ``lanes64`` (parity tests): the testing build's entry point, which keeps
+    the 64-lane kernels where the product takes the half-wave kernel."""
+    fn, args, res, ws = _fwd_call(P, QZ, RR, a, graph, slope, out_scale, loop_rel, self_off, compact, lanes64)
     _launch(fn, args, "rel_attn_fwd_bf16" if P.dtype == torch.bfloat16 else "rel_attn_fwd")
     return res
 

@@ -1,4 +1,4 @@
-"""Shared by tests/test_gpu_persistent_oracle.py and its subprocess worker: ONE seeded graph large enough for the
+"""The case of tests/test_gpu_persistent_oracle.py: ONE seeded graph large enough for the
 PERSISTENT-GRID forms of the aggregation kernels (more than 65 536 by-destination items without inline entries:
 jmac_amd/graph.py INLINE_EDGES_MAX_ITEMS, aggregate.hip launch_rel_attn_fwd), seeded tables on it, and the oracle
 (oracle/jmac_oracle.py aggregate_from_tables_sliced -- the reference's per-destination softmax / weighted sum of

@@ -117,6 +117,15 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in text.replace("# oracle", ""), os.path.join(dp, f)
 
 
+def test_native_sources_read_no_environment():
+    """What a launcher picks depends on its arguments alone: no source of the library reads the process environment.  (A
+    source scan: the library's undefined symbols list getenv whatever the project's code does, through the rocprim headers.)"""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(jmac_amd.__file__)), "csrc")
+    srcs = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+    assert len(srcs) >= 10 and "aggregate.hip" in srcs
+    assert [f for f in srcs if "getenv" in open(os.path.join(csrc, f)).read()] == []
+
+
 def test_state_dict_keys_match_reference():
     from util import load_golden, make_args
     from jmac_amd.model import JMAC

@@ -1,7 +1,7 @@
 """GPU: the PERSISTENT-GRID forms of the aggregation kernels, held directly to the oracle, at d = 300 and d = 256.
 
-``launch_rel_attn_fwd`` (jmac_amd/csrc/aggregate.hip) picks ``rel_attn_fwd_hw_kernel<75|64,12,float>`` /
-``<38|32,12,bf16>`` or the 64-lane ``rel_attn_fwd_kernel<...,U=4>`` only for schedules of more than 16 384 items WITHOUT
+``launch_rel_attn_fwd`` (jmac_amd/csrc/aggregate.hip) picks ``rel_attn_fwd_hw_kernel<75|64,float>`` /
+``<38|32,bf16>`` or the 64-lane ``rel_attn_fwd_kernel<...,U=4>`` only for schedules of more than 16 384 items WITHOUT
 inline entries -- in practice graphs of more than 65 536 by-destination items (jmac_amd/graph.py INLINE_EDGES_MAX_ITEMS).
 Every other oracle test stays below that size, so these kernels -- the ones behind BASELINE config 4 and the HBM-scale roofline
 figure -- used to meet the oracle only transitively.  Here, on one seeded power-law graph (N = 80 000, E = 600 000,
@@ -13,8 +13,8 @@ figure -- used to meet the oracle only transitively.  Here, on one seeded power-
     handed to the oracle; the number of elements whose own sign differs is counted and bounded) -- with the automatic
     schedule (64-entry items) and with config 4's item sizes (256 by destination, 512 by source / relation);
   * forward on (padded) bf16 tables against the float64 oracle on the same bf16-rounded tables;
-  * the selectable forms (JMAC_FWD_HW=0: 64-lane U=4; JMAC_FWD_HOT=1: LDS-staged relation rows; JMAC_FWD_NT=1: streaming gathers;
-    JMAC_FWD_HW_DEPTH=2: guarded pipeline), each in a subprocess (the knobs are read once per process), each against the ORACLE;
+  * the 64-lane U=4 kernel at the same widths (the testing build's entry points: ``rel_attn_split_fwd_raw(..., lanes64=True)``)
+    against the ORACLE, on fp32 and on padded bf16 tables;
   * ``jmac_softmax_parts_merge_f32`` over C = 4 source chunks against the oracle on the whole graph;
   * ``RelationAwareLayer`` itself (projections, relation transform, BatchNorm, tanh around the same kernels) against
     ``oracle.layer_forward`` -- the un-factorised restatement of src/jmac_model.py:33-53 -- at a persistent-form size.
@@ -23,7 +23,6 @@ Reference semantics: src/jmac_model.py:33-53,80-89, modules/helper/message_passi
 d = 300 BASELINE's.  Tolerance: 1e-4 of the tensor's scale (north_star), written below."""
 import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -159,26 +158,24 @@ def test_persistent_bf16_forward_vs_oracle(d, monkeypatch):
     assert_close(o16, _oracle_fwd(d, "bf16"), BF16_RTOL, 1e-7, "bf16-table forward vs float64 oracle on the rounded tables")
 
 
-FORMS = [("lanes64-u4", {"JMAC_FWD_HW": "0"}), ("hot-lds-rows", {"JMAC_FWD_HOT": "1"}), ("nontemporal", {"JMAC_FWD_NT": "1"}),
-         ("guarded-depth2", {"JMAC_FWD_HW_DEPTH": "2"})]
-
-
 @pytest.mark.timeout(1800)
-@pytest.mark.parametrize("form,env", FORMS, ids=[f for f, _ in FORMS])
+@pytest.mark.parametrize("form", ["lanes64-u4"])
 @pytest.mark.parametrize("d", [300, 256])
-def test_forward_forms_vs_oracle(d, form, env, tmp_path):
-    """Every selectable forward form against the ORACLE (not against each other)."""
-    out = str(tmp_path / ("%s_%d.npz" % (form, d)))
-    e = dict(os.environ)
-    for k in ("JMAC_FWD_HW", "JMAC_FWD_HOT", "JMAC_FWD_NT", "JMAC_FWD_HW_DEPTH", "JMAC_FWD_U", "JMAC_GRID"):
-        e.pop(k, None)
-    e.update(env)
-    subprocess.run([sys.executable, os.path.join(HERE, "persistent_worker.py"), str(d), out], env=e, check=True, timeout=900)
-    v = np.load(out)
+def test_forward_forms_vs_oracle(d, form, monkeypatch):
+    """The 64-lane U=4 kernel at the half-wave kernel's widths against the ORACLE (not against the half-wave kernel)."""
+    from jmac_amd import ops
+    dev = torch.device("cuda")
+    _, _, n, nrel = _case()
+    g = _build_graph("auto-items", monkeypatch)
+    PQZ, RR, a, _ = _tables(d)
+    PQZ, RR, a = PQZ.to(dev), RR.to(dev), a.to(dev)
+    P16, R16 = ops.pad_table(PQZ.to(torch.bfloat16), d, 3), ops.pad_table(RR.to(torch.bfloat16), d, 2)
+    v32 = ops.rel_attn_split_fwd_raw(*ops.pqz_views(PQZ), RR, a, g, pc.SLOPE, pc.OUT_SCALE, nrel - 1, 0, lanes64=True)[0]
+    v16 = ops.rel_attn_split_fwd_raw(*ops.pqz_views(P16), R16, a, g, pc.SLOPE, pc.OUT_SCALE, nrel - 1, 0, lanes64=True)[0]
     o32, o64 = _oracle_fwd(d, "f32")
-    assert_close(v["o32"], o32, RTOL, 1e-7, form + ": fp32 tables vs oracle fp32")
-    assert_close(v["o32"], o64, RTOL, 1e-7, form + ": fp32 tables vs oracle float64")
-    assert_close(v["o16"], _oracle_fwd(d, "bf16"), BF16_RTOL, 1e-7, form + ": bf16 tables vs float64 oracle")
+    assert_close(v32, o32, RTOL, 1e-7, form + ": fp32 tables vs oracle fp32")
+    assert_close(v32, o64, RTOL, 1e-7, form + ": fp32 tables vs oracle float64")
+    assert_close(v16, _oracle_fwd(d, "bf16"), BF16_RTOL, 1e-7, form + ": bf16 tables vs float64 oracle")
 
 
 @pytest.mark.timeout(1800)

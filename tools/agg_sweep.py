@@ -1,4 +1,4 @@
-"""fwd/bwd aggregation timing on the config-4 graph under tuning knobs (env JMAC_GRID / JMAC_FWD_U, arg chunk)."""
+"""fwd/bwd aggregation timing on the config-4 graph (args: scale, chunk, d, do_bwd; env BF16, DBG)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -36,7 +36,7 @@ with torch.no_grad():
     for _ in range(5): ops.rel_attn_aggregate(PQZ, RR, a, g, 0.05, nrel - 1, 0.5, 1)
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 5
-print("bf16" if bf16 else "f32", dbg, "GRID=%s U=%s chunk=%s items=%d splits=%d  fwd %.3f ms  %.0f GB/s (%.1f%% of 8TB/s)" % (os.environ.get("JMAC_GRID"), os.environ.get("JMAC_FWD_U"), g.chunk, g.by_dst.n_items_max, g.by_dst.n_splits_max, ms, fb / ms / 1e6, fb / ms / 1e6 / 80))
+print("bf16" if bf16 else "f32", dbg, "chunk=%s items=%d splits=%d  fwd %.3f ms  %.0f GB/s (%.1f%% of 8TB/s)" % (g.chunk, g.by_dst.n_items_max, g.by_dst.n_splits_max, ms, fb / ms / 1e6, fb / ms / 1e6 / 80))
 if do_bwd:
     g.ensure_backward_views()
     out = ops.rel_attn_aggregate(PQZ, RR, a, g, 0.05, nrel - 1, 0.5, 1)

@@ -34,4 +34,4 @@ with torch.no_grad():
     us = timeit(lambda: ops.rel_attn_aggregate(PQZ, RR, a, g, 0.05, nrel - 1, 0.5, 1))
 out = ops.rel_attn_aggregate(PQZ, RR, a, g, 0.05, nrel - 1, 0.5, 1)
 ub = timeit(lambda: torch.autograd.grad(out, [PQZ, RR, a], G, retain_graph=True), 100)
-print("%s bidir=%s N=%d E=%d GRID=%s U=%s chunk=%d: fwd %.1f us (%.0f GB/s, %.1f%%)  bwd %.1f us" % (lang, bid, n, e, os.environ.get("JMAC_GRID"), os.environ.get("JMAC_FWD_U"), g.chunk, us, fb / us / 1e3, fb / us / 1e3 / 80, ub))
+print("%s bidir=%s N=%d E=%d chunk=%d: fwd %.1f us (%.0f GB/s, %.1f%%)  bwd %.1f us" % (lang, bid, n, e, g.chunk, us, fb / us / 1e3, fb / us / 1e3 / 80, ub))

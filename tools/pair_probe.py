@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Pair step (bench.PairWorkload) timing probe: batched vs separate calls as hipGraphs; env knobs JMAC_SMALL_ITEMS / JMAC_FWD_U."""
+"""Pair step (bench.PairWorkload) timing probe: batched vs separate calls as hipGraphs; env knob JMAC_SMALL_ITEMS."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,7 +18,7 @@ x = ap.parse_args()
 a = argparse.Namespace(dim=300, batch=1000, negatives=25, bwd_mode=1)
 dev = torch.device("cuda")
 bench.enable_gemm_tuning(0)
-out = {"JMAC_SMALL_ITEMS": os.environ.get("JMAC_SMALL_ITEMS"), "JMAC_FWD_U": os.environ.get("JMAC_FWD_U"), "batched": x.batched}
+out = {"JMAC_SMALL_ITEMS": os.environ.get("JMAC_SMALL_ITEMS"), "batched": x.batched}
 if x.union:
     a.data, a.torch_adam = "real", False
     m, kgs = bench.union_real_model(a, dev)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Aggregation kernel timing on the DBP-5L-shaped union graph (config 3) and on pair-sized graphs: fwd fp32 / bf16, bwd; env knobs
-JMAC_SMALL_ITEMS / JMAC_FWD_U."""
+"""Aggregation kernel timing on the DBP-5L-shaped union graph (config 3) and on pair-sized graphs: fwd fp32 / bf16, bwd; env knob
+JMAC_SMALL_ITEMS."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,8 +37,7 @@ out = {"env": {k: v for k, v in os.environ.items() if k.startswith("JMAC_")}, "N
        "items": g.by_dst.n_items_max, "coop": g.by_dst.n_coop, "inline": g.by_dst.item_edges is not None}
 with torch.no_grad():
     out["fwd_f32_us"] = t(lambda: ops.rel_attn_aggregate(PQZ, RR, av, g, 0.05, nr, 0.5))
-    pad = os.environ.get("JMAC_FWD_HW", "1") != "0"
-    P16, R16 = (ops.pad_table(PQZ.to(torch.bfloat16), d, 3), ops.pad_table(RR.to(torch.bfloat16), d, 2)) if pad else (PQZ.to(torch.bfloat16), RR.to(torch.bfloat16))
+    P16, R16 = ops.pad_table(PQZ.to(torch.bfloat16), d, 3), ops.pad_table(RR.to(torch.bfloat16), d, 2)
     out["fwd_bf16_us"] = t(lambda: ops.rel_attn_aggregate(P16, R16, av, g, 0.05, nr, 0.5))
 Pq = PQZ.clone().requires_grad_(True); Rq = RR.clone().requires_grad_(True); aq = av.clone().requires_grad_(True)
 o = ops.rel_attn_aggregate(Pq, Rq, aq, g, 0.05, nr, 0.5, 1)
