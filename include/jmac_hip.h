@@ -633,6 +633,35 @@ int jmac_stable_match_f32(const int32_t* cand_idx, const float* cand_val, int64_
                           uint64_t* best, int32_t* match1, int32_t* match2, uint64_t* counters, void* ws, size_t ws_bytes,
                           jmac_stream_t stream);
 
+/* Optimal one-to-one alignment ("Hungarian" in the entity-alignment literature): Bertsekas' auction algorithm on candidate lists,
+ * up to `rounds` synchronous bidding rounds per call.  Rows i in [0, n1) bid for columns j in [0, n2).
+ * Lists (read-only during a call): idx / val / pref [n1, ld >= k], 2 <= k <= min(64, n2) (JMAC_EINVAL); every entry of a row a
+ * different column in [0, n2); val = c(i,j) - price[j] AS OF THE REFILL, best first (equal values -> lower column), pref = the price
+ * of that column then.
+ * State kept between calls: price [n2] fp32 (start: 0), owner [n2] int32 (start: -1 = free), match1 [n1] int32: >= 0 the column
+ * held, -1 open, -2 open and waiting for a refill (start: -1).
+ * One round: every row at -1 at its start takes cur_m = val[i,m] - (price[idx[i,m]] - pref[i,m]) (two fp32 subtractions, in that
+ * order), w1 = the largest (equal values -> lower column), j1 its column, w2 = the largest of the others, bound = val[i,k-1]
+ * (k == n2: -inf).  w2 < bound: no unlisted column is known to be worse than w2 any more; the row becomes -2 and sits the rest of the
+ * call out.  Otherwise it bids (price[j1] + (w1 - w2)) + eps in fp32 (nextafter(price[j1], +inf) if that does not exceed price[j1])
+ * by an atomic max on the column's 64-bit word tk(bid, i) -- highest bid first, equal bids -> lower row.  After all bids every
+ * column with a bid is resolved: its previous owner gets -1, owner / match1 / price are set from the word.  A call stops early once
+ * a round has no bidder.  Any subset of the open rows may bid in a round: the final matching satisfies eps-complementary slackness.
+ * The floats depend on no atomic order (atomic max on packed words and integer counter adds only): bitwise reproducible.
+ * form: 1 = grid (one bid and one resolve launch per round; after a round without a bidder the remaining launches do nothing);
+ *       2 = one workgroup (ONE launch loops over the rounds, the open rows are a queue in LDS of JMAC_AUCTION_QUEUE_ROWS entries;
+ *           n_open above that: JMAC_EINVAL); 0 = 2 if n_open <= JMAC_AUCTION_QUEUE_ROWS, else 1.  Both forms run the same rounds:
+ *           the same state gives the same bits.  n_open: an upper bound of the rows at -1 (the count never grows during a run: a bid
+ *           assigns one row and evicts at most one); rows beyond the queue would sit the call out.
+ * 0 <= rounds <= 4096, eps finite and > 0 (JMAC_EINVAL).  Out: counters [4] uint64 = {rows open (-1 or -2) after the call, rows at
+ * -2, rounds with a bidder run by this call, bids made by this call}.  The workspace holds the columns' bid words; nothing in it is
+ * kept between calls. */
+#define JMAC_AUCTION_QUEUE_ROWS 256
+size_t jmac_auction_rounds_workspace_bytes(int64_t n1, int64_t n2);
+int jmac_auction_rounds_f32(const int32_t* idx, const float* val, const float* pref, int64_t ld, int64_t n1, int64_t n2, int32_t k,
+                            float* price, int32_t* owner, int32_t* match1, float eps, int32_t rounds, int32_t form, int64_t n_open,
+                            uint64_t* counters, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Small fp32 GEMM for the relation-side projections (replaces the torch.mm calls on the ~10^3-row
  * relation tables: src/jmac_model.py:40-42 rel_transform_weight1/2, :195-196 relation MLPs, and the

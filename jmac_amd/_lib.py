@@ -166,6 +166,8 @@ _SIGS = {
     "jmac_l1_csls_rank_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
     "jmac_stable_match_workspace_bytes": (sz, [i64, i64]),
     "jmac_stable_match_f32": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "jmac_auction_rounds_workspace_bytes": (sz, [i64, i64]),
+    "jmac_auction_rounds_f32": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, f32, i32, i32, i64, vp, vp, sz, vp]),
     "jmac_gemm_f32": (C.c_int, [vp, i64, i32, vp, i64, i32, i64, i64, i64, vp, i64, vp]),
     "jmac_triple_l1_fwd_f32": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp, vp]),
     "jmac_triple_l1_bwd_f32": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, vp, vp, i64, vp, i64, vp]),

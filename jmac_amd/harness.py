@@ -273,6 +273,33 @@ def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGr
 
 
 @torch.no_grad()
+def evaluate_auction_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, k=16, eps=1e-3):
+    """The optimal one-to-one alignment of the test pairs of a KG pair (what the literature reports as "Hungarian"; no counterpart
+    in the reference): the pairs' embeddings are selected as in ``evaluate_alignment``, the assignment comes from
+    scoring.auction_alignment (no len(pairs)^2 matrix).  Returns (precision [%], stats), counted as ``evaluate_stable_alignment``
+    counts it: the share of matched rows i with match1[i] == i."""
+    (ei1, et1), (ei2, et2) = graphs
+    b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
+    b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
+    was_training = model.training
+    model.eval()
+    (a1, _), (a2, _) = model.get_emb_blocks([b1, b2], on_device=True)
+    model.train(was_training)
+    pairs = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    scoring.check_index_range(pairs[:, 0], a1.shape[0], "pairs[:, 0]")
+    scoring.check_index_range(pairs[:, 1], a2.shape[0], "pairs[:, 1]")
+    p = torch.from_numpy(pairs).to(a1.device)
+    k = min(int(k), len(pairs))
+    match1, _, _, stats = scoring.auction_alignment(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), k, csls_k,
+                                                    getattr(args, "eval_metric", "cosine"), bool(getattr(args, "eval_norm", False)),
+                                                    eps=eps)
+    matched = match1 >= 0
+    hits = (match1 == torch.arange(match1.numel(), device=match1.device)) & matched
+    precision = 100.0 * float(hits.sum().item()) / max(1, int(matched.sum().item()))
+    return precision, stats
+
+
+@torch.no_grad()
 def evaluate_sinkhorn_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, scale=50.0, iters=10,
                                 top_k=(1, 5, 10), stable_k=None):
     """``evaluate_alignment`` under the Sinkhorn plan of the test pairs instead of CSLS (no counterpart in the reference): the

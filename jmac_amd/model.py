@@ -390,6 +390,24 @@ class JMAC(nn.Module):
             terms = (terms[0].index_select(0, q), terms[1])
         return scoring.stable_alignment(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, max_refills=max_refills)
 
+    def alignment_auction(self, e_index, blocks, k=16, csls_k=10, metric="cosine", normalize=False, eps=1e-3, max_rounds=None,
+                          emb=None, sinkhorn=None):
+        """The optimal one-to-one alignment of the entities ``e_index`` of KG 1 (ids local to their KG) with ALL entities of KG 2:
+        ``(match1 int64 [B], val1 fp32 [B], price fp32, stats)`` of scoring.auction_alignment -- the assignment that maximises the
+        total CSLS-rescored similarity to within min(B, N2) * eps ("Hungarian"), without the matrix; -1 = unmatched.  The
+        neighbourhood terms are those of the two whole tables; ``blocks`` / ``emb`` / ``sinkhorn`` as in ``alignment_topk``."""
+        if emb is None:
+            (a1, _), (a2, _) = self.get_emb_blocks(blocks, on_device=True)
+        else:
+            a1, a2 = emb
+        a, b = scoring._alignment_operands(a1, a2, metric, normalize)
+        down = "manhattan" if metric == "manhattan" else "inner"
+        terms, csls_k = self._alignment_terms(a, b, csls_k, down, sinkhorn)
+        q = _idx(e_index, a1.device, a1.shape[0])
+        if terms is not None:
+            terms = (terms[0].index_select(0, q), terms[1])
+        return scoring.auction_alignment(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, eps=eps, max_rounds=max_rounds)
+
     # ---- losses (src/jmac_model.py:237-292, :316-380): gathers + L1 / cosine fused in HIP (jmac_amd.losses),
     # the margin arithmetic on the resulting [T] / [L] vectors stays in torch ----------------------------
     @staticmethod

@@ -845,6 +845,127 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
     return m1, val1, stats
 
 
+# ---- optimal one-to-one alignment: the auction algorithm on candidate lists ("Hungarian" in the literature) -----------------------------
+AUCTION_QUEUE_ROWS = 256                     # JMAC_AUCTION_QUEUE_ROWS: the open rows the one-workgroup form of the rounds kernel holds
+AUCTION_BATCH = 64                           # rounds per call, whatever its form: a waiting row comes back when its batch ends
+
+
+class _AuctionState:
+    """The device state of one auction run (jmac_auction_rounds_f32): candidate lists (idx, val = c - price as of the refill, pref =
+    the price then), prices, owners and the rows' states.  ``step(rounds, n_open)`` runs up to that many rounds and returns the
+    counters (open, waiting, rounds, bids) -- its one host read."""
+
+    def __init__(self, idx: torch.Tensor, val: torch.Tensor, n2: int, eps: float):
+        dev = idx.device
+        self.idx, self.val, self.n2, self.eps = idx, val, int(n2), float(eps)
+        self.n1, self.k = idx.shape
+        self.pref = torch.zeros_like(val)
+        self.price = torch.zeros(self.n2, dtype=torch.float32, device=dev)
+        self.owner = torch.full((self.n2,), -1, dtype=torch.int32, device=dev)
+        self.match1 = torch.full((self.n1,), -1, dtype=torch.int32, device=dev)
+        self.counters = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.ws_bytes = int(lib().jmac_auction_rounds_workspace_bytes(self.n1, self.n2))
+        self.ws = workspace(self.ws_bytes, dev)
+
+    def step(self, rounds: int, n_open: int, form: int = 0) -> Tuple[int, int, int, int]:
+        check(lib().jmac_auction_rounds_f32(ptr(self.idx), ptr(self.val), ptr(self.pref), self.k, self.n1, self.n2, self.k, ptr(self.price),
+                                            ptr(self.owner), ptr(self.match1), self.eps, int(rounds), int(form), int(n_open),
+                                            ptr(self.counters), ptr(self.ws), self.ws_bytes, stream()), "jmac_auction_rounds_f32")
+        n_open, waiting, done, bids = self.counters.tolist()
+        return int(n_open), int(waiting), int(done), int(bids)
+
+
+def auction_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k: int = 10, metric: str = "cosine",
+                      normalize: bool = False, terms=None, eps: float = 1e-3, max_rounds: Optional[int] = None, form: int = 0):
+    """The OPTIMAL one-to-one alignment: ``(match1 int64 [n1], val1 fp32 [n1], price fp32, stats)``, the assignment that maximises
+    the total of c = ``alignment_sim(emb1, emb2, metric, normalize, csls_k)`` over all one-to-one matchings of the smaller side (what
+    the entity-alignment literature reports as "Hungarian"), to within min(n1, n2) * eps, without the n1 x n2 matrix.  ``match1[i]`` is
+    row i's column or -1, ``val1[i]`` = c(i, match1[i]) to rounding or -inf, ``price`` the dual prices of the columns.
+
+    Bertsekas' auction: an open row bids its best column up by (best - second best) + eps of c - price; the highest bidder takes the
+    column and opens its previous owner.  A row only needs its two best values, so it runs on ``alignment_topk``'s k candidates
+    (2 <= k <= min(64, n2)); prices only rise, so as long as its second best is no worse than the last listed value as of the refill
+    no unlisted column can matter, and a row for which that fails gets its top-k under the current prices -- the rescoring term r2
+    carries the prices through the same fused top-k (``csls_k = 0``: terms (0, 2 price), values halved: exact).  Rounds run in
+    batches on the device (jmac_auction_rounds_f32; one host read per batch); columns never bid on keep price 0, so the final
+    matching and prices satisfy eps-complementary slackness of the rectangular problem.  n1 > n2 runs the transposed instance:
+    n1 - n2 rows are -1, ``price`` has n1 entries, ``stats["transposed"]`` is set.
+
+    ``stats``: rounds, bids, batches (host reads), refills, refill_rows, unmatched, complete (False only when ``max_rounds`` stopped
+    the run; rows still open are -1 then), eps, transposed.  ``form``: 0 lets the library pick the launch form of every batch from
+    the open count, 1 holds it to the grid form (the same bits)."""
+    eps = float(eps)
+    if not (eps > 0.0 and np.isfinite(eps)):
+        raise ValueError("auction_alignment: eps must be finite and positive (got %r)" % eps)
+    if emb1.dim() != 2 or emb2.dim() != 2 or emb1.shape[0] == 0 or emb2.shape[0] == 0:
+        raise ValueError("auction_alignment: empty operand")
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    transposed = a.shape[0] > b.shape[0]
+    if transposed:                                                  # columns bid for rows: c^T, the terms change sides
+        a, b, r1, r2 = b, a, r2, r1
+    n1, d = a.shape
+    n2 = b.shape[0]
+    k = int(k)
+    if not 2 <= k <= min(CSLS_KMAX, n2):
+        raise ValueError("auction_alignment: k must lie in [2, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
+    dev = a.device
+    ws_bytes = max(_topk_bytes(metric, n1, n2, d, k), _topk_bytes(metric, 1, n2, d, k) + d * 4 + 256)
+    ws = workspace(ws_bytes, dev)
+    idx, val = _csls_topk(a, b, k, r1, r2, metric, ws=ws)
+    st = _AuctionState(idx, val, n2, eps)
+    stats = {"rounds": 0, "bids": 0, "batches": 0, "refills": 0, "refill_rows": 0}
+    complete = True
+    n_open, chunk = n1, 0
+    while True:
+        rounds = AUCTION_BATCH if max_rounds is None else min(AUCTION_BATCH, int(max_rounds) - stats["rounds"])
+        n_open, waiting, done, bids = st.step(max(rounds, 0), n_open, form)
+        stats["rounds"] += done
+        stats["bids"] += bids
+        stats["batches"] += 1
+        if n_open == 0:
+            break
+        if max_rounds is not None and stats["rounds"] >= int(max_rounds):
+            complete = False
+            break
+        if waiting == 0:
+            continue
+        # the rows at -2, ascending (a stable sort of "is not waiting" lists them first: no second host read)
+        ids = torch.sort((st.match1 != -2).to(torch.uint8), stable=True).indices[:waiting]
+        chunk = chunk or _refill_chunk_rows(metric, n1, n2, d, k, ws_bytes)
+        if r2 is not None:
+            r2p = r2 + st.price
+        else:
+            r2p = 2.0 * st.price
+        for lo in range(0, waiting, chunk):
+            sel = ids[lo:lo + chunk]
+            rows = sel.numel()
+            sub = ws[ws_bytes - rows * d * 4:].view(torch.float32).view(rows, d)
+            torch.index_select(a, 0, sel, out=sub)
+            r1s = r1.index_select(0, sel) if r1 is not None else torch.zeros(rows, dtype=torch.float32, device=dev)
+            nidx, nval = _csls_topk(sub, b, k, r1s, r2p, metric, ws=ws)
+            if r2 is None:
+                nval = nval * 0.5                                    # (2 S - 2 price) / 2: exact
+            idx[sel], val[sel] = nidx, nval
+            st.pref[sel] = st.price[nidx.to(torch.int64)]
+            st.match1[sel] = -1
+        stats["refills"] += 1
+        stats["refill_rows"] += waiting
+    m1 = st.match1.to(torch.int64).clamp_(min=-1)
+    held = idx.to(torch.int64) == m1.unsqueeze(1)
+    neg = torch.full_like(val[:, 0], float("-inf"))
+    val1 = torch.where(m1 >= 0, torch.where(held, val + st.pref, torch.zeros_like(val)).sum(1), neg)
+    price = st.price
+    if transposed:                                                  # back to the caller's sides: its rows are the columns here
+        rows_of = torch.full((n2,), -1, dtype=torch.int64, device=dev)
+        vals_of = torch.full((n2,), float("-inf"), dtype=torch.float32, device=dev)
+        got = m1 >= 0
+        rows_of[m1[got]] = torch.nonzero(got).squeeze(1)
+        vals_of[m1[got]] = val1[got]
+        m1, val1 = rows_of, vals_of
+    stats.update(unmatched=int((m1 < 0).sum().item()), complete=complete, eps=eps, transposed=transposed)
+    return m1, val1, price, stats
+
+
 def _rank_summary(rank: torch.Tensor, top_k):
     rank = rank.to(torch.float64)
     hits = [float((rank <= k).double().mean().item() * 100.0) for k in top_k]
