@@ -16,13 +16,7 @@ using namespace jmac;
 
 namespace {
 
-#ifndef JMAC_GG_WAVES
-#define JMAC_GG_WAVES 8
-#endif
-#ifndef JMAC_GG_KC
-#define JMAC_GG_KC 304
-#endif
-constexpr int kWaves = JMAC_GG_WAVES;  // waves per 32x32 tile = K split factor
+constexpr int kWaves = 8;              // waves per 32x32 tile = K split factor
 constexpr int kBlock = 64 * kWaves;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -82,7 +76,7 @@ struct GTable {
 //   RC ("r contiguous": A transposed, B not transposed)  lds[k * 32 + r]: fragment = four ds_read_b32, lanes r consecutive
 // Fragment of one 8-deep K step for the 32x32x2 MFMA: lane (r = lane & 31, h = lane >> 5) holds the operand's values for
 // row/column r and k = k0 + 4h + s, s = 0..3; MFMA step s contracts k = {k0 + s, k0 + 4 + s}.
-constexpr int kKc = JMAC_GG_KC;                // K chunk (38 steps of 8)
+constexpr int kKc = 304;                       // K chunk (38 steps of 8)
 constexpr int kLdk = kKc + 4;                  // row pitch of a KC panel (floats): 4 * odd
 constexpr int kPanel = 32 * kLdk;              // floats per panel (KC form; the RC form needs kKc * 32 <= this)
 constexpr int kStage = (32 * (kKc / 4) + kBlock - 1) / kBlock;      // float4s per thread per panel = 5
@@ -159,14 +153,6 @@ __device__ __forceinline__ float4 panel_frag(const float* __restrict__ lds, int 
 // a full 32-column tile for the RC form)
 // MULTI: K spans several chunks -> the next chunk's global loads are prefetched into registers during the MFMAs;
 // single-chunk products (every forward product at d <= 304) prefetch all of a wave's LDS fragments instead.
-#ifdef JMAC_GG_TRACE
-// debug builds (tools/gg_trace.py): per-block timestamps of the phases, written behind the output of task 0's C2 pointer
-#define GG_STAMP(i) do { if (threadIdx.x == 0) { gg_trace_buf[((int64_t)(blockIdx.y * gridDim.x + blockIdx.x)) * 8 + (i)] = __builtin_readcyclecounter(); if ((i) == 0 || (i) == 4) gg_trace_buf[((int64_t)(blockIdx.y * gridDim.x + blockIdx.x)) * 8 + ((i) == 0 ? 5 : 6)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-__device__ unsigned long long* gg_trace_buf;
-#else
-#define GG_STAMP(i)
-#endif
-
 template <bool TA, bool TB, bool VA, bool VB, bool MULTI>
 __device__ __forceinline__ void grouped_tile(const GTask& t, int tile, float* __restrict__ lds) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -180,7 +166,6 @@ __device__ __forceinline__ void grouped_tile(const GTask& t, int tile, float* __
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     // chunk loop: the NEXT chunk's global loads are issued before this chunk's MFMAs (registers), so a long-K product
     // (the weight gradients: K = the ~10^3 relation rows, four chunks) pays one exposed round trip, not four
-    GG_STAMP(1);
     float4 va[kStage], vb[kStage];
     if constexpr (VA) panel_load<!TA>(t.A, m0, M, 0, K, va);            // 10 loads per thread in flight
     if constexpr (VB) panel_load<TB>(t.B, n0, N, 0, K, vb);
@@ -197,7 +182,6 @@ __device__ __forceinline__ void grouped_tile(const GTask& t, int tile, float* __
             if constexpr (VB) panel_load<TB>(t.B, n0, N, k0 + kKc, K, vb);
         }
         __syncthreads();
-        GG_STAMP(2);
         // wave w takes steps w, w + 8, ... (<= kSteps of them): all their fragments are read first (one LDS latency), the
         // dependent MFMA chain follows; steps past the chunk read a clamped address and are skipped (wave-uniform test)
         const int steps = (min(K - k0, kKc) + 7) / 8;          // <= 38
@@ -235,7 +219,6 @@ __device__ __forceinline__ void grouped_tile(const GTask& t, int tile, float* __
             }
         }
     }
-    GG_STAMP(3);
     __syncthreads();                                           // panels are dead: their memory carries the partial tiles
     // every wave leaves its 16 accumulator registers in LDS; wave w then finishes registers 2w and 2w + 1 of the tile: the
     // eight partials are summed in wave order (bitwise reproducible), the epilogue's own loads (act' source, accumulate)
@@ -286,7 +269,6 @@ __device__ __forceinline__ void grouped_tile(const GTask& t, int tile, float* __
 #pragma unroll
     for (int j = 0; j < kRegs; ++j)
         if (ok[j]) gst(cp[j], v[j]);
-    GG_STAMP(4);
 }
 
 // ---- one 64x64 output tile per 8-wave block: the products on LONG relation tables (the 5-KG union: ~4 800 rows) -------------
@@ -355,7 +337,6 @@ __device__ __forceinline__ void grouped_tile64(const GTask& t, int tile, float* 
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    GG_STAMP(1);
     float4 va[kStage2], vb[kStage2];
     panel2_load<true>(t.A, m0, M, 0, K, va);
     panel2_load<TB>(t.B, n0, N, 0, K, vb);
@@ -367,7 +348,6 @@ __device__ __forceinline__ void grouped_tile64(const GTask& t, int tile, float* 
         panel2_load<true>(t.A, m0, M, k0 + kKc2, K, va);           // unconditional: see grouped_tile
         panel2_load<TB>(t.B, n0, N, k0 + kKc2, K, vb);
         __syncthreads();
-        GG_STAMP(2);
         const int steps = (min(K - k0, kKc2) + 7) / 8;             // <= 10
         float4 a = panel2_frag<true>(la, ra, kh * 8 + 4 * h), b = panel2_frag<TB>(lb, rb, kh * 8 + 4 * h);
 #pragma unroll
@@ -384,7 +364,6 @@ __device__ __forceinline__ void grouped_tile64(const GTask& t, int tile, float* 
             b = bn;
         }
     }
-    GG_STAMP(3);
     __syncthreads();
     // wave (q, kh) finishes accumulator registers 8 kh .. 8 kh + 7 of its quadrant: it leaves the other eight in LDS for its
     // partner and reads the partner's; the sum is always (half 0) + (half 1)
@@ -430,7 +409,6 @@ __device__ __forceinline__ void grouped_tile64(const GTask& t, int tile, float* 
             if (ok[j]) gst(cp[j], x);
         }
     }
-    GG_STAMP(4);
 }
 
 // ---- TN products (the weight gradients: C = A^T B, A [K,M], B [K,N], K = the ~10^3 relation rows) without LDS staging ------
@@ -450,7 +428,6 @@ __device__ __forceinline__ void grouped_tile_tn(const GTask& t, int tile, float*
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    GG_STAMP(1);
     // Full batches below the A operand's split run on two incremented row pointers (two VALU adds per load: with the
     // general row() form -- clamp, split select, 64-bit multiply -- per load the loop was bound by its ADDRESS arithmetic,
     // ~45 VALU instructions per k pair, and two blocks on a CU took twice as long as one).  The last, partial batch (and the
@@ -510,8 +487,6 @@ __device__ __forceinline__ void grouped_tile_tn(const GTask& t, int tile, float*
 #pragma unroll
         for (int u = 0; u < TN_U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
     }
-    GG_STAMP(2);
-    GG_STAMP(3);
     float (*red)[16][64] = reinterpret_cast<float (*)[16][64]>(lds);
 #pragma unroll
     for (int i = 0; i < 16; ++i) red[wave][i][lane] = acc[i];
@@ -537,12 +512,10 @@ __device__ __forceinline__ void grouped_tile_tn(const GTask& t, int tile, float*
         if (t.accumulate && in_c) x += gld(cp);
         if (m < M && n < N) gst(cp, x);
     }
-    GG_STAMP(4);
 }
 
 __global__ __launch_bounds__(kBlock, 4) void grouped_gemm_kernel(const GTable tab) {   // 4 waves per SIMD (two 8-wave blocks per CU)
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    GG_STAMP(0);
     // The table is a by-value kernel argument indexed by a run-time task id.  Indexing `tab` itself makes the compiler copy
     // all 3.6 KB of it into per-lane scratch; the kernarg segment is ordinary constant memory, so the scan and the one task
     // this block runs are read from there with scalar loads instead.
@@ -555,7 +528,7 @@ __global__ __launch_bounds__(kBlock, 4) void grouped_gemm_kernel(const GTable ta
     // The task is fetched with ONE vector load per wave (lane i <- dword i of the task) and spread to scalars with
     // v_readlane: a single memory round trip.  Read field by field with scalar loads, the compiler sinks the loads next to
     // their uses -- three dependent trips to the kernarg buffer (task pointers, dimensions, epilogue parameters) at ~1.7 us
-    // each, half of a block's life (phase timestamps: tools/gg_trace.py).
+    // each, half of a block's life.
     GTask t;                                                                 // 38 dwords, block-uniform: SGPRs
     {
         static_assert(sizeof(GTask) / 4 <= 64, "one lane per dword of the task");
@@ -704,12 +677,6 @@ int jmac_gemm_f32(const float* A, int64_t lda, int32_t transA, const float* B, i
     t.C = C; t.ldc = ldc; t.M = M; t.N = N; t.K = K;
     return jmac_gemm_grouped_f32(&t, 1, stream);
 }
-
-#ifdef JMAC_GG_TRACE
-int jmac_gemm_trace_buffer(unsigned long long* buf) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(gg_trace_buf), &buf, sizeof(buf));
-}
-#endif
 
 constexpr int64_t kBigRows = 2048;                   // rows from which a product takes 64x64 tiles
 

@@ -610,17 +610,22 @@ struct SgTile {
     static constexpr int OCC = WJ == 2 ? 3 : 2;     // resident blocks per CU the register budget is set for
 };
 constexpr int SG_SUPER = 8;                 // super-tile of 1024 x 1024 outputs per XCD visit (L2: 2 x 1.2 MB of operand rows at d=300)
-constexpr int SG_FL_CAP = 256;              // FILTER epilogue: passing elements a wave collects before it claims their slots
-// Ablation builds (tools/r6_simgemm_ablation.sh; the product is built with 0): where does the matrix pipe's idle time go?
-//   bit 0  the C tile is not stored (a store behind a never-true data-dependent test keeps the accumulators live)
-//   bit 1  no global loads after a block's first slab (the staging registers are re-used: LDS traffic and barriers stay)
-//   bit 2  no LDS stores, fragment reads or barriers inside the K loop: the MFMA chain alone (implies nothing about results)
-#ifndef JMAC_SG_ABLATE
-#define JMAC_SG_ABLATE 0
-#endif
-constexpr bool SG_NO_STORE = (JMAC_SG_ABLATE & 1) != 0, SG_NO_LOAD = (JMAC_SG_ABLATE & 2) != 0, SG_MFMA_ONLY = (JMAC_SG_ABLATE & 4) != 0;
+constexpr int SG_FL_CAP = 256;              // list epilogues: passing elements a wave collects before it claims their slots
 
-// FILTER = true: the scores are not stored.  An element that reaches its row's threshold tau (a lower bound of the row's k-th
+// What happens to a finished tile: the kernel's one epilogue choice.  SgEpiTraits<EPI> states, beside each epilogue's description
+// below: Ext, the epilogue's arguments (the kernel's last parameter); LISTS, whether it keeps per-wave candidate lists in LDS;
+// WIDE, whether the 128 x 256 tile exists for it (launch_sim chooses between the tiles only then).
+enum SgEpi { SG_STORE, SG_FILTER, SG_STATS, SG_CSLS_COUNT, SG_CSLS_FILTER, SG_CSLS_VIABLE, SG_LSE };
+template <int EPI> struct SgEpiTraits;
+
+// SG_STORE: C = A B^T is stored.
+struct SimStore {};
+template <> struct SgEpiTraits<SG_STORE> {
+    typedef SimStore Ext;
+    static constexpr bool LISTS = false, WIDE = true;
+};
+
+// SG_FILTER: the scores are not stored.  An element that reaches its row's threshold tau (a lower bound of the row's k-th
 // largest score, taken from a column sample: jmac_sim_topk_f32) is appended to the row's candidate list instead -- the running
 // top-k of SURVEY K8: the L x N matrix never exists.
 struct SimFilter {
@@ -632,22 +637,32 @@ struct SimFilter {
     int cap;
     int n_off;               // the product covers columns [n_off, n_off + N) of the full matrix: candidate index = n_off + n
 };
+template <> struct SgEpiTraits<SG_FILTER> {
+    typedef SimFilter Ext;
+    static constexpr bool LISTS = true, WIDE = true;
+    static __device__ const SimFilter& lists(const Ext& e) { return e; }
+};
 
-// STATS = true: the scores are not stored either.  Every wave reduces its 64 x 64 part of the tile to partial softmax statistics of
+// SG_STATS: the scores are not stored either.  Every wave reduces its 64 x 64 part of the tile to partial softmax statistics of
 // the logits z = scale * S, once along its rows and once along its columns (jmac_sim_softmax_stats_f32): per row and 64-column
 // part (max S, l = sum e^(z - max z), t = sum e^(z - max z) (z - max z), first column of the maximum), per column and 64-row part
 // the same.  A part's maximum is exact (taken before the exponentials), the parts are combined by sim_stats_merge_kernel with the
 // online form.  Partials are addressed by the part's POSITION in the matrix, written once with plain stores and merged in
 // ascending order: the results do not depend on the grid, the tile walk or the device's CU count.  The reductions stay in
 // registers (DPP inside a 16-lane row, one cross-lane exchange per further step): no wave touches the operand LDS buffers behind
-// the last slab's barrier, as in the other two epilogues.  Runs on the 128 x 128 tile only (launch_sim_stats).
+// the last slab's barrier, as in the other epilogues.  Written for the 128 x 128 tile only (one partial layout: a part is 64 rows
+// or 64 columns).
 struct SimStats {
     float4* rpart;           // [ceil(N / 64)][M]    (max S, l, t, column index bits)
     float* cpart;            // [ceil(M / 64)][N][3] (scale * max S, l, t): the format of col_softmax_stats_kernel; NULL: rows only
     float2* cbest;           // [ceil(M / 64)][N]    (max S, row index bits)
     float scale;             // > 0
 };
-// CSLS = SG_CSLS_COUNT / SG_CSLS_FILTER: the scores are not stored, and every epilogue decision is taken on the CSLS-rescored value
+template <> struct SgEpiTraits<SG_STATS> {
+    typedef SimStats Ext;
+    static constexpr bool LISTS = false, WIDE = false;
+};
+// SG_CSLS_COUNT / SG_CSLS_FILTER: the scores are not stored, and every epilogue decision is taken on the CSLS-rescored value
 // c(m, n) = csls_value(S[m, n], r1[m], r2[n]) (jmac_sim_csls_rank_f32 / jmac_sim_csls_topk_f32).
 //   COUNT   per row m: the columns whose c beats the row's gold value gval[m] (larger, or equal with a column index below
 //           gold[m]) are counted inside the wave and added to rank[m] with ONE integer atomic per (wave, row): sums of integers,
@@ -661,14 +676,28 @@ struct SimCsls {
     const int32_t* gold;     // COUNT: [M]
     int32_t* rank;           // COUNT: [M], preset to 1
 };
-// CSLS = SG_CSLS_VIABLE: the FILTER form for a suitor that may only list the reviewers it can still win (jmac_sim_csls_topk_viable_f32):
+template <> struct SgEpiTraits<SG_CSLS_COUNT> {
+    typedef SimCsls Ext;
+    static constexpr bool LISTS = false, WIDE = true;
+};
+template <> struct SgEpiTraits<SG_CSLS_FILTER> {
+    typedef SimCsls Ext;
+    static constexpr bool LISTS = true, WIDE = true;
+    static __device__ const SimFilter& lists(const Ext& e) { return e.f; }
+};
+// SG_CSLS_VIABLE: the FILTER form for a suitor that may only list the reviewers it can still win (jmac_sim_csls_topk_viable_f32):
 // an element is appended iff it reaches tau AND tk_pack(c(m, n), row_id[m]) > best[n] -- it would displace what reviewer n holds.
 // r1 == NULL (with r2) is decided at run time here: c = S.
 struct SimViable : SimCsls {
     const int32_t* row_id;               // [M] the suitor id of row m (the rows are a gathered subset): the tie-break of the word
     const unsigned long long* best;      // [n_off + N] the reviewers' words, 0 = free
 };
-// CSLS = SG_LSE: the scores are not stored; every wave reduces its 64 x 64 part to partial log-sum-exps with additive offsets
+template <> struct SgEpiTraits<SG_CSLS_VIABLE> {
+    typedef SimViable Ext;
+    static constexpr bool LISTS = true, WIDE = true;
+    static __device__ const SimFilter& lists(const Ext& e) { return e.f; }
+};
+// SG_LSE: the scores are not stored; every wave reduces its 64 x 64 part to partial log-sum-exps with additive offsets
 // (jmac_sim_lse_f32: the half-steps of a log-domain Sinkhorn iteration).  Per row and 64-column part (max z, sum e^(z - max z)) of
 // z = fma(scale, S[m, n], col_add[n]); per column and 64-row part the same of z = fma(scale, S[m, n], row_add[m]).  The SimStats
 // scheme otherwise: exact part maxima, partials addressed by the part's position, plain stores, merged in ascending order by
@@ -680,13 +709,10 @@ struct SimLse {
     const float* row_add;    // [M] added to the logits of the column side; NULL: 0
     float scale;             // > 0
 };
-constexpr int SG_CSLS_COUNT = 1, SG_CSLS_FILTER = 2, SG_CSLS_VIABLE = 3, SG_LSE = 4;
-template <bool STATS, int CSLS = 0> struct SgExt { typedef SimFilter type; };
-template <> struct SgExt<true, 0> { typedef SimStats type; };
-template <> struct SgExt<false, SG_CSLS_COUNT> { typedef SimCsls type; };
-template <> struct SgExt<false, SG_CSLS_FILTER> { typedef SimCsls type; };
-template <> struct SgExt<false, SG_CSLS_VIABLE> { typedef SimViable type; };
-template <> struct SgExt<false, SG_LSE> { typedef SimLse type; };
+template <> struct SgEpiTraits<SG_LSE> {
+    typedef SimLse Ext;
+    static constexpr bool LISTS = false, WIDE = false;
+};
 
 // the DPP-selected lane's v (old = 0 with bound_ctrl: every source lane of the controls used here exists; ROWS: rows written)
 template <int CTRL, int ROWS = 0xF>
@@ -739,29 +765,373 @@ __device__ __forceinline__ void sg_exp_term(float s, float mx, float scale, floa
 // e^(z - max z) of one logit of the log-sum-exp epilogue; an excluded element (z = -inf, or the whole part excluded: NaN) gives 0
 __device__ __forceinline__ float sg_lse_term(float z, float mx) { return fast_exp(fmaxf(z - mx, -1e30f)); }
 
-template <bool FILTER, int WJ, bool STATS = false, int CSLS = 0>
+// Where a lane stands in the tile it has just accumulated: built once per tile, read by every epilogue.
+// C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+struct SgPos {
+    int m0, n0, M, N;        // the tile's first row and column, the matrix
+    int wm, wn;              // the wave's place in the block's 2 x 2 grid: it owns rows m0 + 64 wm .., columns n0 + 32 WJ wn ..
+    int lane, r, h;          // r = lane & 31, h = lane >> 5
+    bool full;               // block-uniform: the whole tile is inside the matrix
+};
+
+// SG_CSLS_COUNT (SimCsls above)
+template <int WJ>
+__device__ __forceinline__ void sg_epi_count(f32x16 (&acc)[2][WJ], const SgPos& p, const SimCsls& ext) {
+    const int m0 = p.m0, n0 = p.n0, M = p.M, N = p.N, wm = p.wm, wn = p.wn, lane = p.lane, r = p.r, h = p.h;
+    // lane l <-> row l of the wave's 64-row block for everything that is per row: ONE coalesced load each, the value
+    // of accumulator row (i, reg) comes out with v_readlane (rows (i, reg, h = 0 / 1) are 4 apart), as tau below
+    const int mrow = min(m0 + wm * 64 + lane, M - 1);
+    float grow = ext.gval[mrow];
+    int gcol = ext.gold[mrow];
+    const bool rescore = ext.r1 != nullptr;
+    float r1row = rescore ? ext.r1[mrow] : 0.f;
+    float r2col[WJ];
+    unsigned long long inside[WJ];                  // columns >= N hold zero-padded operands: they never count
+#pragma unroll
+    for (int j = 0; j < WJ; ++j) {
+        const int n = n0 + wn * 32 * WJ + j * 32 + r;
+        r2col[j] = rescore ? ext.r2[min(n, N - 1)] : 0.f;
+        inside[j] = __ballot(n < N);
+    }
+    int hits = 0;                                      // of row `lane` of the block
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);           // compile-time
+            // One row pair at a time: the empty statement makes this pair's v_readlane sources depend on the previous
+            // pair's sum.  Left free, the scheduler hoists all 192 lane reads and keeps all 64 popcounts in scalar
+            // registers (218 / 346 spilled SGPRs at WJ = 2 / 4).
+            asm volatile("" : "+v"(grow), "+v"(r1row), "+v"(gcol), "+v"(hits));
+            // (both lane reads first, then a select: read inside the arms of `h ? :` they become two exec-masked branches)
+            const float gs0 = bcast_f(grow, rbase), gs1 = bcast_f(grow, rbase + 4);
+            const float ra0 = bcast_f(r1row, rbase), ra1 = bcast_f(r1row, rbase + 4);
+            const int g0 = __builtin_amdgcn_readlane(gcol, rbase), g1 = __builtin_amdgcn_readlane(gcol, rbase + 4);
+            const float gs = h ? gs1 : gs0, r1v = h ? ra1 : ra0;
+            const int g = h ? g1 : g0;
+            int c0 = 0, c1 = 0;                        // wave-uniform: the hits of row rbase / rbase + 4
+#pragma unroll
+            for (int j = 0; j < WJ; ++j) {
+                const int n = n0 + wn * 32 * WJ + j * 32 + r;
+                const float v = rescore ? csls_value(acc[i][j][reg], r1v, r2col[j]) : acc[i][j][reg];
+                const unsigned long long mask = __ballot(v > gs || (v == gs && n < g)) & inside[j];
+                c0 += __popc((unsigned)mask);
+                c1 += __popc((unsigned)(mask >> 32));
+            }
+            // every lane is written exactly once per tile: (i, reg) -> rbase, rbase + 4 covers 0 .. 63 (a select on
+            // lane == rbase instead keeps 64 loop-invariant compare masks alive across the tile loop: 95 spilled SGPRs)
+            asm("s_nop 0\n\tv_writelane_b32 %0, %1, %2\n\tv_writelane_b32 %0, %3, %4"
+                : "+v"(hits)
+                : "s"(c0), "n"(rbase), "s"(c1), "n"(rbase + 4));
+        }
+    if (hits != 0 && m0 + wm * 64 + lane < M) atomicAdd(ext.rank + m0 + wm * 64 + lane, hits);      // rows >= M: no such row
+}
+
+// SG_LSE (SimLse above)
+__device__ __forceinline__ void sg_epi_lse(f32x16 (&acc)[2][2], const SgPos& p, const SimLse& ext) {
+    const int m0 = p.m0, n0 = p.n0, M = p.M, N = p.N, wm = p.wm, wn = p.wn, lane = p.lane, r = p.r, h = p.h;
+    const float scale = ext.scale;
+    const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
+    const int ncol[2] = {ncol0 + r, ncol0 + 32 + r};
+    const int mlim = M - mrow0 - 4 * h;                       // row (i, reg) of this lane is inside iff its base < mlim
+    // elements outside the matrix become -inf, and so do their logits (scale > 0, finite offsets): as in STATS below
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                const unsigned inside = (unsigned)(rbase - mlim) & (unsigned)(ncol[j] - N) & 0x80000000u;
+                acc[i][j][reg] = fminf(acc[i][j][reg], __uint_as_float(0xff800000u ^ inside));
+            }
+    // rows: (i, reg) is one row per half-wave; the lane's two columns carry their offsets.  Lane 16 of the half stores.
+    if (ext.rpart != nullptr) {
+        const float ca0 = ext.col_add ? ext.col_add[min(ncol[0], N - 1)] : 0.f;
+        const float ca1 = ext.col_add ? ext.col_add[min(ncol[1], N - 1)] : 0.f;
+        float2* const rdst = ext.rpart + (int64_t)(ncol0 >> 6) * M + mrow0 + 4 * h;
+        const bool rstore = r == 16 && ncol0 < N;             // (a part wholly outside the matrix does not exist)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                const float z0 = fmaf(scale, acc[i][0][reg], ca0), z1 = fmaf(scale, acc[i][1][reg], ca1);
+                const float mx = sg_half_max(sg_max(z0, z1));
+                float l = sg_lse_term(z0, mx) + sg_lse_term(z1, mx);
+                l = sg_half_sum_upper(l);
+                if (rstore && rbase < mlim) rdst[rbase] = make_float2(mx, l);
+                if (reg & 1) __builtin_amdgcn_sched_barrier(0);      // two rows' chains interleave, no more
+            }
+    }
+    // columns: a lane holds 32 rows of its column per j, the other half-wave the other 32.  The rows' offsets: ONE
+    // coalesced load (lane l <-> row l of the wave's 64 rows), read out per accumulator row as in the count epilogue; the
+    // logits replace the scores in place (the row side is done with them).
+    if (ext.cpart != nullptr) {
+        float radd = ext.row_add ? ext.row_add[min(mrow0 + lane, M - 1)] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                const float a0 = bcast_f(radd, rbase), a1 = bcast_f(radd, rbase + 4);
+                const float av = h ? a1 : a0;
+                acc[i][0][reg] = fmaf(scale, acc[i][0][reg], av);
+                acc[i][1][reg] = fmaf(scale, acc[i][1][reg], av);
+            }
+        float cm[2], cl[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) mx = sg_max(mx, acc[i][j][reg]);
+            float lo, hi;
+            sg_halves(mx, lo, hi);
+            mx = sg_max(lo, hi);
+            float l = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) l += sg_lse_term(acc[i][j][reg], mx);
+            sg_halves(l, lo, hi);
+            cl[j] = lo + hi;
+            cm[j] = mx;
+        }
+        // the lower half-wave stores the columns of j = 0, the upper half those of j = 1
+        const int col = h ? ncol[1] : ncol[0];
+        if (col < N && mrow0 < M) ext.cpart[(int64_t)(mrow0 >> 6) * N + col] = make_float2(h ? cm[1] : cm[0], h ? cl[1] : cl[0]);
+    }
+}
+
+// SG_STATS (SimStats above)
+__device__ __forceinline__ void sg_epi_stats(f32x16 (&acc)[2][2], const SgPos& p, const SimStats& ext) {
+    const int m0 = p.m0, n0 = p.n0, M = p.M, N = p.N, wm = p.wm, wn = p.wn, r = p.r, h = p.h;
+    const float scale = ext.scale;
+    const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
+    const int ncol[2] = {ncol0 + r, ncol0 + 32 + r};
+    // elements outside the matrix (ragged tiles: the clamped loads' duplicates) leave both reductions as -inf
+    const int mlim = M - mrow0 - 4 * h;                       // row (i, reg) of this lane is inside iff its base < mlim
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                // min(s, +inf) = s inside, min(s, -inf) outside; the bound's sign comes from the two differences' sign bits
+                // (64 compare masks would not fit the scalar registers)
+                const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+                const unsigned inside = (unsigned)(rbase - mlim) & (unsigned)(ncol[j] - N) & 0x80000000u;
+                acc[i][j][reg] = fminf(acc[i][j][reg], __uint_as_float(0xff800000u ^ inside));
+            }
+    // rows: (i, reg) is one row per half-wave, its 64 columns are 2 registers x 32 lanes.  The maximum reaches every lane
+    // (the exponentials need it), the two sums only the half's upper 16 lanes, and lane 16 of the half stores the row at
+    // once (16 bytes; results kept for one wide store at the end would stay live through all 32 chains and spill).  The
+    // first column of the maximum is scalar work: ballots of v == max, lowest set bit of each half.
+    float4* const rdst = ext.rpart + (int64_t)(ncol0 >> 6) * M + mrow0 + 4 * h;
+    const bool rstore = r == 16 && ncol0 < N;                 // (a part wholly outside the matrix does not exist)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
+            const float v0 = acc[i][0][reg], v1 = acc[i][1][reg];
+            const float mx = sg_half_max(sg_max(v0, v1));
+            const unsigned long long e0 = __ballot(v0 == mx), e1 = __ballot(v1 == mx);
+            // per half: bits 0..31 = its lanes' j = 0 columns, 32..63 = their j = 1 columns, i.e. the part's column order
+            const int al = __builtin_ffsll((long long)((e0 & 0xffffffffull) | (e1 << 32))) - 1;      // wave-uniform
+            const int ah = __builtin_ffsll((long long)((e0 >> 32) | (e1 & 0xffffffff00000000ull))) - 1;
+            float l = 0.f, t = 0.f;
+            sg_exp_term(v0, mx, scale, l, t);
+            sg_exp_term(v1, mx, scale, l, t);
+            l = sg_half_sum_upper(l);
+            t = sg_half_sum_upper(t);
+            if (rstore && rbase < mlim) rdst[rbase] = make_float4(mx, l, t, __int_as_float(ncol0 + (h ? ah : al)));
+            // two rows' chains interleave (they fill each other's DPP wait states), no more
+            if (reg & 1) __builtin_amdgcn_sched_barrier(0);
+        }
+    // columns: a lane holds 32 rows of its column per j, the other half-wave the other 32
+    if (ext.cpart != nullptr) {
+        float cm[2], cl[2], ct[2];
+        int ca[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) mx = sg_max(mx, acc[i][j][reg]);
+            float lo, hi;
+            sg_halves(mx, lo, hi);
+            mx = sg_max(lo, hi);
+            // the lane's rows in DESCENDING order: the last match is its lowest row of the maximum (128: none)
+            int a = 128;
+            float l = 0.f, t = 0.f;
+#pragma unroll
+            for (int i = 1; i >= 0; --i)
+#pragma unroll
+                for (int reg = 15; reg >= 0; --reg) {
+                    a = acc[i][j][reg] == mx ? i * 32 + (reg & 3) + 8 * (reg >> 2) : a;
+                    sg_exp_term(acc[i][j][reg], mx, scale, l, t);
+                    if ((reg & 3) == 0) __builtin_amdgcn_sched_barrier(0);
+                }
+            sg_halves(l, lo, hi);
+            cl[j] = lo + hi;
+            sg_halves(t, lo, hi);
+            ct[j] = lo + hi;
+            sg_halves(__int_as_float(a + 4 * h), lo, hi);
+            ca[j] = mrow0 + min(__float_as_int(lo), __float_as_int(hi));
+            cm[j] = mx;
+        }
+        // the lower half-wave stores the columns of j = 0, the upper half those of j = 1
+        const int col = h ? ncol[1] : ncol[0];
+        if (col < N && mrow0 < M) {
+            const int64_t e = (int64_t)(mrow0 >> 6) * N + col;
+            const float mxs = h ? cm[1] : cm[0];
+            ext.cpart[e * 3 + 0] = scale * mxs;
+            ext.cpart[e * 3 + 1] = h ? cl[1] : cl[0];
+            ext.cpart[e * 3 + 2] = h ? ct[1] : ct[0];
+            ext.cbest[e] = make_float2(mxs, __int_as_float(h ? ca[1] : ca[0]));
+        }
+    }
+}
+
+// SG_FILTER, SG_CSLS_FILTER, SG_CSLS_VIABLE: one body.  fl_m, fl_n, fl_v: the wave's own lists of SG_FL_CAP entries in LDS.
+template <int EPI, int WJ>
+__device__ __forceinline__ void sg_epi_lists(f32x16 (&acc)[2][WJ], const SgPos& p, const typename SgEpiTraits<EPI>::Ext& ext, int* fl_m,
+                                             int* fl_n, float* fl_v) {
+    constexpr bool VIABLE = EPI == SG_CSLS_VIABLE;
+    const SimFilter& flt = SgEpiTraits<EPI>::lists(ext);
+    const int m0 = p.m0, n0 = p.n0, M = p.M, N = p.N, wm = p.wm, wn = p.wn, lane = p.lane, r = p.r, h = p.h;
+    // Passing elements are rare (~k * N / Ns per row: under 1 % of the tile).  A returned global atomic per passing
+    // element inside the scan would cost one memory round trip each (measured: the product ran 1.6x longer); the wave
+    // first compacts its passing elements into a small LDS list (ballot + prefix popcount, no memory traffic) and
+    // then claims their slots with ONE batch of atomics per flush.
+    int fcount = 0;                                    // wave-uniform
+    auto flush = [&]() {
+        __threadfence_block();                         // the list's LDS writes are visible to the whole wave
+        for (int e = lane; e < fcount; e += 64) {
+            const int m = fl_m[e];
+            const int pos = atomicAdd(flt.cnt + m, 1);
+            if (pos < flt.cap) {
+                flt.cval[(int64_t)m * flt.cap + pos] = fl_v[e];
+                flt.cidx[(int64_t)m * flt.cap + pos] = fl_n[e];
+            }
+        }
+        __threadfence_block();
+        fcount = 0;
+    };
+    // thresholds of the wave's 64 rows: ONE coalesced load (lane l <-> row l of the wave's row block); the value for
+    // accumulator register (i, reg) comes out of it with two v_readlane (rows (i, reg, h = 0 / 1) are 4 apart)
+    const float trow = flt.tau[(int64_t)min(m0 + wm * 64 + lane, M - 1) * flt.tau_stride];
+    // CSLS: the row terms travel like tau, a lane's WJ column terms are loaded once per tile
+    float r1row = 0.f, r2col[EPI == SG_CSLS_FILTER || VIABLE ? WJ : 1] = {};
+    if constexpr (EPI == SG_CSLS_FILTER) {
+        r1row = ext.r1[min(m0 + wm * 64 + lane, M - 1)];
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) r2col[j] = ext.r2[flt.n_off + min(n0 + wn * 32 * WJ + j * 32 + r, N - 1)];
+    }
+    // VIABLE: the rows' suitor ids travel like tau too, a lane's WJ reviewer words are loaded once per tile
+    int ridrow = 0;
+    unsigned long long bcol[VIABLE ? WJ : 1] = {};
+    bool rescore = false;                              // block-uniform
+    if constexpr (VIABLE) {
+        rescore = ext.r1 != nullptr;
+        ridrow = ext.row_id[min(m0 + wm * 64 + lane, M - 1)];
+        if (rescore) r1row = ext.r1[min(m0 + wm * 64 + lane, M - 1)];
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) {
+            const int n = flt.n_off + min(n0 + wn * 32 * WJ + j * 32 + r, N - 1);
+            if (rescore) r2col[j] = ext.r2[n];
+            bcol[j] = ext.best[n];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);           // compile-time
+            const int m = m0 + wm * 64 + rbase + 4 * h;
+            const float tau = h ? bcast_f(trow, rbase + 4) : bcast_f(trow, rbase);
+            float r1v = 0.f;
+            if constexpr (EPI == SG_CSLS_FILTER || VIABLE) r1v = h ? bcast_f(r1row, rbase + 4) : bcast_f(r1row, rbase);
+            int rid = 0;
+            if constexpr (VIABLE) rid = h ? bcast_i(ridrow, rbase + 4) : bcast_i(ridrow, rbase);
+#pragma unroll
+            for (int j = 0; j < WJ; ++j) {
+                const int n = n0 + wn * 32 * WJ + j * 32 + r;
+                float v = acc[i][j][reg];
+                if constexpr (EPI == SG_CSLS_FILTER) v = csls_value(v, r1v, r2col[j]);
+                if constexpr (VIABLE) v = rescore ? csls_value(v, r1v, r2col[j]) : v;
+                bool pass = m < M && n < N && v >= tau;
+                if constexpr (VIABLE) pass = pass && tk_pack(v, rid) > bcol[j];
+                const unsigned long long mask = __ballot(pass);
+                if (mask != 0ull) {                    // wave-uniform
+                    const int np = __popcll(mask);
+                    if (fcount + np > SG_FL_CAP) flush();
+                    if (pass) {
+                        const int slot = fcount + __popcll(mask & ((1ull << lane) - 1ull));
+                        fl_m[slot] = m;
+                        fl_n[slot] = n + flt.n_off;
+                        fl_v[slot] = v;
+                    }
+                    fcount += np;
+                }
+            }
+        }
+    flush();
+}
+
+// SG_STORE, interior tile: 32 WJ unconditional stores per wave (the caller follows them with its own instance of the next tile's
+// first slab: see tile_prologue)
+template <int WJ>
+__device__ __forceinline__ void sg_epi_store_interior(const f32x16 (&acc)[2][WJ], const SgPos& p, float* __restrict__ C, int64_t ldc) {
+    const int m0 = p.m0, n0 = p.n0, wm = p.wm, wn = p.wn, r = p.r, h = p.h;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) {
+            float* cbase = C + (int64_t)(m0 + wm * 64 + i * 32 + 4 * h) * ldc + (n0 + wn * 32 * WJ + j * 32 + r);
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) cbase[(int64_t)((reg & 3) + 8 * (reg >> 2)) * ldc] = acc[i][j][reg];
+        }
+}
+
+// SG_STORE, a tile that crosses the matrix's edge: every store behind its bounds test
+template <int WJ>
+__device__ __forceinline__ void sg_epi_store_ragged(const f32x16 (&acc)[2][WJ], const SgPos& p, float* __restrict__ C, int64_t ldc) {
+    const int m0 = p.m0, n0 = p.n0, M = p.M, N = p.N, wm = p.wm, wn = p.wn, r = p.r, h = p.h;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < WJ; ++j)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int64_t m = m0 + wm * 64 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+                const int64_t n = n0 + wn * 32 * WJ + j * 32 + r;
+                if (m < M && n < N) C[m * ldc + n] = acc[i][j][reg];
+            }
+}
+
+// The kernel: the persistent tile walk, the software pipeline, the request for the next tile's first slab, and the dispatch to the
+// tile's epilogue above.
+template <int EPI, int WJ>
 __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                           int64_t ldb, int M, int N, int d, float* __restrict__ C, int64_t ldc,
                                                           int tiles_m, int tiles_n, int super_order, int n_ids,
-                                                          typename SgExt<STATS, CSLS>::type ext) {
-    static_assert(!(STATS && (FILTER || WJ != 2)), "the statistics epilogue is written for the plain 128 x 128 tile");
-    static_assert(CSLS == 0 || (!STATS && FILTER == (CSLS == SG_CSLS_FILTER || CSLS == SG_CSLS_VIABLE)), "CSLS: the count form or a filter form");
-    static_assert(CSLS != SG_LSE || WJ == 2, "the log-sum-exp epilogue is written for the plain 128 x 128 tile");
-    constexpr bool VIABLE = CSLS == SG_CSLS_VIABLE;
-    const auto& flt = [&]() -> const auto& {
-        if constexpr (CSLS != 0 && CSLS != SG_LSE) return ext.f;
-        else return ext;
-    }();
-    (void)flt;
+                                                          typename SgEpiTraits<EPI>::Ext ext) {
+    static_assert(WJ == 2 || (WJ == 4 && SgEpiTraits<EPI>::WIDE), "this epilogue is written for the 128 x 128 tile only");
+    constexpr bool LISTS = SgEpiTraits<EPI>::LISTS;
     // LDS image of one operand slab (16 k): plane (q, h) holds, for every tile row, the 4 floats k = 8q + 4h .. +3.
     // Lane (r = l&31, h = l>>5) of a wave reads its float4 of row r from plane (q, h): 32 lanes x 16 B contiguous,
     // conflict free for ds_read_b128's lane groups.  The MFMA step s of a sub-slab contracts k = {8q+s, 8q+4+s}.
     __shared__ __attribute__((aligned(16))) float As[2][SG_IMG];
-    constexpr int SG_WJ = WJ, SG_TN = SgTile<WJ>::TN, SG_PLANE_B = SgTile<WJ>::PLANE_B, SG_LB = SgTile<WJ>::LB, SG_SUPER_N = SgTile<WJ>::SUPER_N;
+    constexpr int SG_TN = SgTile<WJ>::TN, SG_PLANE_B = SgTile<WJ>::PLANE_B, SG_LB = SgTile<WJ>::LB, SG_SUPER_N = SgTile<WJ>::SUPER_N;
     __shared__ __attribute__((aligned(16))) float Bs[2][SgTile<WJ>::IMG_B];
-    __shared__ int fl_m[FILTER ? kBlock / 64 : 1][FILTER ? SG_FL_CAP : 1];      // FILTER: per-wave lists of passing elements
-    __shared__ int fl_n[FILTER ? kBlock / 64 : 1][FILTER ? SG_FL_CAP : 1];
-    __shared__ float fl_v[FILTER ? kBlock / 64 : 1][FILTER ? SG_FL_CAP : 1];
+    __shared__ int fl_m[LISTS ? kBlock / 64 : 1][LISTS ? SG_FL_CAP : 1];        // LISTS: per-wave lists of passing elements
+    __shared__ int fl_n[LISTS ? kBlock / 64 : 1][LISTS ? SG_FL_CAP : 1];
+    __shared__ float fl_v[LISTS ? kBlock / 64 : 1][LISTS ? SG_FL_CAP : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;           // wave grid 2 x 2, each wave 64 x 64
 
@@ -816,19 +1186,19 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
         }
     };
     const int r = lane & 31, h = lane >> 5;
-    const int aoff = h * SG_PLANE + (wm * 64 + r) * 4, boff = h * SG_PLANE_B + (wn * 32 * SG_WJ + r) * 4;
-    auto frags = [&](int buf, int q, float4 (&af)[2], float4 (&bf)[SG_WJ]) {
+    const int aoff = h * SG_PLANE + (wm * 64 + r) * 4, boff = h * SG_PLANE_B + (wn * 32 * WJ + r) * 4;
+    auto frags = [&](int buf, int q, float4 (&af)[2], float4 (&bf)[WJ]) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const float4*>(As[buf] + q * 2 * SG_PLANE + aoff + i * 32 * 4);
 #pragma unroll
-        for (int j = 0; j < SG_WJ; ++j) bf[j] = *reinterpret_cast<const float4*>(Bs[buf] + q * 2 * SG_PLANE_B + boff + j * 32 * 4);
+        for (int j = 0; j < WJ; ++j) bf[j] = *reinterpret_cast<const float4*>(Bs[buf] + q * 2 * SG_PLANE_B + boff + j * 32 * 4);
     };
-    f32x16 acc[2][SG_WJ];
+    f32x16 acc[2][WJ];
     // the 2 WJ accumulators rotate (dependency distance 2 WJ >= 4)
-    auto mfma16 = [&](const float4 (&af)[2], const float4 (&bf)[SG_WJ]) {
+    auto mfma16 = [&](const float4 (&af)[2], const float4 (&bf)[WJ]) {
 #define JMAC_SG_STEP(c)                                                                                              \
         _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                \
-            _Pragma("unroll") for (int j = 0; j < SG_WJ; ++j)                                                        \
+            _Pragma("unroll") for (int j = 0; j < WJ; ++j)                                                        \
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].c, bf[j].c, acc[i][j], 0, 0, 0);
         JMAC_SG_STEP(x)
         JMAC_SG_STEP(y)
@@ -838,26 +1208,27 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
     };
 
     const int nk = (d + SG_K - 1) / SG_K;
-    float4 ra[2], rb[SG_LB], af0[2], bf0[SG_WJ], af1[2], bf1[SG_WJ];
+    float4 ra[2], rb[SG_LB], af0[2], bf0[WJ], af1[2], bf1[WJ];
     int tm, tn;
     int id = next_tile(blockIdx.x, tm, tn);
     if (id >= n_ids) return;
     // A tile's first slab: staged rows -> LDS buffer 0, slab 1 requested, the first fragments read.  Called for the block's first
     // tile here and for every further tile at the END of the loop body, behind the previous tile's epilogue: a separate instance
     // of the code, so that its wait for the slab's loads is counted on that path alone -- the loads were issued BEFORE the epilogue's
-    // 64 stores and vmcnt retires in order, so the stores stay in flight (vmcnt(63)).  With the prologue at the loop's top the
+    // stores and vmcnt retires in order, so the wait can leave stores in flight.  At WJ = 2 a wave has 64 stores behind the loads and
+    // vmcnt(63) keeps them in flight.  At WJ = 4 it has 128, the 6-bit counter saturates at 63, and the same vmcnt(63) first waits
+    // for about 65 of them to be acknowledged: a cost in time only, the results are the same bits.  With the prologue at the loop's top the
     // kernel-entry path (nothing but four loads pending) and the back edge merged into vmcnt(3): every tile began by waiting for
     // the previous tile's stores to be acknowledged (round 6: the "nostore" ablation's 6 %).
     auto tile_prologue = [&](const int m0, const int n0) {
         sstore(As[0], ra, 0);
         sstore(Bs[0], rb, 0);
-        if (nk > 1 && !SG_NO_LOAD) {
+        if (nk > 1) {
             gload(A, lda, m0, M, SG_K, ra);
             gload(Bm, ldb, n0, N, SG_K, rb);
         }
         __syncthreads();
         frags(0, 0, af0, bf0);
-        if (SG_MFMA_ONLY) frags(0, 1, af1, bf1);
     };
     gload(A, lda, tm * SG_T, M, 0, ra);
     gload(Bm, ldb, tn * SG_TN, N, 0, rb);
@@ -867,7 +1238,7 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < SG_WJ; ++j)
+            for (int j = 0; j < WJ; ++j)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
         // Software pipeline, one barrier per slab.  At the top of slab kt: fragment set 0 holds (kt, q=0), the staging registers
@@ -877,9 +1248,9 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
         // memory operations are spread between the MFMAs (sched_group_barrier): one operation behind each MFMA instead of a burst
         // behind sixteen of them (ablation and A/B: profiles/r6_simgemm_ablation.txt; +3 % over the burst form).
         auto slab_body = [&](const int kt, auto has1, auto has2) {
-            constexpr bool HAS1 = decltype(has1)::value && !SG_MFMA_ONLY, HAS2 = decltype(has2)::value && !SG_MFMA_ONLY && !SG_NO_LOAD;
+            constexpr bool HAS1 = decltype(has1)::value, HAS2 = decltype(has2)::value;
             const int cur = kt & 1;
-            if (!SG_MFMA_ONLY) frags(cur, 1, af1, bf1);
+            frags(cur, 1, af1, bf1);
             mfma16(af0, bf0);
             if constexpr (HAS1) {
                 sstore(As[cur ^ 1], ra, (kt + 1) * SG_K);
@@ -889,35 +1260,33 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
                     gload(Bm, ldb, n0, N, (kt + 2) * SG_K, rb);
                 }
             }
-            if constexpr (!SG_MFMA_ONLY) {
-                // 2 + WJ fragment reads, 8 WJ MFMAs, then per staged float4 one LDS store and (HAS2) one global load
+            // 2 + WJ fragment reads, 8 WJ MFMAs, then per staged float4 one LDS store and (HAS2) one global load
 #pragma unroll
-                for (int i = 0; i < 2 + SG_WJ; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, 8 * SG_WJ - (2 + SG_WJ) - (HAS1 ? 2 + SG_LB : 0) - (HAS2 ? 2 + SG_LB : 0), 0);
-                if constexpr (HAS1) {
-#pragma unroll
-                    for (int i = 0; i < 2 + SG_LB; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    }
-                }
-                if constexpr (HAS2) {
-#pragma unroll
-                    for (int i = 0; i < 2 + SG_LB; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    }
-                }
-                __syncthreads();
+            for (int i = 0; i < 2 + WJ; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
+            __builtin_amdgcn_sched_group_barrier(0x008, 8 * WJ - (2 + WJ) - (HAS1 ? 2 + SG_LB : 0) - (HAS2 ? 2 + SG_LB : 0), 0);
+            if constexpr (HAS1) {
+#pragma unroll
+                for (int i = 0; i < 2 + SG_LB; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                }
+            }
+            if constexpr (HAS2) {
+#pragma unroll
+                for (int i = 0; i < 2 + SG_LB; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                }
+            }
+            __syncthreads();
             if constexpr (HAS1) frags(cur ^ 1, 0, af0, bf0);
             mfma16(af1, bf1);
             if constexpr (HAS1) {
 #pragma unroll
-                for (int i = 0; i < 2 + SG_WJ; ++i) {
+                for (int i = 0; i < 2 + WJ; ++i) {
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 }
@@ -932,337 +1301,34 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
             }
             slab_body(kt, std::false_type{}, std::false_type{});
         }
-        if (SG_MFMA_ONLY) __syncthreads();               // (the next tile's first sstore must not race this tile's first fragment reads)
-        // the next tile's first slab is requested BEFORE this tile's 64 KB of results are stored: the stores and the
-        // loads overlap, and no wave reads LDS any more (the last fragment reads precede the last barrier)
+        // the next tile's first slab is requested BEFORE this tile's epilogue runs (the store epilogue: 64 KB of results at WJ = 2,
+        // 128 KB at WJ = 4): the stores and the loads overlap, and no wave reads LDS any more (the last fragment reads precede the
+        // last barrier)
         int ntm = 0, ntn = 0;
         const int nid = next_tile(id + gridDim.x, ntm, ntn);
-        if (nid < n_ids && !SG_NO_LOAD) {
+        if (nid < n_ids) {
             gload(A, lda, ntm * SG_T, M, 0, ra);
             gload(Bm, ldb, ntn * SG_TN, N, 0, rb);
         }
-        // C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
         const bool full = m0 + SG_T <= M && n0 + SG_TN <= N;      // block-uniform: interior tiles store without bounds tests
-        if constexpr (CSLS == SG_CSLS_COUNT) {
-            // lane l <-> row l of the wave's 64-row block for everything that is per row: ONE coalesced load each, the value
-            // of accumulator row (i, reg) comes out with v_readlane (rows (i, reg, h = 0 / 1) are 4 apart), as tau below
-            const int mrow = min(m0 + wm * 64 + lane, M - 1);
-            float grow = ext.gval[mrow];
-            int gcol = ext.gold[mrow];
-            const bool rescore = ext.r1 != nullptr;
-            float r1row = rescore ? ext.r1[mrow] : 0.f;
-            float r2col[SG_WJ];
-            unsigned long long inside[SG_WJ];                  // columns >= N hold zero-padded operands: they never count
-#pragma unroll
-            for (int j = 0; j < SG_WJ; ++j) {
-                const int n = n0 + wn * 32 * SG_WJ + j * 32 + r;
-                r2col[j] = rescore ? ext.r2[min(n, N - 1)] : 0.f;
-                inside[j] = __ballot(n < N);
-            }
-            int hits = 0;                                      // of row `lane` of the block
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);           // compile-time
-                    // One row pair at a time: the empty statement makes this pair's v_readlane sources depend on the previous
-                    // pair's sum.  Left free, the scheduler hoists all 192 lane reads and keeps all 64 popcounts in scalar
-                    // registers (218 / 346 spilled SGPRs at WJ = 2 / 4).
-                    asm volatile("" : "+v"(grow), "+v"(r1row), "+v"(gcol), "+v"(hits));
-                    // (both lane reads first, then a select: read inside the arms of `h ? :` they become two exec-masked branches)
-                    const float gs0 = bcast_f(grow, rbase), gs1 = bcast_f(grow, rbase + 4);
-                    const float ra0 = bcast_f(r1row, rbase), ra1 = bcast_f(r1row, rbase + 4);
-                    const int g0 = __builtin_amdgcn_readlane(gcol, rbase), g1 = __builtin_amdgcn_readlane(gcol, rbase + 4);
-                    const float gs = h ? gs1 : gs0, r1v = h ? ra1 : ra0;
-                    const int g = h ? g1 : g0;
-                    int c0 = 0, c1 = 0;                        // wave-uniform: the hits of row rbase / rbase + 4
-#pragma unroll
-                    for (int j = 0; j < SG_WJ; ++j) {
-                        const int n = n0 + wn * 32 * SG_WJ + j * 32 + r;
-                        const float v = rescore ? csls_value(acc[i][j][reg], r1v, r2col[j]) : acc[i][j][reg];
-                        const unsigned long long mask = __ballot(v > gs || (v == gs && n < g)) & inside[j];
-                        c0 += __popc((unsigned)mask);
-                        c1 += __popc((unsigned)(mask >> 32));
-                    }
-                    // every lane is written exactly once per tile: (i, reg) -> rbase, rbase + 4 covers 0 .. 63 (a select on
-                    // lane == rbase instead keeps 64 loop-invariant compare masks alive across the tile loop: 95 spilled SGPRs)
-                    asm("s_nop 0\n\tv_writelane_b32 %0, %1, %2\n\tv_writelane_b32 %0, %3, %4"
-                        : "+v"(hits)
-                        : "s"(c0), "n"(rbase), "s"(c1), "n"(rbase + 4));
-                }
-            if (hits != 0 && m0 + wm * 64 + lane < M) atomicAdd(ext.rank + m0 + wm * 64 + lane, hits);      // rows >= M: no such row
-        } else if constexpr (CSLS == SG_LSE) {
-            const float scale = ext.scale;
-            const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
-            const int ncol[2] = {ncol0 + r, ncol0 + 32 + r};
-            const int mlim = M - mrow0 - 4 * h;                       // row (i, reg) of this lane is inside iff its base < mlim
-            // elements outside the matrix become -inf, and so do their logits (scale > 0, finite offsets): as in STATS below
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
-                        const unsigned inside = (unsigned)(rbase - mlim) & (unsigned)(ncol[j] - N) & 0x80000000u;
-                        acc[i][j][reg] = fminf(acc[i][j][reg], __uint_as_float(0xff800000u ^ inside));
-                    }
-            // rows: (i, reg) is one row per half-wave; the lane's two columns carry their offsets.  Lane 16 of the half stores.
-            if (ext.rpart != nullptr) {
-                const float ca0 = ext.col_add ? ext.col_add[min(ncol[0], N - 1)] : 0.f;
-                const float ca1 = ext.col_add ? ext.col_add[min(ncol[1], N - 1)] : 0.f;
-                float2* const rdst = ext.rpart + (int64_t)(ncol0 >> 6) * M + mrow0 + 4 * h;
-                const bool rstore = r == 16 && ncol0 < N;             // (a part wholly outside the matrix does not exist)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
-                        const float z0 = fmaf(scale, acc[i][0][reg], ca0), z1 = fmaf(scale, acc[i][1][reg], ca1);
-                        const float mx = sg_half_max(sg_max(z0, z1));
-                        float l = sg_lse_term(z0, mx) + sg_lse_term(z1, mx);
-                        l = sg_half_sum_upper(l);
-                        if (rstore && rbase < mlim) rdst[rbase] = make_float2(mx, l);
-                        if (reg & 1) __builtin_amdgcn_sched_barrier(0);      // two rows' chains interleave, no more
-                    }
-            }
-            // columns: a lane holds 32 rows of its column per j, the other half-wave the other 32.  The rows' offsets: ONE
-            // coalesced load (lane l <-> row l of the wave's 64 rows), read out per accumulator row as in the count epilogue; the
-            // logits replace the scores in place (the row side is done with them).
-            if (ext.cpart != nullptr) {
-                float radd = ext.row_add ? ext.row_add[min(mrow0 + lane, M - 1)] : 0.f;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
-                        const float a0 = bcast_f(radd, rbase), a1 = bcast_f(radd, rbase + 4);
-                        const float av = h ? a1 : a0;
-                        acc[i][0][reg] = fmaf(scale, acc[i][0][reg], av);
-                        acc[i][1][reg] = fmaf(scale, acc[i][1][reg], av);
-                    }
-                float cm[2], cl[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float mx = -INFINITY;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) mx = sg_max(mx, acc[i][j][reg]);
-                    float lo, hi;
-                    sg_halves(mx, lo, hi);
-                    mx = sg_max(lo, hi);
-                    float l = 0.f;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) l += sg_lse_term(acc[i][j][reg], mx);
-                    sg_halves(l, lo, hi);
-                    cl[j] = lo + hi;
-                    cm[j] = mx;
-                }
-                // the lower half-wave stores the columns of j = 0, the upper half those of j = 1
-                const int col = h ? ncol[1] : ncol[0];
-                if (col < N && mrow0 < M) ext.cpart[(int64_t)(mrow0 >> 6) * N + col] = make_float2(h ? cm[1] : cm[0], h ? cl[1] : cl[0]);
-            }
-        } else if constexpr (STATS) {
-            const float scale = flt.scale;
-            const int mrow0 = m0 + wm * 64, ncol0 = n0 + wn * 64;
-            const int ncol[2] = {ncol0 + r, ncol0 + 32 + r};
-            // elements outside the matrix (ragged tiles: the clamped loads' duplicates) leave both reductions as -inf
-            const int mlim = M - mrow0 - 4 * h;                       // row (i, reg) of this lane is inside iff its base < mlim
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        // min(s, +inf) = s inside, min(s, -inf) outside; the bound's sign comes from the two differences' sign bits
-                        // (64 compare masks would not fit the scalar registers)
-                        const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
-                        const unsigned inside = (unsigned)(rbase - mlim) & (unsigned)(ncol[j] - N) & 0x80000000u;
-                        acc[i][j][reg] = fminf(acc[i][j][reg], __uint_as_float(0xff800000u ^ inside));
-                    }
-            // rows: (i, reg) is one row per half-wave, its 64 columns are 2 registers x 32 lanes.  The maximum reaches every lane
-            // (the exponentials need it), the two sums only the half's upper 16 lanes, and lane 16 of the half stores the row at
-            // once (16 bytes; results kept for one wide store at the end would stay live through all 32 chains and spill).  The
-            // first column of the maximum is scalar work: ballots of v == max, lowest set bit of each half.
-            float4* const rdst = flt.rpart + (int64_t)(ncol0 >> 6) * M + mrow0 + 4 * h;
-            const bool rstore = r == 16 && ncol0 < N;                 // (a part wholly outside the matrix does not exist)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);
-                    const float v0 = acc[i][0][reg], v1 = acc[i][1][reg];
-                    const float mx = sg_half_max(sg_max(v0, v1));
-                    const unsigned long long e0 = __ballot(v0 == mx), e1 = __ballot(v1 == mx);
-                    // per half: bits 0..31 = its lanes' j = 0 columns, 32..63 = their j = 1 columns, i.e. the part's column order
-                    const int al = __builtin_ffsll((long long)((e0 & 0xffffffffull) | (e1 << 32))) - 1;      // wave-uniform
-                    const int ah = __builtin_ffsll((long long)((e0 >> 32) | (e1 & 0xffffffff00000000ull))) - 1;
-                    float l = 0.f, t = 0.f;
-                    sg_exp_term(v0, mx, scale, l, t);
-                    sg_exp_term(v1, mx, scale, l, t);
-                    l = sg_half_sum_upper(l);
-                    t = sg_half_sum_upper(t);
-                    if (rstore && rbase < mlim) rdst[rbase] = make_float4(mx, l, t, __int_as_float(ncol0 + (h ? ah : al)));
-                    // two rows' chains interleave (they fill each other's DPP wait states), no more
-                    if (reg & 1) __builtin_amdgcn_sched_barrier(0);
-                }
-            // columns: a lane holds 32 rows of its column per j, the other half-wave the other 32
-            if (flt.cpart != nullptr) {
-                float cm[2], cl[2], ct[2];
-                int ca[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float mx = -INFINITY;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) mx = sg_max(mx, acc[i][j][reg]);
-                    float lo, hi;
-                    sg_halves(mx, lo, hi);
-                    mx = sg_max(lo, hi);
-                    // the lane's rows in DESCENDING order: the last match is its lowest row of the maximum (128: none)
-                    int a = 128;
-                    float l = 0.f, t = 0.f;
-#pragma unroll
-                    for (int i = 1; i >= 0; --i)
-#pragma unroll
-                        for (int reg = 15; reg >= 0; --reg) {
-                            a = acc[i][j][reg] == mx ? i * 32 + (reg & 3) + 8 * (reg >> 2) : a;
-                            sg_exp_term(acc[i][j][reg], mx, scale, l, t);
-                            if ((reg & 3) == 0) __builtin_amdgcn_sched_barrier(0);
-                        }
-                    sg_halves(l, lo, hi);
-                    cl[j] = lo + hi;
-                    sg_halves(t, lo, hi);
-                    ct[j] = lo + hi;
-                    sg_halves(__int_as_float(a + 4 * h), lo, hi);
-                    ca[j] = mrow0 + min(__float_as_int(lo), __float_as_int(hi));
-                    cm[j] = mx;
-                }
-                // the lower half-wave stores the columns of j = 0, the upper half those of j = 1
-                const int col = h ? ncol[1] : ncol[0];
-                if (col < N && mrow0 < M) {
-                    const int64_t e = (int64_t)(mrow0 >> 6) * N + col;
-                    const float mxs = h ? cm[1] : cm[0];
-                    flt.cpart[e * 3 + 0] = scale * mxs;
-                    flt.cpart[e * 3 + 1] = h ? cl[1] : cl[0];
-                    flt.cpart[e * 3 + 2] = h ? ct[1] : ct[0];
-                    flt.cbest[e] = make_float2(mxs, __int_as_float(h ? ca[1] : ca[0]));
-                }
-            }
-        } else if constexpr (FILTER) {
-            // Passing elements are rare (~k * N / Ns per row: under 1 % of the tile).  A returned global atomic per passing
-            // element inside the scan would cost one memory round trip each (measured: the product ran 1.6x longer); the wave
-            // first compacts its passing elements into a small LDS list (ballot + prefix popcount, no memory traffic) and
-            // then claims their slots with ONE batch of atomics per flush.
-            int fcount = 0;                                    // wave-uniform
-            auto flush = [&]() {
-                __threadfence_block();                         // the list's LDS writes are visible to the whole wave
-                for (int e = lane; e < fcount; e += 64) {
-                    const int m = fl_m[wave][e];
-                    const int pos = atomicAdd(flt.cnt + m, 1);
-                    if (pos < flt.cap) {
-                        flt.cval[(int64_t)m * flt.cap + pos] = fl_v[wave][e];
-                        flt.cidx[(int64_t)m * flt.cap + pos] = fl_n[wave][e];
-                    }
-                }
-                __threadfence_block();
-                fcount = 0;
-            };
-            // thresholds of the wave's 64 rows: ONE coalesced load (lane l <-> row l of the wave's row block); the value for
-            // accumulator register (i, reg) comes out of it with two v_readlane (rows (i, reg, h = 0 / 1) are 4 apart)
-            const float trow = flt.tau[(int64_t)min(m0 + wm * 64 + lane, M - 1) * flt.tau_stride];
-            // CSLS: the row terms travel like tau, a lane's WJ column terms are loaded once per tile
-            float r1row = 0.f, r2col[CSLS == SG_CSLS_FILTER || VIABLE ? SG_WJ : 1] = {};
-            if constexpr (CSLS == SG_CSLS_FILTER) {
-                r1row = ext.r1[min(m0 + wm * 64 + lane, M - 1)];
-#pragma unroll
-                for (int j = 0; j < SG_WJ; ++j) r2col[j] = ext.r2[flt.n_off + min(n0 + wn * 32 * SG_WJ + j * 32 + r, N - 1)];
-            }
-            // VIABLE: the rows' suitor ids travel like tau too, a lane's WJ reviewer words are loaded once per tile
-            int ridrow = 0;
-            unsigned long long bcol[VIABLE ? SG_WJ : 1] = {};
-            bool rescore = false;                              // block-uniform
-            if constexpr (VIABLE) {
-                rescore = ext.r1 != nullptr;
-                ridrow = ext.row_id[min(m0 + wm * 64 + lane, M - 1)];
-                if (rescore) r1row = ext.r1[min(m0 + wm * 64 + lane, M - 1)];
-#pragma unroll
-                for (int j = 0; j < SG_WJ; ++j) {
-                    const int n = flt.n_off + min(n0 + wn * 32 * SG_WJ + j * 32 + r, N - 1);
-                    if (rescore) r2col[j] = ext.r2[n];
-                    bcol[j] = ext.best[n];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);           // compile-time
-                    const int m = m0 + wm * 64 + rbase + 4 * h;
-                    const float tau = h ? bcast_f(trow, rbase + 4) : bcast_f(trow, rbase);
-                    float r1v = 0.f;
-                    if constexpr (CSLS == SG_CSLS_FILTER || VIABLE) r1v = h ? bcast_f(r1row, rbase + 4) : bcast_f(r1row, rbase);
-                    int rid = 0;
-                    if constexpr (VIABLE) rid = h ? bcast_i(ridrow, rbase + 4) : bcast_i(ridrow, rbase);
-#pragma unroll
-                    for (int j = 0; j < SG_WJ; ++j) {
-                        const int n = n0 + wn * 32 * SG_WJ + j * 32 + r;
-                        float v = acc[i][j][reg];
-                        if constexpr (CSLS == SG_CSLS_FILTER) v = csls_value(v, r1v, r2col[j]);
-                        if constexpr (VIABLE) v = rescore ? csls_value(v, r1v, r2col[j]) : v;
-                        bool pass = m < M && n < N && v >= tau;
-                        if constexpr (VIABLE) pass = pass && tk_pack(v, rid) > bcol[j];
-                        const unsigned long long mask = __ballot(pass);
-                        if (mask != 0ull) {                    // wave-uniform
-                            const int np = __popcll(mask);
-                            if (fcount + np > SG_FL_CAP) flush();
-                            if (pass) {
-                                const int slot = fcount + __popcll(mask & ((1ull << lane) - 1ull));
-                                fl_m[wave][slot] = m;
-                                fl_n[wave][slot] = n + flt.n_off;
-                                fl_v[wave][slot] = v;
-                            }
-                            fcount += np;
-                        }
-                    }
-                }
-            flush();
-        } else if (SG_NO_STORE || full) {
-            // interior tile: 64 unconditional stores per wave, then (its own instance: see tile_prologue) the next tile's first slab
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < SG_WJ; ++j) {
-                    float* cbase = C + (int64_t)(m0 + wm * 64 + i * 32 + 4 * h) * ldc + (n0 + wn * 32 * SG_WJ + j * 32 + r);
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        if (SG_NO_STORE) {                 // ablation: nothing leaves the CU, the accumulators stay live
-                            if (acc[i][j][reg] == 123456.789f) cbase[(int64_t)((reg & 3) + 8 * (reg >> 2)) * ldc] = acc[i][j][reg];
-                        } else {
-                            cbase[(int64_t)((reg & 3) + 8 * (reg >> 2)) * ldc] = acc[i][j][reg];
-                        }
-                    }
-                }
-            if (nid < n_ids) tile_prologue(ntm * SG_T, ntn * SG_TN);
+        const SgPos pos{m0, n0, M, N, wm, wn, lane, r, h, full};
+        if constexpr (EPI == SG_CSLS_COUNT) {
+            sg_epi_count<WJ>(acc, pos, ext);
+        } else if constexpr (EPI == SG_LSE) {
+            sg_epi_lse(acc, pos, ext);
+        } else if constexpr (EPI == SG_STATS) {
+            sg_epi_stats(acc, pos, ext);
+        } else if constexpr (LISTS) {
+            sg_epi_lists<EPI, WJ>(acc, pos, ext, fl_m[wave], fl_n[wave], fl_v[wave]);
+        } else if (full) {
+            sg_epi_store_interior<WJ>(acc, pos, C, ldc);
+            if (nid < n_ids) tile_prologue(ntm * SG_T, ntn * SG_TN);      // its own instance: see tile_prologue
             id = nid;
             tm = ntm;
             tn = ntn;
             continue;
         } else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < SG_WJ; ++j)
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        const int64_t m = m0 + wm * 64 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                        const int64_t n = n0 + wn * 32 * SG_WJ + j * 32 + r;
-                        if (m < M && n < N) C[m * ldc + n] = acc[i][j][reg];
-                    }
+            sg_epi_store_ragged<WJ>(acc, pos, C, ldc);
         }
         id = nid;
         tm = ntm;
@@ -1270,223 +1336,6 @@ __global__ __launch_bounds__(kBlock, SgTile<WJ>::OCC) void sim_gemm_kernel(const
         if (id < n_ids) tile_prologue(tm * SG_T, tn * SG_TN);     // (no wave reads LDS any more: see above)
     }
 }
-
-// ------------------------------------------------------------------------------------------------
-// The same product with the operand slabs DMA'd straight into LDS (global_load_lds_dwordx4), 32 k per slab (round 6 experiment,
-// JMAC_SG_GLDS).  What the ablation of the register-staged kernel above left on the table (profiles/r6_simgemm_ablation.txt):
-// its loads touch 16 half cache lines per wave instruction, every staged float4 costs a 13-cycle ds_write_b128 on the LDS data
-// path, and there is one barrier per 16 k.  Here one wave instruction fetches 8 FULL 128-byte lines (8 rows x 32 k) into 1 KB of
-// LDS, nothing is staged in registers, and there is one barrier per 32 k.
-//   LDS image of an operand slab: [128 rows][8 slots of 16 B]; slot = kq ^ ((row >> 1) & 7), kq = the float4 index inside the
-//   row's 32 k.  The LDS destination of a DMA is lane-linear (wave base + 16 lane), so the swizzle is applied to the SOURCE address
-//   (lane l of a DMA fetches row 8c + l/8, float4 kq = (l & 7) ^ ((row >> 1) & 7)) and again on the fragment read: a ds_read_b128
-//   lane group (16 rows of one parity pattern, MI355X_MICROARCH.md "LDS") then touches 64 distinct banks.
-//   Contraction order per output element: group g of 8 k, step s: k = {8g + s, 8g + 4 + s} -- the order of sim_gemm_kernel, so
-//   the results are bit-identical to it (and to cand_select_kernel's recomputation).
-//   Pipeline: the (tile, slab) sequence of a block is flat: while slab t is multiplied, slab t+1 -- of this tile or slab 0 of the
-//   block's next tile -- is in flight into the other buffer; one raw s_barrier per slab, behind a counted vmcnt wait (the C stores
-//   of a finished tile stay in flight across it: vmcnt completes in order, the DMAs were issued first).
-// ------------------------------------------------------------------------------------------------
-#ifndef JMAC_SG_GLDS
-#define JMAC_SG_GLDS 0              // 1: tools/r6_simgemm_ablation.sh variant "glds" (closed: 104 vs 103 TF/s of the kernel above)
-#endif
-#if JMAC_SG_GLDS
-constexpr int GL_K = 32;                       // k per slab
-constexpr int GL_OP = SG_T * GL_K;             // floats per operand slab (16 KB)
-__device__ __attribute__((aligned(16))) float sg_zero16[4] = {0.f, 0.f, 0.f, 0.f};      // source of the float4s past d
-
-typedef void __attribute__((address_space(3))) * gl_dst_t;
-// One LDS-DMA: lane l's 16 bytes at gsrc -> LDS byte address lds_dst + 16 l (lds_dst wave-uniform, in an SGPR).  Inline asm, so
-// the compiler neither counts it in its own s_waitcnt bookkeeping nor drains it (vmcnt(0)) before the next ds_read: the kernel
-// counts vmcnt by hand (cdna_hip_programming.md section 5, "Pipelining across barriers").  M0 is written and restored in the
-// same statement.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(uintptr_t)(gl_dst_t)(const_cast<void*>(p));
-}
-// s_waitcnt immediates (gfx9 encoding: vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8])
-constexpr int gl_waitcnt(int vm, int lgkm) { return (vm & 0xf) | ((vm >> 4) << 14) | (0x7 << 4) | ((lgkm & 0xf) << 8); }
-
-__global__ __launch_bounds__(kBlock, 2) void sim_gemm_glds_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
-                                                                int64_t ldb, int M, int N, int d, float* __restrict__ C, int64_t ldc,
-                                                                int tiles_m, int tiles_n, int super_order, int n_ids,
-                                                                const float* __restrict__ zero16) {
-    __shared__ __attribute__((aligned(1024))) float Ls[2][2][GL_OP];          // [buffer][A | B][row * 32 + slot * 4]: 64 KB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    auto tile_of = [&](int id, int& tm, int& tn) -> bool {
-        if (super_order) {
-            const int sup_n = (tiles_n + SG_SUPER - 1) / SG_SUPER, sup_m = (tiles_m + SG_SUPER - 1) / SG_SUPER;
-            const int per = SG_SUPER * SG_SUPER;
-            const int xcd = id & 7, local = id >> 3;
-            const int sup = (local / per) * 8 + xcd, within = local % per;
-            if (sup >= sup_m * sup_n) return false;
-            tm = (sup / sup_n) * SG_SUPER + within / SG_SUPER;
-            tn = (sup % sup_n) * SG_SUPER + within % SG_SUPER;
-            return tm < tiles_m && tn < tiles_n;
-        }
-        tm = id / tiles_n;
-        tn = id % tiles_n;
-        return true;
-    };
-    auto next_tile = [&](int id, int& tm, int& tn) -> int {
-        while (id < n_ids && !tile_of(id, tm, tn)) id += gridDim.x;
-        return id < n_ids ? id : n_ids;
-    };
-    // DMA side: instruction i of a wave fills rows 8 (4 i + wave) .. + 7 of the slab; the lane's row inside them and its float4
-    const int rr = lane >> 3;
-    const int kq_src = (lane & 7) ^ ((((wave & 1) << 2) | (rr >> 1)) & 7);   // ((row >> 1) & 7 with row = 32 i + 8 wave + rr)
-    const float* pa[4];
-    const float* pb[4];
-    auto set_rows = [&](int m0, int n0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = (4 * i + wave) * 8 + rr;
-            pa[i] = A + (int64_t)min(m0 + row, M - 1) * lda + 4 * kq_src;
-            pb[i] = Bm + (int64_t)min(n0 + row, N - 1) * ldb + 4 * kq_src;
-        }
-    };
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr(&Ls[0][0][0]) + wave * 8 * GL_K * 4);     // wave's first DMA target
-    auto issue = [&](int buf, int k0) {
-        // float4s past d (only in a row's last slab, d % 32 != 0) come from 16 zero bytes: an integer select on the ADDRESS
-        const uint64_t keep = k0 + 4 * kq_src < d ? ~0ull : 0ull, zero = (uint64_t)(uintptr_t)zero16 & ~keep;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint64_t sa = ((uint64_t)(uintptr_t)(pa[i] + k0) & keep) | zero;
-            const uint64_t sb = ((uint64_t)(uintptr_t)(pb[i] + k0) & keep) | zero;
-            const unsigned dst = lds0 + (unsigned)((buf * 2 * GL_OP + 4 * i * 8 * GL_K) * 4);
-            glds16(reinterpret_cast<const void*>(sa), dst);
-            glds16(reinterpret_cast<const void*>(sb), dst + GL_OP * 4);
-        }
-    };
-    // fragment side
-    const int r = lane & 31, h = lane >> 5;
-    const int sw = (r >> 1) & 7;
-    const int arow = (wm * 64 + r) * GL_K, brow = (wn * 64 + r) * GL_K;      // + 32 GL_K for the second 32-row sub-tile
-    auto frags = [&](int buf, int g, float4 (&af)[2], float4 (&bf)[2]) {
-        const int slot = (((2 * g + h) ^ sw) & 7) * 4;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            af[i] = *reinterpret_cast<const float4*>(&Ls[buf][0][arow + i * 32 * GL_K + slot]);
-            bf[i] = *reinterpret_cast<const float4*>(&Ls[buf][1][brow + i * 32 * GL_K + slot]);
-        }
-    };
-    f32x16 acc[2][2];
-    auto mfma16 = [&](const float4 (&af)[2], const float4 (&bf)[2]) {
-#define JMAC_GL_STEP(c)                                                                                   \
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0].c, bf[0].c, acc[0][0], 0, 0, 0);          \
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[0].c, bf[1].c, acc[0][1], 0, 0, 0);          \
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1].c, bf[0].c, acc[1][0], 0, 0, 0);          \
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[1].c, bf[1].c, acc[1][1], 0, 0, 0);
-        JMAC_GL_STEP(x)
-        JMAC_GL_STEP(y)
-        JMAC_GL_STEP(z)
-        JMAC_GL_STEP(w)
-#undef JMAC_GL_STEP
-    };
-    const int nk = (d + GL_K - 1) / GL_K;
-    int tm, tn;
-    int id = next_tile(blockIdx.x, tm, tn);
-    if (id >= n_ids) return;
-    set_rows(tm * SG_T, tn * SG_T);
-    issue(0, 0);
-    int buf = 0;
-    __builtin_amdgcn_s_waitcnt(gl_waitcnt(0, 0));
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    float4 af[2][2], bf[2][2];
-    while (id < n_ids) {
-        const int m0 = tm * SG_T, n0 = tn * SG_T;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-        int ntm = 0, ntn = 0;
-        const int nid = next_tile(id + gridDim.x, ntm, ntn);
-        // every slab but the tile's last: the tile's next slab goes into the other buffer (every wave has passed the barrier behind
-        // its last fragment read of that buffer), four groups of 8 k are multiplied with alternating fragment sets
-        for (int kt = 0; kt + 1 < nk; ++kt) {
-            issue(buf ^ 1, (kt + 1) * GL_K);
-            frags(buf, 0, af[0], bf[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            // group g's 16 MFMAs carry group g+1's four fragment reads between them (one read behind each of the first four)
-#define JMAC_GL_OVERLAP()                                                                  \
-            _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                             \
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                         \
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                         \
-            }                                                                              \
-            __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);                            \
-            __builtin_amdgcn_sched_barrier(0);
-            frags(buf, 1, af[1], bf[1]);
-            mfma16(af[0], bf[0]);
-            JMAC_GL_OVERLAP()
-            frags(buf, 2, af[0], bf[0]);
-            mfma16(af[1], bf[1]);
-            JMAC_GL_OVERLAP()
-            frags(buf, 3, af[1], bf[1]);
-            mfma16(af[0], bf[0]);
-            JMAC_GL_OVERLAP()
-#undef JMAC_GL_OVERLAP
-            mfma16(af[1], bf[1]);
-            __builtin_amdgcn_s_waitcnt(gl_waitcnt(0, 0));      // the wave's own DMAs of the next slab have landed
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");                     // no fragment read of the next slab moves above the barrier
-            buf ^= 1;
-        }
-        // the last slab (d % 32 != 0: fewer groups): slab 0 of the block's NEXT tile is requested first
-        if (nid < n_ids) {
-            set_rows(ntm * SG_T, ntn * SG_T);
-            issue(buf ^ 1, 0);
-        }
-        {
-            const int ng = (d - (nk - 1) * GL_K + 7) >> 3;
-            frags(buf, 0, af[0], bf[0]);
-            for (int g = 0; g < ng; ++g) {
-                mfma16(af[0], bf[0]);
-                if (g + 1 < ng) frags(buf, g + 1, af[0], bf[0]);
-            }
-        }
-        {
-            // C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-            const bool full = m0 + SG_T <= M && n0 + SG_T <= N;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float* cbase = C + (int64_t)(m0 + wm * 64 + i * 32 + 4 * h) * ldc + (n0 + wn * 64 + j * 32 + r);
-                    if (full) {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) cbase[(int64_t)((reg & 3) + 8 * (reg >> 2)) * ldc] = acc[i][j][reg];
-                    } else {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) {
-                            const int64_t m = m0 + wm * 64 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                            const int64_t n = n0 + wn * 64 + j * 32 + r;
-                            if (m < M && n < N) C[m * ldc + n] = acc[i][j][reg];
-                        }
-                    }
-                }
-        }
-        // the 8 DMAs of the next tile's first slab were issued before the (up to 64) stores: vmcnt retires in order
-        __builtin_amdgcn_s_waitcnt(gl_waitcnt(63, 0));
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        buf ^= 1;
-        id = nid;
-        tm = ntm;
-        tn = ntn;
-    }
-}
-
-#endif  // JMAC_SG_GLDS
 
 // ------------------------------------------------------------------------------------------------
 // row top-k: one block per row.  Order: value descending, ties -> lower index first.
@@ -2249,14 +2098,14 @@ struct SimGeom {
 
 // persistent grids: as many blocks as are resident at once (occupancy query: 3 per CU for the 128 x 128 tile -- 64 accumulation
 // VGPRs, 33 KB of LDS -- and 2 for 128 x 256), rounded down to a multiple of 8 so that a block's tile ids stay on its XCD
-template <bool FILTER, int WJ, bool STATS = false, int CSLS = 0>
+template <int EPI, int WJ>
 int sim_resident(int dev) {
     static int resident_of[64] = {0};                                     // per device: CU counts may differ between devices
     int& resident = resident_of[dev >= 0 && dev < 64 ? dev : 0];
     if (resident == 0 || dev >= 64) {
         int cus = 256, occ = SgTile<WJ>::OCC;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(sim_gemm_kernel<FILTER, WJ, STATS, CSLS>), kBlock, 0) != hipSuccess || occ < 1)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(sim_gemm_kernel<EPI, WJ>), kBlock, 0) != hipSuccess || occ < 1)
             occ = SgTile<WJ>::OCC;
         resident = (cus * occ) / 8 * 8;
         if (resident < 8) resident = 8;
@@ -2264,91 +2113,40 @@ int sim_resident(int dev) {
     return resident;
 }
 
-#if defined(JMAC_SG_FORCE_WJ)
-constexpr int SG_FORCE_WJ = JMAC_SG_FORCE_WJ;                             // ablation builds: the tile of the plain and the filter product
-#else
-constexpr int SG_FORCE_WJ = 0;
-#endif
-
-// one launch of the product with tile width WJ and the epilogue <FILTER, STATS, CSLS>; ext = that epilogue's arguments
-template <bool FILTER, int WJ, bool STATS, int CSLS>
+// one launch of the product with the epilogue EPI and tile width WJ; ext = that epilogue's arguments
+template <int EPI, int WJ>
 int launch_sim_tile(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
-                    hipStream_t st, const typename SgExt<STATS, CSLS>::type& ext, int dev) {
+                    const typename SgEpiTraits<EPI>::Ext& ext, hipStream_t st, int dev) {
     const SimGeom<WJ> g(M, N);
     if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
-    const int resident = sim_resident<FILTER, WJ, STATS, CSLS>(dev);
+    const int resident = sim_resident<EPI, WJ>(dev);
     const unsigned grid = (unsigned)(g.n_ids < resident ? g.n_ids : resident);
-    hipLaunchKernelGGL((sim_gemm_kernel<FILTER, WJ, STATS, CSLS>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d,
-                       C, ldc, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, ext);
+    hipLaunchKernelGGL((sim_gemm_kernel<EPI, WJ>), dim3(grid), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M, (int)N, (int)d, C, ldc,
+                       g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, ext);
     return (int)hipGetLastError();
 }
 
-// THE launcher of the similarity product, whatever the epilogue.  The statistics epilogue always runs on the 128 x 128 tile (one
-// partial layout: a part is 64 rows or 64 columns).  The others choose.  Which tile?  Both give the same bits.  A round of resident
+// THE launcher of the similarity product, whatever the epilogue (C, ldc: SG_STORE only).  An epilogue that has no wide tile
+// (SgEpiTraits<EPI>::WIDE) runs on the 128 x 128 one.  The others choose.  Which tile?  Both give the same bits.  A round of resident
 // blocks is (resident blocks) x (tile area) of matrix-pipe work, and the wide tile does a given amount of it ~3.5 % faster (fewer
 // barriers and operand bytes per flop) -- but its rounds are coarser.  Take it when its quantised makespan, rounds x resident x
 // area, is no larger than the narrow tile's (measured, config-5 shapes: 12 000^2 and 3 000 x 30 000 tie on that count and gain
 // 3.4 / 3.5 %; 10 500^2 needs 7 168 against 6 912 units and loses 4 %).
-template <bool FILTER, bool STATS = false, int CSLS = 0>
-int launch_sim_epi(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
-                   hipStream_t st, const typename SgExt<STATS, CSLS>::type& ext) {
+template <int EPI>
+int launch_sim(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
+               const typename SgEpiTraits<EPI>::Ext& ext, hipStream_t st) {
     if (M == 0 || N == 0) return 0;
     if (d % 4) return JMAC_EDIM;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if constexpr (!STATS && CSLS != SG_LSE) {
-        bool wide = SG_FORCE_WJ == 4;
-        if (CSLS != 0 || SG_FORCE_WJ == 0) {
-            const SimGeom<2> g2(M, N);
-            const SimGeom<4> g4(M, N);
-            const int64_t r2 = sim_resident<FILTER, 2, STATS, CSLS>(dev), r4 = sim_resident<FILTER, 4, STATS, CSLS>(dev);
-            const int64_t cost2 = (g2.tiles + r2 - 1) / r2 * r2, cost4 = (g4.tiles + r4 - 1) / r4 * r4 * 2;
-            wide = g4.tiles >= r4 && cost4 <= cost2;
-        }
-        if (wide) return launch_sim_tile<FILTER, 4, STATS, CSLS>(A, lda, B, ldb, M, N, d, C, ldc, st, ext, dev);
+    if constexpr (SgEpiTraits<EPI>::WIDE) {
+        const SimGeom<2> g2(M, N);
+        const SimGeom<4> g4(M, N);
+        const int64_t r2 = sim_resident<EPI, 2>(dev), r4 = sim_resident<EPI, 4>(dev);
+        const int64_t cost2 = (g2.tiles + r2 - 1) / r2 * r2, cost4 = (g4.tiles + r4 - 1) / r4 * r4 * 2;
+        if (g4.tiles >= r4 && cost4 <= cost2) return launch_sim_tile<EPI, 4>(A, lda, B, ldb, M, N, d, C, ldc, ext, st, dev);
     }
-    return launch_sim_tile<FILTER, 2, STATS, CSLS>(A, lda, B, ldb, M, N, d, C, ldc, st, ext, dev);
-}
-
-// the stored product (flt == nullptr) or the filter epilogue
-int launch_sim(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, float* C, int64_t ldc,
-               hipStream_t st, const SimFilter* flt = nullptr) {
-#if JMAC_SG_GLDS
-    if (!flt && M != 0 && N != 0 && d % 4 == 0) {                         // closed experiment: the LDS-DMA form of the plain product
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const SimGeom<2> g(M, N);
-        if (g.n_ids >= INT32_MAX) return JMAC_ERANGE;
-        static const float* zero_of[64] = {nullptr};
-        const float*& zero16 = zero_of[dev >= 0 && dev < 64 ? dev : 0];
-        if (zero16 == nullptr || dev >= 64) {
-            void* p = nullptr;
-            if (hipGetSymbolAddress(&p, HIP_SYMBOL(sg_zero16)) != hipSuccess) return (int)hipGetLastError();
-            zero16 = static_cast<const float*>(p);
-        }
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const int res2 = (cus * 2) / 8 * 8;
-        hipLaunchKernelGGL(sim_gemm_glds_kernel, dim3((unsigned)(g.n_ids < res2 ? g.n_ids : res2)), dim3(kBlock), 0, st, A, lda, B, ldb, (int)M,
-                           (int)N, (int)d, C, ldc, g.tiles_m, g.tiles_n, g.super_order, (int)g.n_ids, zero16);
-        return (int)hipGetLastError();
-    }
-#endif
-    return flt ? launch_sim_epi<true>(A, lda, B, ldb, M, N, d, C, ldc, st, *flt) : launch_sim_epi<false>(A, lda, B, ldb, M, N, d, C, ldc, st, SimFilter{});
-}
-int launch_sim_stats(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimStats& sx,
-                     hipStream_t st) {
-    return launch_sim_epi<false, true>(A, lda, B, ldb, M, N, d, nullptr, 0, st, sx);
-}
-template <int CSLS>
-int launch_sim_csls(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimCsls& cx,
-                    hipStream_t st) {
-    return launch_sim_epi<CSLS == SG_CSLS_FILTER, false, CSLS>(A, lda, B, ldb, M, N, d, nullptr, 0, st, cx);
-}
-
-int launch_sim_lse(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t d, const SimLse& lx,
-                   hipStream_t st) {
-    return launch_sim_epi<false, false, SG_LSE>(A, lda, B, ldb, M, N, d, nullptr, 0, st, lx);
+    return launch_sim_tile<EPI, 2>(A, lda, B, ldb, M, N, d, C, ldc, ext, st, dev);
 }
 
 // 64 rows (blocks [0, row_blocks)) or 64 columns (the blocks behind them) per block.  Wave g combines the g-th quarter of a
@@ -2642,7 +2440,7 @@ int jmac_sim_matrix_f32(const float* A, int64_t lda, const float* B, int64_t ldb
     if (!A || !B || !C) return JMAC_EINVAL;
     if (lda % 4 || ldb % 4) return JMAC_EDIM;
     if (M >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
-    return launch_sim(A, lda, B, ldb, M, N, d, C, ldc, (hipStream_t)stream);
+    return launch_sim<SG_STORE>(A, lda, B, ldb, M, N, d, C, ldc, SimStore{}, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -2715,7 +2513,7 @@ static int sim_topk_impl(const float* A, int64_t lda, const float* B, int64_t ld
     const dim3 rows((unsigned)L), block(kBlock);
     return topk_drive(L, N, k, val, idx, (char*)ws, N, st,
         [&](float* S, int64_t ldS, int64_t n) -> int {       // the product of A with B's first n rows
-            if (int rc = launch_sim(A, lda, B, ldb, L, n, d, S, ldS, st)) return rc;
+            if (int rc = launch_sim<SG_STORE>(A, lda, B, ldb, L, n, d, S, ldS, SimStore{}, st)) return rc;
             if (best) hipLaunchKernelGGL(viable_inplace_kernel, rows, block, 0, st, S, ldS, (int)n, r1, r2, row_id, best);
             else if (r1) hipLaunchKernelGGL(csls_inplace_kernel, rows, block, 0, st, S, ldS, (int)n, r1, r2);
             return 0;
@@ -2724,9 +2522,9 @@ static int sim_topk_impl(const float* A, int64_t lda, const float* B, int64_t ld
             SimViable cx{};
             cx.f = f; cx.r1 = r1; cx.r2 = r2; cx.row_id = row_id; cx.best = best;
             const float* Br = B + f.n_off * ldb;
-            return best ? launch_sim_epi<true, false, SG_CSLS_VIABLE>(A, lda, Br, ldb, L, N - f.n_off, d, nullptr, 0, st, cx)
-                   : r1 ? launch_sim_csls<SG_CSLS_FILTER>(A, lda, Br, ldb, L, N - f.n_off, d, cx, st)
-                        : launch_sim(A, lda, Br, ldb, L, N - f.n_off, d, nullptr, 0, st, &f);
+            return best ? launch_sim<SG_CSLS_VIABLE>(A, lda, Br, ldb, L, N - f.n_off, d, nullptr, 0, cx, st)
+                   : r1 ? launch_sim<SG_CSLS_FILTER>(A, lda, Br, ldb, L, N - f.n_off, d, nullptr, 0, cx, st)
+                        : launch_sim<SG_FILTER>(A, lda, Br, ldb, L, N - f.n_off, d, nullptr, 0, f, st);
         },
         [&](const SimFilter& f, const float* val0, const int32_t* idx0) {      // an overflowing row recomputes (and rescores)
             if (best)
@@ -2872,7 +2670,7 @@ int jmac_softmax_entropy_f32(const float* A, int64_t lda, const float* B, int64_
     // softmax(simi.t()) of train.py:245 reads the transpose of the same matrix, not a second product)
     float* S = (float*)ws;
     const size_t soff = align_up((size_t)n1 * (size_t)n2 * 4);
-    if (int rc = launch_sim(A, lda, B, ldb, n1, n2, d, S, n2, st)) return rc;
+    if (int rc = launch_sim<SG_STORE>(A, lda, B, ldb, n1, n2, d, S, n2, SimStore{}, st)) return rc;
     hipLaunchKernelGGL(row_entropy_kernel, dim3((unsigned)n1), dim3(kBlock), 0, st, S, n2, (int)n2, scale, ent_rows);
     return jmac_col_softmax_f32(S, n2, n1, n2, nullptr, nullptr, 0.f, scale, nullptr, 0, ent_cols, (char*)ws + soff,
                                 ws_bytes - soff, stream);
@@ -2900,7 +2698,7 @@ int jmac_sim_softmax_stats_f32(const float* A, int64_t lda, const float* B, int6
     sx.cpart = want_cols ? (float*)((char*)ws + w.cpart) : nullptr;
     sx.cbest = (float2*)((char*)ws + w.cbest);
     sx.scale = scale;
-    if (int rc = launch_sim_stats(A, lda, B, ldb, n1, n2, d, sx, st)) return rc;
+    if (int rc = launch_sim<SG_STATS>(A, lda, B, ldb, n1, n2, d, nullptr, 0, sx, st)) return rc;
     const int rb = want_rows ? (int)((n1 + 63) / 64) : 0, cb = want_cols ? (int)((n2 + 63) / 64) : 0;
     hipLaunchKernelGGL(sim_stats_merge_kernel, dim3((unsigned)(rb + cb)), dim3(kBlock), 0, st, sx.rpart, sx.cpart, sx.cbest, (int)n1,
                        (int)n2, scale, rb, row_max, row_arg, row_sum, row_ent, col_max, col_arg, col_sum, col_ent);
@@ -2929,7 +2727,7 @@ int jmac_sim_lse_f32(const float* A, int64_t lda, const float* B, int64_t ldb, i
     lx.col_add = col_add;
     lx.row_add = row_add;
     lx.scale = scale;
-    if (int rc = launch_sim_lse(A, lda, B, ldb, n1, n2, d, lx, st)) return rc;
+    if (int rc = launch_sim<SG_LSE>(A, lda, B, ldb, n1, n2, d, nullptr, 0, lx, st)) return rc;
     const int rb = row_out ? (int)((n1 + 63) / 64) : 0, cb = col_out ? (int)((n2 + 63) / 64) : 0;
     hipLaunchKernelGGL(sim_lse_merge_kernel, dim3((unsigned)(rb + cb)), dim3(kBlock), 0, st, lx.rpart, lx.cpart, (int)n1, (int)n2, rb,
                        row_shift, col_shift, row_out, col_out);
@@ -3127,7 +2925,7 @@ static int csls_rank_entry(AlignMetric metric, const float* A, int64_t lda, cons
         cx.r1 = r1; cx.r2 = r2; cx.gval = (float*)ws; cx.gold = gold; cx.rank = rank;
         hipLaunchKernelGGL(csls_gold_kernel, dim3((unsigned)((n1 + 32 * (kBlock / 64) - 1) / (32 * (kBlock / 64)))), dim3(kBlock), 0, st, A, lda,
                            B, ldb, (int)n1, (int)d, r1, r2, gold, (float*)ws, rank);
-        return launch_sim_csls<SG_CSLS_COUNT>(A, lda, B, ldb, n1, n2, d, cx, st);
+        return launch_sim<SG_CSLS_COUNT>(A, lda, B, ldb, n1, n2, d, nullptr, 0, cx, st);
     }
     LinkRankArgs a{};
     const bool vec = l1_align_args(a, A, lda, B, ldb, n1, n2, d, r1, r2);

@@ -119,11 +119,28 @@ def test_product_never_imports_oracle():
 
 def test_native_sources_read_no_environment():
     """What a launcher picks depends on its arguments alone: no source of the library reads the process environment.  (A
-    source scan: the library's undefined symbols list getenv whatever the project's code does, through the rocprim headers.)"""
+    source scan: the library's undefined symbols list getenv whatever the project's code does, through the rocprim headers.)
+    Nor does a build flag: the only preprocessor conditionals are a header's include guard (#ifndef X directly followed by
+    #define X) and the testing library's JMAC_TESTING_BUILD."""
     csrc = os.path.join(os.path.dirname(os.path.abspath(jmac_amd.__file__)), "csrc")
     srcs = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
     assert len(srcs) >= 10 and "aggregate.hip" in srcs
     assert [f for f in srcs if "getenv" in open(os.path.join(csrc, f)).read()] == []
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b(.*)$")
+    found = []
+    for f in srcs:
+        lines = open(os.path.join(csrc, f)).read().split("\n")
+        for i, line in enumerate(lines):
+            m = cond.match(line)
+            if not m:
+                continue
+            rest = m.group(2).split("//")[0].strip()
+            if rest in ("JMAC_TESTING_BUILD", "defined(JMAC_TESTING_BUILD)", "!defined(JMAC_TESTING_BUILD)"):
+                continue
+            guard = f.endswith(".h") and m.group(1) == "ifndef" and i + 1 < len(lines) and re.match(r"^\s*#\s*define\s+%s\s*$" % re.escape(rest), lines[i + 1])
+            if not guard:
+                found.append("%s:%d: %s" % (f, i + 1, line.strip()))
+    assert found == []
 
 
 def test_state_dict_keys_match_reference():
