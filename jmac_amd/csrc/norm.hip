@@ -6,6 +6,7 @@
 // column (single pass, no catastrophic cancellation), reduced deterministically: per-block partial
 // rows -> one finalising block.  No atomics.
 #include <initializer_list>
+#include <type_traits>
 
 #include "common.h"
 
@@ -16,12 +17,69 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kStatBlocks = 512;
 
-// partial[b][0][c] = sum_r (x[r][c]-K[c]),  partial[b][1][c] = sum_r (x[r][c]-K[c])^2, K = x[0][:]
-// rows are dealt to blocks round-robin in groups of RPB = kBlock / D4 rows.
-__global__ __launch_bounds__(kBlock) void col_stats_partial_kernel(const float* __restrict__ x, int64_t ldx, int64_t N,
-                                                                   int D4, float* __restrict__ partial) {
+// ---- plain and segmented forms.  Segmented: the rows are a stack of `nb` blocks (KGs of one launch set: the reference's training
+// ---- step encodes two KGs per batch, src/jmac_model.py:325-326,263-264, each forward_base call with batch statistics of ITS rows).
+// Every block has its own batch statistics (mean / invstd [nb, d]); weight, bias and the running estimates are the layer's
+// (shared), and the running estimates are updated once per block in the callers' CALL order (seg.order), exactly what nb
+// separate forward_base calls leave behind:  r <- (1-m)((1-m) r + m b_1) + m b_2 ...
+// The plain form is the one-block case; every kernel below is one body for both, and the plain instantiation sees the constants
+// (block 0, first row 0) that make the block arithmetic vanish.
+constexpr int kMaxSeg = JMAC_BN_MAX_BLOCKS;
+struct SegTab {
+    int nb;
+    int order[kMaxSeg];        // block processed k-th by the running-statistics update
+    int gofs[kMaxSeg + 1];     // first statistics workgroup (= partial row) of each block
+    int64_t ptr[kMaxSeg + 1];  // first row of each block; ptr[nb] = rows in all
+};
+template <bool SEG> using BnRows = std::conditional_t<SEG, SegTab, int64_t>;   // the plain kernels take the row count alone
+
+__device__ __forceinline__ int seg_of_row(const SegTab& s, int64_t r) {
+    int b = 0;
+    for (int k = 1; k < s.nb; ++k) b += r >= s.ptr[k] ? 1 : 0;
+    return b;
+}
+__device__ __forceinline__ int seg_of_group(const SegTab& s, int wg) {
+    int b = 0;
+    for (int k = 1; k < s.nb; ++k) b += wg >= s.gofs[k] ? 1 : 0;
+    return b;
+}
+
+// one block as the statistics passes see it: its rows [r0, r1) and its statistics workgroups = partial rows [p0, p1)
+struct StatBlock {
+    int b;
+    int64_t r0, r1;
+    int p0, p1;
+};
+__device__ __forceinline__ StatBlock stat_block(const SegTab& s, int b) { return {b, s.ptr[b], s.ptr[b + 1], s.gofs[b], s.gofs[b + 1]}; }
+// the block this workgroup of a partial pass works on
+__device__ __forceinline__ StatBlock own_block(int64_t N) { return {0, 0, N, 0, (int)gridDim.x}; }
+__device__ __forceinline__ StatBlock own_block(const SegTab& s) { return stat_block(s, seg_of_group(s, (int)blockIdx.x)); }
+
+// ---- column sums: partial[wg][0][c], partial[wg][1][c] = two sums over the rows dealt to workgroup wg ------------------------
+// The slots' sums, which the caller has put into red [2][rpb][D4], added in slot order -> this workgroup's two partial rows.
+__device__ __forceinline__ void col_sums_fold(const float4* red, int rpb, int D4, float* __restrict__ partial) {
+    __syncthreads();
+    const int tid = threadIdx.x;
+    if (tid < D4) {
+        float4 a1 = red[tid], a2 = red[rpb * D4 + tid];
+        for (int q = 1; q < rpb; ++q) {
+            const float4 b1 = red[q * D4 + tid], b2 = red[(rpb + q) * D4 + tid];
+            a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
+            a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
+        }
+        st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + tid * 4, a1);
+        st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + tid * 4, a2);
+    }
+}
+
+// One workgroup's share of a column-sum pass over block `blk`: the block's rows are dealt to its workgroups round-robin in groups
+// of rpb = kBlock / D4 rows, one row slot per group member; a slot sums its rows in row order (acc.row), the slots are added in
+// slot order.  acc.column(c4, r0) gives what a slot keeps per column quad.  stat_smem(D4) bytes of LDS.
+template <class Acc>
+__device__ __forceinline__ void col_sums_block(const Acc& acc, const StatBlock& blk, int D4, float* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4* red = reinterpret_cast<float4*>(smem);   // [2][rpb][D4]
+    const int lb = (int)blockIdx.x - blk.p0, gb = blk.p1 - blk.p0;
     const int rpb = kBlock / D4 > 0 ? kBlock / D4 : 1;
     const int tid = threadIdx.x;
     // when D4 > kBlock a thread covers several column chunks
@@ -31,13 +89,8 @@ __global__ __launch_bounds__(kBlock) void col_stats_partial_kernel(const float* 
         const bool active = (D4 >= kBlock ? c4 < D4 : tid < rpb * D4);
         float4 s1 = f4zero(), s2 = f4zero();
         if (active) {
-            const float4 K = ld4(x + c4 * 4);
-            for (int64_t r = (int64_t)blockIdx.x * rpb + rsub; r < N; r += (int64_t)gridDim.x * rpb) {
-                float4 v = ld4(x + r * ldx + c4 * 4);
-                v.x -= K.x; v.y -= K.y; v.z -= K.z; v.w -= K.w;
-                s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
-                s2.x = fmaf(v.x, v.x, s2.x); s2.y = fmaf(v.y, v.y, s2.y); s2.z = fmaf(v.z, v.z, s2.z); s2.w = fmaf(v.w, v.w, s2.w);
-            }
+            const auto col = acc.column(c4, blk.r0);
+            for (int64_t r = blk.r0 + (int64_t)lb * rpb + rsub; r < blk.r1; r += (int64_t)gb * rpb) acc.row(col, r, c4, s1, s2);
         }
         if (D4 >= kBlock) {
             if (active) {
@@ -49,92 +102,165 @@ __global__ __launch_bounds__(kBlock) void col_stats_partial_kernel(const float* 
                 red[(0 * rpb + rsub) * D4 + c4] = s1;
                 red[(1 * rpb + rsub) * D4 + c4] = s2;
             }
-            __syncthreads();
-            if (tid < D4) {
-                float4 a1 = red[tid], a2 = red[rpb * D4 + tid];
-                for (int q = 1; q < rpb; ++q) {
-                    float4 b1 = red[q * D4 + tid], b2 = red[(rpb + q) * D4 + tid];
-                    a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
-                    a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
-                }
-                st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + tid * 4, a1);
-                st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + tid * 4, a2);
-            }
+            col_sums_fold(red, rpb, D4, partial);
             break;
         }
     }
 }
 
-// sums[0][c], sums[1][c] = reduced partials
-__global__ void bn_finalize_kernel(const float* __restrict__ sums, const float* __restrict__ x, int64_t N,
-                                   int d, float eps, float momentum, float* __restrict__ running_mean,
-                                   float* __restrict__ running_var, float* __restrict__ save_mean,
-                                   float* __restrict__ save_invstd) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= d) return;
-    const float s1 = sums[c], s2 = sums[d + c];
-    const float n = (float)N;
-    const float K = x[c];
-    const float mshift = s1 / n;
-    const float mean = K + mshift;
-    float var = s2 / n - mshift * mshift;
-    var = var > 0.f ? var : 0.f;
-    save_mean[c] = mean;
-    save_invstd[c] = rsqrtf(var + eps);
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-    if (running_var) {
-        const float unbiased = N > 1 ? var * n / (n - 1.f) : var;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+// shifted statistics: s1 = sum_r (x[r][c]-K[c]),  s2 = sum_r (x[r][c]-K[c])^2,  K = the block's first row
+struct ShiftedStatsAcc {
+    const float* x;
+    int64_t ldx;
+    __device__ __forceinline__ float4 column(int c4, int64_t r0) const { return ld4(x + r0 * ldx + c4 * 4); }
+    __device__ __forceinline__ void row(const float4& K, int64_t r, int c4, float4& s1, float4& s2) const {
+        float4 v = ld4(x + r * ldx + c4 * 4);
+        v.x -= K.x; v.y -= K.y; v.z -= K.z; v.w -= K.w;
+        s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
+        s2.x = fmaf(v.x, v.x, s2.x); s2.y = fmaf(v.y, v.y, s2.y); s2.z = fmaf(v.z, v.z, s2.z); s2.w = fmaf(v.w, v.w, s2.w);
     }
+};
+template <bool SEG>
+__global__ __launch_bounds__(kBlock) void col_stats_partial_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                   BnRows<SEG> rows, int D4,
+                                                                   float* __restrict__ partial) {
+    col_sums_block(ShiftedStatsAcc{x, ldx}, own_block(rows), D4, partial);
 }
 
-// reduce_rows over the [nparts, 2d] partial sums and bn_finalize in one launch: a block owns 16 features and sums both
-// their s1 and s2 columns (64 row lanes each), then finalises them
+// One element of the BatchNorm + tanh backward (gz = g (1 - y^2), xhat = (x - mean) invstd) with its contractions spelt out.  Every
+// backward kernel -- plain, segmented, and fused with the normalise adjoint -- calls these two, so their launches agree bit for bit
+// because they share this text; in particular both passes form gz the same way, so that a one-row batch gets the exact zero it must.
+// FUSED_GZ, the segmented apply alone: gz is fused into the subtraction, fma(1 - y^2, g, -u), where the other kernels round gz first.
+// A one-row block of that form therefore gets the rounding residue of gz instead of the zero.  Each form keeps its rounding: making
+// them agree changes the results of one of them (profiles/bn_one_body.txt).
+__device__ __forceinline__ void bn_bwd_sums_elem(float g, float y, float x, float mu, float is, float& s1, float& s2) {
+#pragma clang fp contract(off)
+    const float om = fmaf(-y, y, 1.f), gz = om * g;
+    s1 = fmaf(om, g, s1);
+    s2 = fmaf(gz, (x - mu) * is, s2);
+}
+template <bool FUSED_GZ = false>
+__device__ __forceinline__ float bn_bwd_apply_elem(float g, float y, float x, float mu, float is, float w, float gw, float gb,
+                                                   int training, float invn) {
+#pragma clang fp contract(off)
+    const float om = fmaf(-y, y, 1.f), gz = om * g;
+    if (!training) return w * is * gz;
+    const float u = invn * fmaf((x - mu) * is, gw, gb);
+    return w * is * (FUSED_GZ ? fmaf(om, g, -u) : gz - u);
+}
+
+// backward column sums: s1 = sum gz, s2 = sum gz * xhat, gz = gy*(1-y^2); mean / invstd are the block's
+struct BnBwdSumsAcc {
+    const float *x, *y, *gy, *gy2;
+    int64_t ldx, ldy, ldgy, ldgy2;
+    const float *mean, *invstd;
+    struct Col {
+        float4 mu, is;
+    };
+    __device__ __forceinline__ Col column(int c4, int64_t) const { return {ld4(mean + c4 * 4), ld4(invstd + c4 * 4)}; }
+    __device__ __forceinline__ void row(const Col& k, int64_t r, int c4, float4& s1, float4& s2) const {
+        const float4 xv = ld4(x + r * ldx + c4 * 4), yv = ld4(y + r * ldy + c4 * 4);
+        float4 g = ld4(gy + r * ldgy + c4 * 4);
+        if (gy2) {                              // the output fed two consumers: their gradients are summed here
+            const float4 g2 = ld4(gy2 + r * ldgy2 + c4 * 4);
+            g.x += g2.x; g.y += g2.y; g.z += g2.z; g.w += g2.w;
+        }
+        bn_bwd_sums_elem(g.x, yv.x, xv.x, k.mu.x, k.is.x, s1.x, s2.x);
+        bn_bwd_sums_elem(g.y, yv.y, xv.y, k.mu.y, k.is.y, s1.y, s2.y);
+        bn_bwd_sums_elem(g.z, yv.z, xv.z, k.mu.z, k.is.z, s1.z, s2.z);
+        bn_bwd_sums_elem(g.w, yv.w, xv.w, k.mu.w, k.is.w, s1.w, s2.w);
+    }
+};
+template <bool SEG>
+__global__ __launch_bounds__(kBlock) void bn_bwd_partial_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                const float* __restrict__ y, int64_t ldy,
+                                                                const float* __restrict__ gy, int64_t ldgy,
+                                                                const float* __restrict__ gy2, int64_t ldgy2,
+                                                                BnRows<SEG> rows, int D4,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                float* __restrict__ partial) {
+    const StatBlock blk = own_block(rows);
+    const int64_t so = (int64_t)blk.b * D4 * 4;
+    col_sums_block(BnBwdSumsAcc{x, y, gy, gy2, ldx, ldy, ldgy, ldgy2, mean + so, invstd + so}, blk, D4, partial);
+}
+
+// ---- forward ----------------------------------------------------------------------------------------------------------------
+// reduce_rows over the partial sums and the finalize in one launch: a workgroup owns 16 features; block after block in CALL order
+// it sums both their s1 and s2 columns over the block's partial rows (64 row lanes each) and finalises the block's statistics,
+// carrying the running estimates of its features through the blocks in registers.  `nparts`: the plain form's partial rows
 constexpr int RF_COLS = 16, RF_LANES = 1024 / RF_COLS;
-__global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const float* __restrict__ partial, int nparts,
-                                                                  const float* __restrict__ x, int64_t N, int d, float eps,
+// One feature's statistics of one block from its shifted sums (K = the feature in the block's first row), and the step of the running
+// estimates r <- (1-m) r + m b, with every contraction spelt out so that both instantiations and every compiler round alike.
+// The running step alone differs between the forms: the plain form rounds both products, the segmented form fuses the first.  Each
+// form keeps its rounding: making them agree changes the results of one of them (profiles/bn_one_body.txt).
+template <bool SEG>
+__device__ __forceinline__ void bn_finalize_elem(float s1, float s2, float K, int64_t nrow, float eps, float m, float& mean,
+                                                 float& invstd, float& rm, float& rv) {
+#pragma clang fp contract(off)
+    const float n = (float)nrow;
+    const float mshift = s1 / n;
+    mean = K + mshift;
+    float var = fmaf(-mshift, mshift, s2 / n);
+    var = var > 0.f ? var : 0.f;
+    invstd = rsqrtf(var + eps);
+    const float unbiased = nrow > 1 ? var * n / (n - 1.f) : var;
+    rm = SEG ? fmaf(1.f - m, rm, m * mean) : (1.f - m) * rm + m * mean;
+    rv = SEG ? fmaf(1.f - m, rv, m * unbiased) : (1.f - m) * rv + m * unbiased;
+}
+template <bool SEG>
+__global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const float* __restrict__ partial, BnRows<SEG> rows,
+                                                                  int nparts, const float* __restrict__ x, int64_t ldx, int d, float eps,
                                                                   float momentum, float* __restrict__ running_mean,
                                                                   float* __restrict__ running_var, float* __restrict__ save_mean,
                                                                   float* __restrict__ save_invstd) {
     __shared__ float red1[RF_LANES][RF_COLS], red2[RF_LANES][RF_COLS];
     const int cl = threadIdx.x % RF_COLS, rl = threadIdx.x / RF_COLS;
     const int c = blockIdx.x * RF_COLS + cl;
-    float a1 = 0.f, a2 = 0.f, b1 = 0.f, b2 = 0.f;
-    if (c < d) {
-        int p = rl;
-        for (; p + RF_LANES < nparts; p += 2 * RF_LANES) {
-            a1 += partial[(int64_t)p * 2 * d + c];
-            a2 += partial[(int64_t)p * 2 * d + d + c];
-            b1 += partial[(int64_t)(p + RF_LANES) * 2 * d + c];
-            b2 += partial[(int64_t)(p + RF_LANES) * 2 * d + d + c];
-        }
-        if (p < nparts) {
-            a1 += partial[(int64_t)p * 2 * d + c];
-            a2 += partial[(int64_t)p * 2 * d + d + c];
-        }
-    }
-    red1[rl][cl] = a1 + b1;
-    red2[rl][cl] = a2 + b2;
-    __syncthreads();
+    float rm = 0.f, rv = 0.f;
     if (rl == 0 && c < d) {
-        float s1 = red1[0][cl], s2 = red2[0][cl];
+        if (running_mean) rm = running_mean[c];
+        if (running_var) rv = running_var[c];
+    }
+    int nb = 1;
+    if constexpr (SEG) nb = rows.nb;
+    for (int k = 0; k < nb; ++k) {
+        StatBlock blk;
+        if constexpr (SEG) blk = stat_block(rows, rows.order[k]);
+        else blk = {0, 0, rows, 0, nparts};                     // the one block: all N rows, all `nparts` partial rows
+        float a1 = 0.f, a2 = 0.f, b1 = 0.f, b2 = 0.f;
+        if (c < d) {
+            int p = blk.p0 + rl;
+            for (; p + RF_LANES < blk.p1; p += 2 * RF_LANES) {
+                a1 += partial[(int64_t)p * 2 * d + c];
+                a2 += partial[(int64_t)p * 2 * d + d + c];
+                b1 += partial[(int64_t)(p + RF_LANES) * 2 * d + c];
+                b2 += partial[(int64_t)(p + RF_LANES) * 2 * d + d + c];
+            }
+            if (p < blk.p1) {
+                a1 += partial[(int64_t)p * 2 * d + c];
+                a2 += partial[(int64_t)p * 2 * d + d + c];
+            }
+        }
+        red1[rl][cl] = a1 + b1;
+        red2[rl][cl] = a2 + b2;
+        __syncthreads();
+        if (rl == 0 && c < d) {
+            float s1 = red1[0][cl], s2 = red2[0][cl];
 #pragma unroll 8
-        for (int r = 1; r < RF_LANES; ++r) {
-            s1 += red1[r][cl];
-            s2 += red2[r][cl];
+            for (int r = 1; r < RF_LANES; ++r) {
+                s1 += red1[r][cl];
+                s2 += red2[r][cl];
+            }
+            float mean, invstd;
+            bn_finalize_elem<SEG>(s1, s2, x[blk.r0 * ldx + c], blk.r1 - blk.r0, eps, momentum, mean, invstd, rm, rv);
+            save_mean[(int64_t)blk.b * d + c] = mean;
+            save_invstd[(int64_t)blk.b * d + c] = invstd;
         }
-        const float n = (float)N;
-        const float mshift = s1 / n;
-        const float mean = x[c] + mshift;
-        float var = s2 / n - mshift * mshift;
-        var = var > 0.f ? var : 0.f;
-        save_mean[c] = mean;
-        save_invstd[c] = rsqrtf(var + eps);
-        if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-        if (running_var) {
-            const float unbiased = N > 1 ? var * n / (n - 1.f) : var;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-        }
+        if (SEG) __syncthreads();              // red is written again for the next block
+    }
+    if (rl == 0 && c < d) {
+        if (running_mean) running_mean[c] = rm;
+        if (running_var) running_var[c] = rv;
     }
 }
 
@@ -158,17 +284,23 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ running_mean, con
     }
 }
 
-__global__ __launch_bounds__(kBlock) void bn_tanh_apply_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int D4,
+// y = tanh((x - mean) invstd weight + bias), mean / invstd [blocks, d] those of the row's block
+template <bool SEG>
+__global__ __launch_bounds__(kBlock) void bn_tanh_apply_kernel(const float* __restrict__ x, int64_t ldx, BnRows<SEG> rows, int D4,
                                                                const float* __restrict__ weight, const float* __restrict__ bias,
                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                float* __restrict__ y, int64_t ldy, float* __restrict__ y2,
                                                                int64_t ldy2) {
-    const int64_t total = N * D4;
+    int64_t total;
+    if constexpr (SEG) total = rows.ptr[rows.nb] * D4;
+    else total = rows * D4;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
         const int64_t r = i / D4;
         const int c4 = (int)(i % D4);
+        int64_t so = 0;
+        if constexpr (SEG) so = (int64_t)seg_of_row(rows, r) * D4 * 4;
         const float4 v = ld4(x + r * ldx + c4 * 4);
-        const float4 mu = ld4(mean + c4 * 4), is = ld4(invstd + c4 * 4), w = ld4(weight + c4 * 4), b = ld4(bias + c4 * 4);
+        const float4 mu = ld4(mean + so + c4 * 4), is = ld4(invstd + so + c4 * 4), w = ld4(weight + c4 * 4), b = ld4(bias + c4 * 4);
         float4 o;
         o.x = tanhf(fmaf((v.x - mu.x) * is.x, w.x, b.x));
         o.y = tanhf(fmaf((v.y - mu.y) * is.y, w.y, b.y));
@@ -179,64 +311,7 @@ __global__ __launch_bounds__(kBlock) void bn_tanh_apply_kernel(const float* __re
     }
 }
 
-// backward column sums: partial[b][0][c] = sum gz, partial[b][1][c] = sum gz * xhat, gz = gy*(1-y^2)
-__global__ __launch_bounds__(kBlock) void bn_bwd_partial_kernel(const float* __restrict__ x, int64_t ldx,
-                                                                const float* __restrict__ y, int64_t ldy,
-                                                                const float* __restrict__ gy, int64_t ldgy,
-                                                                const float* __restrict__ gy2, int64_t ldgy2, int64_t N, int D4,
-                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                float* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* red = reinterpret_cast<float4*>(smem);
-    const int rpb = kBlock / D4 > 0 ? kBlock / D4 : 1;
-    const int tid = threadIdx.x;
-    for (int cbase = 0; cbase < D4; cbase += kBlock) {
-        const int rsub = D4 >= kBlock ? 0 : tid / D4;
-        const int c4 = D4 >= kBlock ? cbase + tid : tid % D4;
-        const bool active = (D4 >= kBlock ? c4 < D4 : tid < rpb * D4);
-        float4 s1 = f4zero(), s2 = f4zero();
-        if (active) {
-            const float4 mu = ld4(mean + c4 * 4), is = ld4(invstd + c4 * 4);
-            for (int64_t r = (int64_t)blockIdx.x * rpb + rsub; r < N; r += (int64_t)gridDim.x * rpb) {
-                const float4 xv = ld4(x + r * ldx + c4 * 4), yv = ld4(y + r * ldy + c4 * 4);
-                float4 g = ld4(gy + r * ldgy + c4 * 4);
-                if (gy2) {                              // the output fed two consumers: their gradients are summed here
-                    const float4 g2 = ld4(gy2 + r * ldgy2 + c4 * 4);
-                    g.x += g2.x; g.y += g2.y; g.z += g2.z; g.w += g2.w;
-                }
-                const float gz0 = g.x * (1.f - yv.x * yv.x), gz1 = g.y * (1.f - yv.y * yv.y);
-                const float gz2 = g.z * (1.f - yv.z * yv.z), gz3 = g.w * (1.f - yv.w * yv.w);
-                s1.x += gz0; s1.y += gz1; s1.z += gz2; s1.w += gz3;
-                s2.x = fmaf(gz0, (xv.x - mu.x) * is.x, s2.x); s2.y = fmaf(gz1, (xv.y - mu.y) * is.y, s2.y);
-                s2.z = fmaf(gz2, (xv.z - mu.z) * is.z, s2.z); s2.w = fmaf(gz3, (xv.w - mu.w) * is.w, s2.w);
-            }
-        }
-        if (D4 >= kBlock) {
-            if (active) {
-                st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + c4 * 4, s1);
-                st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + c4 * 4, s2);
-            }
-        } else {
-            if (active) {
-                red[(0 * rpb + rsub) * D4 + c4] = s1;
-                red[(1 * rpb + rsub) * D4 + c4] = s2;
-            }
-            __syncthreads();
-            if (tid < D4) {
-                float4 a1 = red[tid], a2 = red[rpb * D4 + tid];
-                for (int q = 1; q < rpb; ++q) {
-                    float4 b1 = red[q * D4 + tid], b2 = red[(rpb + q) * D4 + tid];
-                    a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
-                    a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
-                }
-                st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + tid * 4, a1);
-                st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + tid * 4, a2);
-            }
-            break;
-        }
-    }
-}
-
+// ---- backward ---------------------------------------------------------------------------------------------------------------
 __global__ void bn_bwd_finalize_kernel(const float* __restrict__ sums, int d, float* __restrict__ gweight,
                                        float* __restrict__ gbias) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -245,262 +320,9 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ sums, int d, fl
     gweight[c] = sums[d + c];
 }
 
-__global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(const float* __restrict__ x, int64_t ldx,
-                                                              const float* __restrict__ y, int64_t ldy,
-                                                              const float* __restrict__ gy, int64_t ldgy,
-                                                              const float* __restrict__ gy2, int64_t ldgy2, int64_t N, int D4,
-                                                              const float* __restrict__ weight, const float* __restrict__ mean,
-                                                              const float* __restrict__ invstd, const float* __restrict__ gweight,
-                                                              const float* __restrict__ gbias, int training, float invn,
-                                                              float* __restrict__ gx, int64_t ldgx) {
-    const int64_t total = N * D4;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = i / D4;
-        const int c4 = (int)(i % D4);
-        const float4 xv = ld4(x + r * ldx + c4 * 4), yv = ld4(y + r * ldy + c4 * 4);
-        float4 g = ld4(gy + r * ldgy + c4 * 4);
-        if (gy2) {
-            const float4 g2 = ld4(gy2 + r * ldgy2 + c4 * 4);
-            g.x += g2.x; g.y += g2.y; g.z += g2.z; g.w += g2.w;
-        }
-        const float4 mu = ld4(mean + c4 * 4), is = ld4(invstd + c4 * 4), w = ld4(weight + c4 * 4);
-        const float4 gw = ld4(gweight + c4 * 4), gb = ld4(gbias + c4 * 4);
-        float4 o;
-#define JMAC_BN_BWD(comp)                                                                 \
-        {                                                                                 \
-            const float gz = g.comp * (1.f - yv.comp * yv.comp);                          \
-            const float xh = (xv.comp - mu.comp) * is.comp;                               \
-            o.comp = training ? w.comp * is.comp * (gz - invn * (gb.comp + xh * gw.comp)) \
-                              : w.comp * is.comp * gz;                                    \
-        }
-        JMAC_BN_BWD(x) JMAC_BN_BWD(y) JMAC_BN_BWD(z) JMAC_BN_BWD(w)
-#undef JMAC_BN_BWD
-        st4(gx + r * ldgx + c4 * 4, o);
-    }
-}
-
-
-// ---- segmented forms: the rows are a stack of `nb` blocks (KGs of one launch set: the reference's training step encodes
-// ---- two KGs per batch, src/jmac_model.py:325-326,263-264, each forward_base call with batch statistics of ITS rows) ----
-// Every block has its own batch statistics (mean / invstd [nb, d]); weight, bias and the running estimates are the layer's
-// (shared), and the running estimates are updated once per block in the callers' CALL order (seg.order), exactly what nb
-// separate forward_base calls leave behind:  r <- (1-m)((1-m) r + m b_1) + m b_2 ...
-constexpr int kMaxSeg = JMAC_BN_MAX_BLOCKS;
-struct SegTab {
-    int nb;
-    int order[kMaxSeg];        // block processed k-th by the running-statistics update
-    int gofs[kMaxSeg + 1];     // first statistics workgroup (= partial row) of each block
-    int64_t ptr[kMaxSeg + 1];  // first row of each block; ptr[nb] = rows in all
-};
-__device__ __forceinline__ int seg_of_row(const SegTab& s, int64_t r) {
-    int b = 0;
-    for (int k = 1; k < s.nb; ++k) b += r >= s.ptr[k] ? 1 : 0;
-    return b;
-}
-__device__ __forceinline__ int seg_of_group(const SegTab& s, int wg) {
-    int b = 0;
-    for (int k = 1; k < s.nb; ++k) b += wg >= s.gofs[k] ? 1 : 0;
-    return b;
-}
-
-// col_stats_partial_kernel per block: workgroup wg works on block b = seg_of_group(wg); partial row index = wg
-__global__ __launch_bounds__(kBlock) void col_stats_partial_seg_kernel(const float* __restrict__ x, int64_t ldx, SegTab seg, int D4,
-                                                                       float* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* red = reinterpret_cast<float4*>(smem);   // [2][rpb][D4]
-    const int b = seg_of_group(seg, (int)blockIdx.x);
-    const int lb = (int)blockIdx.x - seg.gofs[b], gb = seg.gofs[b + 1] - seg.gofs[b];
-    const int64_t r0 = seg.ptr[b], r1 = seg.ptr[b + 1];
-    const int rpb = kBlock / D4 > 0 ? kBlock / D4 : 1;
-    const int tid = threadIdx.x;
-    for (int cbase = 0; cbase < D4; cbase += kBlock) {
-        const int rsub = D4 >= kBlock ? 0 : tid / D4;
-        const int c4 = D4 >= kBlock ? cbase + tid : tid % D4;
-        const bool active = (D4 >= kBlock ? c4 < D4 : tid < rpb * D4);
-        float4 s1 = f4zero(), s2 = f4zero();
-        if (active) {
-            const float4 K = ld4(x + r0 * ldx + c4 * 4);
-            for (int64_t r = r0 + (int64_t)lb * rpb + rsub; r < r1; r += (int64_t)gb * rpb) {
-                float4 v = ld4(x + r * ldx + c4 * 4);
-                v.x -= K.x; v.y -= K.y; v.z -= K.z; v.w -= K.w;
-                s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
-                s2.x = fmaf(v.x, v.x, s2.x); s2.y = fmaf(v.y, v.y, s2.y); s2.z = fmaf(v.z, v.z, s2.z); s2.w = fmaf(v.w, v.w, s2.w);
-            }
-        }
-        if (D4 >= kBlock) {
-            if (active) {
-                st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + c4 * 4, s1);
-                st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + c4 * 4, s2);
-            }
-        } else {
-            if (active) {
-                red[(0 * rpb + rsub) * D4 + c4] = s1;
-                red[(1 * rpb + rsub) * D4 + c4] = s2;
-            }
-            __syncthreads();
-            if (tid < D4) {
-                float4 a1 = red[tid], a2 = red[rpb * D4 + tid];
-                for (int q = 1; q < rpb; ++q) {
-                    float4 b1 = red[q * D4 + tid], b2 = red[(rpb + q) * D4 + tid];
-                    a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
-                    a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
-                }
-                st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + tid * 4, a1);
-                st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + tid * 4, a2);
-            }
-            break;
-        }
-    }
-}
-
-// bn_reduce_finalize_kernel over the blocks in CALL order: a workgroup owns 16 features, reduces block after block and
-// carries the running estimates of its features through the blocks in registers
-__global__ __launch_bounds__(1024) void bn_reduce_finalize_seg_kernel(const float* __restrict__ partial, SegTab seg,
-                                                                      const float* __restrict__ x, int64_t ldx, int d, float eps,
-                                                                      float momentum, float* __restrict__ running_mean,
-                                                                      float* __restrict__ running_var, float* __restrict__ save_mean,
-                                                                      float* __restrict__ save_invstd) {
-    __shared__ float red1[RF_LANES][RF_COLS], red2[RF_LANES][RF_COLS];
-    const int cl = threadIdx.x % RF_COLS, rl = threadIdx.x / RF_COLS;
-    const int c = blockIdx.x * RF_COLS + cl;
-    float rm = 0.f, rv = 0.f;
-    if (rl == 0 && c < d) {
-        if (running_mean) rm = running_mean[c];
-        if (running_var) rv = running_var[c];
-    }
-    for (int k = 0; k < seg.nb; ++k) {
-        const int b = seg.order[k];
-        const int p0 = seg.gofs[b], p1 = seg.gofs[b + 1];
-        float a1 = 0.f, a2 = 0.f, b1 = 0.f, b2 = 0.f;
-        if (c < d) {
-            int p = p0 + rl;
-            for (; p + RF_LANES < p1; p += 2 * RF_LANES) {
-                a1 += partial[(int64_t)p * 2 * d + c];
-                a2 += partial[(int64_t)p * 2 * d + d + c];
-                b1 += partial[(int64_t)(p + RF_LANES) * 2 * d + c];
-                b2 += partial[(int64_t)(p + RF_LANES) * 2 * d + d + c];
-            }
-            if (p < p1) {
-                a1 += partial[(int64_t)p * 2 * d + c];
-                a2 += partial[(int64_t)p * 2 * d + d + c];
-            }
-        }
-        red1[rl][cl] = a1 + b1;
-        red2[rl][cl] = a2 + b2;
-        __syncthreads();
-        if (rl == 0 && c < d) {
-            float s1 = red1[0][cl], s2 = red2[0][cl];
-#pragma unroll 8
-            for (int r = 1; r < RF_LANES; ++r) {
-                s1 += red1[r][cl];
-                s2 += red2[r][cl];
-            }
-            const int64_t nrow = seg.ptr[b + 1] - seg.ptr[b];
-            const float n = (float)nrow;
-            const float mshift = s1 / n;
-            const float mean = x[seg.ptr[b] * ldx + c] + mshift;
-            float var = s2 / n - mshift * mshift;
-            var = var > 0.f ? var : 0.f;
-            save_mean[(int64_t)b * d + c] = mean;
-            save_invstd[(int64_t)b * d + c] = rsqrtf(var + eps);
-            rm = (1.f - momentum) * rm + momentum * mean;
-            const float unbiased = nrow > 1 ? var * n / (n - 1.f) : var;
-            rv = (1.f - momentum) * rv + momentum * unbiased;
-        }
-        __syncthreads();
-    }
-    if (rl == 0 && c < d) {
-        if (running_mean) running_mean[c] = rm;
-        if (running_var) running_var[c] = rv;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void bn_tanh_apply_seg_kernel(const float* __restrict__ x, int64_t ldx, SegTab seg, int D4,
-                                                                   const float* __restrict__ weight, const float* __restrict__ bias,
-                                                                   const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                   float* __restrict__ y, int64_t ldy, float* __restrict__ y2,
-                                                                   int64_t ldy2) {
-    const int64_t total = seg.ptr[seg.nb] * D4;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = i / D4;
-        const int c4 = (int)(i % D4);
-        const int64_t so = (int64_t)seg_of_row(seg, r) * D4 * 4;
-        const float4 v = ld4(x + r * ldx + c4 * 4);
-        const float4 mu = ld4(mean + so + c4 * 4), is = ld4(invstd + so + c4 * 4), w = ld4(weight + c4 * 4), b = ld4(bias + c4 * 4);
-        float4 o;
-        o.x = tanhf(fmaf((v.x - mu.x) * is.x, w.x, b.x));
-        o.y = tanhf(fmaf((v.y - mu.y) * is.y, w.y, b.y));
-        o.z = tanhf(fmaf((v.z - mu.z) * is.z, w.z, b.z));
-        o.w = tanhf(fmaf((v.w - mu.w) * is.w, w.w, b.w));
-        st4(y + r * ldy + c4 * 4, o);
-        if (y2) st4(y2 + r * ldy2 + c4 * 4, o);
-    }
-}
-
-// bn_bwd_partial_kernel per block (mean / invstd of the workgroup's block)
-__global__ __launch_bounds__(kBlock) void bn_bwd_partial_seg_kernel(const float* __restrict__ x, int64_t ldx,
-                                                                    const float* __restrict__ y, int64_t ldy,
-                                                                    const float* __restrict__ gy, int64_t ldgy,
-                                                                    const float* __restrict__ gy2, int64_t ldgy2, SegTab seg, int D4,
-                                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                    float* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4* red = reinterpret_cast<float4*>(smem);
-    const int b = seg_of_group(seg, (int)blockIdx.x);
-    const int lb = (int)blockIdx.x - seg.gofs[b], gb = seg.gofs[b + 1] - seg.gofs[b];
-    const int64_t r0 = seg.ptr[b], r1 = seg.ptr[b + 1];
-    const int64_t so = (int64_t)b * D4 * 4;
-    const int rpb = kBlock / D4 > 0 ? kBlock / D4 : 1;
-    const int tid = threadIdx.x;
-    for (int cbase = 0; cbase < D4; cbase += kBlock) {
-        const int rsub = D4 >= kBlock ? 0 : tid / D4;
-        const int c4 = D4 >= kBlock ? cbase + tid : tid % D4;
-        const bool active = (D4 >= kBlock ? c4 < D4 : tid < rpb * D4);
-        float4 s1 = f4zero(), s2 = f4zero();
-        if (active) {
-            const float4 mu = ld4(mean + so + c4 * 4), is = ld4(invstd + so + c4 * 4);
-            for (int64_t r = r0 + (int64_t)lb * rpb + rsub; r < r1; r += (int64_t)gb * rpb) {
-                const float4 xv = ld4(x + r * ldx + c4 * 4), yv = ld4(y + r * ldy + c4 * 4);
-                float4 g = ld4(gy + r * ldgy + c4 * 4);
-                if (gy2) {
-                    const float4 g2 = ld4(gy2 + r * ldgy2 + c4 * 4);
-                    g.x += g2.x; g.y += g2.y; g.z += g2.z; g.w += g2.w;
-                }
-                const float gz0 = g.x * (1.f - yv.x * yv.x), gz1 = g.y * (1.f - yv.y * yv.y);
-                const float gz2 = g.z * (1.f - yv.z * yv.z), gz3 = g.w * (1.f - yv.w * yv.w);
-                s1.x += gz0; s1.y += gz1; s1.z += gz2; s1.w += gz3;
-                s2.x = fmaf(gz0, (xv.x - mu.x) * is.x, s2.x); s2.y = fmaf(gz1, (xv.y - mu.y) * is.y, s2.y);
-                s2.z = fmaf(gz2, (xv.z - mu.z) * is.z, s2.z); s2.w = fmaf(gz3, (xv.w - mu.w) * is.w, s2.w);
-            }
-        }
-        if (D4 >= kBlock) {
-            if (active) {
-                st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + c4 * 4, s1);
-                st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + c4 * 4, s2);
-            }
-        } else {
-            if (active) {
-                red[(0 * rpb + rsub) * D4 + c4] = s1;
-                red[(1 * rpb + rsub) * D4 + c4] = s2;
-            }
-            __syncthreads();
-            if (tid < D4) {
-                float4 a1 = red[tid], a2 = red[rpb * D4 + tid];
-                for (int q = 1; q < rpb; ++q) {
-                    float4 b1 = red[q * D4 + tid], b2 = red[(rpb + q) * D4 + tid];
-                    a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
-                    a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
-                }
-                st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + tid * 4, a1);
-                st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + tid * 4, a2);
-            }
-            break;
-        }
-    }
-}
-
 // per-block sums of the backward partial rows -> bsums [nb, 2d] (sum gz | sum gz*xhat of each block) and their totals over
 // the blocks in block order -> gbw [2d] = [grad bias | grad weight] (the parameters are shared by the blocks)
+// Not merged with launch_reduce_rows: two accumulators per lane here, four there, a different association beyond 128 partial rows.
 __global__ __launch_bounds__(1024) void bn_bwd_reduce_seg_kernel(const float* __restrict__ partial, SegTab seg, int W,
                                                                  float* __restrict__ bsums, float* __restrict__ gbias,
                                                                  float* __restrict__ gweight, int d) {
@@ -536,20 +358,31 @@ __global__ __launch_bounds__(1024) void bn_bwd_reduce_seg_kernel(const float* __
     }
 }
 
-__global__ __launch_bounds__(kBlock) void bn_bwd_apply_seg_kernel(const float* __restrict__ x, int64_t ldx,
-                                                                  const float* __restrict__ y, int64_t ldy,
-                                                                  const float* __restrict__ gy, int64_t ldgy,
-                                                                  const float* __restrict__ gy2, int64_t ldgy2, SegTab seg, int D4,
-                                                                  const float* __restrict__ weight, const float* __restrict__ mean,
-                                                                  const float* __restrict__ invstd, const float* __restrict__ bsums,
-                                                                  float* __restrict__ gx, int64_t ldgx) {
-    const int64_t total = seg.ptr[seg.nb] * D4;
+// gx from the column sums of the row's block: sum gz at gbsum + b ldsum, sum gz * xhat at gwsum + b ldsum (plain: gbias, gweight;
+// segmented: the two halves of a bsums row).  `training` and `invn` = 1 / (rows the statistics were taken over, which is not N where
+// the batch spans ranks) are the plain form's; the segmented form is training-only and takes invn from its block
+template <bool SEG>
+__global__ __launch_bounds__(kBlock) void bn_bwd_apply_kernel(const float* __restrict__ x, int64_t ldx,
+                                                              const float* __restrict__ y, int64_t ldy,
+                                                              const float* __restrict__ gy, int64_t ldgy,
+                                                              const float* __restrict__ gy2, int64_t ldgy2, BnRows<SEG> rows, int D4,
+                                                              const float* __restrict__ weight, const float* __restrict__ mean,
+                                                              const float* __restrict__ invstd, const float* __restrict__ gwsum,
+                                                              const float* __restrict__ gbsum, int64_t ldsum, int training,
+                                                              float invn, float* __restrict__ gx, int64_t ldgx) {
+    int64_t total;
+    if constexpr (SEG) total = rows.ptr[rows.nb] * D4;
+    else total = rows * D4;
+    const int tr = SEG ? 1 : training;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
         const int64_t r = i / D4;
         const int c4 = (int)(i % D4);
-        const int b = seg_of_row(seg, r);
+        int b = 0;
+        if constexpr (SEG) {
+            b = seg_of_row(rows, r);
+            invn = 1.f / (float)(rows.ptr[b + 1] - rows.ptr[b]);
+        }
         const int64_t so = (int64_t)b * D4 * 4;
-        const float invn = 1.f / (float)(seg.ptr[b + 1] - seg.ptr[b]);
         const float4 xv = ld4(x + r * ldx + c4 * 4), yv = ld4(y + r * ldy + c4 * 4);
         float4 g = ld4(gy + r * ldgy + c4 * 4);
         if (gy2) {
@@ -557,16 +390,12 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_seg_kernel(const float* _
             g.x += g2.x; g.y += g2.y; g.z += g2.z; g.w += g2.w;
         }
         const float4 mu = ld4(mean + so + c4 * 4), is = ld4(invstd + so + c4 * 4), w = ld4(weight + c4 * 4);
-        const float4 gb = ld4(bsums + 2 * so + c4 * 4), gw = ld4(bsums + 2 * so + D4 * 4 + c4 * 4);
+        const float4 gw = ld4(gwsum + b * ldsum + c4 * 4), gb = ld4(gbsum + b * ldsum + c4 * 4);
         float4 o;
-#define JMAC_BN_BWD(comp)                                                                 \
-        {                                                                                 \
-            const float gz = g.comp * (1.f - yv.comp * yv.comp);                          \
-            const float xh = (xv.comp - mu.comp) * is.comp;                               \
-            o.comp = w.comp * is.comp * (gz - invn * (gb.comp + xh * gw.comp));           \
-        }
-        JMAC_BN_BWD(x) JMAC_BN_BWD(y) JMAC_BN_BWD(z) JMAC_BN_BWD(w)
-#undef JMAC_BN_BWD
+        o.x = bn_bwd_apply_elem<SEG>(g.x, yv.x, xv.x, mu.x, is.x, w.x, gw.x, gb.x, tr, invn);
+        o.y = bn_bwd_apply_elem<SEG>(g.y, yv.y, xv.y, mu.y, is.y, w.y, gw.y, gb.y, tr, invn);
+        o.z = bn_bwd_apply_elem<SEG>(g.z, yv.z, xv.z, mu.z, is.z, w.z, gw.z, gb.z, tr, invn);
+        o.w = bn_bwd_apply_elem<SEG>(g.w, yv.w, xv.w, mu.w, is.w, w.w, gw.w, gb.w, tr, invn);
         st4(gx + r * ldgx + c4 * 4, o);
     }
 }
@@ -1080,23 +909,6 @@ __global__ __launch_bounds__(kBlock) void bn_tanh_normalize_drop_fwd_kernel(cons
     }
 }
 
-// one element of the BatchNorm + tanh backward (gz = g (1 - y^2), xhat = (x - mean) invstd), written out as the compiler contracts
-// bn_bwd_partial_kernel / bn_bwd_apply_kernel -- in particular both passes form gz the same way, so that a one-row batch gets the
-// exact zero it must
-__device__ __forceinline__ void bn_bwd_sums_elem(float g, float y, float x, float mu, float is, float& s1, float& s2) {
-#pragma clang fp contract(off)
-    const float om = fmaf(-y, y, 1.f), gz = om * g;
-    s1 = fmaf(om, g, s1);
-    s2 = fmaf(gz, (x - mu) * is, s2);
-}
-__device__ __forceinline__ float bn_bwd_apply_elem(float g, float y, float x, float mu, float is, float w, float gw, float gb,
-                                                   int training, float invn) {
-#pragma clang fp contract(off)
-    const float gz = fmaf(-y, y, 1.f) * g;
-    if (!training) return w * is * gz;
-    return w * is * (gz - invn * fmaf((x - mu) * is, gw, gb));
-}
-
 // The column sums keep bn_bwd_partial_kernel's association, so that gweight / gbias (and with them gx) come out bit for bit: a block
 // owns the rows that kernel's block owns -- rpb = kBlock / D4 row slots, slot `rsub` of block b holding rows (b rpb + rsub) + k (grid
 // rpb), k = 0, 1, ... summed in that order -- a wave takes the slots wave, wave + waves, ... one after the other (R consecutive k in
@@ -1171,18 +983,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_partial_adj_kernel(const float*
             }
         }
     }
-    __syncthreads();
-    const int tid = threadIdx.x;
-    if (tid < D4) {
-        float4 a1 = red[tid], a2 = red[rpb * D4 + tid];
-        for (int q = 1; q < rpb; ++q) {
-            const float4 b1 = red[q * D4 + tid], b2 = red[(rpb + q) * D4 + tid];
-            a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
-            a2.x += b2.x; a2.y += b2.y; a2.z += b2.z; a2.w += b2.w;
-        }
-        st4(partial + ((int64_t)blockIdx.x * 2 + 0) * D4 * 4 + tid * 4, a1);
-        st4(partial + ((int64_t)blockIdx.x * 2 + 1) * D4 * 4 + tid * 4, a2);
-    }
+    col_sums_fold(red, rpb, D4, partial);
 }
 
 template <bool SEED, bool ROWFORM, int R>
@@ -1239,11 +1040,10 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_adj_kernel(const float* _
                 if (gy2) gg = add4(gg, g2[u][k]);
                 const float4 yy = yv[u][k], xx = xv[u][k];
                 float4 o;
-#define JMAC_BN_BWD(comp)                                                                                                       \
-                o.comp = bn_bwd_apply_elem(gg.comp, yy.comp, xx.comp, mu[k].comp, is[k].comp, w[k].comp, gw[k].comp, gb[k].comp, \
-                                           training, invn);
-                JMAC_BN_BWD(x) JMAC_BN_BWD(y) JMAC_BN_BWD(z) JMAC_BN_BWD(w)
-#undef JMAC_BN_BWD
+                o.x = bn_bwd_apply_elem(gg.x, yy.x, xx.x, mu[k].x, is[k].x, w[k].x, gw[k].x, gb[k].x, training, invn);
+                o.y = bn_bwd_apply_elem(gg.y, yy.y, xx.y, mu[k].y, is[k].y, w[k].y, gw[k].y, gb[k].y, training, invn);
+                o.z = bn_bwd_apply_elem(gg.z, yy.z, xx.z, mu[k].z, is[k].z, w[k].z, gw[k].z, gb[k].z, training, invn);
+                o.w = bn_bwd_apply_elem(gg.w, yy.w, xx.w, mu[k].w, is[k].w, w[k].w, gw[k].w, gb[k].w, training, invn);
                 st4(gx + (r0 + u) * ldgx + cc[k] * 4, o);
             }
         }
@@ -1311,6 +1111,38 @@ size_t jmac_bn_tanh_workspace_bytes(int64_t N, int64_t d) {
     return align_up((size_t)(kStatBlocks + 1) * 2 * (d > 0 ? d : 0) * 4) + 256;
 }
 
+// the forward's statistics into save_mean / save_invstd: training = the batch's (partial sums -> reduce + finalize, which also
+// updates the running estimates), else the running estimates'
+static int launch_bn_fwd_stats(const float* x, int64_t ldx, int64_t N, int64_t d, float* running_mean, float* running_var,
+                               int32_t training, float momentum, float eps, float* save_mean, float* save_invstd, void* ws,
+                               size_t ws_bytes, hipStream_t st) {
+    if (training) {
+        if (!ws || ws_bytes < jmac_bn_tanh_workspace_bytes(N, d)) return JMAC_EWORKSPACE;
+        const int D4 = (int)(d / 4);
+        float* partial = (float*)ws;
+        const unsigned g = stat_grid(N, D4);
+        hipLaunchKernelGGL(col_stats_partial_kernel<false>, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, N, D4, partial);
+        hipLaunchKernelGGL(bn_reduce_finalize_kernel<false>, dim3((unsigned)((d + RF_COLS - 1) / RF_COLS)), dim3(1024), 0, st, partial,
+                           N, (int)g, x, ldx, (int)d, eps, momentum, running_mean, running_var, save_mean, save_invstd);
+    } else {
+        if (!running_mean || !running_var) return JMAC_EINVAL;
+        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, running_mean, running_var,
+                           (int)d, eps, save_mean, save_invstd);
+    }
+    return JMAC_OK;
+}
+
+// the backward's partial rows [g, 2d] summed into gbias and gweight
+static void launch_bn_bwd_param_grads(float* partial, unsigned g, int64_t d, float* gweight, float* gbias, hipStream_t st) {
+    if (gweight == gbias + d) {                  // [gbias | gweight] contiguous: the reduction writes them directly
+        launch_reduce_rows(partial, (int)g, (int)(2 * d), 1.f, gbias, st);
+    } else {
+        float* sums = partial + (size_t)kStatBlocks * 2 * d;
+        launch_reduce_rows(partial, (int)g, (int)(2 * d), 1.f, sums, st);
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, sums, (int)d, gweight, gbias);
+    }
+}
+
 int jmac_bn_tanh_fwd2_f32(const float* x, int64_t ldx, int64_t N, int64_t d, const float* weight, const float* bias,
                           float* running_mean, float* running_var, int32_t training, float momentum, float eps, float* y,
                           int64_t ldy, float* y2, int64_t ldy2, float* save_mean, float* save_invstd, void* ws, size_t ws_bytes,
@@ -1321,20 +1153,11 @@ int jmac_bn_tanh_fwd2_f32(const float* x, int64_t ldx, int64_t N, int64_t d, con
     if (!x || !y) return JMAC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int D4 = (int)(d / 4);
-    if (training) {
-        if (!ws || ws_bytes < jmac_bn_tanh_workspace_bytes(N, d)) return JMAC_EWORKSPACE;
-        float* partial = (float*)ws;
-        const unsigned g = stat_grid(N, D4);
-        hipLaunchKernelGGL(col_stats_partial_kernel, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, N, D4, partial);
-        hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((unsigned)((d + RF_COLS - 1) / RF_COLS)), dim3(1024), 0, st, partial,
-                           (int)g, x, N, (int)d, eps, momentum, running_mean, running_var, save_mean, save_invstd);
-    } else {
-        if (!running_mean || !running_var) return JMAC_EINVAL;
-        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, running_mean, running_var,
-                           (int)d, eps, save_mean, save_invstd);
-    }
-    hipLaunchKernelGGL(bn_tanh_apply_kernel, dim3(stream_grid(N * D4)), dim3(kBlock), 0, st, x, ldx, N, D4, weight, bias,
-                       save_mean, save_invstd, y, ldy, y2, ldy2);
+    if (int rc = launch_bn_fwd_stats(x, ldx, N, d, running_mean, running_var, training, momentum, eps, save_mean, save_invstd, ws,
+                                     ws_bytes, st))
+        return rc;
+    hipLaunchKernelGGL(bn_tanh_apply_kernel<false>, dim3(stream_grid(N * D4)), dim3(kBlock), 0, st, x, ldx, N, D4, weight, bias,
+                       (const float*)save_mean, (const float*)save_invstd, y, ldy, y2, ldy2);
     return (int)hipGetLastError();
 }
 
@@ -1352,19 +1175,14 @@ int jmac_bn_tanh_bwd2_f32(const float* x, int64_t ldx, const float* y, int64_t l
     if (N > 0) {
         if (!x || !y || !gy || !gx) return JMAC_EINVAL;
         g = stat_grid(N, D4);
-        hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, y, ldy, gy, ldgy, gy2, ldgy2, N,
-                           D4, save_mean, save_invstd, partial);
+        hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, y, ldy, gy, ldgy, gy2, ldgy2,
+                           N, D4, save_mean, save_invstd, partial);
     }
-    if (gweight == gbias + d) {                  // [gbias | gweight] contiguous: the reduction writes them directly
-        launch_reduce_rows(partial, (int)g, (int)(2 * d), 1.f, gbias, st);
-    } else {
-        float* sums = partial + (size_t)kStatBlocks * 2 * d;
-        launch_reduce_rows(partial, (int)g, (int)(2 * d), 1.f, sums, st);
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, sums, (int)d, gweight, gbias);
-    }
+    launch_bn_bwd_param_grads(partial, g, d, gweight, gbias, st);
     if (N > 0)
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(N * D4)), dim3(kBlock), 0, st, x, ldx, y, ldy, gy, ldgy, gy2, ldgy2, N,
-                           D4, weight, save_mean, save_invstd, gweight, gbias, training, 1.f / (float)N, gx, ldgx);
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(stream_grid(N * D4)), dim3(kBlock), 0, st, x, ldx, y, ldy, gy, ldgy, gy2,
+                           ldgy2, N, D4, weight, save_mean, save_invstd, (const float*)gweight, (const float*)gbias, (int64_t)0, training,
+                           1.f / (float)N, gx, ldgx);
     return (int)hipGetLastError();
 }
 
@@ -1544,18 +1362,9 @@ int jmac_bn_tanh_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, int64_t
     if (!aligned16({x, y, y_rows, yn, weight, bias, save_mean, save_invstd})) return JMAC_EDIM;
     hipStream_t st = (hipStream_t)stream;
     const int D4 = (int)(d / 4);
-    if (training) {                                              // the statistics launches of jmac_bn_tanh_fwd2_f32
-        if (!ws || ws_bytes < jmac_bn_tanh_workspace_bytes(N, d)) return JMAC_EWORKSPACE;
-        float* partial = (float*)ws;
-        const unsigned g = stat_grid(N, D4);
-        hipLaunchKernelGGL(col_stats_partial_kernel, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, N, D4, partial);
-        hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((unsigned)((d + RF_COLS - 1) / RF_COLS)), dim3(1024), 0, st, partial,
-                           (int)g, x, N, (int)d, eps, momentum, running_mean, running_var, save_mean, save_invstd);
-    } else {
-        if (!running_mean || !running_var) return JMAC_EINVAL;
-        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, running_mean, running_var,
-                           (int)d, eps, save_mean, save_invstd);
-    }
+    if (int rc = launch_bn_fwd_stats(x, ldx, N, d, running_mean, running_var, training, momentum, eps, save_mean, save_invstd, ws,
+                                     ws_bytes, st))
+        return rc;
     JMAC_LAUNCH_SEEDED(bn_tanh_normalize_drop_fwd_kernel, kFuseRows, rows_grid(N, kFuseRows), st, x, ldx, N, D4, weight, bias,
                        (const float*)save_mean, (const float*)save_invstd, y, ldy, row_map, y_rows, ldyr, norm_eps, ds, yn, ldyn, inv);
     return (int)hipGetLastError();
@@ -1591,13 +1400,7 @@ int jmac_bn_tanh_bwd_normadj_f32(const float* x, int64_t ldx, const float* y, in
         else JMAC_PARTIAL(false, false);
 #undef JMAC_PARTIAL
     }
-    if (gweight == gbias + d) {                  // [gbias | gweight] contiguous: the reduction writes them directly
-        launch_reduce_rows(partial, (int)pg, (int)(2 * d), 1.f, gbias, st);
-    } else {
-        float* sums = partial + (size_t)kStatBlocks * 2 * d;
-        launch_reduce_rows(partial, (int)pg, (int)(2 * d), 1.f, sums, st);
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, sums, (int)d, gweight, gbias);
-    }
+    launch_bn_bwd_param_grads(partial, pg, d, gweight, gbias, st);
     if (N > 0)
         JMAC_LAUNCH_ADJ(bn_bwd_apply_adj_kernel, kFuseBwdRows, rows_grid(N, kFuseBwdRows), st, x, ldx, y, ldy, g, ldg, inv, ds,
                            norm_eps, gy2, ldgy2, row_map, N, D4, weight, save_mean, save_invstd, (const float*)gweight,
@@ -1664,12 +1467,12 @@ int jmac_bn_tanh_seg_fwd2_f32(const float* x, int64_t ldx, int64_t d, int32_t nb
     if (!ws || ws_bytes < jmac_bn_tanh_seg_workspace_bytes(nblocks, d)) return JMAC_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)ws;
-    hipLaunchKernelGGL(col_stats_partial_seg_kernel, dim3((unsigned)seg.gofs[nblocks]), dim3(kBlock), stat_smem(D4), st, x, ldx, seg,
+    hipLaunchKernelGGL(col_stats_partial_kernel<true>, dim3((unsigned)seg.gofs[nblocks]), dim3(kBlock), stat_smem(D4), st, x, ldx, seg,
                        D4, partial);
-    hipLaunchKernelGGL(bn_reduce_finalize_seg_kernel, dim3((unsigned)((d + RF_COLS - 1) / RF_COLS)), dim3(1024), 0, st, partial, seg,
-                       x, ldx, (int)d, eps, momentum, running_mean, running_var, save_mean, save_invstd);
-    hipLaunchKernelGGL(bn_tanh_apply_seg_kernel, dim3(stream_grid(seg.ptr[nblocks] * D4)), dim3(kBlock), 0, st, x, ldx, seg, D4,
-                       weight, bias, save_mean, save_invstd, y, ldy, y2, ldy2);
+    hipLaunchKernelGGL(bn_reduce_finalize_kernel<true>, dim3((unsigned)((d + RF_COLS - 1) / RF_COLS)), dim3(1024), 0, st, partial, seg,
+                       0, x, ldx, (int)d, eps, momentum, running_mean, running_var, save_mean, save_invstd);
+    hipLaunchKernelGGL(bn_tanh_apply_kernel<true>, dim3(stream_grid(seg.ptr[nblocks] * D4)), dim3(kBlock), 0, st, x, ldx, seg, D4,
+                       weight, bias, (const float*)save_mean, (const float*)save_invstd, y, ldy, y2, ldy2);
     return (int)hipGetLastError();
 }
 
@@ -1686,12 +1489,13 @@ int jmac_bn_tanh_seg_bwd2_f32(const float* x, int64_t ldx, const float* y, int64
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)ws;
     float* bsums = (float*)((char*)ws + align_up((size_t)nblocks * kStatBlocks * 2 * d * 4));
-    hipLaunchKernelGGL(bn_bwd_partial_seg_kernel, dim3((unsigned)seg.gofs[nblocks]), dim3(kBlock), stat_smem(D4), st, x, ldx, y, ldy,
+    hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, dim3((unsigned)seg.gofs[nblocks]), dim3(kBlock), stat_smem(D4), st, x, ldx, y, ldy,
                        gy, ldgy, gy2, ldgy2, seg, D4, save_mean, save_invstd, partial);
     hipLaunchKernelGGL(bn_bwd_reduce_seg_kernel, dim3((unsigned)((2 * d + RF_COLS - 1) / RF_COLS)), dim3(1024), 0, st, partial, seg,
                        (int)(2 * d), bsums, gbias, gweight, (int)d);
-    hipLaunchKernelGGL(bn_bwd_apply_seg_kernel, dim3(stream_grid(seg.ptr[nblocks] * D4)), dim3(kBlock), 0, st, x, ldx, y, ldy, gy, ldgy,
-                       gy2, ldgy2, seg, D4, weight, save_mean, save_invstd, bsums, gx, ldgx);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(stream_grid(seg.ptr[nblocks] * D4)), dim3(kBlock), 0, st, x, ldx, y, ldy, gy, ldgy,
+                       gy2, ldgy2, seg, D4, weight, save_mean, save_invstd, (const float*)(bsums + d), (const float*)bsums, 2 * d, 1,
+                       0.f, gx, ldgx);
     return (int)hipGetLastError();
 }
 
@@ -1707,7 +1511,7 @@ int jmac_col_moments_f32(const float* x, int64_t ldx, int64_t N, int64_t d, floa
     const int D4 = (int)(d / 4);
     float* partial = (float*)ws;
     const unsigned g = stat_grid(N, D4);
-    hipLaunchKernelGGL(col_stats_partial_kernel, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, N, D4, partial);
+    hipLaunchKernelGGL(col_stats_partial_kernel<false>, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, N, D4, partial);
     float* sums = partial + (size_t)kStatBlocks * 2 * d;
     launch_reduce_rows(partial, (int)g, (int)(2 * d), 1.f, sums, st);
     hipLaunchKernelGGL(moments_finalize_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, st, sums, x, N, (int)d, mean, m2);
@@ -1721,8 +1525,8 @@ int jmac_bn_tanh_apply_f32(const float* x, int64_t ldx, int64_t N, int64_t d, co
     if (N == 0) return JMAC_OK;
     if (!x || !y) return JMAC_EINVAL;
     const int D4 = (int)(d / 4);
-    hipLaunchKernelGGL(bn_tanh_apply_kernel, dim3(stream_grid(N * D4)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, N, D4, weight,
-                       bias, mean, invstd, y, ldy, (float*)nullptr, (int64_t)0);
+    hipLaunchKernelGGL(bn_tanh_apply_kernel<false>, dim3(stream_grid(N * D4)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, N,
+                       D4, weight, bias, mean, invstd, y, ldy, (float*)nullptr, (int64_t)0);
     return (int)hipGetLastError();
 }
 
@@ -1739,7 +1543,7 @@ int jmac_bn_tanh_bwd_sums_f32(const float* x, int64_t ldx, const float* y, int64
     if (N > 0) {
         if (!x || !y || !gy) return JMAC_EINVAL;
         g = stat_grid(N, D4);
-        hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, y, ldy, gy, ldgy,
+        hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3(g), dim3(kBlock), stat_smem(D4), st, x, ldx, y, ldy, gy, ldgy,
                            (const float*)nullptr, (int64_t)0, N, D4, mean, invstd, partial);
     }
     launch_reduce_rows(partial, (int)g, (int)(2 * d), 1.f, sums, st);     // sums[0:d] = sum gz, sums[d:2d] = sum gz * xhat
@@ -1754,9 +1558,9 @@ int jmac_bn_tanh_bwd_apply_f32(const float* x, int64_t ldx, const float* y, int6
     if (N == 0) return JMAC_OK;
     if (!x || !y || !gy || !gx) return JMAC_EINVAL;
     const int D4 = (int)(d / 4);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(N * D4)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, y, ldy, gy, ldgy,
-                       (const float*)nullptr, (int64_t)0, N, D4, weight, mean, invstd, sums + d, sums, 1, 1.f / (float)n_total, gx,
-                       ldgx);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(stream_grid(N * D4)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, y, ldy, gy,
+                       ldgy, (const float*)nullptr, (int64_t)0, N, D4, weight, mean, invstd, sums + d, sums, (int64_t)0, 1,
+                       1.f / (float)n_total, gx, ldgx);
     return (int)hipGetLastError();
 }
 
