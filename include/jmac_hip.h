@@ -491,6 +491,20 @@ int jmac_sim_topk_f32(const float* A, int64_t lda, const float* B, int64_t ldb, 
                       int64_t d, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes,
                       jmac_stream_t stream);
 
+size_t jmac_sim_topk_screened_workspace_bytes(int64_t L, int64_t N, int64_t d, int32_t k);
+/* jmac_sim_topk_f32's result bit for bit -- values, indices, tie order -- with the L x N x d work on the bf16 matrix cores.  The
+ * bf16 product (operands rounded once to bf16, fp32 accumulate) only SCREENS: its score sh of a pair differs from the fp32 score
+ * s by at most e = 0.008 (na + 2^-110)(nb + 2^-110) + 2^-110 (na, nb: upper bounds of the rows' l2 norms; proof: DESIGN section 5),
+ * so the k-th largest sh - e of any set of columns bounds the row's exact k-th score from below and every pair with sh + e under
+ * that bound is out.  What survives (a few dozen columns per row) is rescored with the fp32 product's own instruction sequence and
+ * the k best of those exact scores are returned.  N >= 8192 and k <= 64; any other shape runs jmac_sim_topk_f32's code unchanged.
+ * d % 4 == 0 and d <= 512 (JMAC_EDIM); the other checks and their order are jmac_sim_topk_f32's (+ JMAC_ERANGE for L or N >= 2^31).
+ * n_rescored [L] (may be NULL): the columns row i rescored exactly; -1: the row's candidate list overflowed (mass ties) and it
+ * recomputed all N scores; -2: the shape took the unscreened path.  Finite inputs; no float atomics: two calls return the same bits. */
+int jmac_sim_topk_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d,
+                               int32_t k, float* val, int32_t* idx, int32_t* n_rescored, void* ws, size_t ws_bytes,
+                               jmac_stream_t stream);
+
 /* Row top-k of an existing score matrix (same ordering rule). */
 int jmac_row_topk_f32(const float* S, int64_t lds, int64_t L, int64_t N, int32_t k, float* val,
                       int32_t* idx, jmac_stream_t stream);

@@ -140,6 +140,8 @@ _SIGS = {
     "jmac_sim_matrix_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, i64, vp]),
     "jmac_sim_topk_workspace_bytes": (sz, [i64, i64, i32]),
     "jmac_sim_topk_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
+    "jmac_sim_topk_screened_workspace_bytes": (sz, [i64, i64, i64, i32]),
+    "jmac_sim_topk_screened_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
     "jmac_col_topk_workspace_bytes": (sz, [i64, i64, i32]),
     "jmac_col_topk_f32": (C.c_int, [vp, i64, i64, i64, i32, vp, vp, sz, vp]),
     "jmac_row_topk_f32": (C.c_int, [vp, i64, i64, i64, i32, vp, vp, vp]),

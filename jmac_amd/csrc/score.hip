@@ -18,6 +18,7 @@
 // (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate), so top-k indices are decided on
 // full-precision scores.
 #include "common.h"
+#include "sim_rescore.h"
 #include "topk_select.h"
 #include <type_traits>
 
@@ -590,13 +591,12 @@ __global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) 
 // ------------------------------------------------------------------------------------------------
 // similarity GEMM  C = A * B^T  on the fp32-input MFMA (32x32x2), 128x128 or 128x256 tile per 4-wave block, K staged 16 deep
 // ------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Tile: 128 rows x (64 WJ) columns per 4-wave block, wave grid 2 x 2, a wave owns 64 x (32 WJ).  WJ = 2: the 128 x 128 tile of
 // rounds 1-5 (64 accumulator registers, 3 blocks per CU); WJ = 4: 128 x 256 (128 accumulator registers, 2 blocks per CU): per flop
 // a quarter fewer operand bytes through L2 and LDS and half as many barriers (round 6: +3.5 % where its rounds of resident blocks are
 // no coarser, profiles/r6_simgemm_ablation.txt).  launch_sim picks per shape.  The contraction order per output
 // element is the same for both (planes k = 8q + 4h + s), so the results are bit-identical whichever runs.
-constexpr int SG_T = 128, SG_K = 16;
+constexpr int SG_T = 128;             // (SG_K, the 16-deep k slab: sim_rescore.h)
 constexpr int SG_PLANE = SG_T * 4 + 8;      // floats per (sub-slab q, k-half h) plane; +8: the 4 planes a wave store
                                             // instruction touches start on different banks
 constexpr int SG_IMG = 4 * SG_PLANE;        // one operand slab: planes (q, h) = (0,0) (0,1) (1,0) (1,1)
@@ -1481,41 +1481,7 @@ __global__ __launch_bounds__(kBlock) void row_topk_kernel(const float* __restric
 // are the GEMM's -- once per pass of the two-pass selection (and per arg-max round if even that overflows).  Slow by design:
 // it exists so that degenerate inputs still get the exact answer.
 // ------------------------------------------------------------------------------------------------
-// One 32 x 32 tile of the product with sim_gemm_kernel's contraction sequence per output element: four v_mfma_f32_32x32x2_f32 per
-// (kt, q), planes k = 16 kt + 8 q + 4 h, clamped loads zeroed past d.  Lane (r = lane & 31, h = lane >> 5) supplies row r of
-// both operands; ROW0: only tile row 0 carries A (one row of A against 32 rows of B), the rest is padding.
-template <bool ROW0>
-__device__ __forceinline__ f32x16 sim_tile_32x32(const float* __restrict__ arow, const float* __restrict__ brow, int d) {
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const int nk = (d + SG_K - 1) / SG_K;
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    for (int kt = 0; kt < nk; ++kt)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int k = kt * SG_K + 8 * q + 4 * h;
-            float4 a4 = ld4(arow + min(k, d - 4)), b4 = ld4(brow + min(k, d - 4));
-            if (k >= d) a4 = b4 = f4zero();
-            if (ROW0 && r != 0) a4 = f4zero();
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-        }
-    return acc;
-}
-
-template <class F>
-__device__ __forceinline__ void for_each_row_score(const float* __restrict__ arow, const float* __restrict__ Bm, int64_t ldb, int N,
-                                                   int d, F f) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    for (int n0 = wave * 32; n0 < N; n0 += 32 * (kBlock / 64)) {
-        const f32x16 acc = sim_tile_32x32<true>(arow, Bm + (int64_t)min(n0 + r, N - 1) * ldb, d);
-        if (h == 0 && n0 + r < N) f(n0 + r, acc[0]);           // C/D map: row 0 = register 0 of the lanes with h == 0
-    }
-}
+// (sim_tile_32x32 and for_each_row_score, the recomputation itself: sim_rescore.h -- screen.hip rescores with them too)
 
 // s(m, n) = 1 - dist(m, n) of ONE pair of rows with link_rank_tile_kernel's sum: the single running fp32 sum over k = 0 .. d-1 of
 // |a[k] - b[k]| (the tile's zero padding adds exact zeros), so the bits are the tile's.  One lane per pair.

@@ -1,0 +1,475 @@
+// screen.hip -- jmac_sim_topk_screened_f32: jmac_sim_topk_f32's result, bit for bit, with the L x N x d work done on the bf16
+// matrix cores (v_mfma_f32_32x32x16_bf16) and only a few dozen columns per row on the fp32-input MFMA.
+//
+// The bf16 product never decides anything by itself.  Its score sh(i, j) of a pair -- both operands rounded once to bf16, fp32
+// accumulate -- differs from the fp32 product's score s(i, j) by at most
+//      e(i, j) = KAPPA (na_i + TAU) (nb_j + TAU) + ETA                                         (the proof)
+// with na, nb upper bounds of the rows' l2 norms.  So sh - e <= s <= sh + e, and
+//   prepare   bf16 copies of A and B (rows zero-padded to 32 k) and the two factors of e per row          screen_prepare_kernel
+//   sample    sh - e over the first Ns columns, stored; its k-th largest per row is lower_i <= the row's exact k-th best score
+//                                                                            screen_gemm_kernel<false>, jmac_row_topk_f32
+//   filter    the bf16 product over ALL N columns; (sh, j) joins row i's list unless sh + e < lower_i: every member of the exact
+//             top-k, ties included, is listed (slots claimed with integer atomics, one per row and flush)  screen_gemm_kernel<true>
+//   select    per row: lower'_i = the k-th largest sh - e of the list (>= lower_i); the entries with sh + e >= lower'_i are rescored
+//             with the fp32 product's own instruction sequence (sim_rescore.h), the k best of those exact scores are the answer;
+//                                                                                                          screen_select_kernel
+//             a row whose list overflowed recomputes all N scores (for_each_row_score + tk_select_recomputed)  screen_overflow_kernel
+// Comparisons are written !(x < y): a NaN passes and is then rescored exactly.  No float atomics; list order varies between runs,
+// the selection (a sort of (score, index) words) does not depend on it.
+#include "common.h"
+#include "sim_rescore.h"
+#include "topk_select.h"
+
+using namespace jmac;
+
+namespace {
+
+constexpr int kBlock = 256;
+static_assert(TK_THREADS == kBlock, "the selection routines stride by the block size");
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));        // 16 staged bytes (a native vector: stays in registers)
+
+constexpr int SC_T = 128;                   // 128 x 128 outputs per 4-wave block, waves 2 x 2, 64 x 64 each
+constexpr int SC_BK = 32;                   // k slab: two MFMA k-steps of 16
+constexpr int SC_ROWB = 2 * SC_BK;          // bytes per LDS row
+constexpr int SC_IMG = SC_T * SC_ROWB;      // one operand slab: 8 KB
+constexpr int SC_FL_CAP = 512;              // entries of a wave's LDS list
+constexpr int SC_FL_ROOM = 192;             // flush when a list has less room than this at a tile's end (a typical tile adds ~60)
+constexpr int SC_STRIP_MAX = 64;            // tiles per strip at most: a column's offset in its strip fits 16 bits
+constexpr int SC_CAP = TK_CAP;              // list entries per row
+constexpr int SC_KMAX = 64;
+constexpr int64_t SC_MIN_N = 8192;
+constexpr int64_t SC_DMAX = 512;
+
+// the bound's constants: KAPPA >= 2u + u^2 + 2 (d + 2) 2^-23 (1 + u)^2 for d <= 512 (0.0079513: u = 2^-8, the
+// accumulation counted at one ulp per operation) with 0.6 % to spare for the bound's own roundings; TAU and ETA cover what
+// underflows or is flushed on either path.  The prepare pass writes
+// ka_i = KAPPA (na_i + TAU) for A's rows and nbt_j = nb_j + TAU for B's: e is ONE fma per element, the same one in every kernel.
+constexpr float SC_KAPPA = 0.008f, SC_TAU = 0x1p-110f, SC_ETA = 0x1p-110f;
+__device__ __forceinline__ float screen_err(float ka, float nbt) { return __fmaf_rn(ka, nbt, SC_ETA); }
+
+static inline bool sc_fused(int64_t N, int64_t k) { return N >= SC_MIN_N && k <= SC_KMAX; }
+static inline int64_t sc_dp(int64_t d) { return (d + SC_BK - 1) / SC_BK * SC_BK; }
+// the sample: an eighth of the columns (the fp32 path takes a twelfth: the product is cheap here, and a larger sample is a tighter
+// lower_i, hence shorter lists)
+static inline int64_t sc_sample(int64_t N) {
+    const int64_t ns = N / 8 > 2048 ? N / 8 : 2048;
+    return (ns + 127) / 128 * 128;
+}
+struct ScWs { size_t ab, bb, na, nb, S, val0, idx0, cnt, cval, cidx, total; };
+static ScWs sc_layout(int64_t L, int64_t N, int64_t d, int64_t k) {
+    ScWs w{};
+    size_t off = 0;
+    w.ab = off;   off += align_up((size_t)L * (size_t)sc_dp(d) * 2);
+    w.bb = off;   off += align_up((size_t)N * (size_t)sc_dp(d) * 2);
+    w.na = off;   off += align_up((size_t)L * 4);
+    w.nb = off;   off += align_up((size_t)N * 4);
+    w.S = off;    off += align_up((size_t)L * (size_t)sc_sample(N) * 4);
+    w.val0 = off; off += align_up((size_t)L * (size_t)k * 4);
+    w.idx0 = off; off += align_up((size_t)L * (size_t)k * 4);
+    w.cnt = off;  off += align_up((size_t)L * 4);
+    w.cval = off; off += align_up((size_t)L * SC_CAP * 4);
+    w.cidx = off; off += align_up((size_t)L * SC_CAP * 4);
+    w.total = off + 256;
+    return w;
+}
+
+// ---- prepare: one wave per row: the row rounded to bf16 (nearest even), zero-padded to dp; norm[row] = scale (nrm + TAU) with
+// nrm >= ||row||_2 rounded up to fp32 --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void screen_prepare_kernel(const float* __restrict__ X, int64_t ldx, int rows, int d, int dp,
+                                                                float scale, bf16_t* __restrict__ Xb, float* __restrict__ norm) {
+    const int row = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float* x = X + (int64_t)row * ldx;
+    double ss = 0.0;                        // float64: the squares of the smallest fp32 rows do not underflow
+    for (int c = lane * 4; c < dp; c += 256) {
+        const float4 v = c < d ? ld4(x + c) : f4zero();
+        bf16x2 lo, hi;
+        lo.x = (__bf16)v.x;
+        lo.y = (__bf16)v.y;
+        hi.x = (__bf16)v.z;
+        hi.y = (__bf16)v.w;
+        *reinterpret_cast<uint2*>(Xb + (int64_t)row * dp + c) = make_uint2(__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi));
+        ss += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    if (lane == 0) {
+        // rounded UP to fp32: 1 + 2^-30 covers the float64 sum's and root's roundings; below the normal range the smallest normal
+        const double root = sqrt(ss) * (1.0 + 0x1p-30);
+        float f = (float)root;
+        if ((double)f < root) f = __uint_as_float(__float_as_uint(f) + 1u);
+        if (root > 0.0 && root < 0x1p-126) f = 0x1p-126f;
+        norm[row] = scale * (f + SC_TAU);
+    }
+}
+
+// ---- the bf16 product --------------------------------------------------------------------------------------------------------
+// LDS image of one operand slab: [row][32 k] bf16, 64-byte rows; the 16-byte chunk q (k = 8q .. 8q+7) of row r sits at chunk
+// q ^ ((r >> 2) & 3): the 16 rows a ds_read_b128 lane group touches cover all sixteen 4-dword bank slots (gemm3.hip's image)
+__device__ __forceinline__ int sc_lds_off(int row, int chunk) { return row * SC_ROWB + ((chunk ^ ((row >> 2) & 3)) << 4); }
+
+struct ScreenEpi {
+    const float* na;         // [M] ka: KAPPA (norm bound + TAU)
+    const float* nb;         // [N] nbt: norm bound + TAU
+    float* C;                // store: sh - e at C[m * ldc + n]
+    int64_t ldc;
+    const float* tau;        // filter: lower_m = tau[m * tau_stride]
+    int64_t tau_stride;
+    int* cnt;                // [M] entries seen per row (may exceed cap: the row then recomputes)
+    float* cval;             // [M, cap] sh
+    int* cidx;               // [M, cap]
+    int cap;
+};
+
+// A block owns a strip of `strip` consecutive 128 x 128 tiles of one row tile (m fastest over the blocks: those that share B tiles run
+// together; A's bf16 copy stays in L2).  Operands are the prepared bf16 rows (stride dp, a multiple of 32, zero-padded: no k clamp),
+// staged through registers into two LDS buffers, one barrier per slab; the next tile's first slab is requested before the epilogue.
+// The accumulator of v_mfma_f32_32x32x16_bf16 has the C/D map of the fp32 32x32x2 one (col = lane & 31, row = (reg & 3) +
+// 8 (reg >> 2) + 4 (lane >> 5)), so the epilogues are sim_gemm_kernel's with e folded in -- with one difference in the list form.
+// There a wave claims a list slot per passing element with a returned global atomic; behind the fp32 MFMAs those hide, behind the
+// bf16 ones they were half the kernel's time.  Here each wave compacts into its own LDS list across the
+// strip's tiles, and at a tile's end, when a list is nearly full (and after the last tile), the block counts its entries per row
+// in LDS and claims each row's slots with ONE integer atomic: ~10 x fewer.  A wave whose list is full claims slots directly.
+template <bool FILTER>
+__global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __restrict__ Ab, const bf16_t* __restrict__ Bb, int dp, int M,
+                                                                int N, int tiles_m, int tiles_n, int strip, ScreenEpi ext) {
+    __shared__ __attribute__((aligned(16))) unsigned char As[2][SC_IMG];
+    __shared__ __attribute__((aligned(16))) unsigned char Bs[2][SC_IMG];
+    __shared__ int fl_e[FILTER ? kBlock / 64 : 1][FILTER ? SC_FL_CAP : 1];      // (row in tile) << 16 | column in strip
+    __shared__ float fl_v[FILTER ? kBlock / 64 : 1][FILTER ? SC_FL_CAP : 1];
+    __shared__ int fl_count[kBlock / 64];
+    __shared__ int row_cnt[FILTER ? SC_T : 1], row_base[FILTER ? SC_T : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r = lane & 31, h = lane >> 5;
+    const int m0 = (int)(blockIdx.x % (unsigned)tiles_m) * SC_T;
+    const int tn0 = (int)(blockIdx.x / (unsigned)tiles_m) * strip, tn1 = min(tn0 + strip, tiles_n);
+    const int ns0 = tn0 * SC_T;             // the strip's first column
+
+    // loader: 16-byte chunk f = tid + 256 i (i < 2): row = f >> 2, chunk = f & 3 (4 consecutive lanes read one 64-byte row piece);
+    // unconditional at a clamped row (rows past the end re-read the last row: they feed outputs no epilogue keeps)
+    auto gload = [&](const bf16_t* base, int row0, int nrows, int k0, u32x4 (&v)[2]) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int f = tid + kBlock * i;
+            const int row = min(row0 + (f >> 2), nrows - 1);
+            v[i] = *reinterpret_cast<const u32x4*>(base + (int64_t)row * dp + k0 + 8 * (f & 3));
+        }
+    };
+    auto sstore = [&](unsigned char* S, const u32x4 (&v)[2]) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int f = tid + kBlock * i;
+            *reinterpret_cast<u32x4*>(S + sc_lds_off(f >> 2, f & 3)) = v[i];
+        }
+    };
+    // the epilogue's arguments as locals (the lambdas below capture values, not the by-value struct's address)
+    const float* const na_p = ext.na;
+    const float* const nb_p = ext.nb;
+    float* const C = ext.C;
+    const int64_t ldc = ext.ldc, tau_stride = ext.tau_stride;
+    const float* const tau_p = ext.tau;
+    int* const cnt = ext.cnt;
+    float* const cval = ext.cval;
+    int* const cidx = ext.cidx;
+    const int cap = ext.cap;
+    // per-row terms: lane l <-> row l of the wave's 64 rows, ONE coalesced load each, the value for accumulator register (i, reg)
+    // comes out with two v_readlane (sg_epi_lists' scheme)
+    const int mrow = min(m0 + wm * 64 + lane, M - 1);
+    const float narow = na_p[mrow];
+    float trow = 0.f;
+    if constexpr (FILTER) trow = tau_p[(int64_t)mrow * tau_stride];
+    int fcount = 0;                         // FILTER: entries in the wave's list (wave-uniform)
+    int* const fle = fl_e[FILTER ? wave : 0];
+    float* const flv = fl_v[FILTER ? wave : 0];
+    // FILTER, called by the whole block: the four lists -> the rows' candidate lists, one global atomic per row that has entries
+    auto flush_block = [&]() {
+        if (lane == 0) fl_count[wave] = fcount;
+        if (tid < SC_T) row_cnt[tid] = 0;
+        __syncthreads();
+        for (int w = 0; w < kBlock / 64; ++w)
+            for (int e = tid; e < fl_count[w]; e += kBlock) atomicAdd(&row_cnt[fl_e[w][e] >> 16], 1);
+        __syncthreads();
+        if (tid < SC_T) {
+            const int c = row_cnt[tid];
+            if (c > 0) row_base[tid] = atomicAdd(cnt + m0 + tid, c);
+            row_cnt[tid] = 0;
+        }
+        __syncthreads();
+        for (int w = 0; w < kBlock / 64; ++w)
+            for (int e = tid; e < fl_count[w]; e += kBlock) {
+                const int ml = fl_e[w][e] >> 16;
+                const int pos = row_base[ml] + atomicAdd(&row_cnt[ml], 1);
+                if (pos < cap) {
+                    cval[(int64_t)(m0 + ml) * cap + pos] = fl_v[w][e];
+                    cidx[(int64_t)(m0 + ml) * cap + pos] = ns0 + (fl_e[w][e] & 0xffff);
+                }
+            }
+        __syncthreads();
+        fcount = 0;
+    };
+
+    const int nk = dp / SC_BK;
+    u32x4 ra[2], rb[2];
+    gload(Ab, m0, M, 0, ra);
+    gload(Bb, ns0, N, 0, rb);
+    for (int tn = tn0; tn < tn1; ++tn) {
+        const int n0 = tn * SC_T;
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+        // (no wave reads the operand buffers any more: the last slab's barrier, or the flush's)
+        sstore(As[0], ra);
+        sstore(Bs[0], rb);
+        if (nk > 1) {
+            gload(Ab, m0, M, SC_BK, ra);
+            gload(Bb, n0, N, SC_BK, rb);
+        }
+        __syncthreads();
+        for (int kt = 0; kt < nk; ++kt) {
+            const int cur = kt & 1;
+#pragma unroll
+            for (int s = 0; s < SC_BK / 16; ++s) {
+                // lane (r, h) holds k = 16 s + 8 h .. + 7 of its row = chunk 2 s + h: one 16-byte read per 32 x 32 operand block
+                bf16x8 af[2], bf[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const bf16x8*>(As[cur] + sc_lds_off(wm * 64 + i * 32 + r, 2 * s + h));
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const bf16x8*>(Bs[cur] + sc_lds_off(wn * 64 + j * 32 + r, 2 * s + h));
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+            }
+            if (kt + 1 < nk) {              // the other buffer: every wave's reads of it ended before the last barrier
+                sstore(As[cur ^ 1], ra);
+                sstore(Bs[cur ^ 1], rb);
+                if (kt + 2 < nk) {
+                    gload(Ab, m0, M, (kt + 2) * SC_BK, ra);
+                    gload(Bb, n0, N, (kt + 2) * SC_BK, rb);
+                }
+            }
+            __syncthreads();
+        }
+        if (tn + 1 < tn1) {                 // the next tile's first slab flies across the epilogue
+            gload(Ab, m0, M, 0, ra);
+            gload(Bb, n0 + SC_T, N, 0, rb);
+        }
+        // (opaque copies: the per-register row terms and row addresses below are tile-invariant, and hoisted out of the strip loop
+        // they would hold over a hundred VGPRs across the MFMA loop)
+        float narow_t = narow, trow_t = trow;
+        int m0_t = m0, h_t = h;
+        asm volatile("" : "+v"(narow_t), "+v"(trow_t), "+s"(m0_t), "+v"(h_t));
+        float nbcol[2];                     // a lane's two column terms
+#pragma unroll
+        for (int j = 0; j < 2; ++j) nbcol[j] = nb_p[min(n0 + wn * 64 + j * 32 + r, N - 1)];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int rbase = i * 32 + (reg & 3) + 8 * (reg >> 2);           // compile-time
+                const int ml = wm * 64 + rbase + 4 * h_t, m = m0_t + ml;
+                const float na = h_t ? bcast_f(narow_t, rbase + 4) : bcast_f(narow_t, rbase);
+                float tau = 0.f;
+                if constexpr (FILTER) tau = h_t ? bcast_f(trow_t, rbase + 4) : bcast_f(trow_t, rbase);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int n = n0 + wn * 64 + j * 32 + r;
+                    const float v = acc[i][j][reg], e = screen_err(na, nbcol[j]);
+                    if constexpr (!FILTER) {
+                        if (m < M && n < N) C[(int64_t)m * ldc + n] = v - e;
+                    } else {
+                        const bool pass = m < M && n < N && !(v + e < tau);
+                        const unsigned long long mask = __ballot(pass);
+                        if (mask != 0ull) {                    // wave-uniform
+                            if (pass) {
+                                const int slot = fcount + __popcll(mask & ((1ull << lane) - 1ull));
+                                if (slot < SC_FL_CAP) {
+                                    fle[slot] = (ml << 16) | (n - ns0);
+                                    flv[slot] = v;
+                                } else {                       // the wave's list is full: its own slot, directly
+                                    const int pos = atomicAdd(cnt + m, 1);
+                                    if (pos < cap) {
+                                        cval[(int64_t)m * cap + pos] = v;
+                                        cidx[(int64_t)m * cap + pos] = n;
+                                    }
+                                }
+                            }
+                            fcount = min(fcount + __popcll(mask), SC_FL_CAP);
+                        }
+                    }
+                }
+                // (one register's tests at a time: scheduled ahead, the e and tau of all 64 would be live at once)
+                if constexpr (FILTER) __builtin_amdgcn_sched_barrier(0);
+            }
+        if constexpr (FILTER) {
+            // block-uniform: flush when some wave's list could not take a typical tile any more
+            const bool last = tn + 1 == tn1;
+            if (__syncthreads_or(fcount > SC_FL_CAP - SC_FL_ROOM) || last) flush_block();
+        }
+    }
+}
+
+// ---- prune, rescore, select: one block per row ---------------------------------------------------------------------------------
+// The rows whose list fits.  12 KB of LDS (the list's entries stay in their threads' registers between the two passes over them),
+// so eight blocks share a CU and their gathers of B's rows overlap; the overflowing rows are screen_overflow_kernel's.
+static_assert(SC_CAP == 4 * kBlock, "a thread holds four list entries");
+__global__ __launch_bounds__(kBlock) void screen_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                               int64_t ldb, int d, int k, const float* __restrict__ na,
+                                                               const float* __restrict__ nb, const int* __restrict__ cnt,
+                                                               const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
+                                                               float* __restrict__ val, int32_t* __restrict__ idx,
+                                                               int32_t* __restrict__ n_rescored) {
+    __shared__ unsigned long long skey[SC_CAP];
+    __shared__ int kept_n[SC_CAP];
+    __shared__ int s_kept;
+    __shared__ float s_lower;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int C = cnt[b];
+    if (C > cap) return;
+    const float* arow = A + (int64_t)b * lda;
+    // lower' = the k-th largest sh - e of the list (-inf if it has fewer than k entries)
+    const float nab = na[b];
+    if (tid == 0) s_kept = 0;
+    float hi[4];                            // sh + e of the thread's entries
+    int nn[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = tid + kBlock * i;
+        hi[i] = -INFINITY;
+        nn[i] = 0;
+        if (c < C) {
+            const float v = cval[(int64_t)b * cap + c];
+            nn[i] = cidx[(int64_t)b * cap + c];
+            const float e = screen_err(nab, nb[nn[i]]);
+            hi[i] = v + e;
+            skey[c] = tk_pack(v - e, nn[i]);
+        }
+    }
+    tk_sort_emit(skey, C, k, [&](int c, unsigned long long e) {
+        if (c == k - 1) s_lower = e == 0ull ? -INFINITY : tk_unpack_value(e);
+    });
+    __syncthreads();
+    // the entries that can still be among the k best; their order in the kept list is free (the last sort decides)
+    const float lower = s_lower;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (tid + kBlock * i < C && !(hi[i] < lower)) kept_n[atomicAdd(&s_kept, 1)] = nn[i];
+    __syncthreads();
+    const int K = s_kept;
+    // exact scores: the fp32 product's own sequence, 32 kept columns per wave step.  K is mostly under 64, two steps: odd rows give
+    // them to waves 2 and 3, so that a CU's blocks keep all four SIMDs' matrix pipes busy, not two.
+    const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    for (int c0 = ((wave + 2 * (b & 1)) & 3) * 32; c0 < K; c0 += 32 * (kBlock / 64)) {
+        const int n = kept_n[min(c0 + r, K - 1)];
+        const f32x16 acc = sim_row_tile_grouped(arow, Bm + (int64_t)n * ldb, d);
+        if (h == 0 && c0 + r < K) skey[c0 + r] = tk_pack(acc[0], n);
+    }
+    tk_sort_emit(skey, K, k, [&](int c, unsigned long long e) {
+        idx[(int64_t)b * k + c] = tk_unpack_index(e);
+        if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
+    });
+    if (tid == 0 && n_rescored) n_rescored[b] = K;
+}
+
+// A row whose list overflowed (mass ties: more than cap columns within e of its k-th score): every score recomputed with the
+// product's sequence and selected as jmac_sim_topk_f32's overflowing rows are: slow, exact.  The other rows' blocks return at once.
+__global__ __launch_bounds__(kBlock) void screen_overflow_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                                 int64_t ldb, int N, int d, int k, const int* __restrict__ cnt, int cap,
+                                                                 float* __restrict__ val, int32_t* __restrict__ idx,
+                                                                 int32_t* __restrict__ n_rescored) {
+    __shared__ TkShared tk;
+    const int b = blockIdx.x;
+    if (cnt[b] <= cap) return;
+    const float* arow = A + (int64_t)b * lda;
+    tk_select_recomputed(tk, k, [&](auto f) { for_each_row_score(arow, Bm, ldb, N, d, f); },
+                         [&](int c, unsigned long long e) {
+                             idx[(int64_t)b * k + c] = tk_unpack_index(e);
+                             if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
+                         });
+    if (threadIdx.x == 0 && n_rescored) n_rescored[b] = -1;
+}
+
+__global__ __launch_bounds__(kBlock) void screen_fill_kernel(int32_t* __restrict__ p, int64_t n, int32_t v) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// strip: as few tiles per block as fill the device once (3 resident blocks per CU): more blocks than that would queue behind them,
+// fewer leave CUs idle; the lists' contents do not depend on it
+template <bool FILTER>
+static int launch_screen_gemm(const bf16_t* Ab, const bf16_t* Bb, int64_t dp, int64_t M, int64_t N, const ScreenEpi& ext, hipStream_t st) {
+    const int64_t tiles_m = (M + SC_T - 1) / SC_T, tiles_n = (N + SC_T - 1) / SC_T;
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t resident = 3 * (int64_t)(cus > 0 ? cus : 256);
+    int64_t strip = (tiles_m * tiles_n + resident - 1) / resident;
+    strip = strip < 1 ? 1 : strip > SC_STRIP_MAX ? SC_STRIP_MAX : strip;
+    const int64_t blocks = tiles_m * ((tiles_n + strip - 1) / strip);
+    if (blocks >= INT32_MAX) return JMAC_ERANGE;
+    hipLaunchKernelGGL(screen_gemm_kernel<FILTER>, dim3((unsigned)blocks), dim3(kBlock), 0, st, Ab, Bb, (int)dp, (int)M, (int)N, (int)tiles_m,
+                       (int)tiles_n, (int)strip, ext);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t jmac_sim_topk_screened_workspace_bytes(int64_t L, int64_t N, int64_t d, int32_t k) {
+    if (L < 0 || N < 0 || d <= 0 || k <= 0) return 0;
+    if (!sc_fused(N, k)) return jmac_sim_topk_workspace_bytes(L, N, k);
+    return sc_layout(L, N, d, k).total;
+}
+
+int jmac_sim_topk_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, int32_t k,
+                               float* val, int32_t* idx, int32_t* n_rescored, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N) return JMAC_EINVAL;
+    if (L == 0) return JMAC_OK;
+    if (!A || !B || !idx) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || d % 4 || d > SC_DMAX) return JMAC_EDIM;
+    if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_sim_topk_screened_workspace_bytes(L, N, d, k)) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (!sc_fused(N, k)) {                                   // narrow: no screen, the fp32 entry's own code
+        if (int rc = jmac_sim_topk_f32(A, lda, B, ldb, L, N, d, k, val, idx, ws, ws_bytes, stream)) return rc;
+        if (n_rescored) hipLaunchKernelGGL(screen_fill_kernel, dim3((unsigned)((L + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n_rescored, L, -2);
+        return (int)hipGetLastError();
+    }
+    char* wb = (char*)ws;
+    const ScWs w = sc_layout(L, N, d, k);
+    const int64_t dp = sc_dp(d), Ns = sc_sample(N);
+    bf16_t* Ab = (bf16_t*)(wb + w.ab);
+    bf16_t* Bb = (bf16_t*)(wb + w.bb);
+    float* val0 = (float*)(wb + w.val0);
+    ScreenEpi e{};
+    e.na = (float*)(wb + w.na); e.nb = (float*)(wb + w.nb);
+    e.C = (float*)(wb + w.S); e.ldc = Ns;
+    e.tau = val0 + (k - 1); e.tau_stride = k;
+    e.cnt = (int*)(wb + w.cnt); e.cval = (float*)(wb + w.cval); e.cidx = (int*)(wb + w.cidx); e.cap = SC_CAP;
+    // 1. bf16 copies and norm bounds
+    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((L + 3) / 4)), dim3(kBlock), 0, st, A, lda, (int)L, (int)d, (int)dp, SC_KAPPA, Ab, (float*)e.na);
+    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((N + 3) / 4)), dim3(kBlock), 0, st, B, ldb, (int)N, (int)d, (int)dp, 1.f, Bb, (float*)e.nb);
+    // 2. lower_m = the k-th largest sh - e of row m over the first Ns columns
+    if (int rc = launch_screen_gemm<false>(Ab, Bb, dp, L, Ns, e, st)) return rc;
+    if (int rc = jmac_row_topk_f32(e.C, Ns, L, Ns, k, val0, (int32_t*)(wb + w.idx0), stream)) return rc;
+    // 3. all N columns, the sample's included, through the list epilogue
+    if (hipMemsetAsync(e.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
+    if (int rc = launch_screen_gemm<true>(Ab, Bb, dp, L, N, e, st)) return rc;
+    // 4. prune, rescore exactly, select
+    hipLaunchKernelGGL(screen_select_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)d, (int)k, e.na, e.nb, e.cnt, e.cval,
+                       e.cidx, e.cap, val, idx, n_rescored);
+    hipLaunchKernelGGL(screen_overflow_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, e.cnt, e.cap, val,
+                       idx, n_rescored);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -1,0 +1,81 @@
+// sim_rescore.h -- one row of A against rows of B with the similarity product's own contraction sequence: what score.hip's
+// overflowing rows recompute with, and what screen.hip rescores its surviving candidates with.  The bits are sim_gemm_kernel's.
+#pragma once
+#include "common.h"
+#include "topk_select.h"
+
+namespace jmac {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int SG_K = 16;                    // the product's k slab: the contraction order below is stated in it
+
+// One 32 x 32 tile of the product with sim_gemm_kernel's contraction sequence per output element: four v_mfma_f32_32x32x2_f32 per
+// (kt, q), planes k = 16 kt + 8 q + 4 h, clamped loads zeroed past d.  Lane (r = lane & 31, h = lane >> 5) supplies row r of
+// both operands; ROW0: only tile row 0 carries A (one row of A against 32 rows of B), the rest is padding.
+template <bool ROW0>
+__device__ __forceinline__ f32x16 sim_tile_32x32(const float* __restrict__ arow, const float* __restrict__ brow, int d) {
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int nk = (d + SG_K - 1) / SG_K;
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    for (int kt = 0; kt < nk; ++kt)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int k = kt * SG_K + 8 * q + 4 * h;
+            float4 a4 = ld4(arow + min(k, d - 4)), b4 = ld4(brow + min(k, d - 4));
+            if (k >= d) a4 = b4 = f4zero();
+            if (ROW0 && r != 0) a4 = f4zero();
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
+        }
+    return acc;
+}
+
+// sim_tile_32x32<true>'s register 0 -- one row of A against 32 rows of B -- with the SAME MFMA sequence (step t = 2 kt + q, planes
+// k = 8 t + 4 h, every step of every slab, zeros past d included), the loads of eight steps requested together: a caller with
+// a handful of tiles per row (screen.hip's rescoring) waits for memory once per group instead of once per step.
+__device__ __forceinline__ f32x16 sim_row_tile_grouped(const float* __restrict__ arow, const float* __restrict__ brow, int d) {
+    constexpr int G = 8;
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int steps = 2 * ((d + SG_K - 1) / SG_K);
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    for (int t0 = 0; t0 < steps; t0 += G) {
+        float4 a4[G], b4[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int k = 8 * min(t0 + g, steps - 1) + 4 * h;
+            a4[g] = ld4(arow + min(k, d - 4));
+            b4[g] = ld4(brow + min(k, d - 4));
+            if (k >= d) a4[g] = b4[g] = f4zero();
+            if (r != 0) a4[g] = f4zero();
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (t0 + g < steps) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[g].x, b4[g].x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[g].y, b4[g].y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[g].z, b4[g].z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[g].w, b4[g].w, acc, 0, 0, 0);
+            }
+    }
+    return acc;
+}
+
+// f(n, s(row, n)) for every column n of the row, the block's TK_THREADS / 64 waves taking 32 columns each per step
+template <class F>
+__device__ __forceinline__ void for_each_row_score(const float* __restrict__ arow, const float* __restrict__ Bm, int64_t ldb, int N,
+                                                   int d, F f) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    for (int n0 = wave * 32; n0 < N; n0 += 32 * (TK_THREADS / 64)) {
+        const f32x16 acc = sim_tile_32x32<true>(arow, Bm + (int64_t)min(n0 + r, N - 1) * ldb, d);
+        if (h == 0 && n0 + r < N) f(n0 + r, acc[0]);           // C/D map: row 0 = register 0 of the lanes with h == 0
+    }
+}
+
+}  // namespace jmac

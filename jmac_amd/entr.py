@@ -157,9 +157,10 @@ def seed_enlargement_triple_transferring(output1, output2, align_test_src, align
                 "ent_bases2": ent_bases2, "rel_bases1": rel_bases1, "rel_bases2": rel_bases2}
     if len(pairs):
         k = args.num_negative
+        screen = getattr(args, "sim_screen", None)          # "bf16": the screened top-k (the same indices, scoring.sim_topk)
         feeddict.update(
-            neg2_left=scoring.get_neg(pairs[:, 1].tolist(), output2, output1, k),       # train.py:183
-            neg_right=scoring.get_neg(pairs[:, 0].tolist(), output1, output2, k),       # :184
+            neg2_left=scoring.get_neg(pairs[:, 1].tolist(), output2, output1, k, screen=screen),       # train.py:183
+            neg_right=scoring.get_neg(pairs[:, 0].tolist(), output1, output2, k, screen=screen),       # :184
             neg_left=np.repeat(pairs[:, 0], k).astype(np.float64),                      # :189-193 (float arrays)
             neg2_right=np.repeat(pairs[:, 1], k).astype(np.float64),
             links=pairs)

@@ -214,8 +214,18 @@ def sim_matrix(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = N
     return c
 
 
-def sim_topk(a: torch.Tensor, b: torch.Tensor, k: int, return_values: bool = False):
-    """Indices [L,k] (int64) of the k most similar rows of b for every row of a (descending; ties -> lower index)."""
+def sim_topk(a: torch.Tensor, b: torch.Tensor, k: int, return_values: bool = False, screen: Optional[str] = None,
+             return_stats: bool = False):
+    """Indices [L,k] (int64) of the k most similar rows of b for every row of a (descending; ties -> lower index).
+
+    ``screen="bf16"``: the same indices and values bit for bit from ``jmac_sim_topk_screened_f32`` -- the bf16 matrix cores
+    decide which columns can be among a row's k best, those are rescored with the fp32 product's own instructions (row length
+    <= 512).  ``return_stats`` (screened form only) appends a dict: mean / max columns rescored per row, the rows whose list
+    overflowed and recomputed, and whether the shape was screened at all (one host read)."""
+    if screen not in (None, "bf16"):
+        raise ValueError("sim_topk: screen must be None or 'bf16', not %r" % (screen,))
+    if return_stats and screen is None:
+        raise ValueError("sim_topk: return_stats needs screen='bf16'")
     require_device(a, b)
     a, b = _rows16(a), _rows16(b)
     L_, d = a.shape
@@ -223,12 +233,29 @@ def sim_topk(a: torch.Tensor, b: torch.Tensor, k: int, return_values: bool = Fal
     L = lib()
     idx = torch.empty((L_, k), dtype=torch.int32, device=a.device)
     val = torch.empty((L_, k), dtype=torch.float32, device=a.device) if return_values else None
-    ws_bytes = int(L.jmac_sim_topk_workspace_bytes(L_, N, int(k)))
-    ws = workspace(ws_bytes, a.device)
-    check(L.jmac_sim_topk_f32(ptr(a), d, ptr(b), d, L_, N, d, int(k), ptr(val), ptr(idx), ptr(ws), ws_bytes, stream()),
-          "jmac_sim_topk_f32")
+    stats = None
+    if screen is None:
+        ws_bytes = int(L.jmac_sim_topk_workspace_bytes(L_, N, int(k)))
+        ws = workspace(ws_bytes, a.device)
+        check(L.jmac_sim_topk_f32(ptr(a), d, ptr(b), d, L_, N, d, int(k), ptr(val), ptr(idx), ptr(ws), ws_bytes, stream()),
+              "jmac_sim_topk_f32")
+    else:
+        nres = torch.empty(L_, dtype=torch.int32, device=a.device) if return_stats else None
+        ws_bytes = int(L.jmac_sim_topk_screened_workspace_bytes(L_, N, d, int(k)))
+        ws = workspace(ws_bytes, a.device)
+        check(L.jmac_sim_topk_screened_f32(ptr(a), d, ptr(b), d, L_, N, d, int(k), ptr(val), ptr(idx), ptr(nres), ptr(ws),
+                                           ws_bytes, stream()), "jmac_sim_topk_screened_f32")
+        if return_stats:
+            n = nres.cpu()
+            seen = n[n >= 0].to(torch.float64)
+            stats = dict(rows=L_, screened=bool(L_ == 0 or int(n.min()) > -2), overflow_rows=int((n == -1).sum()),
+                         rescored_mean=float(seen.mean()) if len(seen) else 0.0,
+                         rescored_max=int(seen.max()) if len(seen) else 0, n_rescored=n)
     idx = idx.to(torch.int64)
-    return (idx, val) if return_values else idx
+    out = (idx, val) if return_values else idx
+    if return_stats:
+        return out + (stats,) if return_values else (out, stats)
+    return out
 
 
 def row_topk(s: torch.Tensor, k: int):
@@ -260,10 +287,11 @@ def col_topk_values(s: torch.Tensor, k: int) -> torch.Tensor:
     return val
 
 
-def get_neg(ILL, emb_src: torch.Tensor, emb_dst: torch.Tensor, k: int) -> torch.Tensor:
-    """Same contract as modules/utils/util.py:31-54: flattened [len(ILL)*k] int64 indices into emb_dst."""
+def get_neg(ILL, emb_src: torch.Tensor, emb_dst: torch.Tensor, k: int, screen: Optional[str] = None) -> torch.Tensor:
+    """Same contract as modules/utils/util.py:31-54: flattened [len(ILL)*k] int64 indices into emb_dst.  ``screen``: as
+    ``sim_topk``'s (the same indices either way)."""
     ill = torch.as_tensor(ILL, dtype=torch.long, device=emb_src.device)
-    return sim_topk(emb_src.index_select(0, ill), emb_dst, k).reshape(-1)
+    return sim_topk(emb_src.index_select(0, ill), emb_dst, k, screen=screen).reshape(-1)
 
 
 def align_entropy(e1: torch.Tensor, e2: torch.Tensor, scale: float = 20.0):
@@ -473,10 +501,10 @@ def alignment_stats(emb1: torch.Tensor, emb2: torch.Tensor, list1, list2, scale:
 
 
 # ---- DBPv1 call sites (row a18): ONE embedding table on both sides ------------------------------------------------
-def get_neg_dbpv1(ILL, output_layer: torch.Tensor, k: int) -> torch.Tensor:
+def get_neg_dbpv1(ILL, output_layer: torch.Tensor, k: int, screen: Optional[str] = None) -> torch.Tensor:
     """get_neg(ILL, output_layer, k), JMAC_DBPv1/modules/utils/util.py:35-58: the k most similar rows of the WHOLE
     table (own KG and the entity itself included) for every entity of ILL, flattened [len(ILL)*k] int64."""
-    return get_neg(ILL, output_layer, output_layer, k)
+    return get_neg(ILL, output_layer, output_layer, k, screen=screen)
 
 
 def alignment_quality_dbpv1(embedding: torch.Tensor, list1, list2, scale: float = 20.0):
