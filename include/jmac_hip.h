@@ -611,6 +611,29 @@ int jmac_sim_csls_topk_viable_f32(const float* A, int64_t lda, const float* B, i
                                   const float* r1, const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k,
                                   float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
 
+/* jmac_sim_csls_topk_screened_f32 / jmac_sim_csls_topk_viable_screened_f32: the two entry points above, values, indices and tie
+ * order bit for bit, with the n1 x n2 x d work on the bf16 matrix cores -- jmac_sim_topk_screened_f32's scheme deciding on c.  For
+ * finite r1, r2 the value c = 2 s - r1 - r2, roundings included, is a non-decreasing function of s, so the screen's bounds
+ * fl(sh - e) <= s <= fl(sh + e) give c_lo <= c <= c_hi with the same expression: the k-th largest c_lo bounds a row's k-th best c
+ * from below, a column with c_hi under it is out, the survivors are rescored with the fp32 product's own instructions and c is
+ * formed from that exact s.  The viable predicate is monotone in c as well: a column raises a threshold only when it is viable at
+ * c_lo, is dropped unseen only when it is not viable at c_hi, and the exact predicate runs on the rescored c.  With r1 == r2 ==
+ * NULL the plain form is jmac_sim_topk_screened_f32 bit for bit.  n2 >= 8192 (k <= 64 always holds here); a narrower n2 runs the
+ * fp32 entry's code unchanged, with that entry's workspace, and n_rescored = -2; so does a viable call of fewer than 256 rows (a
+ * refill of a few gathered rows would pay the bf16 copy of all of B for less than it saves: measured), in the
+ * workspace sized below.  Checks and their order: the fp32 entries', then
+ * d % 4 == 0 and d <= 512 (JMAC_EDIM) and n1, n2 < 2^31 (JMAC_ERANGE), both ahead of the workspace check.  n_rescored [n1] (may be
+ * NULL): the columns row i rescored exactly; -1: the row's list overflowed and it recomputed all n2 values.  r1, r2 finite; no float
+ * atomics: two calls return the same bits. */
+size_t jmac_sim_csls_topk_screened_workspace_bytes(int64_t n1, int64_t n2, int64_t d, int32_t k);
+int jmac_sim_csls_topk_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                                    const float* r1, const float* r2, int32_t k, float* val, int32_t* idx, int32_t* n_rescored,
+                                    void* ws, size_t ws_bytes, jmac_stream_t stream);
+int jmac_sim_csls_topk_viable_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2,
+                                           int64_t d, const float* r1, const float* r2, const int32_t* row_id, const uint64_t* best,
+                                           int32_t k, float* val, int32_t* idx, int32_t* n_rescored, void* ws, size_t ws_bytes,
+                                           jmac_stream_t stream);
+
 /* Manhattan alignment (sim(metric='manhattan'), modules/finding/similarity.py:47-49): the three entry points above for
  * s(i,j) = 1 - dist(i,j), dist(i,j) = the single running fp32 sum over k = 0 .. d-1 of |A[i,k] - B[j,k]| -- jmac_l1_score_f32's bits,
  * the same from either side (|x - y| == |y - x|) -- and c(i,j) = 2*s(i,j) - r1[i] - r2[j]; r1 == r2 == NULL: c = s.  Every decision

@@ -47,10 +47,6 @@ __device__ __forceinline__ float add_absdiff(float acc, float a, float b) {
     return r;
 }
 
-// THE rescored value, in this order everywhere it is computed.  2 s is exact in fp32, so fma(2, s, -r1) and the unfused form round
-// identically: the bits do not depend on the compiler's contraction choice.
-__device__ __forceinline__ float csls_value(float s, float r1, float r2) { return 2.f * s - r1 - r2; }
-
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return __uint_as_float((uint32_t)(*p) << 16); }
 

@@ -16,6 +16,15 @@
 //             a row whose list overflowed recomputes all N scores (for_each_row_score + tk_select_recomputed)  screen_overflow_kernel
 // Comparisons are written !(x < y): a NaN passes and is then rescored exactly.  No float atomics; list order varies between runs,
 // the selection (a sort of (score, index) words) does not depend on it.
+//
+// jmac_sim_csls_topk_screened_f32 / jmac_sim_csls_topk_viable_screened_f32: the same stages deciding on the alignment value
+// c = csls_value(s, r1, r2).  For finite r1, r2 that is a non-decreasing function of s with its own roundings included (2 s is exact,
+// each subtraction rounds once, rounding is monotone), so with lo = fl(sh - e) <= s <= fl(sh + e) = hi
+//      c_lo = csls_value(lo, r1, r2) <= c <= csls_value(hi, r1, r2) = c_hi
+// and c_lo / c_hi take the places of sh - e / sh + e in all three decisions (the lists still hold sh: the select stage recomputes
+// both bounds).  The viable predicate tk_pack(c, row_id) > best[j] is monotone in c too: tk_pack(c_lo, id) > best[j] is "certainly
+// viable", !(tk_pack(c_hi, id) > best[j]) "certainly not".  Only certainly viable columns may raise a threshold, only certainly
+// non-viable ones are dropped unseen; the exact predicate runs on the rescored value (ScMode, ScreenAlign below).
 #include "common.h"
 #include "sim_rescore.h"
 #include "topk_select.h"
@@ -50,7 +59,29 @@ constexpr int64_t SC_DMAX = 512;
 constexpr float SC_KAPPA = 0.008f, SC_TAU = 0x1p-110f, SC_ETA = 0x1p-110f;
 __device__ __forceinline__ float screen_err(float ka, float nbt) { return __fmaf_rn(ka, nbt, SC_ETA); }
 
+// what a kernel decides on: the score itself (jmac_sim_topk_screened_f32), c = csls_value(s, r1, r2), or c over the viable columns
+// only -- there the rescoring is decided at run time (r1 == NULL: c = s), as in score.hip's viable forms
+enum ScMode { SC_PLAIN, SC_CSLS, SC_VIABLE };
+struct ScreenAlign {
+    const float* r1;                    // [M]
+    const float* r2;                    // [N]
+    const int32_t* row_id;              // SC_VIABLE: [M] the suitor a row stands for (the predicate's tie-break)
+    const unsigned long long* best;     // SC_VIABLE: [N] the reviewers' words
+};
+template <int MODE>
+__device__ __forceinline__ float sc_value(float s, float r1v, float r2v, bool cs) {
+    if constexpr (MODE == SC_PLAIN) return s;
+    else if constexpr (MODE == SC_CSLS) return csls_value(s, r1v, r2v);
+    else return cs ? csls_value(s, r1v, r2v) : s;
+}
+
 static inline bool sc_fused(int64_t N, int64_t k) { return N >= SC_MIN_N && k <= SC_KMAX; }
+// jmac_sim_csls_topk_viable_screened_f32 -- the matching runs' refill, a handful of gathered rows against the whole table -- screens
+// calls of at least this many rows.  Every call pays the bf16 copy of all of B; measured at 30000 x 300 against the fp32 entry
+// (profiles/align_screen_timing.txt): 1 row 0.095 / 0.084 ms, 32 rows 0.099 / 0.093 (the screen loses), 256 rows
+// 0.108 / 0.120, 2048 rows 0.278 / 0.475 (it wins): the smallest measured count at which it wins.
+constexpr int64_t SC_VIABLE_MIN_ROWS = 256;
+static inline bool sc_fused_viable(int64_t L, int64_t N, int64_t k) { return sc_fused(N, k) && L >= SC_VIABLE_MIN_ROWS; }
 static inline int64_t sc_dp(int64_t d) { return (d + SC_BK - 1) / SC_BK * SC_BK; }
 // the sample: an eighth of the columns (the fp32 path takes a twelfth: the product is cheap here, and a larger sample is a tighter
 // lower_i, hence shorter lists)
@@ -133,9 +164,17 @@ struct ScreenEpi {
 // bf16 ones they were half the kernel's time.  Here each wave compacts into its own LDS list across the
 // strip's tiles, and at a tile's end, when a list is nearly full (and after the last tile), the block counts its entries per row
 // in LDS and claims each row's slots with ONE integer atomic: ~10 x fewer.  A wave whose list is full claims slots directly.
-template <bool FILTER>
+// MODE (FILTER only): the test is on c_hi = sc_value(sh + e) and, SC_VIABLE, on its word against best[n]; the entry stays (sh, n).
+// The alignment forms' terms are a trailing ScreenAlign argument that SC_PLAIN does not have (AL is empty there: the plain
+// instantiations keep the argument list, and the instructions, they had before the alignment forms existed).
+__device__ __forceinline__ ScreenAlign sc_align() { return ScreenAlign{}; }
+__device__ __forceinline__ const ScreenAlign& sc_align(const ScreenAlign& al) { return al; }
+template <bool FILTER, int MODE = SC_PLAIN, class... AL>
 __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __restrict__ Ab, const bf16_t* __restrict__ Bb, int dp, int M,
-                                                                int N, int tiles_m, int tiles_n, int strip, ScreenEpi ext) {
+                                                                int N, int tiles_m, int tiles_n, int strip, ScreenEpi ext, AL... alp) {
+    static_assert(sizeof...(AL) == (MODE == SC_PLAIN ? 0 : 1), "SC_CSLS and SC_VIABLE take one ScreenAlign");
+    const ScreenAlign al = sc_align(alp...);
+    static_assert(FILTER || MODE == SC_PLAIN, "the sample is rescored by screen_sample_align_kernel");
     __shared__ __attribute__((aligned(16))) unsigned char As[2][SC_IMG];
     __shared__ __attribute__((aligned(16))) unsigned char Bs[2][SC_IMG];
     __shared__ int fl_e[FILTER ? kBlock / 64 : 1][FILTER ? SC_FL_CAP : 1];      // (row in tile) << 16 | column in strip
@@ -182,6 +221,17 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
     const float narow = na_p[mrow];
     float trow = 0.f;
     if constexpr (FILTER) trow = tau_p[(int64_t)mrow * tau_stride];
+    // MODE: the row's r1 and id ride with narow; cs: the value is rescored at all
+    bool cs = MODE == SC_CSLS;
+    float r1row = 0.f;
+    int ridrow = 0;
+    if constexpr (MODE != SC_PLAIN) {
+        if constexpr (MODE == SC_VIABLE) {
+            cs = al.r1 != nullptr;
+            ridrow = al.row_id[mrow];
+        }
+        r1row = cs ? al.r1[mrow] : 0.f;
+    }
     int fcount = 0;                         // FILTER: entries in the wave's list (wave-uniform)
     int* const fle = fl_e[FILTER ? wave : 0];
     float* const flv = fl_v[FILTER ? wave : 0];
@@ -270,6 +320,18 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
         float nbcol[2];                     // a lane's two column terms
 #pragma unroll
         for (int j = 0; j < 2; ++j) nbcol[j] = nb_p[min(n0 + wn * 64 + j * 32 + r, N - 1)];
+        float r1row_t = r1row, r2col[2] = {0.f, 0.f};
+        int ridrow_t = ridrow;
+        unsigned long long bestcol[2] = {0ull, 0ull};
+        if constexpr (MODE != SC_PLAIN) {
+            asm volatile("" : "+v"(r1row_t), "+v"(ridrow_t));
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int nc = min(n0 + wn * 64 + j * 32 + r, N - 1);
+                if (cs) r2col[j] = al.r2[nc];
+                if constexpr (MODE == SC_VIABLE) bestcol[j] = al.best[nc];
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -279,6 +341,11 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                 const float na = h_t ? bcast_f(narow_t, rbase + 4) : bcast_f(narow_t, rbase);
                 float tau = 0.f;
                 if constexpr (FILTER) tau = h_t ? bcast_f(trow_t, rbase + 4) : bcast_f(trow_t, rbase);
+                float r1v = 0.f;
+                int rid = 0;
+                if constexpr (MODE != SC_PLAIN) r1v = h_t ? bcast_f(r1row_t, rbase + 4) : bcast_f(r1row_t, rbase);
+                if constexpr (MODE == SC_VIABLE)
+                    rid = __float_as_int(h_t ? bcast_f(__int_as_float(ridrow_t), rbase + 4) : bcast_f(__int_as_float(ridrow_t), rbase));
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int n = n0 + wn * 64 + j * 32 + r;
@@ -286,7 +353,14 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                     if constexpr (!FILTER) {
                         if (m < M && n < N) C[(int64_t)m * ldc + n] = v - e;
                     } else {
-                        const bool pass = m < M && n < N && !(v + e < tau);
+                        bool pass;
+                        if constexpr (MODE == SC_PLAIN) {
+                            pass = m < M && n < N && !(v + e < tau);
+                        } else {
+                            const float chi = sc_value<MODE>(v + e, r1v, r2col[j], cs);
+                            pass = m < M && n < N && !(chi < tau);
+                            if constexpr (MODE == SC_VIABLE) pass = pass && tk_pack(chi, rid) > bestcol[j];
+                        }
                         const unsigned long long mask = __ballot(pass);
                         if (mask != 0ull) {                    // wave-uniform
                             if (pass) {
@@ -317,16 +391,44 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
     }
 }
 
+// The sample of the alignment forms, in place behind screen_gemm_kernel<false>: S[m][n] = sh - e becomes c_lo, and -inf in the viable
+// form unless the column is certainly viable (fewer than k of those: lower_m = -inf, every possibly viable column is listed)
+template <bool VIABLE>
+__global__ __launch_bounds__(kBlock) void screen_sample_align_kernel(float* __restrict__ S, int64_t lds, int n, ScreenAlign al) {
+    float* row = S + (int64_t)blockIdx.x * lds;
+    const bool cs = al.r1 != nullptr;
+    const float r1b = cs ? al.r1[blockIdx.x] : 0.f;
+    int rid = 0;
+    if constexpr (VIABLE) rid = al.row_id[blockIdx.x];
+    for (int j = threadIdx.x; j < n; j += kBlock) {
+        const float clo = cs ? csls_value(row[j], r1b, al.r2[j]) : row[j];
+        if constexpr (VIABLE) row[j] = tk_pack(clo, rid) > al.best[j] ? clo : -INFINITY;
+        else row[j] = clo;
+    }
+}
+
 // ---- prune, rescore, select: one block per row ---------------------------------------------------------------------------------
 // The rows whose list fits.  12 KB of LDS (the list's entries stay in their threads' registers between the two passes over them),
 // so eight blocks share a CU and their gathers of B's rows overlap; the overflowing rows are screen_overflow_kernel's.
 static_assert(SC_CAP == 4 * kBlock, "a thread holds four list entries");
+// a viable row may run out of columns: (idx -1, val -inf), cand_select_body's rule
+__device__ __forceinline__ void sc_emit_viable(int64_t at, unsigned long long e, float* __restrict__ val, int32_t* __restrict__ idx) {
+    const bool none = e == 0ull || tk_unpack_value(e) == -INFINITY;
+    idx[at] = none ? -1 : tk_unpack_index(e);
+    val[at] = none ? -INFINITY : tk_unpack_value(e);
+}
+
+// MODE: lower' is the k-th largest c_lo (SC_VIABLE: of the certainly viable entries), an entry is kept unless c_hi < lower' (or it
+// is certainly not viable), the exact score is rescored to c and, SC_VIABLE, put to the exact predicate before the last sort
+template <int MODE = SC_PLAIN, class... AL>
 __global__ __launch_bounds__(kBlock) void screen_select_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                                int64_t ldb, int d, int k, const float* __restrict__ na,
                                                                const float* __restrict__ nb, const int* __restrict__ cnt,
                                                                const float* __restrict__ cval, const int* __restrict__ cidx, int cap,
                                                                float* __restrict__ val, int32_t* __restrict__ idx,
-                                                               int32_t* __restrict__ n_rescored) {
+                                                               int32_t* __restrict__ n_rescored, AL... alp) {
+    static_assert(sizeof...(AL) == (MODE == SC_PLAIN ? 0 : 1), "SC_CSLS and SC_VIABLE take one ScreenAlign");
+    const ScreenAlign al = sc_align(alp...);
     __shared__ unsigned long long skey[SC_CAP];
     __shared__ int kept_n[SC_CAP];
     __shared__ int s_kept;
@@ -337,6 +439,16 @@ __global__ __launch_bounds__(kBlock) void screen_select_kernel(const float* __re
     const float* arow = A + (int64_t)b * lda;
     // lower' = the k-th largest sh - e of the list (-inf if it has fewer than k entries)
     const float nab = na[b];
+    bool cs = MODE == SC_CSLS;
+    float r1b = 0.f;
+    int rid = 0;
+    if constexpr (MODE != SC_PLAIN) {
+        if constexpr (MODE == SC_VIABLE) {
+            cs = al.r1 != nullptr;
+            rid = al.row_id[b];
+        }
+        r1b = cs ? al.r1[b] : 0.f;
+    }
     if (tid == 0) s_kept = 0;
     float hi[4];                            // sh + e of the thread's entries
     int nn[4];
@@ -349,8 +461,21 @@ __global__ __launch_bounds__(kBlock) void screen_select_kernel(const float* __re
             const float v = cval[(int64_t)b * cap + c];
             nn[i] = cidx[(int64_t)b * cap + c];
             const float e = screen_err(nab, nb[nn[i]]);
-            hi[i] = v + e;
-            skey[c] = tk_pack(v - e, nn[i]);
+            if constexpr (MODE == SC_PLAIN) {
+                hi[i] = v + e;
+                skey[c] = tk_pack(v - e, nn[i]);
+            } else {
+                const float r2n = cs ? al.r2[nn[i]] : 0.f;
+                const float clo = sc_value<MODE>(v - e, r1b, r2n, cs);
+                hi[i] = sc_value<MODE>(v + e, r1b, r2n, cs);
+                if constexpr (MODE == SC_VIABLE) {
+                    const unsigned long long held = al.best[nn[i]];
+                    skey[c] = tk_pack(clo, rid) > held ? tk_pack(clo, nn[i]) : 0ull;
+                    if (!(tk_pack(hi[i], rid) > held)) nn[i] = -1;         // certainly not viable
+                } else {
+                    skey[c] = tk_pack(clo, nn[i]);
+                }
+            }
         }
     }
     tk_sort_emit(skey, C, k, [&](int c, unsigned long long e) {
@@ -361,7 +486,7 @@ __global__ __launch_bounds__(kBlock) void screen_select_kernel(const float* __re
     const float lower = s_lower;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        if (tid + kBlock * i < C && !(hi[i] < lower)) kept_n[atomicAdd(&s_kept, 1)] = nn[i];
+        if (tid + kBlock * i < C && !(hi[i] < lower) && (MODE != SC_VIABLE || nn[i] >= 0)) kept_n[atomicAdd(&s_kept, 1)] = nn[i];
     __syncthreads();
     const int K = s_kept;
     // exact scores: the fp32 product's own sequence, 32 kept columns per wave step.  K is mostly under 64, two steps: odd rows give
@@ -370,33 +495,70 @@ __global__ __launch_bounds__(kBlock) void screen_select_kernel(const float* __re
     for (int c0 = ((wave + 2 * (b & 1)) & 3) * 32; c0 < K; c0 += 32 * (kBlock / 64)) {
         const int n = kept_n[min(c0 + r, K - 1)];
         const f32x16 acc = sim_row_tile_grouped(arow, Bm + (int64_t)n * ldb, d);
-        if (h == 0 && c0 + r < K) skey[c0 + r] = tk_pack(acc[0], n);
+        if (h == 0 && c0 + r < K) {
+            if constexpr (MODE == SC_PLAIN) {
+                skey[c0 + r] = tk_pack(acc[0], n);
+            } else {
+                const float c = sc_value<MODE>(acc[0], r1b, cs ? al.r2[n] : 0.f, cs);
+                if constexpr (MODE == SC_VIABLE) skey[c0 + r] = tk_pack(c, rid) > al.best[n] ? tk_pack(c, n) : 0ull;
+                else skey[c0 + r] = tk_pack(c, n);
+            }
+        }
     }
-    tk_sort_emit(skey, K, k, [&](int c, unsigned long long e) {
-        idx[(int64_t)b * k + c] = tk_unpack_index(e);
-        if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
-    });
+    if constexpr (MODE == SC_VIABLE) {
+        tk_sort_emit(skey, K, k, [&](int c, unsigned long long e) { sc_emit_viable((int64_t)b * k + c, e, val, idx); });
+    } else {
+        tk_sort_emit(skey, K, k, [&](int c, unsigned long long e) {
+            idx[(int64_t)b * k + c] = tk_unpack_index(e);
+            if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
+        });
+    }
     if (tid == 0 && n_rescored) n_rescored[b] = K;
 }
-
 // A row whose list overflowed (mass ties: more than cap columns within e of its k-th score): every score recomputed with the
 // product's sequence and selected as jmac_sim_topk_f32's overflowing rows are: slow, exact.  The other rows' blocks return at once.
+// MODE: on c, and SC_VIABLE over the columns that pass the exact predicate, as cand_select_body's overflowing rows.
+template <int MODE = SC_PLAIN, class... AL>
 __global__ __launch_bounds__(kBlock) void screen_overflow_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                                  int64_t ldb, int N, int d, int k, const int* __restrict__ cnt, int cap,
                                                                  float* __restrict__ val, int32_t* __restrict__ idx,
-                                                                 int32_t* __restrict__ n_rescored) {
+                                                                 int32_t* __restrict__ n_rescored, AL... alp) {
+    static_assert(sizeof...(AL) == (MODE == SC_PLAIN ? 0 : 1), "SC_CSLS and SC_VIABLE take one ScreenAlign");
+    const ScreenAlign al = sc_align(alp...);
     __shared__ TkShared tk;
     const int b = blockIdx.x;
     if (cnt[b] <= cap) return;
     const float* arow = A + (int64_t)b * lda;
-    tk_select_recomputed(tk, k, [&](auto f) { for_each_row_score(arow, Bm, ldb, N, d, f); },
-                         [&](int c, unsigned long long e) {
-                             idx[(int64_t)b * k + c] = tk_unpack_index(e);
-                             if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
-                         });
+    if constexpr (MODE == SC_PLAIN) {
+        tk_select_recomputed(tk, k, [&](auto f) { for_each_row_score(arow, Bm, ldb, N, d, f); },
+                             [&](int c, unsigned long long e) {
+                                 idx[(int64_t)b * k + c] = tk_unpack_index(e);
+                                 if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
+                             });
+    } else {
+        const bool cs = MODE == SC_CSLS || al.r1 != nullptr;
+        const float r1b = cs ? al.r1[b] : 0.f;
+        int rid = 0;
+        if constexpr (MODE == SC_VIABLE) rid = al.row_id[b];
+        tk_select_recomputed(
+            tk, k,
+            [&](auto f) {
+                for_each_row_score(arow, Bm, ldb, N, d, [&](int n, float v) {
+                    const float c = sc_value<MODE>(v, r1b, cs ? al.r2[n] : 0.f, cs);
+                    if (MODE != SC_VIABLE || tk_pack(c, rid) > al.best[n]) f(n, c);
+                });
+            },
+            [&](int c, unsigned long long e) {
+                if constexpr (MODE == SC_VIABLE) {
+                    sc_emit_viable((int64_t)b * k + c, e, val, idx);
+                } else {
+                    idx[(int64_t)b * k + c] = tk_unpack_index(e);
+                    if (val) val[(int64_t)b * k + c] = tk_unpack_value(e);
+                }
+            });
+    }
     if (threadIdx.x == 0 && n_rescored) n_rescored[b] = -1;
 }
-
 __global__ __launch_bounds__(kBlock) void screen_fill_kernel(int32_t* __restrict__ p, int64_t n, int32_t v) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n) p[i] = v;
@@ -404,8 +566,9 @@ __global__ __launch_bounds__(kBlock) void screen_fill_kernel(int32_t* __restrict
 
 // strip: as few tiles per block as fill the device once (3 resident blocks per CU): more blocks than that would queue behind them,
 // fewer leave CUs idle; the lists' contents do not depend on it
-template <bool FILTER>
-static int launch_screen_gemm(const bf16_t* Ab, const bf16_t* Bb, int64_t dp, int64_t M, int64_t N, const ScreenEpi& ext, hipStream_t st) {
+template <bool FILTER, int MODE = SC_PLAIN>
+static int launch_screen_gemm(const bf16_t* Ab, const bf16_t* Bb, int64_t dp, int64_t M, int64_t N, const ScreenEpi& ext, hipStream_t st,
+                              const ScreenAlign& al = ScreenAlign{}) {
     const int64_t tiles_m = (M + SC_T - 1) / SC_T, tiles_n = (N + SC_T - 1) / SC_T;
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
@@ -415,9 +578,83 @@ static int launch_screen_gemm(const bf16_t* Ab, const bf16_t* Bb, int64_t dp, in
     strip = strip < 1 ? 1 : strip > SC_STRIP_MAX ? SC_STRIP_MAX : strip;
     const int64_t blocks = tiles_m * ((tiles_n + strip - 1) / strip);
     if (blocks >= INT32_MAX) return JMAC_ERANGE;
-    hipLaunchKernelGGL(screen_gemm_kernel<FILTER>, dim3((unsigned)blocks), dim3(kBlock), 0, st, Ab, Bb, (int)dp, (int)M, (int)N, (int)tiles_m,
-                       (int)tiles_n, (int)strip, ext);
+    if constexpr (MODE == SC_PLAIN)
+        hipLaunchKernelGGL((screen_gemm_kernel<FILTER>), dim3((unsigned)blocks), dim3(kBlock), 0, st, Ab, Bb, (int)dp, (int)M, (int)N,
+                           (int)tiles_m, (int)tiles_n, (int)strip, ext);
+    else
+        hipLaunchKernelGGL((screen_gemm_kernel<FILTER, MODE, ScreenAlign>), dim3((unsigned)blocks), dim3(kBlock), 0, st, Ab, Bb, (int)dp,
+                           (int)M, (int)N, (int)tiles_m, (int)tiles_n, (int)strip, ext, al);
     return (int)hipGetLastError();
+}
+
+static int sc_fill_unscreened(int32_t* n_rescored, int64_t L, hipStream_t st) {
+    if (n_rescored) hipLaunchKernelGGL(screen_fill_kernel, dim3((unsigned)((L + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n_rescored, L, -2);
+    return (int)hipGetLastError();
+}
+
+// the four stages for a screened shape (sc_fused), every decision on what MODE names; al: SC_CSLS / SC_VIABLE's terms
+template <int MODE>
+static int sc_run(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, int32_t k, float* val,
+                  int32_t* idx, int32_t* n_rescored, void* ws, hipStream_t st, const ScreenAlign& al = ScreenAlign{}) {
+    char* wb = (char*)ws;
+    const ScWs w = sc_layout(L, N, d, k);
+    const int64_t dp = sc_dp(d), Ns = sc_sample(N);
+    bf16_t* Ab = (bf16_t*)(wb + w.ab);
+    bf16_t* Bb = (bf16_t*)(wb + w.bb);
+    float* val0 = (float*)(wb + w.val0);
+    ScreenEpi e{};
+    e.na = (float*)(wb + w.na); e.nb = (float*)(wb + w.nb);
+    e.C = (float*)(wb + w.S); e.ldc = Ns;
+    e.tau = val0 + (k - 1); e.tau_stride = k;
+    e.cnt = (int*)(wb + w.cnt); e.cval = (float*)(wb + w.cval); e.cidx = (int*)(wb + w.cidx); e.cap = SC_CAP;
+    const dim3 rows((unsigned)L), block(kBlock);
+    // 1. bf16 copies and norm bounds
+    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((L + 3) / 4)), block, 0, st, A, lda, (int)L, (int)d, (int)dp, SC_KAPPA, Ab, (float*)e.na);
+    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((N + 3) / 4)), block, 0, st, B, ldb, (int)N, (int)d, (int)dp, 1.f, Bb, (float*)e.nb);
+    // 2. lower_m = the k-th largest sh - e (c_lo; of the certainly viable columns) of row m over the first Ns columns
+    if (int rc = launch_screen_gemm<false>(Ab, Bb, dp, L, Ns, e, st)) return rc;
+    if constexpr (MODE != SC_PLAIN) hipLaunchKernelGGL(screen_sample_align_kernel<MODE == SC_VIABLE>, rows, block, 0, st, e.C, Ns, (int)Ns, al);
+    if (int rc = jmac_row_topk_f32(e.C, Ns, L, Ns, k, val0, (int32_t*)(wb + w.idx0), (jmac_stream_t)st)) return rc;
+    // 3. all N columns, the sample's included, through the list epilogue
+    if (hipMemsetAsync(e.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
+    if (int rc = launch_screen_gemm<true, MODE>(Ab, Bb, dp, L, N, e, st, al)) return rc;
+    // 4. prune, rescore exactly, select
+    if constexpr (MODE == SC_PLAIN) {
+        hipLaunchKernelGGL((screen_select_kernel<>), rows, block, 0, st, A, lda, B, ldb, (int)d, (int)k, e.na, e.nb, e.cnt, e.cval, e.cidx, e.cap,
+                           val, idx, n_rescored);
+        hipLaunchKernelGGL((screen_overflow_kernel<>), rows, block, 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, e.cnt, e.cap, val, idx, n_rescored);
+    } else {
+        hipLaunchKernelGGL((screen_select_kernel<MODE, ScreenAlign>), rows, block, 0, st, A, lda, B, ldb, (int)d, (int)k, e.na, e.nb, e.cnt, e.cval,
+                           e.cidx, e.cap, val, idx, n_rescored, al);
+        hipLaunchKernelGGL((screen_overflow_kernel<MODE, ScreenAlign>), rows, block, 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, e.cnt, e.cap, val,
+                           idx, n_rescored, al);
+    }
+    return (int)hipGetLastError();
+}
+
+// jmac_sim_csls_topk_screened_f32 (best == NULL) and jmac_sim_csls_topk_viable_screened_f32: the fp32 entries' checks in their order,
+// with the screen's two (row length, 2^31) ahead of the workspace
+static int sc_align_entry(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                          const float* r2, bool viable, const int32_t* row_id, const uint64_t* best, int32_t k, float* val, int32_t* idx,
+                          int32_t* n_rescored, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    if (L < 0 || N <= 0 || d <= 0 || k <= 0 || k > N || k > SC_KMAX || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (L == 0) return JMAC_OK;
+    if (!A || !B || !idx || (viable && (!val || !row_id || !best))) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || d % 4 || d > SC_DMAX) return JMAC_EDIM;
+    if (L >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
+    const bool screened = viable ? sc_fused_viable(L, N, k) : sc_fused(N, k);
+    if (!ws || ws_bytes < jmac_sim_csls_topk_screened_workspace_bytes(L, N, d, k)) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (!screened) {                                         // narrow, or a refill of a few rows: no screen, the fp32 entry's own code
+        const int rc = viable ? jmac_sim_csls_topk_viable_f32(A, lda, B, ldb, L, N, d, r1, r2, row_id, best, k, val, idx, ws, ws_bytes, stream)
+                              : jmac_sim_csls_topk_f32(A, lda, B, ldb, L, N, d, r1, r2, k, val, idx, ws, ws_bytes, stream);
+        return rc ? rc : sc_fill_unscreened(n_rescored, L, st);
+    }
+    ScreenAlign al{};
+    al.r1 = r1; al.r2 = r2; al.row_id = row_id; al.best = reinterpret_cast<const unsigned long long*>(best);
+    if (viable) return sc_run<SC_VIABLE>(A, lda, B, ldb, L, N, d, k, val, idx, n_rescored, ws, st, al);
+    if (r1) return sc_run<SC_CSLS>(A, lda, B, ldb, L, N, d, k, val, idx, n_rescored, ws, st, al);
+    return sc_run<SC_PLAIN>(A, lda, B, ldb, L, N, d, k, val, idx, n_rescored, ws, st);      // c = s: jmac_sim_topk_screened_f32's launches
 }
 
 }  // namespace
@@ -441,35 +678,30 @@ int jmac_sim_topk_screened_f32(const float* A, int64_t lda, const float* B, int6
     hipStream_t st = (hipStream_t)stream;
     if (!sc_fused(N, k)) {                                   // narrow: no screen, the fp32 entry's own code
         if (int rc = jmac_sim_topk_f32(A, lda, B, ldb, L, N, d, k, val, idx, ws, ws_bytes, stream)) return rc;
-        if (n_rescored) hipLaunchKernelGGL(screen_fill_kernel, dim3((unsigned)((L + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, n_rescored, L, -2);
-        return (int)hipGetLastError();
+        return sc_fill_unscreened(n_rescored, L, st);
     }
-    char* wb = (char*)ws;
-    const ScWs w = sc_layout(L, N, d, k);
-    const int64_t dp = sc_dp(d), Ns = sc_sample(N);
-    bf16_t* Ab = (bf16_t*)(wb + w.ab);
-    bf16_t* Bb = (bf16_t*)(wb + w.bb);
-    float* val0 = (float*)(wb + w.val0);
-    ScreenEpi e{};
-    e.na = (float*)(wb + w.na); e.nb = (float*)(wb + w.nb);
-    e.C = (float*)(wb + w.S); e.ldc = Ns;
-    e.tau = val0 + (k - 1); e.tau_stride = k;
-    e.cnt = (int*)(wb + w.cnt); e.cval = (float*)(wb + w.cval); e.cidx = (int*)(wb + w.cidx); e.cap = SC_CAP;
-    // 1. bf16 copies and norm bounds
-    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((L + 3) / 4)), dim3(kBlock), 0, st, A, lda, (int)L, (int)d, (int)dp, SC_KAPPA, Ab, (float*)e.na);
-    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((N + 3) / 4)), dim3(kBlock), 0, st, B, ldb, (int)N, (int)d, (int)dp, 1.f, Bb, (float*)e.nb);
-    // 2. lower_m = the k-th largest sh - e of row m over the first Ns columns
-    if (int rc = launch_screen_gemm<false>(Ab, Bb, dp, L, Ns, e, st)) return rc;
-    if (int rc = jmac_row_topk_f32(e.C, Ns, L, Ns, k, val0, (int32_t*)(wb + w.idx0), stream)) return rc;
-    // 3. all N columns, the sample's included, through the list epilogue
-    if (hipMemsetAsync(e.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
-    if (int rc = launch_screen_gemm<true>(Ab, Bb, dp, L, N, e, st)) return rc;
-    // 4. prune, rescore exactly, select
-    hipLaunchKernelGGL(screen_select_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)d, (int)k, e.na, e.nb, e.cnt, e.cval,
-                       e.cidx, e.cap, val, idx, n_rescored);
-    hipLaunchKernelGGL(screen_overflow_kernel, dim3((unsigned)L), dim3(kBlock), 0, st, A, lda, B, ldb, (int)N, (int)d, (int)k, e.cnt, e.cap, val,
-                       idx, n_rescored);
-    return (int)hipGetLastError();
+    return sc_run<SC_PLAIN>(A, lda, B, ldb, L, N, d, k, val, idx, n_rescored, ws, st);
+}
+
+size_t jmac_sim_csls_topk_screened_workspace_bytes(int64_t n1, int64_t n2, int64_t d, int32_t k) {
+    if (n1 < 0 || n2 < 0 || d <= 0 || k <= 0) return 0;
+    const size_t fp32 = jmac_sim_csls_topk_workspace_bytes(n1, n2, k);
+    if (!sc_fused(n2, k)) return fp32;
+    const size_t screened = sc_layout(n1, n2, d, k).total;    // (a viable call of a few rows runs the fp32 code in the same workspace)
+    return screened > fp32 ? screened : fp32;
+}
+
+int jmac_sim_csls_topk_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                                    const float* r1, const float* r2, int32_t k, float* val, int32_t* idx, int32_t* n_rescored, void* ws,
+                                    size_t ws_bytes, jmac_stream_t stream) {
+    return sc_align_entry(A, lda, B, ldb, n1, n2, d, r1, r2, false, nullptr, nullptr, k, val, idx, n_rescored, ws, ws_bytes, stream);
+}
+
+int jmac_sim_csls_topk_viable_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                                           const float* r1, const float* r2, const int32_t* row_id, const uint64_t* best, int32_t k,
+                                           float* val, int32_t* idx, int32_t* n_rescored, void* ws, size_t ws_bytes,
+                                           jmac_stream_t stream) {
+    return sc_align_entry(A, lda, B, ldb, n1, n2, d, r1, r2, true, row_id, best, k, val, idx, n_rescored, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -6,6 +6,10 @@
 
 namespace jmac {
 
+// THE rescored value, in this order everywhere it is computed.  2 s is exact in fp32, so fma(2, s, -r1) and the unfused form round
+// identically: the bits do not depend on the compiler's contraction choice.
+__device__ __forceinline__ float csls_value(float s, float r1, float r2) { return 2.f * s - r1 - r2; }
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int SG_K = 16;                    // the product's k slab: the contraction order below is stated in it
 

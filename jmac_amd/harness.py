@@ -247,11 +247,11 @@ def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pa
 
 
 @torch.no_grad()
-def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, k=16):
+def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, k=16, screen=None):
     """stable_alignment (JMAC_DBPv1/modules/finding/alignment.py:90-134) on the test pairs of a KG pair, run to convergence: the
     pairs' embeddings are selected as in ``evaluate_alignment``, the one-to-one matching comes from scoring.stable_alignment (no
     len(pairs)^2 matrix).  Returns (precision [%], stats): "stable alignment precision" (:128-133), the share of matched suitors
-    i with match1[i] == i, and the run's refills / proposals / unmatched / complete."""
+    i with match1[i] == i, and the run's refills / proposals / unmatched / complete.  ``screen``: scoring.stable_alignment's."""
     (ei1, et1), (ei2, et2) = graphs
     b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
     b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
@@ -265,7 +265,8 @@ def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGr
     p = torch.from_numpy(pairs).to(a1.device)
     k = min(int(k), len(pairs))
     match1, _, stats = scoring.stable_alignment(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), k, csls_k,
-                                                getattr(args, "eval_metric", "cosine"), bool(getattr(args, "eval_norm", False)))
+                                                getattr(args, "eval_metric", "cosine"), bool(getattr(args, "eval_norm", False)),
+                                                screen=screen)
     matched = match1 >= 0
     hits = (match1 == torch.arange(match1.numel(), device=match1.device)) & matched
     precision = 100.0 * float(hits.sum().item()) / max(1, int(matched.sum().item()))
@@ -273,11 +274,12 @@ def evaluate_stable_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGr
 
 
 @torch.no_grad()
-def evaluate_auction_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, k=16, eps=1e-3):
+def evaluate_auction_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, k=16, eps=1e-3,
+                               screen=None):
     """The optimal one-to-one alignment of the test pairs of a KG pair (what the literature reports as "Hungarian"; no counterpart
     in the reference): the pairs' embeddings are selected as in ``evaluate_alignment``, the assignment comes from
     scoring.auction_alignment (no len(pairs)^2 matrix).  Returns (precision [%], stats), counted as ``evaluate_stable_alignment``
-    counts it: the share of matched rows i with match1[i] == i."""
+    counts it: the share of matched rows i with match1[i] == i.  ``screen``: scoring.auction_alignment's."""
     (ei1, et1), (ei2, et2) = graphs
     b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
     b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
@@ -292,7 +294,7 @@ def evaluate_auction_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeG
     k = min(int(k), len(pairs))
     match1, _, _, stats = scoring.auction_alignment(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), k, csls_k,
                                                     getattr(args, "eval_metric", "cosine"), bool(getattr(args, "eval_norm", False)),
-                                                    eps=eps)
+                                                    eps=eps, screen=screen)
     matched = match1 >= 0
     hits = (match1 == torch.arange(match1.numel(), device=match1.device)) & matched
     precision = 100.0 * float(hits.sum().item()) / max(1, int(matched.sum().item()))

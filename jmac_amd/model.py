@@ -344,69 +344,76 @@ class JMAC(nn.Module):
                                      k, index, pred_head, table_dtype=getattr(self, "table_dtype", torch.float32))
 
     @staticmethod
-    def _alignment_terms(a, b, csls_k, down, sinkhorn):
+    def _alignment_terms(a, b, csls_k, down, sinkhorn, screen=None):
         """The rescoring terms of the two WHOLE (prepared) tables: csls_terms, or -- ``sinkhorn=dict(scale=.., iters=..)`` --
         scoring.sinkhorn_terms; the csls_k the scoring entry points are then called with (any positive one selects the terms)."""
         if sinkhorn is not None:
             return scoring.sinkhorn_terms(a, b, metric=down, normalize=False, **sinkhorn), max(int(csls_k), 1)
-        return (scoring.csls_terms(a, b, csls_k, down) if int(csls_k) > 0 else None), csls_k
+        return (scoring.csls_terms(a, b, csls_k, down, screen=screen) if int(csls_k) > 0 else None), csls_k
 
-    def alignment_topk(self, e_index, k, blocks, csls_k=10, metric="cosine", normalize=False, emb=None, sinkhorn=None):
+    def alignment_topk(self, e_index, k, blocks, csls_k=10, metric="cosine", normalize=False, emb=None, sinkhorn=None, screen=None):
         """The k best matches in KG 2 for the entities ``e_index`` of KG 1 (ids local to their KG): ``(idx int64 [B, k], val fp32
         [B, k])`` under the evaluator's CSLS-rescored similarity (scoring.alignment_topk: test_alignment_, train.py:105-113, without
         the matrix), best first, over ALL entities of both KGs -- the neighbourhood terms are those of the two whole tables.
         ``blocks``: the pair's two (edge_index, edge_type, ent_bases, rel_bases); ``emb``: their alignment embeddings
         ``(a1, a2)`` on the device (``get_emb_blocks(blocks, on_device=True)``), if the caller has them.
         ``sinkhorn=dict(scale=.., iters=..)``: the terms are scoring.sinkhorn_terms of the two whole tables instead -- the matches
-        under the Sinkhorn plan, val = (2 / scale) log P."""
+        under the Sinkhorn plan, val = (2 / scale) log P.  ``screen="bf16"``: scoring.alignment_topk's screened form (the same
+        bits; the CSLS terms of the whole tables screened as well)."""
         if emb is None:
             (a1, _), (a2, _) = self.get_emb_blocks(blocks, on_device=True)
         else:
             a1, a2 = emb
         a, b = scoring._alignment_operands(a1, a2, metric, normalize)
         down = "manhattan" if metric == "manhattan" else "inner"               # the operands are prepared: not again below
-        terms, csls_k = self._alignment_terms(a, b, csls_k, down, sinkhorn)
+        scoring._check_screen("alignment_topk", screen, down)
+        terms, csls_k = self._alignment_terms(a, b, csls_k, down, sinkhorn, screen)
         q = _idx(e_index, a1.device, a1.shape[0])
         if terms is not None:
             terms = (terms[0].index_select(0, q), terms[1])
-        return scoring.alignment_topk(a.index_select(0, q), b, k, csls_k, down, False, terms=terms)
+        return scoring.alignment_topk(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, screen=screen)
 
     def alignment_stable(self, e_index, blocks, k=16, csls_k=10, metric="cosine", normalize=False, max_refills=None, emb=None,
-                         sinkhorn=None):
+                         sinkhorn=None, screen=None):
         """A one-to-one alignment of the entities ``e_index`` of KG 1 (suitors, ids local to their KG) with ALL entities of KG 2
         (reviewers): ``(match1 int64 [B], val1 fp32 [B], stats)`` of scoring.stable_alignment -- the suitor-optimal stable matching
         under the evaluator's CSLS-rescored similarity (galeshapley, modules/finding/alignment.py:115-168, run to convergence),
         without the matrix; -1 = unmatched.  Ties between suitors go to the one listed first in ``e_index``.  The neighbourhood
-        terms are those of the two whole tables; ``blocks`` / ``emb`` / ``sinkhorn`` as in ``alignment_topk``."""
+        terms are those of the two whole tables; ``blocks`` / ``emb`` / ``sinkhorn`` / ``screen`` as in ``alignment_topk``."""
         if emb is None:
             (a1, _), (a2, _) = self.get_emb_blocks(blocks, on_device=True)
         else:
             a1, a2 = emb
         a, b = scoring._alignment_operands(a1, a2, metric, normalize)
         down = "manhattan" if metric == "manhattan" else "inner"
-        terms, csls_k = self._alignment_terms(a, b, csls_k, down, sinkhorn)
+        scoring._check_screen("alignment_stable", screen, down)
+        terms, csls_k = self._alignment_terms(a, b, csls_k, down, sinkhorn, screen)
         q = _idx(e_index, a1.device, a1.shape[0])
         if terms is not None:
             terms = (terms[0].index_select(0, q), terms[1])
-        return scoring.stable_alignment(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, max_refills=max_refills)
+        return scoring.stable_alignment(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, max_refills=max_refills,
+                                        screen=screen)
 
     def alignment_auction(self, e_index, blocks, k=16, csls_k=10, metric="cosine", normalize=False, eps=1e-3, max_rounds=None,
-                          emb=None, sinkhorn=None):
+                          emb=None, sinkhorn=None, screen=None):
         """The optimal one-to-one alignment of the entities ``e_index`` of KG 1 (ids local to their KG) with ALL entities of KG 2:
         ``(match1 int64 [B], val1 fp32 [B], price fp32, stats)`` of scoring.auction_alignment -- the assignment that maximises the
         total CSLS-rescored similarity to within min(B, N2) * eps ("Hungarian"), without the matrix; -1 = unmatched.  The
-        neighbourhood terms are those of the two whole tables; ``blocks`` / ``emb`` / ``sinkhorn`` as in ``alignment_topk``."""
+        neighbourhood terms are those of the two whole tables; ``blocks`` / ``emb`` / ``sinkhorn`` / ``screen`` as in
+        ``alignment_topk``."""
         if emb is None:
             (a1, _), (a2, _) = self.get_emb_blocks(blocks, on_device=True)
         else:
             a1, a2 = emb
         a, b = scoring._alignment_operands(a1, a2, metric, normalize)
         down = "manhattan" if metric == "manhattan" else "inner"
-        terms, csls_k = self._alignment_terms(a, b, csls_k, down, sinkhorn)
+        scoring._check_screen("alignment_auction", screen, down)
+        terms, csls_k = self._alignment_terms(a, b, csls_k, down, sinkhorn, screen)
         q = _idx(e_index, a1.device, a1.shape[0])
         if terms is not None:
             terms = (terms[0].index_select(0, q), terms[1])
-        return scoring.auction_alignment(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, eps=eps, max_rounds=max_rounds)
+        return scoring.auction_alignment(a.index_select(0, q), b, k, csls_k, down, False, terms=terms, eps=eps, max_rounds=max_rounds,
+                                         screen=screen)
 
     # ---- losses (src/jmac_model.py:237-292, :316-380): gathers + L1 / cosine fused in HIP (jmac_amd.losses),
     # the margin arithmetic on the resulting [T] / [L] vectors stays in torch ----------------------------

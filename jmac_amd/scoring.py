@@ -246,11 +246,7 @@ def sim_topk(a: torch.Tensor, b: torch.Tensor, k: int, return_values: bool = Fal
         check(L.jmac_sim_topk_screened_f32(ptr(a), d, ptr(b), d, L_, N, d, int(k), ptr(val), ptr(idx), ptr(nres), ptr(ws),
                                            ws_bytes, stream()), "jmac_sim_topk_screened_f32")
         if return_stats:
-            n = nres.cpu()
-            seen = n[n >= 0].to(torch.float64)
-            stats = dict(rows=L_, screened=bool(L_ == 0 or int(n.min()) > -2), overflow_rows=int((n == -1).sum()),
-                         rescored_mean=float(seen.mean()) if len(seen) else 0.0,
-                         rescored_max=int(seen.max()) if len(seen) else 0, n_rescored=n)
+            stats = _screen_stats(nres)
     idx = idx.to(torch.int64)
     out = (idx, val) if return_values else idx
     if return_stats:
@@ -595,37 +591,64 @@ def _check_k(who: str, k, n2: int) -> int:
     return k
 
 
-def _topk_bytes(metric: str, rows: int, n2: int, d: int, k: int) -> int:
-    """Workspace bytes of the fused top-k of ``rows`` rows on the machine ``metric`` runs on."""
+def _check_screen(who: str, screen, metric: str = "inner"):
+    """``screen`` is None or "bf16" (``sim_topk``'s rule); the L1 tile kernel has no bf16 form."""
+    if screen not in (None, "bf16"):
+        raise ValueError("%s: screen must be None or 'bf16', not %r" % (who, screen))
+    if screen is not None and _l1_metric(metric):
+        raise ValueError("%s: metric 'manhattan' has no screened form (screen must be None)" % who)
+
+
+def _topk_bytes(metric: str, rows: int, n2: int, d: int, k: int, screen: Optional[str] = None) -> int:
+    """Workspace bytes of the fused top-k of ``rows`` rows on the machine ``metric`` runs on (``screen``: of its screened form)."""
     if _l1_metric(metric):
         return int(lib().jmac_l1_csls_topk_workspace_bytes(rows, n2, d, k))
+    if screen is not None:
+        return int(lib().jmac_sim_csls_topk_screened_workspace_bytes(rows, n2, d, k))
     return int(lib().jmac_sim_csls_topk_workspace_bytes(rows, n2, k))
 
 
-def _csls_topk(a: torch.Tensor, b: torch.Tensor, k: int, r1=None, r2=None, metric: str = "inner", row_id=None, best=None, ws=None):
+def _csls_topk(a: torch.Tensor, b: torch.Tensor, k: int, r1=None, r2=None, metric: str = "inner", row_id=None, best=None, ws=None,
+               screen: Optional[str] = None, n_rescored: Optional[torch.Tensor] = None):
     """(idx int32 [n1, k], val fp32 [n1, k]) of jmac_{sim,l1}_csls_topk_f32 -- with ``best`` (and ``row_id``) of the _viable_f32 form --
-    on prepared operands (``_rows16``).  ``ws``: a caller-held workspace of at least ``_topk_bytes`` bytes, whose head is used."""
+    on prepared operands (``_rows16``).  ``ws``: a caller-held workspace of at least ``_topk_bytes`` bytes, whose head is used.
+    ``screen="bf16"``: the same bits from the _screened_f32 forms; ``n_rescored`` (int32 [n1], optional) takes their per-row counts."""
+    _check_screen("_csls_topk", screen, metric)
     n1, d = a.shape
     n2 = b.shape[0]
     idx = torch.empty((n1, k), dtype=torch.int32, device=a.device)
     val = torch.empty((n1, k), dtype=torch.float32, device=a.device)
-    ws_bytes = _topk_bytes(metric, n1, n2, d, k)
+    ws_bytes = _topk_bytes(metric, n1, n2, d, k, screen)
     ws = workspace(ws_bytes, a.device) if ws is None else ws
-    name = ("jmac_l1_csls_topk" if _l1_metric(metric) else "jmac_sim_csls_topk") + ("_f32" if best is None else "_viable_f32")
+    name = ("jmac_l1_csls_topk" if _l1_metric(metric) else "jmac_sim_csls_topk") + ("" if best is None else "_viable") + \
+        ("_f32" if screen is None else "_screened_f32")
     viable = () if best is None else (ptr(row_id), ptr(best))
-    check(getattr(lib(), name)(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), *viable, k, ptr(val), ptr(idx), ptr(ws), ws_bytes,
-                               stream()), name)
+    counts = () if screen is None else (ptr(n_rescored),)
+    check(getattr(lib(), name)(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), *viable, k, ptr(val), ptr(idx), *counts, ptr(ws),
+                               ws_bytes, stream()), name)
     return idx, val
 
 
-def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int, metric: str = "inner") -> Tuple[torch.Tensor, torch.Tensor]:
+def _screen_stats(n_rescored: torch.Tensor) -> dict:
+    """``sim_topk``'s statistics dict from a screened entry's per-row counts (one host read)."""
+    n = n_rescored.cpu()
+    seen = n[n >= 0].to(torch.float64)
+    return dict(rows=int(n.numel()), screened=bool(n.numel() == 0 or int(n.min()) > -2), overflow_rows=int((n == -1).sum()),
+                rescored_mean=float(seen.mean()) if len(seen) else 0.0, rescored_max=int(seen.max()) if len(seen) else 0,
+                n_rescored=n)
+
+
+def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int, metric: str = "inner",
+               screen: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(r1 [n1], r2 [n2])`` of csls_sim (similarity.py:58-78) for S = a @ b.T, which is never written: r1[i] is the mean of
     the ``csls_k`` largest entries of row i, r2[j] of column j.  Two fused top-k products: ``sim_topk(a, b)`` for the rows,
     ``sim_topk(b, a)`` for the columns -- every element of b a^T is the same commuting products in the same contraction order
     as the transposed element of a b^T, so both equal the stored forms (``row_topk(sim_matrix(a, b), k)[0].mean(1)``,
     ``col_topk_values(sim_matrix(a, b), k).mean(1)``) bit for bit.  1 <= csls_k <= 64.
     ``metric="manhattan"``: the same terms of S = 1 - l1_scores(a, b) from two fused L1 top-k passes; |x - y| == |y - x| and the
-    sum runs over k in the same order from either side, so the transposed pass has the stored matrix's bits as well."""
+    sum runs over k in the same order from either side, so the transposed pass has the stored matrix's bits as well.
+    ``screen="bf16"``: both products through ``sim_topk``'s screened form -- the same terms bit for bit."""
+    _check_screen("csls_terms", screen, metric)
     csls_k = int(csls_k)
     if not 1 <= csls_k <= CSLS_KMAX or csls_k > min(a.shape[0], b.shape[0]):
         raise ValueError("csls_terms: csls_k must lie in [1, min(%d, n1, n2)] (got %d)" % (CSLS_KMAX, csls_k))
@@ -633,8 +656,8 @@ def csls_terms(a: torch.Tensor, b: torch.Tensor, csls_k: int, metric: str = "inn
         require_device(a, b)
         a, b = _rows16(a.detach()), _rows16(b.detach())
         return _csls_topk(a, b, csls_k, metric=metric)[1].mean(1), _csls_topk(b, a, csls_k, metric=metric)[1].mean(1)
-    r1 = sim_topk(a, b, csls_k, return_values=True)[1].mean(1)
-    r2 = sim_topk(b, a, csls_k, return_values=True)[1].mean(1)
+    r1 = sim_topk(a, b, csls_k, return_values=True, screen=screen)[1].mean(1)
+    r2 = sim_topk(b, a, csls_k, return_values=True, screen=screen)[1].mean(1)
     return r1, r2
 
 
@@ -694,7 +717,7 @@ def sinkhorn_terms(emb1: torch.Tensor, emb2: torch.Tensor, scale: float = 50.0, 
     return f * w, g * w
 
 
-def _csls_operands(emb1, emb2, csls_k, metric, normalize, terms):
+def _csls_operands(emb1, emb2, csls_k, metric, normalize, terms, screen=None):
     require_device(emb1, emb2)
     a, b = _alignment_operands(emb1, emb2, metric, normalize)
     a, b = _rows16(a.detach()), _rows16(b.detach())
@@ -702,7 +725,7 @@ def _csls_operands(emb1, emb2, csls_k, metric, normalize, terms):
         raise ValueError("the two embedding tables disagree in width")
     r1 = r2 = None
     if int(csls_k) > 0:
-        r1, r2 = terms if terms is not None else csls_terms(a, b, csls_k, metric)
+        r1, r2 = terms if terms is not None else csls_terms(a, b, csls_k, metric, screen)
         r1, r2 = r1.contiguous(), r2.contiguous()
         if r1.shape != (a.shape[0],) or r2.shape != (b.shape[0],) or r1.dtype != torch.float32 or r2.dtype != torch.float32:
             raise ValueError("terms must be fp32 vectors of n1 and n2 entries")
@@ -736,12 +759,21 @@ def alignment_ranks(emb1: torch.Tensor, emb2: torch.Tensor, gold, csls_k: int = 
 
 
 def alignment_topk(emb1: torch.Tensor, emb2: torch.Tensor, k: int, csls_k: int = 10, metric: str = "cosine",
-                   normalize: bool = False, terms=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   normalize: bool = False, terms=None, screen: Optional[str] = None, return_stats: bool = False):
     """The alignment itself: ``(idx int64 [n1, k], val fp32 [n1, k])``, per row of emb1 the k best matches among the rows of emb2
     under ``alignment_sim(.., csls_k)``, best first (ties -> lower index first) == ``row_topk(alignment_sim(..), k)`` bit for
-    bit, without the n1 x n2 matrix (greedy_alignment's alignment_rest, alignment.py:10-112, is column 0).  1 <= k <= 64."""
-    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
-    idx, val = _csls_topk(a, b, _check_k("alignment_topk", k, b.shape[0]), r1, r2, metric)
+    bit, without the n1 x n2 matrix (greedy_alignment's alignment_rest, alignment.py:10-112, is column 0).  1 <= k <= 64.
+    ``screen="bf16"``: the same result bit for bit from jmac_sim_csls_topk_screened_f32 (the CSLS terms' two products screened as
+    well): the bf16 matrix cores rule columns out, the survivors are rescored with the fp32 product's own instructions (not for
+    'manhattan'; row length <= 512).  ``return_stats`` (screened form only) appends ``sim_topk``'s statistics dict."""
+    _check_screen("alignment_topk", screen, metric)
+    if return_stats and screen is None:
+        raise ValueError("alignment_topk: return_stats needs screen='bf16'")
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms, screen)
+    nres = torch.empty(a.shape[0], dtype=torch.int32, device=a.device) if return_stats else None
+    idx, val = _csls_topk(a, b, _check_k("alignment_topk", k, b.shape[0]), r1, r2, metric, screen=screen, n_rescored=nres)
+    if return_stats:
+        return idx.to(torch.int64), val, _screen_stats(nres)
     return idx.to(torch.int64), val
 
 
@@ -794,12 +826,15 @@ def stable_matching(idx: torch.Tensor, val: torch.Tensor, n2: int) -> Tuple[torc
 
 
 def alignment_topk_viable(emb1: torch.Tensor, emb2: torch.Tensor, k: int, best: torch.Tensor, row_id=None, csls_k: int = 10,
-                          metric: str = "cosine", normalize: bool = False, terms=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                          metric: str = "cosine", normalize: bool = False, terms=None,
+                          screen: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``alignment_topk`` over the reviewers a suitor can still win: column j counts for row m only if the word of
     (c(m, j), row_id[m]) -- larger c first, equal c -> lower id -- is above ``best[j]`` (int64 [n2], the reviewers' 64-bit words of
     a deferred-acceptance run, 0 = free).  ``row_id`` (default 0 .. n1-1) names the suitor each row stands for.  A row with fewer
-    than k such columns ends in (idx -1, val -inf).  With ``best`` all zero this is ``alignment_topk`` bit for bit."""
-    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    than k such columns ends in (idx -1, val -inf).  With ``best`` all zero this is ``alignment_topk`` bit for bit.
+    ``screen="bf16"``: the same bits from jmac_sim_csls_topk_viable_screened_f32 (as in ``alignment_topk``)."""
+    _check_screen("alignment_topk_viable", screen, metric)
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms, screen)
     n1, n2 = a.shape[0], b.shape[0]
     k = _check_k("alignment_topk_viable", k, n2)
     require_device(best)
@@ -809,13 +844,41 @@ def alignment_topk_viable(emb1: torch.Tensor, emb2: torch.Tensor, k: int, best: 
         torch.as_tensor(row_id, device=a.device).to(torch.int32).contiguous()
     if rid.shape != (n1,):
         raise ValueError("row_id must have one entry per row of emb1")
-    idx, val = _csls_topk(a, b, k, r1, r2, metric, rid, best.contiguous())
+    idx, val = _csls_topk(a, b, k, r1, r2, metric, rid, best.contiguous(), screen=screen)
     return idx.to(torch.int64), val
 
 
-def _refill_chunk_rows(metric: str, n1: int, n2: int, d: int, k: int, ws_bytes: int) -> int:
+# A refill gathers a handful of rows, and a screened call of any size pays the bf16 copy of the whole table: below this many rows the
+# fp32 entry is faster (measured).  The viable entry applies the same count itself (SC_VIABLE_MIN_ROWS, screen.hip);
+# the auction's refill runs through the plain entry, which screens whatever it is given, so that one is routed here.
+SCREEN_REFILL_MIN_ROWS = 256
+
+
+class _ScreenedCalls:
+    """Counts, on the device, the refill calls of a matching run that took the screen: a call's ``n_rescored`` is -2 throughout when
+    its shape ran the fp32 code (a narrow table; a viable refill of fewer rows than the library screens).  No host read per call."""
+
+    def __init__(self, device):
+        self.calls = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def buffer(self, rows: int) -> torch.Tensor:
+        self.n = torch.empty(rows, dtype=torch.int32, device=self.calls.device)
+        return self.n
+
+    def count(self):
+        self.calls += (self.n[:1] > -2)
+
+
+def _run_screen_stats(n_rescored: torch.Tensor, refills: _ScreenedCalls) -> dict:
+    """``stats["screen"]`` of a matching run: the initial call's list statistics and the refill calls that took the screen"""
+    s = _screen_stats(n_rescored)
+    return dict(rows=s["rows"], overflow_rows=s["overflow_rows"], rescored_mean=s["rescored_mean"],
+                refill_calls_screened=int(refills.calls.item()))
+
+
+def _refill_chunk_rows(metric: str, n1: int, n2: int, d: int, k: int, ws_bytes: int, screen: Optional[str] = None) -> int:
     """Most rows L whose top-k workspace AND gathered operand rows fit ``ws_bytes`` together (both grow linearly with L)."""
-    need = lambda rows: _topk_bytes(metric, rows, n2, d, k) + rows * d * 4 + 256      # noqa: E731
+    need = lambda rows: _topk_bytes(metric, rows, n2, d, k, screen) + rows * d * 4 + 256      # noqa: E731
     rows = n1
     while rows > 1 and need(rows) > ws_bytes:
         rows = max(1, min(rows - 1, rows * ws_bytes // need(rows)))
@@ -823,7 +886,7 @@ def _refill_chunk_rows(metric: str, n1: int, n2: int, d: int, k: int, ws_bytes: 
 
 
 def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k: int = 10, metric: str = "cosine",
-                     normalize: bool = False, terms=None, max_refills: Optional[int] = None):
+                     normalize: bool = False, terms=None, max_refills: Optional[int] = None, screen: Optional[str] = None):
     """A one-to-one alignment: ``(match1 int64 [n1], val1 fp32 [n1], stats)``, the suitor-optimal stable matching of the full
     n1 x n2 instance under c = ``alignment_sim(emb1, emb2, metric, normalize, csls_k)`` (suitors: rows of emb1; both sides prefer the
     larger c, ties -> lower index), without the matrix.  ``match1[i]`` is suitor i's reviewer or -1 (exactly max(0, n1 - n2)
@@ -833,17 +896,24 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
     candidates have rejected it gets the k best of the reviewers it could still win (the viable top-k), and so on until nobody is
     left without candidates.  A reviewer only trades up, so a reviewer left out of a refill would have rejected the suitor anyway:
     the result is that of the full lists.  One host read per round.  ``stats``: refills (rounds of refill), proposals, unmatched,
-    complete (False only when ``max_refills`` stopped the loop; suitors still open are -1 then)."""
-    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    complete (False only when ``max_refills`` stopped the loop; suitors still open are -1 then).
+    ``screen="bf16"``: the initial lists and every refill come from the screened top-k entries -- the same lists bit for bit, hence
+    the same run; ``stats["screen"]`` then holds rows, overflow_rows and rescored_mean of the initial call and the number of
+    refill calls that took the screen (refill_calls_screened: the library runs a viable refill of fewer than 256 rows on the fp32
+    code, where the bf16 copy of the whole table costs more than it saves)."""
+    _check_screen("stable_alignment", screen, metric)
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms, screen)
     n1, d = a.shape
     n2 = b.shape[0]
     k = _check_k("stable_alignment", k, n2)
     # one workspace for every top-k of the run; a refill's gathered rows of `a` live in its tail
-    ws_bytes = max(_topk_bytes(metric, n1, n2, d, k), _topk_bytes(metric, 1, n2, d, k) + d * 4 + 256)
+    ws_bytes = max(_topk_bytes(metric, n1, n2, d, k, screen), _topk_bytes(metric, 1, n2, d, k, screen) + d * 4 + 256)
     ws = workspace(ws_bytes, a.device)
-    idx, val = _csls_topk(a, b, k, r1, r2, metric, ws=ws)
+    nres = torch.empty(n1, dtype=torch.int32, device=a.device) if screen is not None else None
+    idx, val = _csls_topk(a, b, k, r1, r2, metric, ws=ws, screen=screen, n_rescored=nres)
     st = _StableState(idx, val, n2)
     refills = proposals = 0
+    refill_calls = _ScreenedCalls(a.device) if screen is not None else None
     complete = True
     chunk = 0
     while n1 > 0:
@@ -855,7 +925,7 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
             complete = False
             break
         ids = st.exhausted_ids(exhausted)
-        chunk = chunk or _refill_chunk_rows(metric, n1, n2, d, k, ws_bytes)
+        chunk = chunk or _refill_chunk_rows(metric, n1, n2, d, k, ws_bytes, screen)
         for lo in range(0, exhausted, chunk):
             rid = ids[lo:lo + chunk].contiguous()
             rows = rid.numel()
@@ -863,13 +933,18 @@ def stable_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k
             sub = ws[ws_bytes - rows * d * 4:].view(torch.float32).view(rows, d)       # (ws_bytes and the offset: multiples of 16)
             torch.index_select(a, 0, sel, out=sub)
             r1s = r1.index_select(0, sel) if r1 is not None else None
-            idx[sel], val[sel] = _csls_topk(sub, b, k, r1s, r2, metric, rid, st.best, ws)       # the workspace's head
+            nres_r = refill_calls.buffer(rows) if screen is not None else None
+            idx[sel], val[sel] = _csls_topk(sub, b, k, r1s, r2, metric, rid, st.best, ws, screen=screen, n_rescored=nres_r)   # the workspace's head
             st.ptr[sel] = 0
+            if screen is not None:
+                refill_calls.count()
         refills += 1
     m1 = st.match1.to(torch.int64)
     held = (st.ptr & 0x7fffffff).to(torch.int64).clamp_(max=k - 1).unsqueeze(1)
     val1 = torch.where(m1 >= 0, val.gather(1, held).squeeze(1), torch.full_like(val[:, 0], float("-inf")))
     stats = {"refills": refills, "proposals": proposals, "unmatched": int((m1 < 0).sum().item()), "complete": complete}
+    if screen is not None:
+        stats["screen"] = _run_screen_stats(nres, refill_calls)
     return m1, val1, stats
 
 
@@ -904,7 +979,8 @@ class _AuctionState:
 
 
 def auction_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_k: int = 10, metric: str = "cosine",
-                      normalize: bool = False, terms=None, eps: float = 1e-3, max_rounds: Optional[int] = None, form: int = 0):
+                      normalize: bool = False, terms=None, eps: float = 1e-3, max_rounds: Optional[int] = None, form: int = 0,
+                      screen: Optional[str] = None):
     """The OPTIMAL one-to-one alignment: ``(match1 int64 [n1], val1 fp32 [n1], price fp32, stats)``, the assignment that maximises
     the total of c = ``alignment_sim(emb1, emb2, metric, normalize, csls_k)`` over all one-to-one matchings of the smaller side (what
     the entity-alignment literature reports as "Hungarian"), to within min(n1, n2) * eps, without the n1 x n2 matrix.  ``match1[i]`` is
@@ -921,13 +997,16 @@ def auction_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_
 
     ``stats``: rounds, bids, batches (host reads), refills, refill_rows, unmatched, complete (False only when ``max_rounds`` stopped
     the run; rows still open are -1 then), eps, transposed.  ``form``: 0 lets the library pick the launch form of every batch from
-    the open count, 1 holds it to the grid form (the same bits)."""
+    the open count, 1 holds it to the grid form (the same bits).  ``screen="bf16"``: the initial lists and every price-carrying
+    refill of at least ``SCREEN_REFILL_MIN_ROWS`` rows (r2 + price is one more finite r2) come from the screened top-k entry, bit
+    for bit the same; smaller refills stay on the fp32 entry, which is faster there.  ``stats["screen"]`` as in ``stable_alignment``."""
+    _check_screen("auction_alignment", screen, metric)
     eps = float(eps)
     if not (eps > 0.0 and np.isfinite(eps)):
         raise ValueError("auction_alignment: eps must be finite and positive (got %r)" % eps)
     if emb1.dim() != 2 or emb2.dim() != 2 or emb1.shape[0] == 0 or emb2.shape[0] == 0:
         raise ValueError("auction_alignment: empty operand")
-    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms, screen)
     transposed = a.shape[0] > b.shape[0]
     if transposed:                                                  # columns bid for rows: c^T, the terms change sides
         a, b, r1, r2 = b, a, r2, r1
@@ -937,9 +1016,11 @@ def auction_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_
     if not 2 <= k <= min(CSLS_KMAX, n2):
         raise ValueError("auction_alignment: k must lie in [2, min(64, n2)] (got %d, n2 = %d)" % (k, n2))
     dev = a.device
-    ws_bytes = max(_topk_bytes(metric, n1, n2, d, k), _topk_bytes(metric, 1, n2, d, k) + d * 4 + 256)
+    ws_bytes = max(_topk_bytes(metric, n1, n2, d, k, screen), _topk_bytes(metric, 1, n2, d, k, screen) + d * 4 + 256)
     ws = workspace(ws_bytes, dev)
-    idx, val = _csls_topk(a, b, k, r1, r2, metric, ws=ws)
+    nres = torch.empty(n1, dtype=torch.int32, device=dev) if screen is not None else None
+    idx, val = _csls_topk(a, b, k, r1, r2, metric, ws=ws, screen=screen, n_rescored=nres)
+    refill_calls = _ScreenedCalls(dev) if screen is not None else None
     st = _AuctionState(idx, val, n2, eps)
     stats = {"rounds": 0, "bids": 0, "batches": 0, "refills": 0, "refill_rows": 0}
     complete = True
@@ -959,7 +1040,7 @@ def auction_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_
             continue
         # the rows at -2, ascending (a stable sort of "is not waiting" lists them first: no second host read)
         ids = torch.sort((st.match1 != -2).to(torch.uint8), stable=True).indices[:waiting]
-        chunk = chunk or _refill_chunk_rows(metric, n1, n2, d, k, ws_bytes)
+        chunk = chunk or _refill_chunk_rows(metric, n1, n2, d, k, ws_bytes, screen)
         if r2 is not None:
             r2p = r2 + st.price
         else:
@@ -970,7 +1051,11 @@ def auction_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_
             sub = ws[ws_bytes - rows * d * 4:].view(torch.float32).view(rows, d)
             torch.index_select(a, 0, sel, out=sub)
             r1s = r1.index_select(0, sel) if r1 is not None else torch.zeros(rows, dtype=torch.float32, device=dev)
-            nidx, nval = _csls_topk(sub, b, k, r1s, r2p, metric, ws=ws)
+            if screen is not None and rows >= SCREEN_REFILL_MIN_ROWS:
+                nidx, nval = _csls_topk(sub, b, k, r1s, r2p, metric, ws=ws, screen=screen, n_rescored=refill_calls.buffer(rows))
+                refill_calls.count()
+            else:
+                nidx, nval = _csls_topk(sub, b, k, r1s, r2p, metric, ws=ws)
             if r2 is None:
                 nval = nval * 0.5                                    # (2 S - 2 price) / 2: exact
             idx[sel], val[sel] = nidx, nval
@@ -991,6 +1076,8 @@ def auction_alignment(emb1: torch.Tensor, emb2: torch.Tensor, k: int = 16, csls_
         vals_of[m1[got]] = val1[got]
         m1, val1 = rows_of, vals_of
     stats.update(unmatched=int((m1 < 0).sum().item()), complete=complete, eps=eps, transposed=transposed)
+    if screen is not None:
+        stats["screen"] = _run_screen_stats(nres, refill_calls)
     return m1, val1, price, stats
 
 

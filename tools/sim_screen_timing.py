@@ -20,8 +20,8 @@ sys.path.insert(0, ROOT)
 
 K = 25
 CASES = [(3000, 30000, 300, "unit"), (3000, 30000, 300, "emb"), (2264, 13996, 256, "unit"), (2264, 13996, 256, "emb")]
-STAGES = [("screen_prepare_kernel", "prepare (bf16 copies, norms)"), ("screen_gemm_kernel<false>", "sample product (bf16)"),
-          ("row_topk_kernel", "sample row top-k"), ("screen_gemm_kernel<true>", "filter product (bf16)"),
+STAGES = [("screen_prepare_kernel", "prepare (bf16 copies, norms)"), ("screen_gemm_kernel<false", "sample product (bf16)"),
+          ("row_topk_kernel", "sample row top-k"), ("screen_gemm_kernel<true", "filter product (bf16)"),
           ("screen_select_kernel", "prune + rescore + select"), ("sim_gemm_kernel", "fp32 product (sample + filter)"),
           ("cand_select_kernel", "fp32 entry's select")]
 
