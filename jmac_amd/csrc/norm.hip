@@ -457,7 +457,7 @@ __global__ __launch_bounds__(kBlock) void row_normalize_bwd_kernel(const float* 
 // y = x * inv * m  with m = mask * scale (mask: the caller's {0,1} draws; NULL = no dropout).  The backward recomputes the
 // normalised row from x and inv (nothing but inv [N] is kept from the forward):
 //   gn = g * m;  gx (+)= inv * (gn - xn (gn . xn)),  xn = x * inv   (no radial term on rows whose norm was clamped)
-// one wave per row, 16 bytes per lane (d % 4 == 0, leading dimensions % 4 == 0).
+// 16 bytes per lane (d % 4 == 0, leading dimensions % 4 == 0).
 // Dropout draws made in the kernel (SEED form): Philox4x32-10 keyed by the caller's device-resident seed, counter = index of
 // the float4 (row * d/4 + column quad): its four words decide the four elements.  The backward regenerates the same draws, so
 // no mask tensor is written or read (28 MB each way at DBP-5L size, plus the launch that drew it).  (philox4x32_10: common.h)
@@ -468,6 +468,11 @@ struct DropSrc {
     uint32_t keep_thr;       // keep iff word < keep_thr  (keep probability = keep_thr / 2^32)
     float scale;
 };
+__device__ __forceinline__ uint2 drop_key(const DropSrc& ds, bool seeded) {
+    if (!seeded) return make_uint2(0u, 0u);
+    const uint64_t sd = (uint64_t)ds.seed[0];
+    return make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
+}
 template <bool SEED>
 __device__ __forceinline__ float4 drop_factors(const DropSrc& s, uint2 key, int64_t r, int c, int D4) {
     if (SEED) {
@@ -480,332 +485,59 @@ __device__ __forceinline__ float4 drop_factors(const DropSrc& s, uint2 key, int6
     return make_float4(m.x * s.scale, m.y * s.scale, m.z * s.scale, m.w * s.scale);
 }
 
-template <bool SEED>
-__global__ __launch_bounds__(kBlock) void row_normalize_drop_fwd_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int D4,
-                                                                        float eps, DropSrc ds, float* __restrict__ y, int64_t ldy,
-                                                                        float* __restrict__ inv) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
-    uint2 key = make_uint2(0u, 0u);
-    if (SEED) {
-        const uint64_t sd = (uint64_t)ds.seed[0];
-        key = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
-    }
-    const bool drop = SEED || ds.mask != nullptr;
-    for (int64_t r = w0; r < N; r += nw) {
-        const float* xr = x + r * ldx;
-        float ss = 0.f;
-        for (int c = lane; c < D4; c += 64) {
-            const float4 v = ld4(xr + c * 4);
-            ss = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, ss))));
-        }
-        ss = wave_sum(ss);
-        const float iv = 1.f / fmaxf(sqrtf(ss), eps);
-        for (int c = lane; c < D4; c += 64) {
-            float4 v = ld4(xr + c * 4);
-            v.x *= iv; v.y *= iv; v.z *= iv; v.w *= iv;
-            if (drop) {
-                const float4 m = drop_factors<SEED>(ds, key, r, c, D4);
-                v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
-            }
-            st4(y + r * ldy + c * 4, v);
-        }
-        if (lane == 0) inv[r] = iv;
-    }
-}
+// Where a lane stands: its wave among the grid's (kBlock / 64 per block; waves take rows or row groups w0, w0 + nw, ...) and, for
+// the kernels that hold whole rows in registers (d <= 512), its two column quads cc[k] with ok[k] = inside the row.
+struct WaveLanes {
+    int lane;
+    int64_t w0, nw;
+    int cc[2];
+    bool ok[2];
+    __device__ __forceinline__ explicit WaveLanes(int D4)
+        : lane(lane_id()), w0((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)), nw((int64_t)gridDim.x * (kBlock / 64)),
+          cc{lane, lane + 64}, ok{cc[0] < D4, cc[1] < D4} {}
+};
 
-template <bool SEED>
-__global__ __launch_bounds__(kBlock) void row_normalize_drop_bwd_kernel(const float* __restrict__ x, int64_t ldx,
-                                                                        const float* __restrict__ inv, DropSrc ds,
-                                                                        const float* __restrict__ g, int64_t ldg, int64_t N, int D4,
-                                                                        float eps, float* __restrict__ gx, int64_t ldgx,
-                                                                        int accumulate) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
-    uint2 key = make_uint2(0u, 0u);
-    if (SEED) {
-        const uint64_t sd = (uint64_t)ds.seed[0];
-        key = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
-    }
-    const bool drop = SEED || ds.mask != nullptr;
-    for (int64_t r = w0; r < N; r += nw) {
-        const float* xr = x + r * ldx;
-        const float* gr = g + r * ldg;
-        const float iv = inv[r];
-        float dot = 0.f;
-        for (int c = lane; c < D4; c += 64) {
-            const float4 v = ld4(xr + c * 4);
-            float4 q = ld4(gr + c * 4);
-            if (drop) {
-                const float4 m = drop_factors<SEED>(ds, key, r, c, D4);
-                q.x *= m.x; q.y *= m.y; q.z *= m.z; q.w *= m.w;
-            }
-            dot = fmaf(q.x, v.x * iv, fmaf(q.y, v.y * iv, fmaf(q.z, v.z * iv, fmaf(q.w, v.w * iv, dot))));
-        }
-        dot = wave_sum(dot);
-        if (iv * eps >= 1.f) dot = 0.f;                // ||x|| <= eps: y = x / eps, no radial term
-        for (int c = lane; c < D4; c += 64) {
-            const float4 v = ld4(xr + c * 4);
-            float4 q = ld4(gr + c * 4);
-            if (drop) {
-                const float4 m = drop_factors<SEED>(ds, key, r, c, D4);
-                q.x *= m.x; q.y *= m.y; q.z *= m.z; q.w *= m.w;
-            }
-            float4 o;
-            o.x = iv * (q.x - v.x * iv * dot); o.y = iv * (q.y - v.y * iv * dot);
-            o.z = iv * (q.z - v.z * iv * dot); o.w = iv * (q.w - v.w * iv * dot);
-            if (accumulate) {
-                const float4 p = ld4(gx + r * ldgx + c * 4);
-                o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w;
-            }
-            st4(gx + r * ldgx + c * 4, o);
-        }
-    }
-}
-
-// ---- the same two kernels with R rows per wave in flight (rows of up to 128 float4: d <= 512) ---------------------------------
-// The forms above give every row a wave that reads it, reduces, reads it AGAIN and writes: two dependent round trips per row and
-// (backward) two Philox evaluations per element; at DBP-5L size (11 805 rows x 300) they move 28-56 MB at 2.2 TB/s.  Here a wave
-// keeps R rows in registers (two float4 per lane and row), issues all their loads before the first reduction (interleaved DPP
-// chains: wave_sum_n) and writes from registers.  Per-lane summation order as above: the same bits.
-template <bool SEED, int R>
-__global__ __launch_bounds__(kBlock) void row_normalize_drop_fwd_rows_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int D4,
-                                                                             float eps, DropSrc ds, float* __restrict__ y, int64_t ldy,
-                                                                             float* __restrict__ inv) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
-    uint2 key = make_uint2(0u, 0u);
-    if (SEED) {
-        const uint64_t sd = (uint64_t)ds.seed[0];
-        key = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
-    }
-    const bool drop = SEED || ds.mask != nullptr;
-    const int cc[2] = {lane, lane + 64};
-    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
-    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
-        float4 v[R][2];
-        float ss[R];
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const float* xr = x + (r0 + u < N ? r0 + u : N - 1) * ldx;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) v[u][k] = ld4(xr + (ok[k] ? cc[k] : 0) * 4);
-        }
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            ss[u] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 q = v[u][k];
-                ss[u] = fmaf(q.x, q.x, fmaf(q.y, q.y, fmaf(q.z, q.z, fmaf(q.w, q.w, ss[u]))));
-            }
-        }
-        wave_sum_n<R>(ss);
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int64_t r = r0 + u;
-            if (r >= N) break;                                     // wave-uniform
-            const float iv = 1.f / fmaxf(sqrtf(ss[u]), eps);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) continue;
-                float4 q = v[u][k];
-                q.x *= iv; q.y *= iv; q.z *= iv; q.w *= iv;
-                if (drop) {
-                    const float4 m = drop_factors<SEED>(ds, key, r, cc[k], D4);
-                    q.x *= m.x; q.y *= m.y; q.z *= m.z; q.w *= m.w;
-                }
-                st4(y + r * ldy + cc[k] * 4, q);
-            }
-            if (lane == 0) inv[r] = iv;
-        }
-    }
-}
-
-template <bool SEED, int R>
-__global__ __launch_bounds__(kBlock) void row_normalize_drop_bwd_rows_kernel(const float* __restrict__ x, int64_t ldx,
-                                                                             const float* __restrict__ inv, DropSrc ds,
-                                                                             const float* __restrict__ g, int64_t ldg, int64_t N, int D4,
-                                                                             float eps, float* __restrict__ gx, int64_t ldgx,
-                                                                             int accumulate) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
-    uint2 key = make_uint2(0u, 0u);
-    if (SEED) {
-        const uint64_t sd = (uint64_t)ds.seed[0];
-        key = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
-    }
-    const bool drop = SEED || ds.mask != nullptr;
-    const int cc[2] = {lane, lane + 64};
-    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
-    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
-        float4 v[R][2], q[R][2], p[R][2];
-        float iv[R], dot[R];
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int64_t r = r0 + u < N ? r0 + u : N - 1;
-            iv[u] = inv[r];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int c = ok[k] ? cc[k] : 0;
-                v[u][k] = ld4(x + r * ldx + c * 4);
-                q[u][k] = ld4(g + r * ldg + c * 4);
-                if (accumulate) p[u][k] = ld4(gx + r * ldgx + c * 4);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int64_t r = r0 + u < N ? r0 + u : N - 1;
-            dot[u] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) {
-                    q[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                } else if (drop) {
-                    const float4 m = drop_factors<SEED>(ds, key, r, cc[k], D4);
-                    q[u][k].x *= m.x; q[u][k].y *= m.y; q[u][k].z *= m.z; q[u][k].w *= m.w;
-                }
-                const float4 a = v[u][k], b = q[u][k];
-                dot[u] = fmaf(b.x, a.x * iv[u], fmaf(b.y, a.y * iv[u], fmaf(b.z, a.z * iv[u], fmaf(b.w, a.w * iv[u], dot[u]))));
-            }
-        }
-        wave_sum_n<R>(dot);
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int64_t r = r0 + u;
-            if (r >= N) break;                                     // wave-uniform
-            const float d_ = iv[u] * eps >= 1.f ? 0.f : dot[u];   // ||x|| <= eps: y = x / eps, no radial term
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) continue;
-                const float4 a = v[u][k], b = q[u][k];
-                float4 o;
-                o.x = iv[u] * (b.x - a.x * iv[u] * d_); o.y = iv[u] * (b.y - a.y * iv[u] * d_);
-                o.z = iv[u] * (b.z - a.z * iv[u] * d_); o.w = iv[u] * (b.w - a.w * iv[u] * d_);
-                if (accumulate) {
-                    o.x += p[u][k].x; o.y += p[u][k].y; o.z += p[u][k].z; o.w += p[u][k].w;
-                }
-                st4(gx + r * ldgx + cc[k] * 4, o);
-            }
-        }
-    }
-}
-
-// ---- fused row passes of the encoder node's completion chain (jmac_amd/encoder.py, FUSE_ROW_PASSES) ---------------------------------
-// The node runs its entities in class order (a row permutation) and normalises + drops what it hands from layer to layer; run as
-// separate launches, four of those passes only re-read a [N, d] table the launch before has just written.  The forms below keep the
-// *_rows layout above (a wave holds R rows, lanes hold column chunks `lane` and `lane + 64`: d <= 512; every load of a row group is
-// issued before its first use) and take an optional int64 row map `map` (class-order row -> caller's row; entries in [0, N)):
-//   rows_normalize_drop_fwd      x[map[r]] -> a copy in class order, normalise + dropout, inv          (gather + normalise)
-//   bn_tanh_normalize_drop_fwd   BatchNorm apply + tanh -> y[r], y[map[r]], normalise + dropout of the row in registers, inv
-//   bn_bwd_{partial,apply}_adj   BatchNorm + tanh backward whose incoming gradient is the normalise/dropout ADJOINT of g, formed per
-//                                row from y (the adjoint's x), inv and the draws -- never stored; gy2 read as gy2[map[r]]
-//                                (the partial pass deals rows to waves as bn_bwd_partial_kernel deals them to threads: same sums)
-//   row_normalize_drop_bwd_scatter   the adjoint + add[r], stored (or accumulated) to dst[map[r]]       (adjoint + scatter)
-// Dropout is the SEED form or none.  The Philox index stays (class-order row, chunk), the per-lane summation order and the DPP chains
-// those of the *_rows kernels, the adjoint is contracted as the separate launch of that row count contracts it
-// (normalize_drop_adjoint_rows) and the BatchNorm backward's column sums keep their association: the bits of the separate launches.
-constexpr int kFuseRows = 4;             // rows per wave: one or two tables in flight
-constexpr int kFuseBwdRows = 2;          // ... four tables in flight
-
-__device__ __forceinline__ uint2 drop_key(const DropSrc& ds, bool seeded) {
-    if (!seeded) return make_uint2(0u, 0u);
-    const uint64_t sd = (uint64_t)ds.seed[0];
-    return make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
-}
-
-// normalise + dropout of R rows held in registers (v: zero on lanes past the row) -> y rows, inv; rows r0 + u >= N are skipped
-template <bool SEED, int R>
-__device__ __forceinline__ void normalize_drop_store_rows(const DropSrc& ds, uint2 key, int64_t r0, int64_t N, int D4, const int (&cc)[2],
-                                                          const bool (&ok)[2], float eps, const float4 (&v)[R][2],
-                                                          float* __restrict__ y, int64_t ldy, float* __restrict__ inv) {
-    float ss[R];
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-        ss[u] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const float4 q = v[u][k];
-            ss[u] = fmaf(q.x, q.x, fmaf(q.y, q.y, fmaf(q.z, q.z, fmaf(q.w, q.w, ss[u]))));
-        }
-    }
-    wave_sum_n<R>(ss);
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-        const int64_t r = r0 + u;
-        if (r >= N) break;                                     // wave-uniform
-        const float iv = 1.f / fmaxf(sqrtf(ss[u]), eps);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (!ok[k]) continue;
-            float4 q = v[u][k];
-            q.x *= iv; q.y *= iv; q.z *= iv; q.w *= iv;
-            if (SEED) {
-                const float4 m = drop_factors<true>(ds, key, r, cc[k], D4);
-                q.x *= m.x; q.y *= m.y; q.z *= m.z; q.w *= m.w;
-            }
-            st4(y + r * ldy + cc[k] * 4, q);
-        }
-        if (lane_id() == 0) inv[r] = iv;
-    }
-}
-
-// q <- q m - xn (q m . xn), xn = v inv: the normalise/dropout adjoint of R rows held in registers, up to its last factor inv
-// (adjoint_scale below); row[u]: their class-order rows, for the draws; v and q come back zero on lanes past the row.
-// The launches these fused forms replace leave the contraction of this expression to the compiler, which fuses it one way in
-// row_normalize_drop_bwd_rows_kernel (ROWFORM: what drop_bwd launches from kDropRowsMinN rows on) and another way in
-// row_normalize_drop_bwd_kernel; so that a fused launch reproduces the bits of the launch it replaces at every N, both ways are
-// written out here (explicit fmaf, no further contraction):
-//   ROWFORM   s = fma(-xn, dot, q m)            gx = inv s        accumulating: gx = fma(inv, s, old)
-//   otherwise s = fma(m, q, -(xn dot))  (no dropout: fma(-xn, dot, q))    gx = inv s        accumulating: gx = inv s + old
-template <bool SEED, bool ROWFORM, int R>
-__device__ __forceinline__ void normalize_drop_adjoint_rows(const DropSrc& ds, uint2 key, const int64_t (&row)[R], int D4,
-                                                            const int (&cc)[2], const bool (&ok)[2], float eps, const float (&iv)[R],
-                                                            float4 (&v)[R][2], float4 (&q)[R][2]) {
+// The element arithmetic of every kernel of this group, one float4 at a time, each rounding spelt out (no contraction beyond the
+// fmaf written here), so that kernels which call the same function round alike whatever the compiler would have chosen.
+//   forward    ss = sumsq4 over the row;  y = mul4(scale4(x, inv), m)
+//   backward   dot = adjoint_dot4 over the row (b = g m, rounded);  s = adjoint_combine4;  gx = adjoint_scale[_add]
+// The adjoint has two forms, which the launches have always rounded differently (profiles/normalize_one_body.txt); each keeps its
+// rounding, making them agree changes the results of one:
+//   ROWFORM (R rows per wave, serving N >= kDropRowsMinN)   s = fma(-xn, dot, g m)      gx = inv s   accumulating: fma(inv, s, old)
+//   otherwise (the row-per-wave kernels' form)              s = fma(m, g, -(xn dot)) with the draws made in the kernel (SEED),
+//                                                           fma(-xn, dot, g m) with a mask or none
+//                                                                                       gx = inv s   accumulating: inv s + old
+__device__ __forceinline__ float sumsq4(float4 v, float acc) {
 #pragma clang fp contract(off)
-    float dot[R];
-    float4 m[R][2];
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-        dot[u] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            float4 b = q[u][k];
-            if (!ok[k]) {
-                b = q[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            } else if (SEED) {
-                m[u][k] = drop_factors<true>(ds, key, row[u], cc[k], D4);
-                b.x *= m[u][k].x; b.y *= m[u][k].y; b.z *= m[u][k].z; b.w *= m[u][k].w;
-                if (ROWFORM) q[u][k] = b;
-            }
-            const float4 a = v[u][k];
-            dot[u] = fmaf(b.x, a.x * iv[u], fmaf(b.y, a.y * iv[u], fmaf(b.z, a.z * iv[u], fmaf(b.w, a.w * iv[u], dot[u]))));
-        }
-    }
-    wave_sum_n<R>(dot);
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-        const float d_ = iv[u] * eps >= 1.f ? 0.f : dot[u];       // ||x|| <= eps: y = x / eps, no radial term
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (!ok[k]) continue;
-            const float4 a = v[u][k], b = q[u][k];
-            float4 o;
-            if (ROWFORM || !SEED) {
-                o.x = fmaf(-(a.x * iv[u]), d_, b.x); o.y = fmaf(-(a.y * iv[u]), d_, b.y);
-                o.z = fmaf(-(a.z * iv[u]), d_, b.z); o.w = fmaf(-(a.w * iv[u]), d_, b.w);
-            } else {
-                o.x = fmaf(m[u][k].x, b.x, -(a.x * iv[u] * d_)); o.y = fmaf(m[u][k].y, b.y, -(a.y * iv[u] * d_));
-                o.z = fmaf(m[u][k].z, b.z, -(a.z * iv[u] * d_)); o.w = fmaf(m[u][k].w, b.w, -(a.w * iv[u] * d_));
-            }
-            q[u][k] = o;
-        }
-    }
+    return fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, acc))));
 }
-// the adjoint's last factor, and the table an accumulating launch adds (see above)
+__device__ __forceinline__ float4 scale4(float4 v, float s) {
+#pragma clang fp contract(off)
+    return make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
+}
+__device__ __forceinline__ float4 mul4(float4 a, float4 b) {
+#pragma clang fp contract(off)
+    return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
+}
+__device__ __forceinline__ float4 add4(float4 a, float4 b) {
+#pragma clang fp contract(off)
+    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+// acc + b . xn, xn = a inv
+__device__ __forceinline__ float adjoint_dot4(float4 b, float4 a, float iv, float acc) {
+#pragma clang fp contract(off)
+    return fmaf(b.x, a.x * iv, fmaf(b.y, a.y * iv, fmaf(b.z, a.z * iv, fmaf(b.w, a.w * iv, acc))));
+}
+// FUSE_M: q = g, the factors m fused into the subtraction; otherwise q = g m, rounded (or g where nothing is dropped)
+template <bool FUSE_M>
+__device__ __forceinline__ float4 adjoint_combine4(float4 a, float iv, float dot, float4 q, const float4& m) {
+#pragma clang fp contract(off)
+    if (FUSE_M)
+        return make_float4(fmaf(m.x, q.x, -(a.x * iv * dot)), fmaf(m.y, q.y, -(a.y * iv * dot)), fmaf(m.z, q.z, -(a.z * iv * dot)),
+                           fmaf(m.w, q.w, -(a.w * iv * dot)));
+    return make_float4(fmaf(-(a.x * iv), dot, q.x), fmaf(-(a.y * iv), dot, q.y), fmaf(-(a.z * iv), dot, q.z), fmaf(-(a.w * iv), dot, q.w));
+}
+// the adjoint's last factor, and the table an accumulating launch adds
 __device__ __forceinline__ float4 adjoint_scale(float iv, float4 s) {
 #pragma clang fp contract(off)
     return make_float4(iv * s.x, iv * s.y, iv * s.z, iv * s.w);
@@ -816,43 +548,179 @@ __device__ __forceinline__ float4 adjoint_scale_add(float iv, float4 s, float4 p
     if (ROWFORM) return make_float4(fmaf(iv, s.x, p.x), fmaf(iv, s.y, p.y), fmaf(iv, s.z, p.z), fmaf(iv, s.w, p.w));
     return make_float4(iv * s.x + p.x, iv * s.y + p.y, iv * s.z + p.z, iv * s.w + p.w);
 }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-#pragma clang fp contract(off)
-    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+
+// ---- one wave per row: any d, and every N below kDropRowsMinN.  A wave reads its row, reduces, reads it again and writes.
+template <bool SEED>
+__global__ __launch_bounds__(kBlock) void row_normalize_drop_fwd_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int D4,
+                                                                        float eps, DropSrc ds, float* __restrict__ y, int64_t ldy,
+                                                                        float* __restrict__ inv) {
+    const WaveLanes L(D4);
+    const uint2 key = drop_key(ds, SEED);
+    const bool drop = SEED || ds.mask != nullptr;
+    for (int64_t r = L.w0; r < N; r += L.nw) {
+        const float* xr = x + r * ldx;
+        float ss = 0.f;
+        for (int c = L.lane; c < D4; c += 64) ss = sumsq4(ld4(xr + c * 4), ss);
+        ss = wave_sum(ss);
+        const float iv = 1.f / fmaxf(sqrtf(ss), eps);
+        for (int c = L.lane; c < D4; c += 64) {
+            float4 v = scale4(ld4(xr + c * 4), iv);
+            if (drop) v = mul4(v, drop_factors<SEED>(ds, key, r, c, D4));
+            st4(y + r * ldy + c * 4, v);
+        }
+        if (L.lane == 0) inv[r] = iv;
+    }
 }
 
-template <bool SEED, int R>
+template <bool SEED>
+__global__ __launch_bounds__(kBlock) void row_normalize_drop_bwd_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                        const float* __restrict__ inv, DropSrc ds,
+                                                                        const float* __restrict__ g, int64_t ldg, int64_t N, int D4,
+                                                                        float eps, float* __restrict__ gx, int64_t ldgx,
+                                                                        int accumulate) {
+    const WaveLanes L(D4);
+    const uint2 key = drop_key(ds, SEED);
+    const bool drop = SEED || ds.mask != nullptr;
+    for (int64_t r = L.w0; r < N; r += L.nw) {
+        const float* xr = x + r * ldx;
+        const float* gr = g + r * ldg;
+        const float iv = inv[r];
+        float dot = 0.f;
+        for (int c = L.lane; c < D4; c += 64) {
+            float4 q = ld4(gr + c * 4);
+            if (drop) q = mul4(q, drop_factors<SEED>(ds, key, r, c, D4));
+            dot = adjoint_dot4(q, ld4(xr + c * 4), iv, dot);
+        }
+        dot = wave_sum(dot);
+        if (iv * eps >= 1.f) dot = 0.f;                // ||x|| <= eps: y = x / eps, no radial term
+        for (int c = L.lane; c < D4; c += 64) {
+            float4 q = ld4(gr + c * 4), m = f4zero();
+            if (drop) m = drop_factors<SEED>(ds, key, r, c, D4);
+            if (drop && !SEED) q = mul4(q, m);
+            float4 o = adjoint_scale(iv, adjoint_combine4<SEED>(ld4(xr + c * 4), iv, dot, q, m));
+            if (accumulate) o = add4(o, ld4(gx + r * ldgx + c * 4));
+            st4(gx + r * ldgx + c * 4, o);
+        }
+    }
+}
+
+// ---- R rows per wave in flight (rows of up to 128 float4: d <= 512) -------------------------------------------------------------
+// The kernels above give every row a wave that makes two dependent round trips per row and (backward) two Philox evaluations per
+// element; at DBP-5L size (11 805 rows x 300) they move 28-56 MB at 2.2 TB/s.  Here a wave keeps R rows in registers (two float4 per
+// lane and row), issues all their loads before the first reduction (interleaved DPP chains: wave_sum_n) and writes from registers.
+// Per-lane summation order as above.  One body per pass -- normalize_drop_store_rows forward, normalize_drop_adjoint_rows backward --
+// serves the plain launches (PLAIN: drop_fwd / drop_bwd from kDropRowsMinN rows on; dropout from a mask, a seed or none) and the
+// fused row passes of the encoder node's completion chain (jmac_amd/encoder.py, FUSE_ROW_PASSES; dropout from a seed or none).
+// The node runs its entities in class order (a row permutation) and normalises + drops what it hands from layer to layer; run as
+// separate launches, four of those passes only re-read a [N, d] table the launch before has just written.  The fused forms take an
+// optional int64 row map `map` (class-order row -> caller's row; entries in [0, N)):
+//   rows_normalize_drop_fwd      x[map[r]] -> a copy in class order, normalise + dropout, inv          (gather + normalise)
+//   bn_tanh_normalize_drop_fwd   BatchNorm apply + tanh -> y[r], y[map[r]], normalise + dropout of the row in registers, inv
+//   bn_bwd_{partial,apply}_adj   BatchNorm + tanh backward whose incoming gradient is the normalise/dropout ADJOINT of g, formed per
+//                                row from y (the adjoint's x), inv and the draws -- never stored; gy2 read as gy2[map[r]]
+//                                (the partial pass deals rows to waves as bn_bwd_partial_kernel deals them to threads: same sums)
+//   row_normalize_drop_bwd_scatter   the adjoint + add[r], stored (or accumulated) to dst[map[r]]       (adjoint + scatter)
+// The Philox index stays (class-order row, chunk).  A fused launch takes the adjoint's form (ROWFORM, above) of the separate launch
+// of its row count, and the BatchNorm backward's column sums keep their association: the bits of the separate launches.
+constexpr int kDropRows = 4;             // rows per wave of the plain launches
+constexpr int64_t kDropRowsMinN = 2048;  // below this the one-row-per-wave kernels have more waves to hide latency with
+constexpr int kFuseRows = 4;             // rows per wave of the fused passes: one or two tables in flight
+constexpr int kFuseBwdRows = 2;          // ... four tables in flight
+
+// normalise + dropout of R rows held in registers (v: zero on lanes past the row) -> y rows, inv; rows r0 + u >= N are skipped.
+// MASK: ds.mask may be set (the plain launches alone: the test for it costs the fused forms registers)
+template <bool SEED, bool MASK, int R>
+__device__ __forceinline__ void normalize_drop_store_rows(const DropSrc& ds, uint2 key, int64_t r0, int64_t N, int D4, const WaveLanes& L,
+                                                          float eps, const float4 (&v)[R][2], float* __restrict__ y, int64_t ldy,
+                                                          float* __restrict__ inv) {
+    const bool drop = SEED || (MASK && ds.mask != nullptr);
+    float ss[R];
+#pragma unroll
+    for (int u = 0; u < R; ++u) ss[u] = sumsq4(v[u][1], sumsq4(v[u][0], 0.f));
+    wave_sum_n<R>(ss);
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        const int64_t r = r0 + u;
+        if (r >= N) break;                                     // wave-uniform
+        const float iv = 1.f / fmaxf(sqrtf(ss[u]), eps);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (!L.ok[k]) continue;
+            float4 q = scale4(v[u][k], iv);
+            if (drop) q = mul4(q, drop_factors<SEED>(ds, key, r, L.cc[k], D4));
+            st4(y + r * ldy + L.cc[k] * 4, q);
+        }
+        if (L.lane == 0) inv[r] = iv;
+    }
+}
+
+// q <- the normalise/dropout adjoint of R rows held in registers, up to its last factor inv (adjoint_scale[_add]); row[u]: their
+// class-order rows, for the draws; v and q come back zero on lanes past the row.  ROWFORM, MASK: see above.
+template <bool SEED, bool ROWFORM, bool MASK, int R>
+__device__ __forceinline__ void normalize_drop_adjoint_rows(const DropSrc& ds, uint2 key, const int64_t (&row)[R], int D4,
+                                                            const WaveLanes& L, float eps, const float (&iv)[R], float4 (&v)[R][2],
+                                                            float4 (&q)[R][2]) {
+    constexpr bool FUSE_M = SEED && !ROWFORM;
+    const bool drop = SEED || (MASK && ds.mask != nullptr);
+    float dot[R];
+    float4 m[R][2];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        dot[u] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            float4 b = q[u][k];
+            if (!L.ok[k]) {
+                b = q[u][k] = f4zero();
+                v[u][k] = f4zero();
+            } else if (drop) {
+                m[u][k] = drop_factors<SEED>(ds, key, row[u], L.cc[k], D4);
+                b = mul4(b, m[u][k]);
+                if (!FUSE_M) q[u][k] = b;
+            }
+            dot[u] = adjoint_dot4(b, v[u][k], iv[u], dot[u]);
+        }
+    }
+    wave_sum_n<R>(dot);
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+        const float d_ = iv[u] * eps >= 1.f ? 0.f : dot[u];       // ||x|| <= eps: y = x / eps, no radial term
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (L.ok[k]) q[u][k] = adjoint_combine4<FUSE_M>(v[u][k], iv[u], d_, q[u][k], m[u][k]);
+    }
+}
+
+// PLAIN: the plain launch -- no row map, no copy (map and xr are not read), dropout from a mask too
+template <bool SEED, bool PLAIN, int R>
 __global__ __launch_bounds__(kBlock) void rows_normalize_drop_fwd_kernel(const float* __restrict__ x, int64_t ldx,
                                                                          const int64_t* __restrict__ map, int64_t N, int D4, float eps,
                                                                          DropSrc ds, float* __restrict__ xr, int64_t ldxr,
                                                                          float* __restrict__ y, int64_t ldy, float* __restrict__ inv) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const WaveLanes L(D4);
     const uint2 key = drop_key(ds, SEED);
-    const int cc[2] = {lane, lane + 64};
-    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
-    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+    for (int64_t r0 = L.w0 * R; r0 < N; r0 += L.nw * R) {
         float4 v[R][2];
         int64_t s[R];
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             const int64_t r = r0 + u < N ? r0 + u : N - 1;
-            s[u] = map ? map[r] : r;
+            s[u] = !PLAIN && map ? map[r] : r;
         }
 #pragma unroll
         for (int u = 0; u < R; ++u) {
 #pragma unroll
-            for (int k = 0; k < 2; ++k) v[u][k] = ld4(x + s[u] * ldx + (ok[k] ? cc[k] : 0) * 4);
+            for (int k = 0; k < 2; ++k) v[u][k] = ld4(x + s[u] * ldx + (L.ok[k] ? L.cc[k] : 0) * 4);
         }
 #pragma unroll
         for (int u = 0; u < R; ++u) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                else if (xr && r0 + u < N) st4(xr + (r0 + u) * ldxr + cc[k] * 4, v[u][k]);
+                if (!L.ok[k]) v[u][k] = f4zero();
+                else if (!PLAIN && xr && r0 + u < N) st4(xr + (r0 + u) * ldxr + L.cc[k] * 4, v[u][k]);
             }
         }
-        normalize_drop_store_rows<SEED, R>(ds, key, r0, N, D4, cc, ok, eps, v, y, ldy, inv);
+        normalize_drop_store_rows<SEED, PLAIN, R>(ds, key, r0, N, D4, L, eps, v, y, ldy, inv);
     }
 }
 
@@ -864,18 +732,15 @@ __global__ __launch_bounds__(kBlock) void bn_tanh_normalize_drop_fwd_kernel(cons
                                                                             const int64_t* __restrict__ map, float* __restrict__ yr,
                                                                             int64_t ldyr, float eps, DropSrc ds, float* __restrict__ yn,
                                                                             int64_t ldyn, float* __restrict__ inv) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const WaveLanes L(D4);
     const uint2 key = drop_key(ds, SEED);
-    const int cc[2] = {lane, lane + 64};
-    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
     float4 mu[2], is[2], w[2], b[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int c = (ok[k] ? cc[k] : 0) * 4;
+        const int c = (L.ok[k] ? L.cc[k] : 0) * 4;
         mu[k] = ld4(mean + c); is[k] = ld4(invstd + c); w[k] = ld4(weight + c); b[k] = ld4(bias + c);
     }
-    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+    for (int64_t r0 = L.w0 * R; r0 < N; r0 += L.nw * R) {
         float4 v[R][2];
         int64_t s[R];
 #pragma unroll
@@ -883,14 +748,14 @@ __global__ __launch_bounds__(kBlock) void bn_tanh_normalize_drop_fwd_kernel(cons
             const int64_t r = r0 + u < N ? r0 + u : N - 1;
             s[u] = map ? map[r] : r;
 #pragma unroll
-            for (int k = 0; k < 2; ++k) v[u][k] = ld4(x + r * ldx + (ok[k] ? cc[k] : 0) * 4);
+            for (int k = 0; k < 2; ++k) v[u][k] = ld4(x + r * ldx + (L.ok[k] ? L.cc[k] : 0) * 4);
         }
 #pragma unroll
         for (int u = 0; u < R; ++u) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) {
-                    v[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!L.ok[k]) {
+                    v[u][k] = f4zero();
                     continue;
                 }
                 float4 o;
@@ -900,12 +765,12 @@ __global__ __launch_bounds__(kBlock) void bn_tanh_normalize_drop_fwd_kernel(cons
                 o.w = tanhf(fmaf((v[u][k].w - mu[k].w) * is[k].w, w[k].w, b[k].w));
                 v[u][k] = o;
                 if (r0 + u < N) {
-                    st4(y + (r0 + u) * ldy + cc[k] * 4, o);
-                    if (yr) st4(yr + s[u] * ldyr + cc[k] * 4, o);   // the same row at its place in the caller's order
+                    st4(y + (r0 + u) * ldy + L.cc[k] * 4, o);
+                    if (yr) st4(yr + s[u] * ldyr + L.cc[k] * 4, o);   // the same row at its place in the caller's order
                 }
             }
         }
-        normalize_drop_store_rows<SEED, R>(ds, key, r0, N, D4, cc, ok, eps, v, yn, ldyn, inv);
+        normalize_drop_store_rows<SEED, false, R>(ds, key, r0, N, D4, L, eps, v, yn, ldyn, inv);
     }
 }
 
@@ -924,14 +789,13 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_partial_adj_kernel(const float*
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4* red = reinterpret_cast<float4*>(smem);   // [2][rpb][D4]
     const int rpb = kBlock / D4;                      // >= 2 (D4 <= 128)
-    const int lane = lane_id(), wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
+    const WaveLanes L(D4);
+    const int wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
     const uint2 key = drop_key(ds, SEED);
-    const int cc[2] = {lane, lane + 64};
-    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
     float4 mu[2], is[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int c = (ok[k] ? cc[k] : 0) * 4;
+        const int c = (L.ok[k] ? L.cc[k] : 0) * 4;
         mu[k] = ld4(mean + c); is[k] = ld4(invstd + c);
     }
     const int64_t stride = (int64_t)gridDim.x * rpb;
@@ -951,20 +815,20 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_partial_adj_kernel(const float*
                 iv[u] = inv[row[u]];
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    const int c = (ok[k] ? cc[k] : 0) * 4;
+                    const int c = (L.ok[k] ? L.cc[k] : 0) * 4;
                     xv[u][k] = ld4(x + row[u] * ldx + c);
                     yv[u][k] = ld4(y + row[u] * ldy + c);
                     q[u][k] = ld4(g + row[u] * ldg + c);
                     if (gy2) g2[u][k] = ld4(gy2 + s[u] * ldgy2 + c);
                 }
             }
-            normalize_drop_adjoint_rows<SEED, ROWFORM, R>(ds, key, row, D4, cc, ok, eps, iv, yv, q);
+            normalize_drop_adjoint_rows<SEED, ROWFORM, false, R>(ds, key, row, D4, L, eps, iv, yv, q);
 #pragma unroll
             for (int u = 0; u < R; ++u) {
                 if (rb + u * stride >= N) break;                   // wave-uniform
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    if (!ok[k]) continue;
+                    if (!L.ok[k]) continue;
                     float4 gg = adjoint_scale(iv[u], q[u][k]);
                     if (gy2) gg = add4(gg, g2[u][k]);
                     const float4 yy = yv[u][k], xx = xv[u][k];
@@ -977,9 +841,9 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_partial_adj_kernel(const float*
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            if (ok[k]) {
-                red[(0 * rpb + rsub) * D4 + cc[k]] = s1[k];
-                red[(1 * rpb + rsub) * D4 + cc[k]] = s2[k];
+            if (L.ok[k]) {
+                red[(0 * rpb + rsub) * D4 + L.cc[k]] = s1[k];
+                red[(1 * rpb + rsub) * D4 + L.cc[k]] = s2[k];
             }
         }
     }
@@ -996,19 +860,16 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_adj_kernel(const float* _
                                                                   const float* __restrict__ invstd, const float* __restrict__ gweight,
                                                                   const float* __restrict__ gbias, int training, float invn,
                                                                   float* __restrict__ gx, int64_t ldgx) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const WaveLanes L(D4);
     const uint2 key = drop_key(ds, SEED);
-    const int cc[2] = {lane, lane + 64};
-    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
     float4 mu[2], is[2], w[2], gw[2], gb[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int c = (ok[k] ? cc[k] : 0) * 4;
+        const int c = (L.ok[k] ? L.cc[k] : 0) * 4;
         mu[k] = ld4(mean + c); is[k] = ld4(invstd + c); w[k] = ld4(weight + c);
         gw[k] = training ? ld4(gweight + c) : f4zero(); gb[k] = training ? ld4(gbias + c) : f4zero();
     }
-    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+    for (int64_t r0 = L.w0 * R; r0 < N; r0 += L.nw * R) {
         float4 xv[R][2], yv[R][2], q[R][2], g2[R][2];
         float iv[R];
         int64_t row[R], s[R];
@@ -1022,20 +883,20 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_adj_kernel(const float* _
             iv[u] = inv[row[u]];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const int c = (ok[k] ? cc[k] : 0) * 4;
+                const int c = (L.ok[k] ? L.cc[k] : 0) * 4;
                 xv[u][k] = ld4(x + row[u] * ldx + c);
                 yv[u][k] = ld4(y + row[u] * ldy + c);
                 q[u][k] = ld4(g + row[u] * ldg + c);
                 if (gy2) g2[u][k] = ld4(gy2 + s[u] * ldgy2 + c);
             }
         }
-        normalize_drop_adjoint_rows<SEED, ROWFORM, R>(ds, key, row, D4, cc, ok, eps, iv, yv, q);
+        normalize_drop_adjoint_rows<SEED, ROWFORM, false, R>(ds, key, row, D4, L, eps, iv, yv, q);
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             if (r0 + u >= N) break;                                // wave-uniform
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) continue;
+                if (!L.ok[k]) continue;
                 float4 gg = adjoint_scale(iv[u], q[u][k]);
                 if (gy2) gg = add4(gg, g2[u][k]);
                 const float4 yy = yv[u][k], xx = xv[u][k];
@@ -1044,63 +905,75 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_apply_adj_kernel(const float* _
                 o.y = bn_bwd_apply_elem(gg.y, yy.y, xx.y, mu[k].y, is[k].y, w[k].y, gw[k].y, gb[k].y, training, invn);
                 o.z = bn_bwd_apply_elem(gg.z, yy.z, xx.z, mu[k].z, is[k].z, w[k].z, gw[k].z, gb[k].z, training, invn);
                 o.w = bn_bwd_apply_elem(gg.w, yy.w, xx.w, mu[k].w, is[k].w, w[k].w, gw[k].w, gb[k].w, training, invn);
-                st4(gx + (r0 + u) * ldgx + cc[k] * 4, o);
+                st4(gx + (r0 + u) * ldgx + L.cc[k] * 4, o);
             }
         }
     }
 }
 
-template <bool SEED, bool ROWFORM, int R>
+// PLAIN: the plain launch -- the row map is not read, dropout may come from a mask, and an accumulating launch passes its
+// destination as `add` with accumulate = 0 (gx += adjoint is fma(inv, s, old), the add table's rounding): one table less in flight.
+// There add and dst are the same memory, so neither is __restrict__ in that instantiation.
+template <bool ALIASED, class T> using MaybeAliased = std::conditional_t<ALIASED, T*, T* __restrict__>;
+template <bool SEED, bool ROWFORM, bool PLAIN, int R>
 __global__ __launch_bounds__(kBlock) void row_normalize_drop_bwd_scatter_kernel(const float* __restrict__ x, int64_t ldx,
                                                                                 const float* __restrict__ inv, DropSrc ds,
                                                                                 const float* __restrict__ g, int64_t ldg,
-                                                                                const float* __restrict__ add, int64_t ldadd,
+                                                                                MaybeAliased<PLAIN, const float> add, int64_t ldadd,
                                                                                 const int64_t* __restrict__ map, int64_t N, int D4,
-                                                                                float eps, float* __restrict__ dst, int64_t lddst,
+                                                                                float eps, MaybeAliased<PLAIN, float> dst, int64_t lddst,
                                                                                 int accumulate) {
-    const int lane = lane_id();
-    const int64_t w0 = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
+    const WaveLanes L(D4);
     const uint2 key = drop_key(ds, SEED);
-    const int cc[2] = {lane, lane + 64};
-    const bool ok[2] = {cc[0] < D4, cc[1] < D4};
-    for (int64_t r0 = w0 * R; r0 < N; r0 += nw * R) {
+    const bool onto = !PLAIN && accumulate;
+    for (int64_t r0 = L.w0 * R; r0 < N; r0 += L.nw * R) {
         float4 v[R][2], q[R][2], p[R][2], old[R][2];
         float iv[R];
         int64_t row[R], s[R];
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             row[u] = r0 + u < N ? r0 + u : N - 1;
-            s[u] = map ? map[row[u]] : row[u];
+            s[u] = !PLAIN && map ? map[row[u]] : row[u];
         }
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             iv[u] = inv[row[u]];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const int c = (ok[k] ? cc[k] : 0) * 4;
+                const int c = (L.ok[k] ? L.cc[k] : 0) * 4;
                 v[u][k] = ld4(x + row[u] * ldx + c);
                 q[u][k] = ld4(g + row[u] * ldg + c);
                 if (add) p[u][k] = ld4(add + row[u] * ldadd + c);
-                if (accumulate) old[u][k] = ld4(dst + s[u] * lddst + c);
+                if (onto) old[u][k] = ld4(dst + s[u] * lddst + c);
             }
         }
-        normalize_drop_adjoint_rows<SEED, ROWFORM, R>(ds, key, row, D4, cc, ok, eps, iv, v, q);
+        normalize_drop_adjoint_rows<SEED, ROWFORM, PLAIN, R>(ds, key, row, D4, L, eps, iv, v, q);
 #pragma unroll
         for (int u = 0; u < R; ++u) {
             if (r0 + u >= N) break;                                // wave-uniform
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                if (!ok[k]) continue;
+                if (!L.ok[k]) continue;
                 float4 o = add ? adjoint_scale_add<ROWFORM>(iv[u], q[u][k], p[u][k]) : adjoint_scale(iv[u], q[u][k]);
-                if (accumulate) o = add4(o, old[u][k]);
-                st4(dst + s[u] * lddst + cc[k] * 4, o);
+                if (onto) o = add4(o, old[u][k]);
+                st4(dst + s[u] * lddst + L.cc[k] * 4, o);
             }
         }
     }
 }
 
-constexpr int kDropRows = 4;             // rows per wave of the *_rows forms
-constexpr int64_t kDropRowsMinN = 2048;  // below this the one-row-per-wave forms have more waves to hide latency with
+inline unsigned rows_grid(int64_t N, int R) {                      // a wave per R rows, kBlock / 64 waves per block
+    const int64_t rb = ((N + R - 1) / R + kBlock / 64 - 1) / (kBlock / 64);
+    return (unsigned)(rb > 8192 ? 8192 : rb);
+}
+// f(SEED, ROWFORM) with the two as std::bool_constant values, so that a generic lambda names its kernel's instantiation by them
+template <class F>
+inline void with_drop_form(bool seeded, bool rowform, F&& f) {
+    if (seeded && rowform) f(std::true_type{}, std::true_type{});
+    else if (seeded) f(std::true_type{}, std::false_type{});
+    else if (rowform) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
 
 }  // namespace
 
@@ -1191,9 +1064,7 @@ int jmac_row_normalize_fwd_f32(const float* x, int64_t ldx, int64_t N, int64_t d
     if (N < 0 || d <= 0 || d >= INT32_MAX) return JMAC_EINVAL;
     if (N == 0) return JMAC_OK;
     if (!x || !y || !inv) return JMAC_EINVAL;
-    int64_t blocks = (N + kBlock / 64 - 1) / (kBlock / 64);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(row_normalize_fwd_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, N, (int)d, eps,
+    hipLaunchKernelGGL(row_normalize_fwd_kernel, dim3(rows_grid(N, 1)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, N, (int)d, eps,
                        y, ldy, inv);
     return (int)hipGetLastError();
 }
@@ -1203,13 +1074,12 @@ int jmac_row_normalize_bwd_f32(const float* y, int64_t ldy, const float* g, int6
     if (N < 0 || d <= 0 || d >= INT32_MAX) return JMAC_EINVAL;
     if (N == 0) return JMAC_OK;
     if (!y || !g || !inv || !gx) return JMAC_EINVAL;
-    int64_t blocks = (N + kBlock / 64 - 1) / (kBlock / 64);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(row_normalize_bwd_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, y, ldy, g, ldg, inv, N,
+    hipLaunchKernelGGL(row_normalize_bwd_kernel, dim3(rows_grid(N, 1)), dim3(kBlock), 0, (hipStream_t)stream, y, ldy, g, ldg, inv, N,
                        (int)d, eps, gx, ldgx);
     return (int)hipGetLastError();
 }
 
+// the plain launches: from kDropRowsMinN rows of up to 512 columns on, the R-rows bodies (PLAIN); else a wave per row
 static int drop_fwd(const float* x, int64_t ldx, int64_t N, int64_t d, float eps, const DropSrc& ds, bool seeded, float* y, int64_t ldy,
                     float* inv, jmac_stream_t stream) {
     if (N < 0 || d <= 0 || d >= INT32_MAX) return JMAC_EINVAL;
@@ -1217,25 +1087,16 @@ static int drop_fwd(const float* x, int64_t ldx, int64_t N, int64_t d, float eps
     if (N == 0) return JMAC_OK;
     if (!x || !y || !inv) return JMAC_EINVAL;
     if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)ds.mask) & 15) != 0) return JMAC_EDIM;
-    if (d <= 512 && N >= kDropRowsMinN) {                          // R rows per wave in flight
-        int64_t rb = ((N + kDropRows - 1) / kDropRows + kBlock / 64 - 1) / (kBlock / 64);
-        if (rb > 8192) rb = 8192;
-        if (seeded)
-            hipLaunchKernelGGL((row_normalize_drop_fwd_rows_kernel<true, kDropRows>), dim3((unsigned)rb), dim3(kBlock), 0,
-                               (hipStream_t)stream, x, ldx, N, (int)(d / 4), eps, ds, y, ldy, inv);
+    const bool rowform = d <= 512 && N >= kDropRowsMinN;
+    with_drop_form(seeded, rowform, [&](auto SD, auto RF) {
+        if constexpr (RF.value)
+            hipLaunchKernelGGL((rows_normalize_drop_fwd_kernel<SD.value, true, kDropRows>), dim3(rows_grid(N, kDropRows)), dim3(kBlock), 0,
+                               (hipStream_t)stream, x, ldx, (const int64_t*)nullptr, N, (int)(d / 4), eps, ds, (float*)nullptr,
+                               (int64_t)0, y, ldy, inv);
         else
-            hipLaunchKernelGGL((row_normalize_drop_fwd_rows_kernel<false, kDropRows>), dim3((unsigned)rb), dim3(kBlock), 0,
-                               (hipStream_t)stream, x, ldx, N, (int)(d / 4), eps, ds, y, ldy, inv);
-        return (int)hipGetLastError();
-    }
-    int64_t blocks = (N + kBlock / 64 - 1) / (kBlock / 64);
-    if (blocks > 8192) blocks = 8192;
-    if (seeded)
-        hipLaunchKernelGGL(row_normalize_drop_fwd_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, N,
-                           (int)(d / 4), eps, ds, y, ldy, inv);
-    else
-        hipLaunchKernelGGL(row_normalize_drop_fwd_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, N,
-                           (int)(d / 4), eps, ds, y, ldy, inv);
+            hipLaunchKernelGGL(row_normalize_drop_fwd_kernel<SD.value>, dim3(rows_grid(N, 1)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx,
+                               N, (int)(d / 4), eps, ds, y, ldy, inv);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1246,25 +1107,16 @@ static int drop_bwd(const float* x, int64_t ldx, const float* inv, const DropSrc
     if (N == 0) return JMAC_OK;
     if (!x || !inv || !g || !gx) return JMAC_EINVAL;
     if ((((uintptr_t)x | (uintptr_t)g | (uintptr_t)gx | (uintptr_t)ds.mask) & 15) != 0) return JMAC_EDIM;
-    if (d <= 512 && N >= kDropRowsMinN) {
-        int64_t rb = ((N + kDropRows - 1) / kDropRows + kBlock / 64 - 1) / (kBlock / 64);
-        if (rb > 8192) rb = 8192;
-        if (seeded)
-            hipLaunchKernelGGL((row_normalize_drop_bwd_rows_kernel<true, kDropRows>), dim3((unsigned)rb), dim3(kBlock), 0,
-                               (hipStream_t)stream, x, ldx, inv, ds, g, ldg, N, (int)(d / 4), eps, gx, ldgx, accumulate ? 1 : 0);
+    const bool rowform = d <= 512 && N >= kDropRowsMinN;
+    with_drop_form(seeded, rowform, [&](auto SD, auto RF) {
+        if constexpr (RF.value)                                    // accumulating: gx is the table that is added
+            hipLaunchKernelGGL((row_normalize_drop_bwd_scatter_kernel<SD.value, true, true, kDropRows>), dim3(rows_grid(N, kDropRows)),
+                               dim3(kBlock), 0, (hipStream_t)stream, x, ldx, inv, ds, g, ldg, accumulate ? (const float*)gx : nullptr,
+                               ldgx, (const int64_t*)nullptr, N, (int)(d / 4), eps, gx, ldgx, 0);
         else
-            hipLaunchKernelGGL((row_normalize_drop_bwd_rows_kernel<false, kDropRows>), dim3((unsigned)rb), dim3(kBlock), 0,
-                               (hipStream_t)stream, x, ldx, inv, ds, g, ldg, N, (int)(d / 4), eps, gx, ldgx, accumulate ? 1 : 0);
-        return (int)hipGetLastError();
-    }
-    int64_t blocks = (N + kBlock / 64 - 1) / (kBlock / 64);
-    if (blocks > 8192) blocks = 8192;
-    if (seeded)
-        hipLaunchKernelGGL(row_normalize_drop_bwd_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, inv,
-                           ds, g, ldg, N, (int)(d / 4), eps, gx, ldgx, accumulate ? 1 : 0);
-    else
-        hipLaunchKernelGGL(row_normalize_drop_bwd_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, inv,
-                           ds, g, ldg, N, (int)(d / 4), eps, gx, ldgx, accumulate ? 1 : 0);
+            hipLaunchKernelGGL(row_normalize_drop_bwd_kernel<SD.value>, dim3(rows_grid(N, 1)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx,
+                               inv, ds, g, ldg, N, (int)(d / 4), eps, gx, ldgx, accumulate ? 1 : 0);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1314,25 +1166,6 @@ static bool aligned16(std::initializer_list<const void*> ps) {
     for (const void* p : ps) a |= (uintptr_t)p;
     return (a & 15) == 0;
 }
-static unsigned rows_grid(int64_t N, int R) {                      // a wave per R rows, kBlock / 64 waves per block
-    int64_t rb = ((N + R - 1) / R + kBlock / 64 - 1) / (kBlock / 64);
-    return (unsigned)(rb > 8192 ? 8192 : rb);
-}
-#define JMAC_LAUNCH_SEEDED(kernel, R, grid, st, ...)                                                                      \
-    do {                                                                                                                  \
-        if (ds.seed) hipLaunchKernelGGL((kernel<true, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);                 \
-        else hipLaunchKernelGGL((kernel<false, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);                        \
-    } while (0)
-// ... and the backward forms: the adjoint as the separate launch forms it at this N (normalize_drop_adjoint_rows)
-#define JMAC_LAUNCH_ADJ(kernel, R, grid, st, ...)                                                                         \
-    do {                                                                                                                  \
-        const bool rowform = N >= kDropRowsMinN;                                                                          \
-        if (ds.seed && rowform) hipLaunchKernelGGL((kernel<true, true, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__); \
-        else if (ds.seed) hipLaunchKernelGGL((kernel<true, false, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);     \
-        else if (rowform) hipLaunchKernelGGL((kernel<false, true, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);     \
-        else hipLaunchKernelGGL((kernel<false, false, R>), dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__);                 \
-    } while (0)
-
 int jmac_rows_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, const int64_t* row_map, int64_t N, int64_t d, float eps,
                                          const int64_t* seed, float p_drop, float* x_rows, int64_t ldxr, float* y, int64_t ldy,
                                          float* inv, jmac_stream_t stream) {
@@ -1343,8 +1176,10 @@ int jmac_rows_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, const int6
     if (N == 0) return JMAC_OK;
     if (!x || !y || !inv) return JMAC_EINVAL;
     if (!aligned16({x, y, x_rows})) return JMAC_EDIM;
-    JMAC_LAUNCH_SEEDED(rows_normalize_drop_fwd_kernel, kFuseRows, rows_grid(N, kFuseRows), (hipStream_t)stream, x, ldx, row_map, N,
-                       (int)(d / 4), eps, ds, x_rows, ldxr, y, ldy, inv);
+    with_drop_form(ds.seed != nullptr, false, [&](auto SD, auto) {
+        hipLaunchKernelGGL((rows_normalize_drop_fwd_kernel<SD.value, false, kFuseRows>), dim3(rows_grid(N, kFuseRows)), dim3(kBlock), 0,
+                           (hipStream_t)stream, x, ldx, row_map, N, (int)(d / 4), eps, ds, x_rows, ldxr, y, ldy, inv);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1365,8 +1200,11 @@ int jmac_bn_tanh_normalize_dropseed_fwd_f32(const float* x, int64_t ldx, int64_t
     if (int rc = launch_bn_fwd_stats(x, ldx, N, d, running_mean, running_var, training, momentum, eps, save_mean, save_invstd, ws,
                                      ws_bytes, st))
         return rc;
-    JMAC_LAUNCH_SEEDED(bn_tanh_normalize_drop_fwd_kernel, kFuseRows, rows_grid(N, kFuseRows), st, x, ldx, N, D4, weight, bias,
-                       (const float*)save_mean, (const float*)save_invstd, y, ldy, row_map, y_rows, ldyr, norm_eps, ds, yn, ldyn, inv);
+    with_drop_form(ds.seed != nullptr, false, [&](auto SD, auto) {
+        hipLaunchKernelGGL((bn_tanh_normalize_drop_fwd_kernel<SD.value, kFuseRows>), dim3(rows_grid(N, kFuseRows)), dim3(kBlock), 0, st, x,
+                           ldx, N, D4, weight, bias, (const float*)save_mean, (const float*)save_invstd, y, ldy, row_map, y_rows, ldyr,
+                           norm_eps, ds, yn, ldyn, inv);
+    });
     return (int)hipGetLastError();
 }
 
@@ -1385,26 +1223,24 @@ int jmac_bn_tanh_bwd_normadj_f32(const float* x, int64_t ldx, const float* y, in
     const int D4 = (int)(d / 4);
     float* partial = (float*)ws;
     unsigned pg = 0;
+    const bool rowform = N >= kDropRowsMinN;                      // the adjoint as the separate launch forms it at this N
     if (N > 0) {
         if (!x || !y || !inv || !g || !gx) return JMAC_EINVAL;
         pg = stat_grid(N, D4);                                    // bn_bwd_partial_kernel's blocks and row slots: the same sums
         const int rpb = kBlock / D4;
         const unsigned threads = 64u * (unsigned)(rpb < kBlock / 64 ? rpb : kBlock / 64);
-        const bool rowform = N >= kDropRowsMinN;
-#define JMAC_PARTIAL(SD, RF)                                                                                                      \
-        hipLaunchKernelGGL((bn_bwd_partial_adj_kernel<SD, RF, kFuseBwdRows>), dim3(pg), dim3(threads), stat_smem(D4), st, x, ldx, \
-                           y, ldy, g, ldg, inv, ds, norm_eps, gy2, ldgy2, row_map, N, D4, save_mean, save_invstd, partial)
-        if (ds.seed && rowform) JMAC_PARTIAL(true, true);
-        else if (ds.seed) JMAC_PARTIAL(true, false);
-        else if (rowform) JMAC_PARTIAL(false, true);
-        else JMAC_PARTIAL(false, false);
-#undef JMAC_PARTIAL
+        with_drop_form(ds.seed != nullptr, rowform, [&](auto SD, auto RF) {
+            hipLaunchKernelGGL((bn_bwd_partial_adj_kernel<SD.value, RF.value, kFuseBwdRows>), dim3(pg), dim3(threads), stat_smem(D4), st, x,
+                               ldx, y, ldy, g, ldg, inv, ds, norm_eps, gy2, ldgy2, row_map, N, D4, save_mean, save_invstd, partial);
+        });
     }
     launch_bn_bwd_param_grads(partial, pg, d, gweight, gbias, st);
     if (N > 0)
-        JMAC_LAUNCH_ADJ(bn_bwd_apply_adj_kernel, kFuseBwdRows, rows_grid(N, kFuseBwdRows), st, x, ldx, y, ldy, g, ldg, inv, ds,
-                           norm_eps, gy2, ldgy2, row_map, N, D4, weight, save_mean, save_invstd, (const float*)gweight,
-                           (const float*)gbias, training ? 1 : 0, 1.f / (float)N, gx, ldgx);
+        with_drop_form(ds.seed != nullptr, rowform, [&](auto SD, auto RF) {
+            hipLaunchKernelGGL((bn_bwd_apply_adj_kernel<SD.value, RF.value, kFuseBwdRows>), dim3(rows_grid(N, kFuseBwdRows)), dim3(kBlock),
+                               0, st, x, ldx, y, ldy, g, ldg, inv, ds, norm_eps, gy2, ldgy2, row_map, N, D4, weight, save_mean,
+                               save_invstd, (const float*)gweight, (const float*)gbias, training ? 1 : 0, 1.f / (float)N, gx, ldgx);
+        });
     return (int)hipGetLastError();
 }
 
@@ -1419,12 +1255,13 @@ int jmac_row_normalize_dropseed_bwd_rows_f32(const float* x, int64_t ldx, const 
     if (N == 0) return JMAC_OK;
     if (!x || !inv || !g || !dst) return JMAC_EINVAL;
     if (!aligned16({x, g, add, dst})) return JMAC_EDIM;
-    JMAC_LAUNCH_ADJ(row_normalize_drop_bwd_scatter_kernel, kFuseBwdRows, rows_grid(N, kFuseBwdRows), (hipStream_t)stream, x, ldx,
-                       inv, ds, g, ldg, add, ldadd, row_map, N, (int)(d / 4), eps, dst, lddst, accumulate ? 1 : 0);
+    with_drop_form(ds.seed != nullptr, N >= kDropRowsMinN, [&](auto SD, auto RF) {
+        hipLaunchKernelGGL((row_normalize_drop_bwd_scatter_kernel<SD.value, RF.value, false, kFuseBwdRows>),
+                           dim3(rows_grid(N, kFuseBwdRows)), dim3(kBlock), 0, (hipStream_t)stream, x, ldx, inv, ds, g, ldg, add, ldadd,
+                           row_map, N, (int)(d / 4), eps, dst, lddst, accumulate ? 1 : 0);
+    });
     return (int)hipGetLastError();
 }
-#undef JMAC_LAUNCH_SEEDED
-#undef JMAC_LAUNCH_ADJ
 
 // ---- segmented BatchNorm + tanh (block-batched encoder: several KGs in one launch set) ------------------------------
 static int make_seg(int32_t nblocks, const int64_t* blk_ptr, const int32_t* order, int D4, SegTab& s) {

@@ -11,9 +11,11 @@ jmac_amd/csrc/norm.hip) against the separate launches they replace, composed her
 Shapes: d = 300 (the second column chunk is valid on lanes 0-10 only), 64 (one chunk, lanes 16-63 idle), 512 (both chunks full);
 N = 1, 5, 1031 (no multiple of the rows per wave; 1031 no multiple of the waves per block either); row map none / identity / a
 random permutation; destination pitch 2d and 3d; p_drop 0 and 0.4 (seed form); one all-zero row and one row with norm below eps;
-with and without the second gradient; and N = 2053, d = 300: from 2048 rows on the separate normalise launches take their
-four-rows-per-wave kernels, whose backward the compiler contracts differently from the row-per-wave one (the fused forms follow
-the launch they replace).  Then the node itself, FUSE_ROW_PASSES on against off."""
+with and without the second gradient; and N = 2053, d = 300: from 2048 rows on the separate normalise launches take the
+four-rows-per-wave form, whose adjoint is rounded differently from the row-per-wave kernels' (norm.hip spells both forms out; a
+fused launch takes the form of the launch it replaces).  From that row count on the separate launches and the fused ones run the
+same forward and backward body, so A and E compare a body with itself there: tests/test_gpu_normalize_forms.py holds oracles from
+outside the library.  Then the node itself, FUSE_ROW_PASSES on against off."""
 import types
 
 import numpy as np
