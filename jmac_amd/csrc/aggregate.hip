@@ -102,16 +102,22 @@ __device__ __forceinline__ float4 sel4(bool c, float4 a) { return c ? a : f4zero
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
+// The work schedule of one forward launch, for either lane map.  Map (Lanes64Map, HalfWaveMap below) supplies what depends on
+// how a [Q|Z] row lies on the lanes:
+//   P, Z, Acc, Out, Stash     a destination's raw P / Z rows, the per-lane accumulators, what a lane stores, Out's LDS image
+//   Map(a, lane)              per-wave setup: lane offsets, a_att, the loop relation's Rz row
+//   load_p, load_z            the raw loads of P[i] / Z[i]
+//   edge_loop                 online softmax over an item's entries: (m, l, acc) from zero
+//   reduce                    Acc -> Out
+//   put, scale, merge         Out -> Stash;  o *= f;  o += f * Stash   (the cooperative merge)
+//   finish, finish_empty      out[i] = out_scale * (scale * o + Z[i] - Rz[loop]);  the same without edges
+//   store_part                the partial accumulator of a split destination's item
 // bid / nblk: the block's index and the block count of ITS job (one launch may carry two independent jobs: below)
-template <int NCH, int U, int D4T, typename TT>
-__device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bid, const int nblk) {
-    typedef typename RawOf<TT>::type raw_t;
+template <class Map>
+__device__ __forceinline__ void fwd_schedule(const FwdArgs& a, const int bid, const int nblk) {
     // cooperative segments: the partial softmax states of the block's four waves meet here
-    __shared__ float4 coop_acc[kWavesPerBlock][NCH][64];
+    __shared__ typename Map::Stash coop_acc[kWavesPerBlock];
     __shared__ float coop_ml[kWavesPerBlock][2];
-    const TT* const tP = static_cast<const TT*>(a.P);
-    const TT* const tQZ = static_cast<const TT*>(a.QZ);
-    const TT* const tRR = static_cast<const TT*>(a.RR);
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int nwaves = nblk * kWavesPerBlock;
@@ -119,204 +125,42 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
     const int n_empty = a.counts[3];
     const int n_coop = a.n_coop;                  // == counts[4]; from the host so that no address below waits for it
     const int n_reg = n_items - n_empty;          // items with entries come first, the empty segments are the tail of the list
-    Lanes<NCH, D4T> L;
-    L.init(lane, a.D4, a.zoff - 4 * a.D4);
-    const int voff = 4 * L.D4();
-    float4 av[NCH];
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) av[k] = L.any_h(k) ? sel4(L.is_h[k], ld4(a.a_att + (L.is_h[k] ? L.coff[k] : 0))) : f4zero();
-    const bool has_loop = a.loop_rel >= 0;
-    const TT* rloop = tRR + (int64_t)(has_loop ? a.loop_rel : 0) * a.ldrr;
+    const Map M(a, lane);
 
     // Work units of a launch, in this order for every block / wave:
-    //   1. cooperative segments (block cb = blockIdx, blockIdx + grid, ...): four waves, one quarter of the entries each
+    //   1. cooperative segments (block cb = bid, bid + nblk, ...): four waves, one quarter of the entries each
     //   2. items (wave-strided over the item list behind the cooperative items)
     //   3. packs of kEmptyPack empty segments
     // Items are software-pipelined: while item k computes, the header of item k+2 and the first col/type
     // batch of item k+1 are already in flight, so a wave's critical path per item is one gather round trip
     // instead of header -> col/type -> gather (measured: 65k rows of degree 1 took 114 us serialised).
     // The first header is fetched at a clamped index so that it does not wait for the device-side counts.
-    const int it0 = bid * kWavesPerBlock + wave;
-    // the loop relation's Rz row is the same for every destination: one read per wave
-    // (kept RAW like the Z[i] chunks below: half the registers for bf16 tables, converted where they are used)
-    raw_t rl[NCH];
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-        if (L.any_v(k)) rl[k] = ldraw(rloop + L.coffc[k]);
 
-    // ---- the edges [item.beg, item.end) of destination item.seg: online softmax over them into (m, l, acc) ----------
-    // my_col / my_typ: source and type of entry item.beg + lane (first batch of up to 64), supplied by the caller
-    auto edge_loop = [&](const jmac_item_t& item, int my_col, int my_typ, const float4 (&pv)[NCH], float& m, float& l,
-                         float4 (&acc)[NCH]) {
-        for (int e0 = item.beg; e0 < item.end; e0 += 64) {
-            const int nb = min(64, item.end - e0);
-            if (e0 != item.beg) {
-                const int le = min(lane, nb - 1);
-                my_col = a.col[e0 + le];
-                my_typ = a.etype[e0 + le];
-            }
-            // group body for UU edges that are all valid; dispatched on the edges left (4 / 2 / 1) so that a
-            // degree-1 destination does not pay the instruction count of a full 4-edge group
-            auto group = [&](auto uu_c, const int u0) {
-                constexpr int UU = decltype(uu_c)::value;
-                raw_t qraw[UU][NCH], rraw[UU][NCH];
-                float4 q[UU][NCH];
-                // 1) issue every gather of the group before any arithmetic
-#pragma unroll
-                for (int u = 0; u < UU; ++u) {
-                    const int j = bcast_i(my_col, u0 + u);
-                    const int t = bcast_i(my_typ, u0 + u);
-                    const TT* qrow = tQZ + (int64_t)j * a.ldqz;
-                    const TT* rrow = tRR + (int64_t)t * a.ldrr;
-#pragma unroll
-                    for (int k = 0; k < NCH; ++k) {
-                        qraw[u][k] = ldraw(qrow + L.coffc[k]);
-                        rraw[u][k] = ldraw(rrow + L.coffc[k]);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);   // measured: 11.6 ms vs 13.3 ms with the IGroupLP form (config 4)
-                // 2) logits
-                float s[UU];
-#pragma unroll
-                for (int u = 0; u < UU; ++u) {
-                    float part = 0.f;
-#pragma unroll
-                    for (int k = 0; k < NCH; ++k) {
-                        q[u][k] = sub4(cvt4(qraw[u][k]), cvt4(rraw[u][k]));
-                        if (!L.all_valid(k)) q[u][k] = sel4(L.valid[k], q[u][k]);
-                        if (L.any_h(k)) part += dot4(av[k], leaky4<D4T != 0>(add4(pv[k], q[u][k]), a.slope));
-                    }
-                    s[u] = part;
-                }
-                wave_sum_n<UU>(s);
-                // 3) online softmax update
-                float gmax = s[0];
-#pragma unroll
-                for (int u = 1; u < UU; ++u) gmax = fmaxf(gmax, s[u]);
-                const float mn = fmaxf(m, gmax);
-                const float sc = fast_exp(m - mn);
-                float w[UU], wsum = 0.f;
-#pragma unroll
-                for (int u = 0; u < UU; ++u) {
-                    w[u] = fast_exp(s[u] - mn);
-                    wsum += w[u];
-                }
-                l = l * sc + wsum;
-#pragma unroll
-                for (int k = 0; k < NCH; ++k) {
-                    if (!L.any_v(k)) continue;
-                    float4 x = mul4(acc[k], sc);
-#pragma unroll
-                    for (int u = 0; u < UU; ++u) x = fma4(q[u][k], w[u], x);
-                    acc[k] = x;
-                }
-                m = mn;
-            };
-            if constexpr (U >= 4) {
-                // Large graphs (HBM-bound): groups of two edges, SOFTWARE-PIPELINED -- the gathers of group g+1 are in
-                // flight while group g is reduced, so a wave always has rows outstanding (with "load 4, wait, compute 4"
-                // a wave's memory queue is empty for the whole compute phase).  Two register buffers, roles fixed per
-                // unrolled half; an odd tail edge is issued twice (clamped) and weighted zero.
-                // Group size: two fp32 edges or FOUR bf16 edges -- a bf16 row is half the bytes, so pairs would leave half as
-                // many bytes in flight per wave (measured with pairs: 0.45 of the HBM peak on bf16 tables against 0.59 on fp32).
-                constexpr int GS = sizeof(TT) == 2 ? 4 : 2;
-                raw_t qA[GS][NCH], rA[GS][NCH], qB[GS][NCH], rB[GS][NCH];
-                auto issue = [&](const int g, raw_t (&qr)[GS][NCH], raw_t (&rr)[GS][NCH]) {
-#pragma unroll
-                    for (int u = 0; u < GS; ++u) {
-                        const int le = min(GS * g + u, nb - 1);
-                        const int j = bcast_i(my_col, le);
-                        const int t = bcast_i(my_typ, le);
-                        const TT* qrow = tQZ + (int64_t)j * a.ldqz;
-                        const TT* rrow = tRR + (int64_t)t * a.ldrr;
-#pragma unroll
-                        for (int k = 0; k < NCH; ++k) {
-                            qr[u][k] = ldraw(qrow + L.coffc[k]);
-                            rr[u][k] = ldraw(rrow + L.coffc[k]);
-                        }
-                    }
-                };
-                auto consume = [&](const int g, const raw_t (&qr)[GS][NCH], const raw_t (&rr)[GS][NCH]) {
-                    float4 q[GS][NCH];
-                    float sv[GS];
-#pragma unroll
-                    for (int u = 0; u < GS; ++u) {
-                        float part = 0.f;
-#pragma unroll
-                        for (int k = 0; k < NCH; ++k) {
-                            q[u][k] = sub4(cvt4(qr[u][k]), cvt4(rr[u][k]));
-                            if (!L.all_valid(k)) q[u][k] = sel4(L.valid[k], q[u][k]);
-                            if (L.any_h(k)) part += dot4(av[k], leaky4<D4T != 0>(add4(pv[k], q[u][k]), a.slope));
-                        }
-                        sv[u] = part;
-                    }
-                    wave_sum_n<GS>(sv);
-                    float mn = m;
-#pragma unroll
-                    for (int u = 0; u < GS; ++u) {
-                        if (u > 0 && GS * g + u >= nb) sv[u] = -INFINITY;   // tail: the clamped duplicates get weight exp(-inf) = 0
-                        mn = fmaxf(mn, sv[u]);
-                    }
-                    const float sc = fast_exp(m - mn);
-                    float w[GS], wsum = 0.f;
-#pragma unroll
-                    for (int u = 0; u < GS; ++u) {
-                        w[u] = fast_exp(sv[u] - mn);
-                        wsum += w[u];
-                    }
-                    l = l * sc + wsum;
-#pragma unroll
-                    for (int k = 0; k < NCH; ++k) {
-                        if (!L.any_v(k)) continue;
-                        float4 x = mul4(acc[k], sc);
-#pragma unroll
-                        for (int u = 0; u < GS; ++u) x = fma4(q[u][k], w[u], x);
-                        acc[k] = x;
-                    }
-                    m = mn;
-                };
-                const int ngr = (nb + GS - 1) / GS;
-                issue(0, qA, rA);
-                for (int g = 0; g < ngr; g += 2) {
-                    if (g + 1 < ngr) issue(g + 1, qB, rB);
-                    __builtin_amdgcn_sched_barrier(0);
-                    consume(g, qA, rA);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (g + 1 < ngr) {
-                        if (g + 2 < ngr) issue(g + 2, qA, rA);
-                        __builtin_amdgcn_sched_barrier(0);
-                        consume(g + 1, qB, rB);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            } else {
-                int u0 = 0;
-                for (; u0 + 2 <= nb; u0 += 2) group(std::integral_constant<int, 2>{}, u0);
-                if (u0 < nb) group(std::integral_constant<int, 1>{}, u0);
-            }
-        }
-    };
-    // ---- out[i] = out_scale * ( sqrt(deg) / l * acc  +  Z[i] - Rz[loop] ),  softmax statistics for the backward ---------
-    auto finish = [&](int i, int deg, float m, float l, const float4 (&acc)[NCH], const raw_t (&zs)[NCH]) {
-        const float scale = l > 0.f ? sqrtf((float)deg) / l : 0.f;
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            if (L.any_v(k) && L.is_v(k)) {
-                const float4 self = has_loop ? sub4(cvt4(zs[k]), cvt4(rl[k])) : f4zero();
-                const float4 o = add4(mul4(acc[k], scale), self);                 // + Z[i] - Rz[loop]
-                st4(a.out + (int64_t)i * a.ldo + (L.coff[k] - voff), mul4(o, a.out_scale));
-            }
-        }
-        if (lane == 0) {
-            a.seg_max[i] = m;
-            a.seg_den[i] = l;
-        }
-    };
+    // source and type of entry item.beg + lane (first batch of up to 64)
     auto first_batch = [&](const jmac_item_t& item, int& c, int& t) {
         const int cnb = min(64, item.end - item.beg);
         const int idx = cnb > 0 ? item.beg + min(lane, cnb - 1) : 0;
         c = a.col[idx];
         t = a.etype[idx];
+    };
+    // the output row and the softmax statistics for the backward
+    auto finish = [&](int i, int deg, float m, float l, const typename Map::Out& o, const typename Map::Z& z) {
+        M.finish(i, l > 0.f ? sqrtf((float)deg) / l : 0.f, o, z);
+        if (lane == 0) {
+            a.seg_max[i] = m;
+            a.seg_den[i] = l;
+        }
+    };
+    // This function puts nothing between load_p / load_z and edge_loop and never reads p or z itself: the half-wave map keeps
+    // them raw and issues the item's first gathers in the same basic block, ahead of its conversion of P[i]
+    // (HalfWaveMap::edge_loop).  What a map's own load_p does with its row is the map's business (the 64-lane map converts there).
+    auto aggregate = [&](const jmac_item_t& item, int col, int typ, float& m, float& l, typename Map::Out& o, typename Map::Z& z) {
+        typename Map::P p;
+        typename Map::Acc acc;
+        M.load_p(item.seg, p);
+        M.load_z(item.seg, z);          // the self-loop term, fetched with the header-dependent loads rather than after the edges
+        M.edge_loop(item, col, typ, p, m, l, acc);
+        M.reduce(acc, o);
     };
 
     // ---- 1. cooperative segments: one workgroup per segment -----------------------------------------------------------
@@ -325,25 +169,12 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
         const int i = item.seg;
         int ccol, ctyp;
         first_batch(item, ccol, ctyp);
-        float4 pv[NCH], acc[NCH];
-        raw_t zs[NCH];
-        const TT* prow = tP + (int64_t)i * a.ldp;
-        const TT* zrow = tQZ + ((int64_t)(has_loop ? i : 0) + a.self_off) * a.ldqz;   // no loop: row 0 (valid, unused)
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            pv[k] = L.any_h(k) ? cvt4(ldraw(prow + (L.is_h[k] ? L.coff[k] : 0))) : f4zero();
-            if (L.any_v(k)) zs[k] = ldraw(zrow + L.coffc[k]);
-            acc[k] = f4zero();
-        }
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-            if (L.any_h(k) && L.any_v(k)) pv[k] = sel4(L.is_h[k], pv[k]);
-        float m = -INFINITY, l = 0.f;
-        edge_loop(item, ccol, ctyp, pv, m, l, acc);
+        float m, l;
+        typename Map::Out o;
+        typename Map::Z z;                                // (wave 0 uses it)
+        aggregate(item, ccol, ctyp, m, l, o, z);
         if (wave != 0) {
-#pragma unroll
-            for (int k = 0; k < NCH; ++k)
-                if (L.any_v(k)) coop_acc[wave][k][lane] = acc[k];
+            M.put(coop_acc[wave], o);
             if (lane == 0) {
                 coop_ml[wave][0] = m;
                 coop_ml[wave][1] = l;
@@ -351,23 +182,20 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
         }
         __syncthreads();
         if (wave == 0) {
-            // merge in wave order (fixed summation order): M = max m_w, state_w scaled by e^(m_w - M)
-            float M = m;
+            // merge in wave order (fixed summation order): mx = max m_w, state_w scaled by e^(m_w - mx)
+            float mx = m;
 #pragma unroll
-            for (int w = 1; w < kWavesPerBlock; ++w) M = fmaxf(M, coop_ml[w][0]);
-            float f = fast_exp(m - M);               // a wave without entries: m = -inf, l = 0 -> factor 0
+            for (int w = 1; w < kWavesPerBlock; ++w) mx = fmaxf(mx, coop_ml[w][0]);
+            float f = fast_exp(m - mx);              // a wave without entries: m = -inf, l = 0 -> factor 0
             float lsum = l * f;
-#pragma unroll
-            for (int k = 0; k < NCH; ++k) acc[k] = mul4(acc[k], f);
+            M.scale(o, f);
 #pragma unroll
             for (int w = 1; w < kWavesPerBlock; ++w) {
-                f = fast_exp(coop_ml[w][0] - M);
+                f = fast_exp(coop_ml[w][0] - mx);
                 lsum = fmaf(coop_ml[w][1], f, lsum);
-#pragma unroll
-                for (int k = 0; k < NCH; ++k)
-                    if (L.any_v(k)) acc[k] = fma4(coop_acc[w][k][lane], f, acc[k]);
+                M.merge(o, coop_acc[w], f);
             }
-            finish(i, a.rowptr[i + 1] - a.rowptr[i], M, lsum, acc, zs);
+            finish(i, a.rowptr[i + 1] - a.rowptr[i], mx, lsum, o, z);
         }
         __syncthreads();
     }
@@ -377,28 +205,18 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
         const int n_packs = (n_empty + kEmptyPack - 1) / kEmptyPack;
         for (int p = p0; p < n_packs; p += nwaves) {
             int seg[kEmptyPack];
-            raw_t zs[kEmptyPack][NCH];
+            typename Map::Z z[kEmptyPack];
 #pragma unroll
             for (int u = 0; u < kEmptyPack; ++u) seg[u] = a.items[min(n_reg + p * kEmptyPack + u, n_items - 1)].seg;
 #pragma unroll
-            for (int u = 0; u < kEmptyPack; ++u) {
-                const TT* zrow = tQZ + ((int64_t)(has_loop ? seg[u] : 0) + a.self_off) * a.ldqz;
-#pragma unroll
-                for (int k = 0; k < NCH; ++k)
-                    if (L.any_v(k)) zs[u][k] = ldraw(zrow + L.coffc[k]);
-            }
+            for (int u = 0; u < kEmptyPack; ++u) M.load_z(seg[u], z[u]);
 #pragma unroll
             for (int u = 0; u < kEmptyPack; ++u) {
                 if (p * kEmptyPack + u >= n_empty) break;
-                const int i = seg[u];
-#pragma unroll
-                for (int k = 0; k < NCH; ++k)
-                    if (L.any_v(k) && L.is_v(k))
-                        st4(a.out + (int64_t)i * a.ldo + (L.coff[k] - voff),
-                            mul4(has_loop ? sub4(cvt4(zs[u][k]), cvt4(rl[k])) : f4zero(), a.out_scale));
+                M.finish_empty(seg[u], z[u]);
                 if (lane == 0) {
-                    a.seg_max[i] = -INFINITY;
-                    a.seg_den[i] = 0.f;
+                    a.seg_max[seg[u]] = -INFINITY;
+                    a.seg_den[seg[u]] = 0.f;
                 }
             }
         }
@@ -406,7 +224,7 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
 
     // ---- 2. items ---------------------------------------------------------------------------------------------------------
     const int it_base = n_coop * kWavesPerBlock;           // the cooperative items occupy the head of the item list
-    int it = it_base + it0;
+    int it = it_base + bid * kWavesPerBlock + wave;
     jmac_item_t item = a.items[min(it, a.n_items_max - 1)];     // clamped: does not wait for the device-side counts
     // the first two entries of the item arrive WITH its header (item_edges): a short item starts its row gathers one
     // dependent round trip earlier
@@ -433,29 +251,15 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
         const jmac_item_t nnitem = a.items[min(it + 2 * nwaves, n_items - 1)];
         int ncol, ntyp;
         first_batch(nitem, ncol, ntyp);
-        const int i = item.seg;
-        float4 pv[NCH], acc[NCH];
-        raw_t zs[NCH];
-        const TT* prow = tP + (int64_t)i * a.ldp;
-        const TT* zrow = tQZ + ((int64_t)(has_loop ? i : 0) + a.self_off) * a.ldqz;   // no loop: row 0 (valid, unused)
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            pv[k] = L.any_h(k) ? cvt4(ldraw(prow + (L.is_h[k] ? L.coff[k] : 0))) : f4zero();
-            // self-loop term Z[i] (v-role lanes), fetched with the header-dependent loads rather than after the edges
-            if (L.any_v(k)) zs[k] = ldraw(zrow + L.coffc[k]);
-            acc[k] = f4zero();
-        }
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-            if (L.any_h(k) && L.any_v(k)) pv[k] = sel4(L.is_h[k], pv[k]);
-        float m = -INFINITY, l = 0.f;
-        edge_loop(item, ccol, ctyp, pv, m, l, acc);
+        float m, l;
+        typename Map::Out o;
+        typename Map::Z z;
+        aggregate(item, ccol, ctyp, m, l, o, z);
         if (item.pslot < 0) {
-            finish(i, item.end - item.beg, m, l, acc, zs);
+            finish(item.seg, item.end - item.beg, m, l, o, z);
         } else {
-#pragma unroll
-            for (int k = 0; k < NCH; ++k)
-                if (L.any_v(k) && L.is_v(k)) st4(a.part_acc + (int64_t)item.pslot * voff + (L.coff[k] - voff), acc[k]);
+            // partial state of a split destination: the combine pass reads d floats per slot in row order
+            M.store_part(item.pslot, o);
             if (lane == 0) {
                 a.part_ml[2 * item.pslot] = m;
                 a.part_ml[2 * item.pslot + 1] = l;
@@ -471,24 +275,223 @@ __device__ __forceinline__ void rel_attn_fwd_body(const FwdArgs& a, const int bi
     empties(it - n_reg);                    // persistent grids: the waves share the empty segments after their items
 }
 
+// ---- the 64-lane lane map: chunk c = lane + 64 k of a [Q|Z] row (Lanes above), one edge per wave instruction; U edges per group
+template <int NCH, int U, int D4T, typename TT>
+struct Lanes64Map {
+    typedef typename RawOf<TT>::type raw_t;
+    typedef float4 P[NCH];
+    typedef raw_t Z[NCH];
+    typedef float4 Acc[NCH];
+    typedef float4 Out[NCH];
+    typedef float4 Stash[NCH][64];
+    const FwdArgs& a;
+    const TT *tP, *tQZ, *tRR;
+    int lane, voff;
+    Lanes<NCH, D4T> L;
+    float4 av[NCH];
+    bool has_loop;
+    raw_t rl[NCH];
+
+    __device__ __forceinline__ Lanes64Map(const FwdArgs& a_, int lane_)
+        : a(a_), tP(static_cast<const TT*>(a_.P)), tQZ(static_cast<const TT*>(a_.QZ)), tRR(static_cast<const TT*>(a_.RR)), lane(lane_) {
+        L.init(lane, a.D4, a.zoff - 4 * a.D4);
+        voff = 4 * L.D4();
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) av[k] = L.any_h(k) ? sel4(L.is_h[k], ld4(a.a_att + (L.is_h[k] ? L.coff[k] : 0))) : f4zero();
+        has_loop = a.loop_rel >= 0;
+        // the loop relation's Rz row is the same for every destination: one read per wave
+        // (kept RAW like the Z[i] chunks: half the registers for bf16 tables, converted where they are used)
+        const TT* rloop = tRR + (int64_t)(has_loop ? a.loop_rel : 0) * a.ldrr;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_v(k)) rl[k] = ldraw(rloop + L.coffc[k]);
+    }
+    __device__ __forceinline__ void load_p(int i, P& pv) const {
+        const TT* prow = tP + (int64_t)i * a.ldp;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) pv[k] = L.any_h(k) ? cvt4(ldraw(prow + (L.is_h[k] ? L.coff[k] : 0))) : f4zero();
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_h(k) && L.any_v(k)) pv[k] = sel4(L.is_h[k], pv[k]);
+    }
+    __device__ __forceinline__ void load_z(int i, Z& zs) const {
+        const TT* zrow = tQZ + ((int64_t)(has_loop ? i : 0) + a.self_off) * a.ldqz;   // no loop: row 0 (valid, unused)
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_v(k)) zs[k] = ldraw(zrow + L.coffc[k]);
+    }
+    // the gathers of UU entries, e .. e + UU - 1 of the batch of nb whose sources / types the lanes hold in (my_col, my_typ);
+    // CLAMP: entries past the batch re-read its last one
+    template <int UU, bool CLAMP>
+    __device__ __forceinline__ void issue(int my_col, int my_typ, int e, int nb, raw_t (&qr)[UU][NCH], raw_t (&rr)[UU][NCH]) const {
+#pragma unroll
+        for (int u = 0; u < UU; ++u) {
+            const int le = CLAMP ? min(e + u, nb - 1) : e + u;
+            const int j = bcast_i(my_col, le);
+            const int t = bcast_i(my_typ, le);
+            const TT* qrow = tQZ + (int64_t)j * a.ldqz;
+            const TT* rrow = tRR + (int64_t)t * a.ldrr;
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                qr[u][k] = ldraw(qrow + L.coffc[k]);
+                rr[u][k] = ldraw(rrow + L.coffc[k]);
+            }
+        }
+    }
+    // the raw gathered rows of those UU entries -> logits, wave sum, online-softmax update of (m, l, acc).  CLAMP: the clamped
+    // duplicates past the batch get weight exp(-inf) = 0
+    template <int UU, bool CLAMP>
+    __device__ __forceinline__ void step(const raw_t (&qr)[UU][NCH], const raw_t (&rr)[UU][NCH], int e, int nb, const P& pv, float& m,
+                                         float& l, Acc& acc) const {
+        float4 q[UU][NCH];
+        float s[UU];
+#pragma unroll
+        for (int u = 0; u < UU; ++u) {
+            float part = 0.f;
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                q[u][k] = sub4(cvt4(qr[u][k]), cvt4(rr[u][k]));
+                if (!L.all_valid(k)) q[u][k] = sel4(L.valid[k], q[u][k]);
+                if (L.any_h(k)) part += dot4(av[k], leaky4<D4T != 0>(add4(pv[k], q[u][k]), a.slope));
+            }
+            s[u] = part;
+        }
+        wave_sum_n<UU>(s);
+        // (the group's maximum first, then the running one: with the running maximum alone the compiler contracts the logits of
+        // the D4T = 64, U = 2 kernels differently -- seen in the ISA and in the last bits of seg_max)
+        float gmax = s[0];
+#pragma unroll
+        for (int u = 1; u < UU; ++u) {
+            if (CLAMP && e + u >= nb) s[u] = -INFINITY;
+            gmax = fmaxf(gmax, s[u]);
+        }
+        const float mn = fmaxf(m, gmax);
+        const float sc = fast_exp(m - mn);
+        float w[UU], wsum = 0.f;
+#pragma unroll
+        for (int u = 0; u < UU; ++u) {
+            w[u] = fast_exp(s[u] - mn);
+            wsum += w[u];
+        }
+        l = l * sc + wsum;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (!L.any_v(k)) continue;
+            float4 x = mul4(acc[k], sc);
+#pragma unroll
+            for (int u = 0; u < UU; ++u) x = fma4(q[u][k], w[u], x);
+            acc[k] = x;
+        }
+        m = mn;
+    }
+    // my_col / my_typ: source and type of entry item.beg + lane (first batch of up to 64), supplied by the caller
+    __device__ __forceinline__ void edge_loop(const jmac_item_t& item, int my_col, int my_typ, const P& pv, float& m, float& l,
+                                              Acc& acc) const {
+        m = -INFINITY;
+        l = 0.f;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) acc[k] = f4zero();
+        for (int e0 = item.beg; e0 < item.end; e0 += 64) {
+            const int nb = min(64, item.end - e0);
+            if (e0 != item.beg) {
+                const int le = min(lane, nb - 1);
+                my_col = a.col[e0 + le];
+                my_typ = a.etype[e0 + le];
+            }
+            if constexpr (U >= 4) {
+                // Large graphs (HBM-bound): groups of two edges, SOFTWARE-PIPELINED -- the gathers of group g+1 are in
+                // flight while group g is reduced, so a wave always has rows outstanding (with "load 4, wait, compute 4"
+                // a wave's memory queue is empty for the whole compute phase).  Two register buffers, roles fixed per
+                // unrolled half; an odd tail edge is issued twice (clamped) and weighted zero.
+                // Group size: two fp32 edges or FOUR bf16 edges -- a bf16 row is half the bytes, so pairs would leave half as
+                // many bytes in flight per wave (measured with pairs: 0.45 of the HBM peak on bf16 tables against 0.59 on fp32).
+                constexpr int GS = sizeof(TT) == 2 ? 4 : 2;
+                raw_t qA[GS][NCH], rA[GS][NCH], qB[GS][NCH], rB[GS][NCH];
+                const int ngr = (nb + GS - 1) / GS;
+                issue<GS, true>(my_col, my_typ, 0, nb, qA, rA);
+                for (int g = 0; g < ngr; g += 2) {
+                    if (g + 1 < ngr) issue<GS, true>(my_col, my_typ, GS * (g + 1), nb, qB, rB);
+                    __builtin_amdgcn_sched_barrier(0);
+                    step<GS, true>(qA, rA, GS * g, nb, pv, m, l, acc);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (g + 1 < ngr) {
+                        if (g + 2 < ngr) issue<GS, true>(my_col, my_typ, GS * (g + 2), nb, qA, rA);
+                        __builtin_amdgcn_sched_barrier(0);
+                        step<GS, true>(qB, rB, GS * (g + 1), nb, pv, m, l, acc);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            } else {
+                // small graphs: every gather of a group before any arithmetic, no pipeline; groups of two valid edges and a
+                // single one, so that a degree-1 destination does not pay the instruction count of a full group
+                auto group = [&](auto uu_c, const int u0) {
+                    constexpr int UU = decltype(uu_c)::value;
+                    raw_t qr[UU][NCH], rr[UU][NCH];
+                    this->template issue<UU, false>(my_col, my_typ, u0, nb, qr, rr);
+                    __builtin_amdgcn_sched_barrier(0);   // measured: 11.6 ms vs 13.3 ms with the IGroupLP form (config 4)
+                    this->template step<UU, false>(qr, rr, u0, nb, pv, m, l, acc);
+                };
+                int u0 = 0;
+                for (; u0 + 2 <= nb; u0 += 2) group(std::integral_constant<int, 2>{}, u0);
+                if (u0 < nb) group(std::integral_constant<int, 1>{}, u0);
+            }
+        }
+    }
+    __device__ __forceinline__ void reduce(const Acc& acc, Out& o) const {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) o[k] = acc[k];
+    }
+    __device__ __forceinline__ void put(Stash& st, const Out& o) const {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_v(k)) st[k][lane] = o[k];
+    }
+    __device__ __forceinline__ void scale(Out& o, float f) const {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) o[k] = mul4(o[k], f);
+    }
+    __device__ __forceinline__ void merge(Out& o, const Stash& st, float f) const {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_v(k)) o[k] = fma4(st[k][lane], f, o[k]);
+    }
+    __device__ __forceinline__ float4 self(const Z& zs, int k) const { return has_loop ? sub4(cvt4(zs[k]), cvt4(rl[k])) : f4zero(); }
+    __device__ __forceinline__ void finish(int i, float scale, const Out& o, const Z& zs) const {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_v(k) && L.is_v(k))
+                st4(a.out + (int64_t)i * a.ldo + (L.coff[k] - voff), mul4(add4(mul4(o[k], scale), self(zs, k)), a.out_scale));
+    }
+    __device__ __forceinline__ void finish_empty(int i, const Z& zs) const {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_v(k) && L.is_v(k)) st4(a.out + (int64_t)i * a.ldo + (L.coff[k] - voff), mul4(self(zs, k), a.out_scale));
+    }
+    __device__ __forceinline__ void store_part(int pslot, const Out& o) const {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (L.any_v(k) && L.is_v(k)) st4(a.part_acc + (int64_t)pslot * voff + (L.coff[k] - voff), o[k]);
+    }
+};
+
 template <int NCH, int U, int D4T, typename TT>
 __global__ __launch_bounds__(kBlock) void rel_attn_fwd_kernel(FwdArgs a) {
-    rel_attn_fwd_body<NCH, U, D4T, TT>(a, (int)blockIdx.x, (int)gridDim.x);
+    fwd_schedule<Lanes64Map<NCH, U, D4T, TT>>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // TWO independent aggregation jobs in one launch (blocks [0, g0): job 0, the rest: job 1): conv1_alignment and conv1_completion of
 // JMAC.forward_name (src/jmac_model.py:183,190) read different tables, weights and loop rows but share the graph and do not depend
 // on each other -- at DBP-5L size each launch is a chain of dependent round trips with most of the chip idle, so two jobs side by
-// side cost little more than one.  Same body, same per-row arithmetic and order: results are those of two launches, bit for bit.
-// The body is instantiated once per job, each on ITS by-value argument struct: a struct picked at run time (a reference, or a
+// side cost little more than one.  Same schedule, same per-row arithmetic and order: results are those of two launches, bit for bit.
+// The schedule is instantiated once per job, each on ITS by-value argument struct: a struct picked at run time (a reference, or a
 // copy fetched from the kernarg segment at a run-time offset) loses the "kernel arguments point to global memory" inference --
 // 90 flat_loads instead of global_loads in the ISA, each counted on two wait counters.
 template <int NCH, int U, int D4T, typename TT>
 __global__ __launch_bounds__(kBlock) void rel_attn_fwd_jobs_kernel(FwdArgs a0, FwdArgs a1, int g0) {
     if ((int)blockIdx.x < g0)                                         // block-uniform
-        rel_attn_fwd_body<NCH, U, D4T, TT>(a0, (int)blockIdx.x, g0);
+        fwd_schedule<Lanes64Map<NCH, U, D4T, TT>>(a0, (int)blockIdx.x, g0);
     else
-        rel_attn_fwd_body<NCH, U, D4T, TT>(a1, (int)blockIdx.x - g0, (int)gridDim.x - g0);
+        fwd_schedule<Lanes64Map<NCH, U, D4T, TT>>(a1, (int)blockIdx.x - g0, (int)gridDim.x - g0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -502,8 +505,8 @@ __global__ __launch_bounds__(kBlock) void rel_attn_fwd_jobs_kernel(FwdArgs a0, F
 // Per edge PAIR: one set of gather instructions, ONE cross-lane reduction of the logits (five DPP steps inside the 32-lane
 // halves, lanes 31 / 63 read out), one online-softmax update with a per-half weight; the two halves' accumulators meet once
 // per item (v_permlane32_swap of two chunk registers: the lower half ends with one complete chunk, the upper half with
-// another -- no LDS, no shuffle per element).  Schedule, cooperative segments, combine pass and outputs are those of
-// rel_attn_fwd_kernel.  DC = chunks per half row (compile time: 75 / 64 fp32, 38 / 32 bf16).
+// another -- no LDS, no shuffle per element).  The schedule is fwd_schedule, on this lane map; the combine pass and the outputs
+// are those of rel_attn_fwd_kernel.  DC = chunks per half row (compile time: 75 / 64 fp32, 38 / 32 bf16).
 template <typename TT> struct HwElem;
 template <> struct HwElem<float> { static constexpr int CH = 4; };
 template <> struct HwElem<bf16_t> { static constexpr int CH = 8; };
@@ -557,82 +560,142 @@ __device__ __forceinline__ float halves_meet(float a, float b) {
 // measured 8.94 against 6.66 ms).  The forms measured against it and closed -- LDS-staged hot relation rows, streaming [Q|Z]
 // gathers, a guarded two-deep and a load / reduce in turn pipeline -- are recorded in profiles/HISTORY.md.
 template <int DC, typename TT>
-__device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
-    constexpr int GP = 1;
-    constexpr int CH = HwElem<TT>::CH;
-    constexpr int NCH = (2 * DC + 31) / 32;            // chunk slots per lane
-    constexpr int KH = (DC + 31) / 32;                 // slots k < KH hold attention-half (h) chunks on some lane
-    constexpr int KV0 = DC / 32;                       // slots k >= KV0 hold message-half (v) chunks on some lane
-    constexpr int NV = NCH - KV0;
-    constexpr int NP = (NV + 1) / 2;                   // v slots in pairs: one complete chunk per half after halves_meet
+struct HalfWaveMap {
+    static constexpr int GP = 1;
+    static constexpr int CH = HwElem<TT>::CH;
+    static constexpr int NCH = (2 * DC + 31) / 32;            // chunk slots per lane
+    static constexpr int KH = (DC + 31) / 32;                 // slots k < KH hold attention-half (h) chunks on some lane
+    static constexpr int KV0 = DC / 32;                       // slots k >= KV0 hold message-half (v) chunks on some lane
+    static constexpr int NV = NCH - KV0;
+    static constexpr int NP = (NV + 1) / 2;                   // v slots in pairs: one complete chunk per half after halves_meet
     typedef VF<CH> vf;
-    __shared__ float coop_acc[kWavesPerBlock][NP][CH][64];
-    __shared__ float coop_ml[kWavesPerBlock][2];
-    const TT* const tP = static_cast<const TT*>(a.P);
-    const TT* const tQZ = static_cast<const TT*>(a.QZ);
-    const TT* const tRR = static_cast<const TT*>(a.RR);
-    const int lane = lane_id();
-    const int hl = lane & 31;
-    const bool upper = lane >= 32;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int nwaves = gridDim.x * kWavesPerBlock;
-    const int n_items = a.counts[0];
-    const int n_empty = a.counts[3];
-    const int n_coop = a.n_coop;
-    const int n_reg = n_items - n_empty;
-    const int dtrue = 4 * a.D4;                        // output width (<= DC * CH: the tables' pad columns are zero)
+    // Every load stays RAW (uint4) until its first use: a conversion or a select right behind a load is waited for where it
+    // stands, i.e. in front of the gathers that should be in flight together with it (one more round trip per item).
+    typedef uint4 P[KH];
+    typedef uint4 Z[NP];                                      // in the OUTPUT layout (oc below); converted in finish
+    typedef vf Acc[NCH];                                      // both halves carry PARTIAL accumulators
+    typedef vf Out[NP];
+    typedef float Stash[NP][CH][64];
+    const FwdArgs& a;
+    const TT *tP, *tQZ, *tRR;
+    int lane, hl, dtrue;
+    bool upper, has_loop;
     int coff[NCH];                                     // element offset of the lane's chunk in a [Q|Z] row, clamped to a valid one
     bool valid[NCH], is_h[NCH];
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-        const int c = hl + 32 * k;
-        valid[k] = c < 2 * DC;
-        is_h[k] = c < DC;
-        coff[k] = valid[k] ? c * CH : 0;
-    }
-    auto all_valid = [](int k) { return 32 * (k + 1) <= 2 * DC; };
     vf av[KH];
-#pragma unroll
-    for (int k = 0; k < KH; ++k)
-#pragma unroll
-        for (int e = 0; e < CH; ++e) {
-            const int col = (hl + 32 * k) * CH + e;
-            av[k].v[e] = (is_h[k] && col < dtrue) ? a.a_att[col] : 0.f;
-        }
-    const bool has_loop = a.loop_rel >= 0;
-    const TT* rloop = tRR + (int64_t)(has_loop ? a.loop_rel : 0) * a.ldrr;
     // chunk of the [Q|Z] row that OUTPUT slot p holds on this lane once the halves have met (the lower half keeps v slot
     // KV0 + 2p, the upper half v slot KV0 + 2p + 1); -1: none (an h chunk, past the row, or an unpaired last slot)
     int oc[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int k = KV0 + 2 * p + (upper ? 1 : 0);
-        const int c = hl + 32 * k;
-        oc[p] = (k < NCH && c >= DC && c < 2 * DC) ? c : -1;
-    }
-    // Every load stays RAW (uint4) until its first use: a conversion or a select right behind a load is waited for where it
-    // stands, i.e. in front of the gathers that should be in flight together with it (one more round trip per item).
     uint4 rlraw[NP];                                   // the loop relation's Rz chunks in the OUTPUT layout: one read per wave
-#pragma unroll
-    for (int p = 0; p < NP; ++p) rlraw[p] = ld16(rloop + (oc[p] >= 0 ? oc[p] : 0) * CH);
+    static __device__ __forceinline__ bool all_valid(int k) { return 32 * (k + 1) <= 2 * DC; }
 
-    // ---- online softmax over the entries [item.beg, item.end) of one destination; both halves carry PARTIAL accumulators
-    auto edge_loop = [&](const jmac_item_t& item, int my_col, int my_typ, const uint4 (&praw)[KH], float& m, float& l, vf (&acc)[NCH]) {
-        auto issue = [&](const int nb, const int mc, const int mt, const int p0, uint4 (&qr)[GP][NCH], uint4 (&rr)[GP][NCH]) {
+    __device__ __forceinline__ HalfWaveMap(const FwdArgs& a_, int lane_)
+        : a(a_), tP(static_cast<const TT*>(a_.P)), tQZ(static_cast<const TT*>(a_.QZ)), tRR(static_cast<const TT*>(a_.RR)), lane(lane_) {
+        hl = lane & 31;
+        upper = lane >= 32;
+        dtrue = 4 * a.D4;                              // output width (<= DC * CH: the tables' pad columns are zero)
 #pragma unroll
-            for (int u = 0; u < GP; ++u) {
-                const int ea = max(min(2 * (p0 + u), nb - 1), 0), eb = max(min(2 * (p0 + u) + 1, nb - 1), 0);
-                const int ja = bcast_i(mc, ea), jb = bcast_i(mc, eb);
-                const int ta = bcast_i(mt, ea), tb = bcast_i(mt, eb);
-                const TT* qrow = tQZ + (int64_t)(upper ? jb : ja) * a.ldqz;
-                const TT* rrow = tRR + (int64_t)(upper ? tb : ta) * a.ldrr;
+        for (int k = 0; k < NCH; ++k) {
+            const int c = hl + 32 * k;
+            valid[k] = c < 2 * DC;
+            is_h[k] = c < DC;
+            coff[k] = valid[k] ? c * CH : 0;
+        }
 #pragma unroll
-                for (int k = 0; k < NCH; ++k) {
-                    qr[u][k] = ld16(qrow + coff[k]);
-                    rr[u][k] = ld16(rrow + coff[k]);
+        for (int k = 0; k < KH; ++k)
+#pragma unroll
+            for (int e = 0; e < CH; ++e) {
+                const int col = (hl + 32 * k) * CH + e;
+                av[k].v[e] = (is_h[k] && col < dtrue) ? a.a_att[col] : 0.f;
+            }
+        has_loop = a.loop_rel >= 0;
+        const TT* rloop = tRR + (int64_t)(has_loop ? a.loop_rel : 0) * a.ldrr;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int k = KV0 + 2 * p + (upper ? 1 : 0);
+            const int c = hl + 32 * k;
+            oc[p] = (k < NCH && c >= DC && c < 2 * DC) ? c : -1;
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) rlraw[p] = ld16(rloop + (oc[p] >= 0 ? oc[p] : 0) * CH);
+    }
+    __device__ __forceinline__ void load_p(int i, P& praw) const {
+        const TT* prow = tP + (int64_t)i * a.ldp;
+#pragma unroll
+        for (int k = 0; k < KH; ++k) praw[k] = ld16(prow + (is_h[k] ? (hl + 32 * k) * CH : 0));
+    }
+    __device__ __forceinline__ void load_z(int i, Z& zraw) const {
+        const TT* zrow = tQZ + ((int64_t)(has_loop ? i : 0) + a.self_off) * a.ldqz;   // no loop: row 0 (valid, unused)
+#pragma unroll
+        for (int p = 0; p < NP; ++p) zraw[p] = ld16(zrow + (oc[p] >= 0 ? oc[p] : 0) * CH);
+    }
+    // the gathers of pairs p0 .. p0 + GP - 1 of a batch of nb entries: the lower half takes a pair's first edge, the upper its second
+    __device__ __forceinline__ void issue(const int nb, const int mc, const int mt, const int p0, uint4 (&qr)[GP][NCH],
+                                          uint4 (&rr)[GP][NCH]) const {
+#pragma unroll
+        for (int u = 0; u < GP; ++u) {
+            const int ea = max(min(2 * (p0 + u), nb - 1), 0), eb = max(min(2 * (p0 + u) + 1, nb - 1), 0);
+            const int ja = bcast_i(mc, ea), jb = bcast_i(mc, eb);
+            const int ta = bcast_i(mt, ea), tb = bcast_i(mt, eb);
+            const TT* qrow = tQZ + (int64_t)(upper ? jb : ja) * a.ldqz;
+            const TT* rrow = tRR + (int64_t)(upper ? tb : ta) * a.ldrr;
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                qr[u][k] = ld16(qrow + coff[k]);
+                rr[u][k] = ld16(rrow + coff[k]);
+            }
+        }
+    }
+    __device__ __forceinline__ void consume(const int nb, const int p0, const uint4 (&qr)[GP][NCH], const uint4 (&rr)[GP][NCH],
+                                            const vf (&pv)[KH], float& m, float& l, Acc& acc) const {
+        vf x[GP][NCH];
+        float part[GP];
+#pragma unroll
+        for (int u = 0; u < GP; ++u) {
+            part[u] = 0.f;
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                const vf q = hw_cvt<TT>(qr[u][k]), r = hw_cvt<TT>(rr[u][k]);
+#pragma unroll
+                for (int e = 0; e < CH; ++e) {
+                    float d = q.v[e] - r.v[e];
+                    if (!all_valid(k)) d = valid[k] ? d : 0.f;
+                    x[u][k].v[e] = d;
+                    if (k < KH) part[u] = fmaf(av[k].v[e], leaky01(pv[k].v[e] + d, a.slope), part[u]);   // av = 0 off the h lanes
                 }
             }
-        };
+        }
+        float sa[GP], sb[GP];
+        half_sum_n<GP>(part, sa, sb);
+        float mn = m;
+#pragma unroll
+        for (int u = 0; u < GP; ++u) {
+            if (2 * (p0 + u) >= nb) sa[u] = -INFINITY;          // pairs / edges past the batch: weight exp(-inf) = 0
+            if (2 * (p0 + u) + 1 >= nb) sb[u] = -INFINITY;
+            mn = fmaxf(mn, fmaxf(sa[u], sb[u]));
+        }
+        const float sc = fast_exp(m - mn);
+        float w[GP], wsum = 0.f;
+#pragma unroll
+        for (int u = 0; u < GP; ++u) {
+            const float wa = fast_exp(sa[u] - mn), wb = fast_exp(sb[u] - mn);
+            wsum += wa + wb;
+            w[u] = upper ? wb : wa;
+        }
+        l = l * sc + wsum;
+#pragma unroll
+        for (int k = KV0; k < NCH; ++k)
+#pragma unroll
+            for (int e = 0; e < CH; ++e) {
+                float t = acc[k].v[e] * sc;
+#pragma unroll
+                for (int u = 0; u < GP; ++u) t = fmaf(x[u][k].v[e], w[u], t);
+                acc[k].v[e] = t;
+            }
+        m = mn;
+    }
+    __device__ __forceinline__ void edge_loop(const jmac_item_t& item, int my_col, int my_typ, const P& praw, float& m, float& l,
+                                              Acc& acc) const {
         // the item's FIRST group of gathers goes out here, in one basic block with the loads of P[i] / Z[i] and ahead of the
         // conversion of P[i]: that conversion waits for P[i] only (the gathers are younger), not the other way round
         uint4 qA[GP][NCH], rA[GP][NCH];
@@ -645,6 +708,12 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
 #pragma unroll
                 for (int e = 0; e < CH; ++e) pv[k].v[e] = is_h[k] ? pv[k].v[e] : 0.f;
         }
+        m = -INFINITY;
+        l = 0.f;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+#pragma unroll
+            for (int e = 0; e < CH; ++e) acc[k].v[e] = 0.f;
         for (int e0 = item.beg; e0 < item.end; e0 += 64) {
             const int nb = min(64, item.end - e0);
             if (e0 != item.beg) {
@@ -654,53 +723,6 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
                 issue(nb, my_col, my_typ, 0, qA, rA);
             }
             const int npairs = (nb + 1) >> 1;
-            auto consume = [&](const int p0, const uint4 (&qr)[GP][NCH], const uint4 (&rr)[GP][NCH]) {
-                vf x[GP][NCH];
-                float part[GP];
-#pragma unroll
-                for (int u = 0; u < GP; ++u) {
-                    part[u] = 0.f;
-#pragma unroll
-                    for (int k = 0; k < NCH; ++k) {
-                        const vf q = hw_cvt<TT>(qr[u][k]), r = hw_cvt<TT>(rr[u][k]);
-#pragma unroll
-                        for (int e = 0; e < CH; ++e) {
-                            float d = q.v[e] - r.v[e];
-                            if (!all_valid(k)) d = valid[k] ? d : 0.f;
-                            x[u][k].v[e] = d;
-                            if (k < KH) part[u] = fmaf(av[k].v[e], leaky01(pv[k].v[e] + d, a.slope), part[u]);   // av = 0 off the h lanes
-                        }
-                    }
-                }
-                float sa[GP], sb[GP];
-                half_sum_n<GP>(part, sa, sb);
-                float mn = m;
-#pragma unroll
-                for (int u = 0; u < GP; ++u) {
-                    if (2 * (p0 + u) >= nb) sa[u] = -INFINITY;          // pairs / edges past the batch: weight exp(-inf) = 0
-                    if (2 * (p0 + u) + 1 >= nb) sb[u] = -INFINITY;
-                    mn = fmaxf(mn, fmaxf(sa[u], sb[u]));
-                }
-                const float sc = fast_exp(m - mn);
-                float w[GP], wsum = 0.f;
-#pragma unroll
-                for (int u = 0; u < GP; ++u) {
-                    const float wa = fast_exp(sa[u] - mn), wb = fast_exp(sb[u] - mn);
-                    wsum += wa + wb;
-                    w[u] = upper ? wb : wa;
-                }
-                l = l * sc + wsum;
-#pragma unroll
-                for (int k = KV0; k < NCH; ++k)
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) {
-                        float t = acc[k].v[e] * sc;
-#pragma unroll
-                        for (int u = 0; u < GP; ++u) t = fmaf(x[u][k].v[e], w[u], t);
-                        acc[k].v[e] = t;
-                    }
-                m = mn;
-            };
             // two groups in flight, EVERY path issuing the same loads: a group past the batch's end re-reads the last pair's rows
             // (an L1 hit; it is never reduced).  The compiler's vmcnt bookkeeping is exact only when all paths into a wait have
             // issued the same number of loads: behind a conditional issue (the guarded two-deep and three-deep forms this replaced)
@@ -711,31 +733,49 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
             for (;;) {
                 issue(nb, my_col, my_typ, p + GP, qB, rB);
                 __builtin_amdgcn_sched_barrier(0);
-                consume(p, qA, rA);
+                consume(nb, p, qA, rA, pv, m, l, acc);
                 __builtin_amdgcn_sched_barrier(0);
                 p += GP;
                 if (p >= npairs) break;
                 issue(nb, my_col, my_typ, p + GP, qA, rA);
                 __builtin_amdgcn_sched_barrier(0);
-                consume(p, qB, rB);
+                consume(nb, p, qB, rB, pv, m, l, acc);
                 __builtin_amdgcn_sched_barrier(0);
                 p += GP;
                 if (p >= npairs) break;
             }
         }
-    };
-    // ---- the two halves' partial accumulators -> NP complete chunks per lane (oc[p]): an odd last slot is paired with slot
-    // ---- KV0 once more (the upper half's copy of that pair is not used)
-    auto meet = [&](const vf (&acc)[NCH], vf (&outv)[NP]) {
+    }
+    // the two halves' partial accumulators -> NP complete chunks per lane (oc[p]): an odd last slot is paired with slot KV0 once
+    // more (the upper half's copy of that pair is not used)
+    __device__ __forceinline__ void reduce(const Acc& acc, Out& o) const {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             constexpr int dummy = KV0;
             const int k1 = KV0 + 2 * p, k2 = (KV0 + 2 * p + 1 < NCH) ? KV0 + 2 * p + 1 : dummy;
 #pragma unroll
-            for (int e = 0; e < CH; ++e) outv[p].v[e] = halves_meet(acc[k1].v[e], acc[k2].v[e]);
+            for (int e = 0; e < CH; ++e) o[p].v[e] = halves_meet(acc[k1].v[e], acc[k2].v[e]);
         }
-    };
-    auto store_chunks = [&](float* rowp, const vf (&o)[NP]) {
+    }
+    __device__ __forceinline__ void put(Stash& st, const Out& o) const {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int e = 0; e < CH; ++e) st[p][e][lane] = o[p].v[e];
+    }
+    __device__ __forceinline__ void scale(Out& o, float f) const {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int e = 0; e < CH; ++e) o[p].v[e] *= f;
+    }
+    __device__ __forceinline__ void merge(Out& o, const Stash& st, float f) const {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int e = 0; e < CH; ++e) o[p].v[e] = fmaf(st[p][e][lane], f, o[p].v[e]);
+    }
+    __device__ __forceinline__ void store_chunks(float* rowp, const Out& o) const {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             if (oc[p] < 0) continue;
@@ -744,16 +784,9 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
             for (int e = 0; e < CH; e += 4)
                 if (col + e < dtrue) st4(rowp + col + e, make_float4(o[p].v[e], o[p].v[e + 1], o[p].v[e + 2], o[p].v[e + 3]));
         }
-    };
-    // raw Z[i] chunks in the OUTPUT layout (the fused self loop); converted in finish
-    auto load_z = [&](int i, uint4 (&zraw)[NP]) {
-        const TT* zrow = tQZ + ((int64_t)(has_loop ? i : 0) + a.self_off) * a.ldqz;   // no loop: row 0 (valid, unused)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) zraw[p] = ld16(zrow + (oc[p] >= 0 ? oc[p] : 0) * CH);
-    };
-    // out[i] = out_scale * (scale * o + Z[i] - Rz[loop])
-    auto finish = [&](int i, float scale, const vf (&o)[NP], const uint4 (&zraw)[NP]) {
-        vf r[NP];
+    }
+    __device__ __forceinline__ void finish(int i, float scale, const Out& o, const Z& zraw) const {
+        Out r;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const vf z = hw_cvt<TT>(zraw[p]), rz = hw_cvt<TT>(rlraw[p]);
@@ -764,170 +797,25 @@ __device__ __forceinline__ void rel_attn_fwd_hw_body(const FwdArgs& a) {
             }
         }
         store_chunks(a.out + (int64_t)i * a.ldo, r);
-    };
-    auto first_batch = [&](const jmac_item_t& item, int& c, int& t) {
-        const int cnb = min(64, item.end - item.beg);
-        const int idx = cnb > 0 ? item.beg + min(lane, cnb - 1) : 0;
-        c = a.col[idx];
-        t = a.etype[idx];
-    };
-    auto load_p = [&](int i, uint4 (&praw)[KH]) {
-        const TT* prow = tP + (int64_t)i * a.ldp;
-#pragma unroll
-        for (int k = 0; k < KH; ++k) praw[k] = ld16(prow + (is_h[k] ? (hl + 32 * k) * CH : 0));
-    };
-    auto zero_acc = [&](vf (&acc)[NCH]) {
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int e = 0; e < CH; ++e) acc[k].v[e] = 0.f;
-    };
-
-    // ---- 1. cooperative segments: one workgroup per segment ------------------------------------------------------------
-    for (int cb = blockIdx.x; cb < n_coop; cb += gridDim.x) {
-        const jmac_item_t item = a.items[cb * kWavesPerBlock + wave];
-        const int i = item.seg;
-        int ccol, ctyp;
-        first_batch(item, ccol, ctyp);
-        uint4 praw[KH], zraw[NP];
-        vf acc[NCH], o[NP];
-        load_p(i, praw);
-        load_z(i, zraw);                                  // (wave 0 uses it)
-        zero_acc(acc);
-        float m = -INFINITY, l = 0.f;
-        edge_loop(item, ccol, ctyp, praw, m, l, acc);
-        meet(acc, o);
-        if (wave != 0) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-#pragma unroll
-                for (int e = 0; e < CH; ++e) coop_acc[wave][p][e][lane] = o[p].v[e];
-            if (lane == 0) {
-                coop_ml[wave][0] = m;
-                coop_ml[wave][1] = l;
-            }
-        }
-        __syncthreads();
-        if (wave == 0) {
-            float M = m;
-#pragma unroll
-            for (int w = 1; w < kWavesPerBlock; ++w) M = fmaxf(M, coop_ml[w][0]);
-            float f = fast_exp(m - M);
-            float lsum = l * f;
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-#pragma unroll
-                for (int e = 0; e < CH; ++e) o[p].v[e] *= f;
-#pragma unroll
-            for (int w = 1; w < kWavesPerBlock; ++w) {
-                f = fast_exp(coop_ml[w][0] - M);
-                lsum = fmaf(coop_ml[w][1], f, lsum);
-#pragma unroll
-                for (int p = 0; p < NP; ++p)
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) o[p].v[e] = fmaf(coop_acc[w][p][e][lane], f, o[p].v[e]);
-            }
-            const int deg = a.rowptr[i + 1] - a.rowptr[i];
-            finish(i, lsum > 0.f ? sqrtf((float)deg) / lsum : 0.f, o, zraw);
-            if (lane == 0) {
-                a.seg_max[i] = M;
-                a.seg_den[i] = lsum;
-            }
-        }
-        __syncthreads();
     }
-
-    // ---- 3. empty segments, kEmptyPack to a wave: out = out_scale * (Z[i] - Rz[loop]) ----------------------------------------
-    auto empties = [&](int p0) {
-        const int n_packs = (n_empty + kEmptyPack - 1) / kEmptyPack;
-        for (int pk = p0; pk < n_packs; pk += nwaves) {
-            int seg[kEmptyPack];
-            uint4 zraw[kEmptyPack][NP];
+    __device__ __forceinline__ void finish_empty(int i, const Z& zraw) const {
+        Out zero;
 #pragma unroll
-            for (int u = 0; u < kEmptyPack; ++u) seg[u] = a.items[min(n_reg + pk * kEmptyPack + u, n_items - 1)].seg;
+        for (int p = 0; p < NP; ++p)
 #pragma unroll
-            for (int u = 0; u < kEmptyPack; ++u) load_z(seg[u], zraw[u]);
-#pragma unroll
-            for (int u = 0; u < kEmptyPack; ++u) {
-                if (pk * kEmptyPack + u >= n_empty) break;
-                vf zero[NP];
-#pragma unroll
-                for (int p = 0; p < NP; ++p)
-#pragma unroll
-                    for (int e = 0; e < CH; ++e) zero[p].v[e] = 0.f;
-                finish(seg[u], 0.f, zero, zraw[u]);
-                if (lane == 0) {
-                    a.seg_max[seg[u]] = -INFINITY;
-                    a.seg_den[seg[u]] = 0.f;
-                }
-            }
-        }
-    };
-
-    // ---- 2. items ---------------------------------------------------------------------------------------------------------
-    const int it_base = n_coop * kWavesPerBlock;
-    const int it0 = blockIdx.x * kWavesPerBlock + wave;
-    int it = it_base + it0;
-    jmac_item_t item = a.items[min(it, a.n_items_max - 1)];
-    int4 e4 = make_int4(0, 0, 0, 0);
-    if (a.item_edges) e4 = a.item_edges[min(it, a.n_items_max - 1)];
-    if (it >= n_reg) {
-        empties(it - n_reg);
-        return;
+            for (int e = 0; e < CH; ++e) zero[p].v[e] = 0.f;
+        finish(i, 0.f, zero, zraw);
     }
-    jmac_item_t nitem = a.items[min(it + nwaves, n_items - 1)];
-    int ccol, ctyp;
-    {
-        const int cnb = min(64, item.end - item.beg);
-        if (a.item_edges && cnb <= 2) {
-            ccol = lane == 0 ? e4.x : e4.z;
-            ctyp = lane == 0 ? e4.y : e4.w;
-            ccol = cnb > lane ? ccol : e4.x;
-            ctyp = cnb > lane ? ctyp : e4.y;
-        } else {
-            first_batch(item, ccol, ctyp);
-        }
-    }
-    for (;;) {
-        const jmac_item_t nnitem = a.items[min(it + 2 * nwaves, n_items - 1)];
-        int ncol, ntyp;
-        first_batch(nitem, ncol, ntyp);
-        const int i = item.seg;
-        uint4 praw[KH], zraw[NP];
-        vf acc[NCH], o[NP];
-        load_p(i, praw);
-        load_z(i, zraw);
-        zero_acc(acc);
-        float m = -INFINITY, l = 0.f;
-        edge_loop(item, ccol, ctyp, praw, m, l, acc);
-        meet(acc, o);
-        if (item.pslot < 0) {
-            finish(i, l > 0.f ? sqrtf((float)(item.end - item.beg)) / l : 0.f, o, zraw);
-            if (lane == 0) {
-                a.seg_max[i] = m;
-                a.seg_den[i] = l;
-            }
-        } else {
-            // partial state of a split destination: the combine pass reads d floats per slot in row order
-            store_chunks(a.part_acc + (int64_t)item.pslot * dtrue, o);
-            if (lane == 0) {
-                a.part_ml[2 * item.pslot] = m;
-                a.part_ml[2 * item.pslot + 1] = l;
-            }
-        }
-        it += nwaves;
-        if (it >= n_reg) break;
-        item = nitem;
-        nitem = nnitem;
-        ccol = ncol;
-        ctyp = ntyp;
-    }
-    empties(it - n_reg);
-}
+    __device__ __forceinline__ void store_part(int pslot, const Out& o) const { store_chunks(a.part_acc + (int64_t)pslot * dtrue, o); }
+};
 
+// The five-slot map (fp32, d = 300) is held to two waves per SIMD, which is what its 174 VGPRs gave it before the schedule was
+// shared: the shared form fits 168 and so a third wave, and config 4 then runs 2-5 % slower (measured twice, parent / with /
+// without this bound alternating: profiles/fwd_schedule_one_walk.txt, section 5).  The other maps are not bounded.
 template <int DC, typename TT>
-__global__ __launch_bounds__(kBlock) void rel_attn_fwd_hw_kernel(FwdArgs a) {
-    rel_attn_fwd_hw_body<DC, TT>(a);
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, HalfWaveMap<DC, TT>::NCH >= 5 ? 2 : 8)))
+void rel_attn_fwd_hw_kernel(FwdArgs a) {
+    fwd_schedule<HalfWaveMap<DC, TT>>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // merges the partial (max, denominator, accumulator) triples of destinations that were split: one BLOCK per split

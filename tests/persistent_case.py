@@ -3,6 +3,7 @@ PERSISTENT-GRID forms of the aggregation kernels (more than 65 536 by-destinatio
 jmac_amd/graph.py INLINE_EDGES_MAX_ITEMS, aggregate.hip launch_rel_attn_fwd), seeded tables on it, and the oracle
 (oracle/jmac_oracle.py aggregate_from_tables_sliced -- the reference's per-destination softmax / weighted sum of
 modules/helper/message_passing.py:24-28 on the node / relation tables of src/jmac_model.py:75-88)."""
+import functools
 import os
 import sys
 
@@ -54,3 +55,38 @@ def rel_err(got, ref):
     got = torch.as_tensor(got).detach().double().cpu()
     ref = torch.as_tensor(ref).detach().double().cpu()
     return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-30)
+
+
+# ---- the two small cases of tests/test_gpu_hw_variants.py (tools/aggregate_bits_dump.py runs them too) ----
+def small_graph():
+    """N = 300, E = 3000, 7 relations + the loop relation; destination 0 has 200 in-edges (four 64-entry batches), destinations
+    290 .. 299 have none."""
+    rng = np.random.default_rng(11)
+    n, e, nr = 300, 3000, 7
+    dst = rng.integers(1, 290, size=e)
+    dst[:200] = 0
+    ei = np.stack([dst, rng.integers(0, n, size=e)]).astype(np.int64)
+    et = rng.integers(0, nr, size=e).astype(np.int64)
+    return ei, et, n, nr + 1
+
+
+@functools.lru_cache(maxsize=None)
+def coop_case():
+    """N = 17 000 destinations (just past the 16 384 items where the launcher leaves the U = 2 form), 7 relations + the loop
+    relation.  In-degrees: 17, 23, ..., 251 and 256 (cooperative segments: four quarters, of exactly 64 entries for 256);
+    257, 300, 513, 700 (split at 256: multi-batch items, a 1-entry item, the combine pass); 1, 2, 3, 5; the rest from
+    {0 .. 4} with the number of empty rows not a multiple of kEmptyPack = 4.  -> (edge_index, edge_type, N, nrel, degrees)"""
+    rng = np.random.default_rng(23)
+    n, nr = 17000, 7
+    special = [17 + 6 * r for r in range(40)] + [256, 257, 300, 513, 700, 1, 2, 3, 5]
+    deg = rng.integers(0, 5, size=n)
+    rows = rng.permutation(n)
+    deg[rows[:len(special)]] = special
+    if int((deg == 0).sum()) % 4 == 0:
+        deg[rows[len(special)]] = 0 if deg[rows[len(special)]] else 1
+    dst = np.repeat(np.arange(n), deg)
+    e = dst.size
+    order = rng.permutation(e)
+    ei = np.stack([dst, rng.integers(0, n, size=e)])[:, order].astype(np.int64)
+    et = rng.integers(0, nr, size=e)[order].astype(np.int64)
+    return ei, et, n, nr + 1, deg

@@ -4,10 +4,20 @@ entry points keep at the widths the product gives to the half-wave kernel (ops.r
   * on a graph large enough for the persistent grid the two agree to rounding (a different summation tree across lanes), on
     fp32 tables and on padded bf16 tables;
   * on a graph small enough to carry inline entries both entry points choose the 64-lane U = 2 kernel -- the testing entry
-    point differs from the product's in the half-wave gate alone -- so out, seg_max and seg_den are bitwise equal."""
+    point differs from the product's in the half-wave gate alone -- so out, seg_max and seg_den are bitwise equal;
+  * on a schedule with COOPERATIVE segments and no inline entries (a combination graph.py does not build: its cooperative
+    schedules carry inline entries and take the U = 2 kernel) the half-wave kernel and the 64-lane U = 4 kernel both walk the
+    cooperative section, the split items and the empty packs: against the float64 oracle, and against each other."""
+import functools
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import persistent_case as pc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -36,25 +46,13 @@ def test_half_wave_forms_agree():
     assert float(np.abs(w16 - o16).max()) <= 2e-5 * scale
 
 
-def _small_graph():
-    """N = 300, E = 3000, 7 relations + the loop relation; destination 0 has 200 in-edges (four 64-entry batches), destinations
-    290 .. 299 have none."""
-    rng = np.random.default_rng(11)
-    n, e, nr = 300, 3000, 7
-    dst = rng.integers(1, 290, size=e)
-    dst[:200] = 0
-    ei = np.stack([dst, rng.integers(0, n, size=e)]).astype(np.int64)
-    et = rng.integers(0, nr, size=e).astype(np.int64)
-    return ei, et, n, nr + 1
-
-
 @pytest.mark.parametrize("table", ["f32", "bf16-padded"])
 @pytest.mark.parametrize("d", [300, 256])
 def test_small_graph_testing_entry_equals_product_bitwise(d, table):
     from jmac_amd import ops
     from jmac_amd.graph import RelGraph
     dev = torch.device("cuda")
-    ei, et, n, nrel = _small_graph()
+    ei, et, n, nrel = pc.small_graph()
     g = RelGraph(torch.from_numpy(ei).to(dev), torch.from_numpy(et).to(dev), n, nrel)
     assert g.by_dst.item_edges is not None                                    # inline entries: the small-graph form
     deg = np.bincount(ei[0], minlength=n)
@@ -75,3 +73,52 @@ def test_small_graph_testing_entry_equals_product_bitwise(d, table):
     for name, w, v in zip(("out", "seg_max", "seg_den"), want, got):
         assert torch.equal(w[:n], v[:n]), name
     assert bool((want[1][:n].cpu()[torch.from_numpy(deg == 0)] == -float("inf")).all())
+
+
+@functools.lru_cache(maxsize=None)
+def _coop_tables(d, table):
+    """([P|Q|Z], [Rq|Rz], a) on the CPU and the float64 oracle on them (bf16: on the rounded tables)."""
+    ei, et, n, nrel, _ = pc.coop_case()
+    PQZ, RR, a, _ = pc.tables(n, nrel, d, seed=d)
+    if table == "bf16-padded":
+        PQZ, RR = PQZ.to(torch.bfloat16), RR.to(torch.bfloat16)
+    ref = pc.oracle_aggregate(PQZ.double(), RR.double(), a, ei, et, nrel - 1, torch.float64)
+    return PQZ, RR, a, ref
+
+
+@pytest.mark.parametrize("table", ["f32", "bf16-padded"])
+@pytest.mark.parametrize("d", [300, 256])
+def test_cooperative_schedule_without_inline_entries(d, table):
+    """The half-wave kernel (product entry) and the 64-lane U = 4 kernel (lanes64 entry) on cooperative segments."""
+    from jmac_amd import ops
+    from jmac_amd.graph import RelGraph, _Schedule
+    dev = torch.device("cuda")
+    ei, et, n, nrel, deg = pc.coop_case()
+    g = RelGraph(torch.from_numpy(ei).to(dev), torch.from_numpy(et).to(dev), n, nrel, chunk=256)
+    g.by_dst = _Schedule(g.rowptr, n, ei.shape[1], 256, None, coop=True)
+    s = g.by_dst
+    n_empty = int((deg == 0).sum())
+    assert s.item_edges is None and s.n_items_max > 16384 and s.n_coop >= 41 and s.n_splits_max > s.n_coop
+    assert s.n_empty == n_empty and n_empty >= 1000 and n_empty % 4 != 0
+    PQZ, RR, a, ref = _coop_tables(d, table)
+    PQZ, RR, a = PQZ.to(dev), RR.to(dev), a.to(dev)
+    if table == "bf16-padded":
+        PQZ, RR = ops.pad_table(PQZ, d, 3), ops.pad_table(RR, d, 2)
+        assert PQZ.shape[1] == 3 * ops.bf16_pad(d)
+    P, QZ = ops.pqz_views(PQZ)
+    hw = ops.rel_attn_split_fwd_raw(P, QZ, RR, a, g, pc.SLOPE, pc.OUT_SCALE, nrel - 1, 0)
+    l64 = ops.rel_attn_split_fwd_raw(P, QZ, RR, a, g, pc.SLOPE, pc.OUT_SCALE, nrel - 1, 0, lanes64=True)
+    torch.cuda.synchronize()
+    scale = float(ref.abs().max())
+    assert scale > 0.1
+    e_hw = float((hw[0].double().cpu() - ref).abs().max())
+    e_64 = float((l64[0].double().cpu() - ref).abs().max())
+    e_x = float((hw[0] - l64[0]).abs().max())
+    print("cooperative d=%d %s: half-wave vs oracle %.2e, lanes64 vs oracle %.2e, half-wave vs lanes64 %.2e (of scale)"
+          % (d, table, e_hw / scale, e_64 / scale, e_x / scale))
+    assert e_hw <= 1e-4 * scale                   # test_gpu_persistent_oracle.py's RTOL
+    assert e_64 <= 1e-4 * scale
+    assert e_x <= 2e-5 * scale                    # test_half_wave_forms_agree's bound
+    empty = torch.from_numpy(deg == 0)
+    for res in (hw, l64):
+        assert bool((res[1][:n].cpu()[empty] == -float("inf")).all()) and bool((res[2][:n].cpu()[empty] == 0).all())

@@ -145,24 +145,30 @@ def shape_cases(N, d, out):
                         out.put(name + "/gbw", gbw)
 
 
-def main():
+def all_cases(out):
+    for d in DS:
+        for N in NS:
+            shape_cases(N, d, out)
+
+
+def main(cases=all_cases):
+    """--write / --check of every tensor that ``cases(sink)`` puts (tools/aggregate_bits_dump.py runs its own cases through it)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--write")
     ap.add_argument("--check")
     ap.add_argument("--digest", action="store_true")
+    ap.add_argument("--list", type=int, default=40, help="differing tensors named in the report")
     a = ap.parse_args()
     if bool(a.write) == bool(a.check):
         ap.error("one of --write DIR, --check DIR")
     out = Sink(a.write or a.check, bool(a.check), a.digest)
     print("library:", _lib.LIB_PATH)
-    for d in DS:
-        for N in NS:
-            shape_cases(N, d, out)
+    cases(out)
     print("  " + ", ".join("%s %d" % kv for kv in sorted(out.groups.items())) + " tensors")
     if not a.check:
         print("WROTE: %d tensors (%.0f MB)%s" % (out.count, out.nbytes / 1e6, ", as digests" if a.digest else ""))
         return 0
-    for name in out.differ[:40]:
+    for name in out.differ[:a.list]:
         print("  differs:", name)
     print("RESULT: %d tensors (%.0f MB) compared%s, %d differ" % (out.count, out.nbytes / 1e6, " by digest" if a.digest else "",
                                                                   len(out.differ)))
