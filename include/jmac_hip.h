@@ -634,6 +634,22 @@ int jmac_sim_csls_topk_viable_screened_f32(const float* A, int64_t lda, const fl
                                            int32_t k, float* val, int32_t* idx, int32_t* n_rescored, void* ws, size_t ws_bytes,
                                            jmac_stream_t stream);
 
+/* jmac_sim_csls_rank_screened_f32: jmac_sim_csls_rank_f32's ranks bit for bit with the n1 x n2 x d work on the bf16 matrix cores.  The
+ * count predicate before(c, j) = c > g || (c == g && j < G) -- g = c(i, gold[i]) with the fp32 product's bits, G = gold[i] -- is
+ * monotone in c, and the screen bounds every element, c_lo <= c <= c_hi (above): a column with before(c_lo, j) is counted unseen, one
+ * with c_hi < g || (c_hi == g && j > G) is dropped, and only the columns with g inside [c_lo, c_hi] are rescored with the fp32
+ * product's own instructions and put to the exact predicate (the gold column is always one of them).  n_rescored [n1] (may be NULL):
+ * that many columns of row i were rescored.  A row with more than 512 of them overflows: n_rescored = -1, and with finish != 0 the
+ * entry recounts the row over all n2 columns (slow, exact), with finish == 0 it returns rank[i] = 0 for the caller to run the row
+ * through jmac_sim_csls_rank_f32 (a valid rank is >= 1).  n2 >= 8192; a narrower n2 runs the fp32 entry's code unchanged in the
+ * workspace sized below, n_rescored = -2.  Checks and their order: jmac_sim_csls_rank_f32's, with d <= 512 next to d % 4 == 0
+ * (JMAC_EDIM) ahead of the range and workspace checks.  r1, r2 finite (both NULL: c = S); integer atomics only, no host
+ * synchronisation: two calls return the same bits. */
+size_t jmac_sim_csls_rank_screened_workspace_bytes(int64_t n1, int64_t n2, int64_t d);
+int jmac_sim_csls_rank_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                                    const float* r1, const float* r2, const int32_t* gold, int32_t* rank, int32_t* n_rescored,
+                                    int32_t finish, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
 /* Manhattan alignment (sim(metric='manhattan'), modules/finding/similarity.py:47-49): the three entry points above for
  * s(i,j) = 1 - dist(i,j), dist(i,j) = the single running fp32 sum over k = 0 .. d-1 of |A[i,k] - B[j,k]| -- jmac_l1_score_f32's bits,
  * the same from either side (|x - y| == |y - x|) -- and c(i,j) = 2*s(i,j) - r1[i] - r2[j]; r1 == r2 == NULL: c = s.  Every decision

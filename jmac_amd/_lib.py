@@ -164,6 +164,8 @@ _SIGS = {
     "jmac_sim_csls_topk_screened_workspace_bytes": (sz, [i64, i64, i64, i32]),
     "jmac_sim_csls_topk_screened_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
     "jmac_sim_csls_topk_viable_screened_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "jmac_sim_csls_rank_screened_workspace_bytes": (sz, [i64, i64, i64]),
+    "jmac_sim_csls_rank_screened_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     "jmac_l1_csls_topk_workspace_bytes": (sz, [i64, i64, i64, i32]),
     "jmac_l1_csls_topk_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp, vp, sz, vp]),
     "jmac_l1_csls_topk_viable_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),

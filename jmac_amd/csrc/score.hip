@@ -1580,29 +1580,13 @@ __global__ __launch_bounds__(kBlock) void cand_select_viable_kernel(const float*
     cand_select_body<false, true, L1>(A, lda, Bm, ldb, N, d, k, cnt, cval, cidx, cap, sval, sidx, val, idx, r1, r2, row_id, best);
 }
 
-// c(i, gold[i]) of every row, from the product's own contraction sequence (sim_tile_32x32: v_mfma_f32_32x32x2_f32 over k in
-// sim_gemm_kernel's order), so that the value carries the bits the tile kernel produces for that element -- the count epilogue's
-// "equal, lower index first" test is then exact at the gold column itself.  One wave per 32 rows: row t of the MFMA tile is row t
-// of A, column t the gold row of B; only the diagonal is kept.  Also presets rank[i] = 1.
+// c(i, gold[i]) of every row with the bits the tile kernel produces for that element, and rank[i] = 1 (csls_gold_body, sim_rescore.h:
+// screen.hip's ranks take their gold values from the same body)
 __global__ __launch_bounds__(kBlock) void csls_gold_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                            int64_t ldb, int M, int d, const float* __restrict__ r1,
                                                            const float* __restrict__ r2, const int32_t* __restrict__ gold,
                                                            float* __restrict__ gval, int32_t* __restrict__ rank) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int m0 = (blockIdx.x * (kBlock / 64) + wave) * 32;
-    if (m0 >= M) return;                                       // wave-uniform
-    const int m = min(m0 + r, M - 1), g = gold[m];
-    const f32x16 acc = sim_tile_32x32<false>(A + (int64_t)m * lda, Bm + (int64_t)g * ldb, d);
-    // C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  Element (t, t) lives in lane t + 32 ((t >> 2) & 1),
-    // register (t & 3) + 4 (t >> 3): the lane whose r is t holds it iff its h matches
-    if (h != ((r >> 2) & 1) || m0 + r >= M) return;
-    const int want = (r & 3) + 4 * (r >> 3);
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s = q == want ? acc[q] : s;
-    gval[m] = r1 != nullptr ? csls_value(s, r1[m], r2[g]) : s;
-    rank[m] = 1;
+    csls_gold_body(A, lda, Bm, ldb, M, d, r1, r2, gold, gval, rank);
 }
 
 // S[i][j] = csls_value(S[i][j], r1[i], r2[j]) in place: the column sample (or a narrow matrix) staged in the workspace

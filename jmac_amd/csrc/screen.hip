@@ -25,6 +25,15 @@
 // both bounds).  The viable predicate tk_pack(c, row_id) > best[j] is monotone in c too: tk_pack(c_lo, id) > best[j] is "certainly
 // viable", !(tk_pack(c_hi, id) > best[j]) "certainly not".  Only certainly viable columns may raise a threshold, only certainly
 // non-viable ones are dropped unseen; the exact predicate runs on the rescored value (ScMode, ScreenAlign below).
+//
+// jmac_sim_csls_rank_screened_f32: rank_i = 1 + #{j : before(c(i, j), j)} with before(c, j) := c > g || (c == g && j < G), g the gold
+// value of row i (the fp32 product's bits, csls_gold_body) and G its column.  before is monotone in c, so with c_lo <= c <= c_hi
+//   certainly before    before(c_lo, j): counted in the bf16 product's epilogue (ballots, popcounts, integer atomics), never rescored
+//   certainly not       c_hi < g || (c_hi == g && j > G): dropped
+//   everything else     g lies in [c_lo, c_hi]: the column joins the row's list (the gold column always does: n_rescored >= 1) and
+//                       screen_rank_resolve_kernel puts its rescored c to the exact predicate.
+// No sample stage: the threshold is g, known before the product starts.  A non-finite sh or e decides nothing (the column is listed).
+// A row with more than RK_CAP undecided columns is recounted densely -- by the entry (finish != 0) or by the caller.
 #include "common.h"
 #include "sim_rescore.h"
 #include "topk_select.h"
@@ -48,6 +57,10 @@ constexpr int SC_FL_CAP = 512;              // entries of a wave's LDS list
 constexpr int SC_FL_ROOM = 192;             // flush when a list has less room than this at a tile's end (a typical tile adds ~60)
 constexpr int SC_STRIP_MAX = 64;            // tiles per strip at most: a column's offset in its strip fits 16 bits
 constexpr int SC_CAP = TK_CAP;              // list entries per row
+// list entries per row of the ranks.  A listed column costs about 32 dense ones (sim_row_tile_grouped uses one row of a 32 x 32 tile),
+// so a row with more than ~N / 32 undecided columns is cheaper on the dense product: 256 at the narrowest screened width, ~940 at
+// N = 30000; 512 lies between (profiles/rank_screen_timing.txt has 256 and 1024 next to it).  tests/screen_rank_ref.py restates it.
+constexpr int RK_CAP = 512;
 constexpr int SC_KMAX = 64;
 constexpr int64_t SC_MIN_N = 8192;
 constexpr int64_t SC_DMAX = 512;
@@ -61,12 +74,15 @@ __device__ __forceinline__ float screen_err(float ka, float nbt) { return __fmaf
 
 // what a kernel decides on: the score itself (jmac_sim_topk_screened_f32), c = csls_value(s, r1, r2), or c over the viable columns
 // only -- there the rescoring is decided at run time (r1 == NULL: c = s), as in score.hip's viable forms
-enum ScMode { SC_PLAIN, SC_CSLS, SC_VIABLE };
+// -- or, SC_RANK (jmac_sim_csls_rank_screened_f32), the count of the columns that come before a row's gold column
+enum ScMode { SC_PLAIN, SC_CSLS, SC_VIABLE, SC_RANK };
 struct ScreenAlign {
     const float* r1;                    // [M]
     const float* r2;                    // [N]
     const int32_t* row_id;              // SC_VIABLE: [M] the suitor a row stands for (the predicate's tie-break)
     const unsigned long long* best;     // SC_VIABLE: [N] the reviewers' words
+    const int32_t* gold;                // SC_RANK: [M] the gold column G (its value g is the epilogue's tau)
+    int32_t* rank;                      // SC_RANK: [M], preset to 1: the certain counts are added to it
 };
 template <int MODE>
 __device__ __forceinline__ float sc_value(float s, float r1v, float r2v, bool cs) {
@@ -165,6 +181,8 @@ struct ScreenEpi {
 // strip's tiles, and at a tile's end, when a list is nearly full (and after the last tile), the block counts its entries per row
 // in LDS and claims each row's slots with ONE integer atomic: ~10 x fewer.  A wave whose list is full claims slots directly.
 // MODE (FILTER only): the test is on c_hi = sc_value(sh + e) and, SC_VIABLE, on its word against best[n]; the entry stays (sh, n).
+// SC_RANK: tau is the row's gold value and both ends of the bound are tested -- certainly-before columns are counted (one ballot per
+// accumulator register, the two rows' popcounts written into the lanes that stand for them), undecided ones take the list path, index only.
 // The alignment forms' terms are a trailing ScreenAlign argument that SC_PLAIN does not have (AL is empty there: the plain
 // instantiations keep the argument list, and the instructions, they had before the alignment forms existed).
 __device__ __forceinline__ ScreenAlign sc_align() { return ScreenAlign{}; }
@@ -230,8 +248,13 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
             cs = al.r1 != nullptr;
             ridrow = al.row_id[mrow];
         }
+        if constexpr (MODE == SC_RANK) {                      // the gold column rides where the suitor id does
+            cs = al.r1 != nullptr;
+            ridrow = al.gold[mrow];
+        }
         r1row = cs ? al.r1[mrow] : 0.f;
     }
+    int before_row = 0;                     // SC_RANK: the certainly-before columns of row `lane` of the wave's 64, over the strip
     int fcount = 0;                         // FILTER: entries in the wave's list (wave-uniform)
     int* const fle = fl_e[FILTER ? wave : 0];
     float* const flv = fl_v[FILTER ? wave : 0];
@@ -254,7 +277,7 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                 const int ml = fl_e[w][e] >> 16;
                 const int pos = row_base[ml] + atomicAdd(&row_cnt[ml], 1);
                 if (pos < cap) {
-                    cval[(int64_t)(m0 + ml) * cap + pos] = fl_v[w][e];
+                    if constexpr (MODE != SC_RANK) cval[(int64_t)(m0 + ml) * cap + pos] = fl_v[w][e];      // (the ranks need the column only)
                     cidx[(int64_t)(m0 + ml) * cap + pos] = ns0 + (fl_e[w][e] & 0xffff);
                 }
             }
@@ -332,6 +355,7 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                 if constexpr (MODE == SC_VIABLE) bestcol[j] = al.best[nc];
             }
         }
+        int before_tile = 0;                // SC_RANK: this tile's part of before_row
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -344,8 +368,9 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                 float r1v = 0.f;
                 int rid = 0;
                 if constexpr (MODE != SC_PLAIN) r1v = h_t ? bcast_f(r1row_t, rbase + 4) : bcast_f(r1row_t, rbase);
-                if constexpr (MODE == SC_VIABLE)
+                if constexpr (MODE == SC_VIABLE || MODE == SC_RANK)
                     rid = __float_as_int(h_t ? bcast_f(__int_as_float(ridrow_t), rbase + 4) : bcast_f(__int_as_float(ridrow_t), rbase));
+                int c0 = 0, c1 = 0;            // SC_RANK, wave-uniform: the certainly-before columns of rows rbase / rbase + 4
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int n = n0 + wn * 64 + j * 32 + r;
@@ -356,6 +381,17 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                         bool pass;
                         if constexpr (MODE == SC_PLAIN) {
                             pass = m < M && n < N && !(v + e < tau);
+                        } else if constexpr (MODE == SC_RANK) {
+                            // tau = g, rid = G.  Both certain tests fail on a NaN bound, and `fin` keeps a non-finite sh or e (bf16
+                            // overflow) from deciding: such a column is listed and rescored.  Columns >= N never count.
+                            const float clo = sc_value<MODE>(v - e, r1v, r2col[j], cs), chi = sc_value<MODE>(v + e, r1v, r2col[j], cs);
+                            const bool in = m < M && n < N, fin = fabsf(v) + e < INFINITY;
+                            const bool before = in && fin && (clo > tau || (clo == tau && n < rid));
+                            const bool never = fin && (chi < tau || (chi == tau && n > rid));
+                            pass = in && !before && !never;
+                            const unsigned long long bm = __ballot(before);
+                            c0 += __popc((unsigned)bm);
+                            c1 += __popc((unsigned)(bm >> 32));
                         } else {
                             const float chi = sc_value<MODE>(v + e, r1v, r2col[j], cs);
                             pass = m < M && n < N && !(chi < tau);
@@ -367,11 +403,11 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                                 const int slot = fcount + __popcll(mask & ((1ull << lane) - 1ull));
                                 if (slot < SC_FL_CAP) {
                                     fle[slot] = (ml << 16) | (n - ns0);
-                                    flv[slot] = v;
+                                    if constexpr (MODE != SC_RANK) flv[slot] = v;
                                 } else {                       // the wave's list is full: its own slot, directly
                                     const int pos = atomicAdd(cnt + m, 1);
                                     if (pos < cap) {
-                                        cval[(int64_t)m * cap + pos] = v;
+                                        if constexpr (MODE != SC_RANK) cval[(int64_t)m * cap + pos] = v;
                                         cidx[(int64_t)m * cap + pos] = n;
                                     }
                                 }
@@ -380,15 +416,25 @@ __global__ __launch_bounds__(kBlock, 3) void screen_gemm_kernel(const bf16_t* __
                         }
                     }
                 }
+                // SC_RANK: rows rbase and rbase + 4 are lanes rbase and rbase + 4 of before_row; (i, reg) covers every lane once per
+                // tile (sg_epi_count's scheme: the counts are scalars, a lane write each, no compare masks kept alive)
+                if constexpr (MODE == SC_RANK)
+                    asm("s_nop 0\n\tv_writelane_b32 %0, %1, %2\n\tv_writelane_b32 %0, %3, %4"
+                        : "+v"(before_tile)
+                        : "s"(c0), "n"(rbase), "s"(c1), "n"(rbase + 4));
                 // (one register's tests at a time: scheduled ahead, the e and tau of all 64 would be live at once)
                 if constexpr (FILTER) __builtin_amdgcn_sched_barrier(0);
             }
+        before_row += before_tile;
         if constexpr (FILTER) {
             // block-uniform: flush when some wave's list could not take a typical tile any more
             const bool last = tn + 1 == tn1;
             if (__syncthreads_or(fcount > SC_FL_CAP - SC_FL_ROOM) || last) flush_block();
         }
     }
+    // SC_RANK: one integer atomic per (wave, row) and strip; sums of integers: the same bits whatever the grid (rows >= M: no such row)
+    if constexpr (MODE == SC_RANK)
+        if (before_row != 0 && m0 + wm * 64 + lane < M) atomicAdd(al.rank + m0 + wm * 64 + lane, before_row);
 }
 
 // The sample of the alignment forms, in place behind screen_gemm_kernel<false>: S[m][n] = sh - e becomes c_lo, and -inf in the viable
@@ -564,6 +610,65 @@ __global__ __launch_bounds__(kBlock) void screen_fill_kernel(int32_t* __restrict
     if (i < n) p[i] = v;
 }
 
+// ---- the ranks: gold values, then (behind screen_gemm_kernel<true, SC_RANK>) the undecided columns, one block per row ------------
+__global__ __launch_bounds__(kBlock) void screen_gold_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                             int64_t ldb, int M, int d, const float* __restrict__ r1,
+                                                             const float* __restrict__ r2, const int32_t* __restrict__ gold,
+                                                             float* __restrict__ gval, int32_t* __restrict__ rank) {
+    csls_gold_body(A, lda, Bm, ldb, M, d, r1, r2, gold, gval, rank);
+}
+
+// rank[b] holds 1 + the certainly-before count.  A list that fits: its columns rescored with the fp32 product's own sequence, the exact
+// predicate's hits added.  One that does not (more than cap columns within the bound of the gold value): the partial count is dropped;
+// finish != 0 recounts the row over all N columns here (slow, exact, as the top-k forms' overflowing rows), finish == 0 leaves
+// rank = 0 for the caller's dense pass.  Hits are integers summed through LDS: no order dependence.
+__global__ __launch_bounds__(kBlock) void screen_rank_resolve_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                                     int64_t ldb, int N, int d, const float* __restrict__ r1,
+                                                                     const float* __restrict__ r2, const int32_t* __restrict__ gold,
+                                                                     const float* __restrict__ gval, const int* __restrict__ cnt,
+                                                                     const int* __restrict__ cidx, int cap, int finish,
+                                                                     int32_t* __restrict__ rank, int32_t* __restrict__ n_rescored) {
+    __shared__ int s_hits;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int C = cnt[b];
+    const bool over = C > cap;              // block-uniform
+    if (over && !finish) {
+        if (tid == 0) {
+            rank[b] = 0;
+            if (n_rescored) n_rescored[b] = -1;
+        }
+        return;
+    }
+    if (tid == 0) s_hits = 0;
+    __syncthreads();
+    const float* arow = A + (int64_t)b * lda;
+    const bool cs = r1 != nullptr;
+    const float r1b = cs ? r1[b] : 0.f, g = gval[b];
+    const int G = gold[b];
+    int hits = 0;
+    auto test = [&](int n, float s) {
+        const float c = cs ? csls_value(s, r1b, r2[n]) : s;
+        hits += c > g || (c == g && n < G);
+    };
+    if (over) {
+        for_each_row_score(arow, Bm, ldb, N, d, test);
+    } else {
+        // 32 listed columns per wave step; odd rows start at waves 2 and 3 (screen_select_kernel's spread over the SIMDs)
+        const int lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+        for (int c0 = ((wave + 2 * (b & 1)) & 3) * 32; c0 < C; c0 += 32 * (kBlock / 64)) {
+            const int n = cidx[(int64_t)b * cap + min(c0 + r, C - 1)];
+            const f32x16 acc = sim_row_tile_grouped(arow, Bm + (int64_t)n * ldb, d);
+            if (h == 0 && c0 + r < C) test(n, acc[0]);
+        }
+    }
+    if (hits) atomicAdd(&s_hits, hits);
+    __syncthreads();
+    if (tid == 0) {
+        rank[b] = (over ? 1 : rank[b]) + s_hits;
+        if (n_rescored) n_rescored[b] = over ? -1 : C;
+    }
+}
+
 // strip: as few tiles per block as fill the device once (3 resident blocks per CU): more blocks than that would queue behind them,
 // fewer leave CUs idle; the lists' contents do not depend on it
 template <bool FILTER, int MODE = SC_PLAIN>
@@ -657,6 +762,52 @@ static int sc_align_entry(const float* A, int64_t lda, const float* B, int64_t l
     return sc_run<SC_PLAIN>(A, lda, B, ldb, L, N, d, k, val, idx, n_rescored, ws, st);      // c = s: jmac_sim_topk_screened_f32's launches
 }
 
+// jmac_sim_csls_rank_screened_f32's workspace and stages
+struct RkWs { size_t ab, bb, na, nb, gval, cnt, cidx, total; };
+static RkWs rk_layout(int64_t L, int64_t N, int64_t d) {
+    RkWs w{};
+    size_t off = 0;
+    w.ab = off;   off += align_up((size_t)L * (size_t)sc_dp(d) * 2);
+    w.bb = off;   off += align_up((size_t)N * (size_t)sc_dp(d) * 2);
+    w.na = off;   off += align_up((size_t)L * 4);
+    w.nb = off;   off += align_up((size_t)N * 4);
+    w.gval = off; off += align_up((size_t)L * 4);
+    w.cnt = off;  off += align_up((size_t)L * 4);
+    w.cidx = off; off += align_up((size_t)L * RK_CAP * 4);
+    w.total = off + 256;
+    return w;
+}
+
+static int rk_run(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t L, int64_t N, int64_t d, const float* r1,
+                  const float* r2, const int32_t* gold, int32_t* rank, int32_t* n_rescored, int32_t finish, void* ws, hipStream_t st) {
+    char* wb = (char*)ws;
+    const RkWs w = rk_layout(L, N, d);
+    const int64_t dp = sc_dp(d);
+    bf16_t* Ab = (bf16_t*)(wb + w.ab);
+    bf16_t* Bb = (bf16_t*)(wb + w.bb);
+    float* gval = (float*)(wb + w.gval);
+    ScreenEpi e{};
+    e.na = (float*)(wb + w.na); e.nb = (float*)(wb + w.nb);
+    e.tau = gval; e.tau_stride = 1;
+    e.cnt = (int*)(wb + w.cnt); e.cidx = (int*)(wb + w.cidx); e.cap = RK_CAP;
+    ScreenAlign al{};
+    al.r1 = r1; al.r2 = r2; al.gold = gold; al.rank = rank;
+    const dim3 block(kBlock);
+    // 1. bf16 copies and norm bounds
+    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((L + 3) / 4)), block, 0, st, A, lda, (int)L, (int)d, (int)dp, SC_KAPPA, Ab, (float*)e.na);
+    hipLaunchKernelGGL(screen_prepare_kernel, dim3((unsigned)((N + 3) / 4)), block, 0, st, B, ldb, (int)N, (int)d, (int)dp, 1.f, Bb, (float*)e.nb);
+    // 2. g_i with the fp32 product's bits; rank = 1
+    hipLaunchKernelGGL(screen_gold_kernel, dim3((unsigned)((L + 32 * (kBlock / 64) - 1) / (32 * (kBlock / 64)))), block, 0, st, A, lda, B, ldb,
+                       (int)L, (int)d, r1, r2, gold, gval, rank);
+    // 3. all N columns: certain ones counted into rank, undecided ones listed
+    if (hipMemsetAsync(e.cnt, 0, (size_t)L * 4, st) != hipSuccess) return (int)hipGetLastError();
+    if (int rc = launch_screen_gemm<true, SC_RANK>(Ab, Bb, dp, L, N, e, st, al)) return rc;
+    // 4. the lists rescored; 5. the rows whose list overflowed
+    hipLaunchKernelGGL(screen_rank_resolve_kernel, dim3((unsigned)L), block, 0, st, A, lda, B, ldb, (int)N, (int)d, r1, r2, gold, gval, e.cnt,
+                       e.cidx, e.cap, (int)finish, rank, n_rescored);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -702,6 +853,32 @@ int jmac_sim_csls_topk_viable_screened_f32(const float* A, int64_t lda, const fl
                                            float* val, int32_t* idx, int32_t* n_rescored, void* ws, size_t ws_bytes,
                                            jmac_stream_t stream) {
     return sc_align_entry(A, lda, B, ldb, n1, n2, d, r1, r2, true, row_id, best, k, val, idx, n_rescored, ws, ws_bytes, stream);
+}
+
+size_t jmac_sim_csls_rank_screened_workspace_bytes(int64_t n1, int64_t n2, int64_t d) {
+    if (n1 < 0 || n2 < 0 || d <= 0) return 0;
+    const size_t fp32 = jmac_sim_csls_rank_workspace_bytes(n1, n2);
+    if (n2 < SC_MIN_N) return fp32;
+    const size_t screened = rk_layout(n1, n2, d).total;
+    return screened > fp32 ? screened : fp32;
+}
+
+int jmac_sim_csls_rank_screened_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t n1, int64_t n2, int64_t d,
+                                    const float* r1, const float* r2, const int32_t* gold, int32_t* rank, int32_t* n_rescored,
+                                    int32_t finish, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    // jmac_sim_csls_rank_f32's checks in its order, the screen's row-length check ahead of the workspace
+    if (n1 < 0 || n2 <= 0 || d <= 0 || (r1 == nullptr) != (r2 == nullptr)) return JMAC_EINVAL;
+    if (n1 == 0) return JMAC_OK;
+    if (!A || !B || !gold || !rank) return JMAC_EINVAL;
+    if (lda % 4 || ldb % 4 || d % 4 || d > SC_DMAX) return JMAC_EDIM;
+    if (n1 >= INT32_MAX || n2 >= INT32_MAX) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_sim_csls_rank_screened_workspace_bytes(n1, n2, d)) return JMAC_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n2 < SC_MIN_N) {                                     // narrow: no screen, the fp32 entry's own code
+        if (int rc = jmac_sim_csls_rank_f32(A, lda, B, ldb, n1, n2, d, r1, r2, gold, rank, ws, ws_bytes, stream)) return rc;
+        return sc_fill_unscreened(n_rescored, n1, st);
+    }
+    return rk_run(A, lda, B, ldb, n1, n2, d, r1, r2, gold, rank, n_rescored, finish, ws, st);
 }
 
 }  // extern "C"

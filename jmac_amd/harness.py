@@ -225,12 +225,12 @@ def evaluate_completion(model: JMAC, kg: KnowledgeGraph, ei, et, args, split="va
 
 @torch.no_grad()
 def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, top_k=(1, 5, 10),
-                       matrix_free=True):
+                       matrix_free=True, screen=None):
     """test_alignment_ (train.py:105-113) on the test pairs of a KG pair: row i of ``pairs`` aligns entity pairs[i, 0] of kg1
     with pairs[i, 1] of kg2 (ids local to their KG).  ``graphs``: ((ei1, et1), (ei2, et2)).  One encoder pass in eval mode, the
     alignment embeddings of the listed entities gathered on the device, then scoring.alignment_test -- by default its
     matrix-free form (no len(pairs)^2 matrix) -- under ``args.eval_metric`` ('cosine', 'inner', 'manhattan') and ``args.eval_norm``
-    (train.py:95-96; absent: 'cosine', False).  Returns (top_k, hits [%], mr, mrr)."""
+    (train.py:95-96; absent: 'cosine', False).  Returns (top_k, hits [%], mr, mrr).  ``screen``: scoring.alignment_test's."""
     (ei1, et1), (ei2, et2) = graphs
     b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
     b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
@@ -243,7 +243,7 @@ def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pa
     scoring.check_index_range(pairs[:, 1], a2.shape[0], "pairs[:, 1]")
     p = torch.from_numpy(pairs).to(a1.device)
     return scoring.alignment_test(a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1]), top_k, getattr(args, "eval_metric", "cosine"),
-                                  bool(getattr(args, "eval_norm", False)), csls_k, matrix_free=matrix_free)
+                                  bool(getattr(args, "eval_norm", False)), csls_k, matrix_free=matrix_free, screen=screen)
 
 
 @torch.no_grad()
@@ -303,12 +303,13 @@ def evaluate_auction_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeG
 
 @torch.no_grad()
 def evaluate_sinkhorn_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, scale=50.0, iters=10,
-                                top_k=(1, 5, 10), stable_k=None):
+                                top_k=(1, 5, 10), stable_k=None, screen=None):
     """``evaluate_alignment`` under the Sinkhorn plan of the test pairs instead of CSLS (no counterpart in the reference): the
     pairs' embeddings are selected as there, scoring.sinkhorn_terms gives the rescoring terms (2 ``iters`` products, no
     len(pairs)^2 matrix) and scoring.alignment_ranks the ranks.  ``args.eval_metric`` ('cosine', 'inner'; 'manhattan' is not
     built) and ``args.eval_norm`` as there.  Returns (top_k, hits [%], mr, mrr); with ``stable_k`` a fifth entry, the one-to-one
-    precision [%] of scoring.stable_alignment (k = ``stable_k``) under the same terms, as ``evaluate_stable_alignment`` counts it."""
+    precision [%] of scoring.stable_alignment (k = ``stable_k``) under the same terms, as ``evaluate_stable_alignment`` counts it.
+    ``screen``: scoring.alignment_ranks's and scoring.stable_alignment's (the Sinkhorn iterations themselves are not screened)."""
     (ei1, et1), (ei2, et2) = graphs
     b1 = (ei1, et1, [kg1.entity_id_base, kg1.upper_entity_base], [kg1.relation_id_base, kg1.upper_relation_base])
     b2 = (ei2, et2, [kg2.entity_id_base, kg2.upper_entity_base], [kg2.relation_id_base, kg2.upper_relation_base])
@@ -326,10 +327,10 @@ def evaluate_sinkhorn_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: Knowledge
     e1, e2 = a1.index_select(0, p[:, 0]), a2.index_select(0, p[:, 1])
     terms = scoring.sinkhorn_terms(e1, e2, scale, iters, metric, norm)
     gold = torch.arange(e1.shape[0], device=e1.device, dtype=torch.int32)
-    out = scoring._rank_summary(scoring.alignment_ranks(e1, e2, gold, 1, metric, norm, terms=terms), top_k)
+    out = scoring._rank_summary(scoring.alignment_ranks(e1, e2, gold, 1, metric, norm, terms=terms, screen=screen), top_k)
     if stable_k is None:
         return out
-    match1, _, _ = scoring.stable_alignment(e1, e2, min(int(stable_k), len(pairs)), 1, metric, norm, terms=terms)
+    match1, _, _ = scoring.stable_alignment(e1, e2, min(int(stable_k), len(pairs)), 1, metric, norm, terms=terms, screen=screen)
     matched = match1 >= 0
     hits = (match1 == torch.arange(match1.numel(), device=match1.device)) & matched
     return (*out, 100.0 * float(hits.sum().item()) / max(1, int(matched.sum().item())))

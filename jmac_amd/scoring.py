@@ -734,14 +734,25 @@ def _csls_operands(emb1, emb2, csls_k, metric, normalize, terms, screen=None):
 
 
 def alignment_ranks(emb1: torch.Tensor, emb2: torch.Tensor, gold, csls_k: int = 10, metric: str = "cosine",
-                    normalize: bool = False, terms=None) -> torch.Tensor:
+                    normalize: bool = False, terms=None, screen: Optional[str] = None, return_stats: bool = False):
     """int32 ranks [n1]: the 1-based rank of column gold[i] in row i of ``alignment_sim(emb1, emb2, metric, normalize, csls_k)``
     (descending, ties -> lower index first) == ``csls_rank(sim_matrix(..), csls_k, gold)`` (``csls_k = 0``:
     ``filtered_rank(sim_matrix(..), gold, descending=True)``) bit for bit, without the n1 x n2 matrix: the count runs in the
     product's epilogue (``metric="manhattan"``: in the L1 tile kernel's, against ``1 - l1_scores``).  ``terms``: ``csls_terms`` of the
     same operands and metric, if the caller has them already -- or ``sinkhorn_terms``: the ranks are then those under the
-    Sinkhorn plan (any positive ``csls_k``)."""
-    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms)
+    Sinkhorn plan (any positive ``csls_k``).
+    ``screen="bf16"``: the same ranks bit for bit from jmac_sim_csls_rank_screened_f32 (the CSLS terms' two products screened as
+    well; not for 'manhattan'; row length <= 512).  The bf16 matrix cores decide every column whose bounds lie on one side of the
+    row's gold value; the undecided ones are rescored with the fp32 product's own instructions.  A row with more than 512 undecided
+    columns (its gold sits in the bulk of the row) comes back unranked and is finished here by the fp32 entry on the gathered
+    rows: such rows cost what they cost without the screen, on top of the screen's pass, so the screen pays for golds near the top
+    of their rows -- a trained model's -- and is NOT expected to win when most golds are random.  One host read
+    (are there unranked rows).  ``return_stats`` (screened form only) appends ``sim_topk``'s statistics dict; overflow_rows is the
+    number of rows finished dense."""
+    _check_screen("alignment_ranks", screen, metric)
+    if return_stats and screen is None:
+        raise ValueError("alignment_ranks: return_stats needs screen='bf16'")
+    a, b, r1, r2 = _csls_operands(emb1, emb2, csls_k, metric, normalize, terms, screen)
     n1, d = a.shape
     n2 = b.shape[0]
     check_index_range(gold, n2, "gold")
@@ -750,6 +761,24 @@ def alignment_ranks(emb1: torch.Tensor, emb2: torch.Tensor, gold, csls_k: int = 
         raise ValueError("gold must have one entry per row of emb1")
     rank = torch.empty(n1, dtype=torch.int32, device=a.device)
     L = lib()
+    if screen is not None:
+        nres = torch.empty(n1, dtype=torch.int32, device=a.device)
+        ws_bytes = int(L.jmac_sim_csls_rank_screened_workspace_bytes(n1, n2, d))
+        ws = workspace(ws_bytes, a.device)
+        check(L.jmac_sim_csls_rank_screened_f32(ptr(a), d, ptr(b), d, n1, n2, d, ptr(r1), ptr(r2), ptr(gold), ptr(rank), ptr(nres), 0,
+                                                ptr(ws), ws_bytes, stream()), "jmac_sim_csls_rank_screened_f32")
+        rows = (rank == 0).nonzero().flatten()                         # the host read: the rows whose list overflowed
+        if rows.numel():
+            sub = torch.empty(rows.numel(), dtype=torch.int32, device=a.device)
+            ws_bytes = int(L.jmac_sim_csls_rank_workspace_bytes(rows.numel(), n2))
+            ws = workspace(ws_bytes, a.device)
+            # (held in names: a temporary would be freed, and its memory reused, before the launch that reads it)
+            a_s, gold_s = a.index_select(0, rows).contiguous(), gold.index_select(0, rows).contiguous()
+            r1s = None if r1 is None else r1.index_select(0, rows).contiguous()
+            check(L.jmac_sim_csls_rank_f32(ptr(a_s), d, ptr(b), d, rows.numel(), n2, d, ptr(r1s), ptr(r2), ptr(gold_s), ptr(sub), ptr(ws),
+                                           ws_bytes, stream()), "jmac_sim_csls_rank_f32")
+            rank[rows] = sub
+        return (rank, _screen_stats(nres)) if return_stats else rank
     name = "jmac_l1_csls_rank" if _l1_metric(metric) else "jmac_sim_csls_rank"
     ws_bytes = int(getattr(L, name + "_workspace_bytes")(n1, n2))
     ws = workspace(ws_bytes, a.device)
@@ -1088,13 +1117,17 @@ def _rank_summary(rank: torch.Tensor, top_k):
 
 
 def alignment_test(embeds1: torch.Tensor, embeds2: torch.Tensor, top_k=(1, 5, 10), metric: str = "cosine",
-                   normalize: bool = False, csls_k: int = 10, matrix_free: bool = False):
+                   normalize: bool = False, csls_k: int = 10, matrix_free: bool = False, screen: Optional[str] = None):
     """test() / greedy_alignment() / calculate_rank(accurate=True), evaluation.py:20-28, alignment.py:10-112:
     row i of embeds1 is aligned with row i of embeds2.  Returns (top_k, hits [%], mr, mrr).  ``matrix_free``: the same ranks,
-    hence the same tuple, from ``csls_terms`` + ``alignment_ranks`` -- three products, no n x n matrix."""
+    hence the same tuple, from ``csls_terms`` + ``alignment_ranks`` -- three products, no n x n matrix.  ``screen``:
+    ``alignment_ranks``'s, with ``matrix_free`` only (the stored matrix has no screened form)."""
+    _check_screen("alignment_test", screen, metric)
+    if screen is not None and not matrix_free:
+        raise ValueError("alignment_test: screen needs matrix_free=True")
     if matrix_free:
         gold = torch.arange(embeds1.shape[0], device=embeds1.device, dtype=torch.int32)
-        return _rank_summary(alignment_ranks(embeds1, embeds2, gold, csls_k, metric, normalize), top_k)
+        return _rank_summary(alignment_ranks(embeds1, embeds2, gold, csls_k, metric, normalize, screen=screen), top_k)
     s = alignment_sim(embeds1, embeds2, metric, normalize, 0)
     n = s.shape[0]
     gold = torch.arange(n, device=s.device, dtype=torch.int32)
