@@ -187,6 +187,40 @@ typedef struct {
 } jmac_agg_fwd_job_t;
 int jmac_rel_attn_aggregate_fwd_jobs_f32(const jmac_agg_fwd_job_t* jobs, int32_t n_jobs, jmac_stream_t stream);
 
+/* Attention export: the per-edge softmax weights of the layer above, which its forward kernel folds into an online softmax
+ * and never writes (the reference computes them as scatter_softmax(s, dst) of the neighbour branch, src/jmac_model.py:71-89 and
+ * modules/helper/message_passing.py:24-28).  On the same factorised tables, for an edge e = (i <- j, type t):
+ *     h_e = P[i] + Q[j] - Rq[t]          s_e = sum_k a_k LeakyReLU_slope(h_e[k])          (the forward kernel's logit)
+ *     alpha_e = exp(s_e - m_i) / sum_{e' in in(i)} exp(s_e' - m_i),   m_i = max over in(i)   (sums to 1 over a non-empty i)
+ *     scale_by_degree != 0: alpha_e * sqrt(deg_i)      (what message_passing.py:26 multiplies the messages with)
+ *     seg_entropy[i] = -sum_e alpha_e log alpha_e      (0 for an empty destination; always of the UNscaled alpha)
+ *     seg_argmax[i]  = ORIGINAL edge id of the largest alpha of destination i, ties -> the lowest original edge id; -1 for an
+ *                      empty destination
+ * alpha [E] and logit [E] (may be NULL) are in the CALLER's edge order: the value of CSR slot x goes to position perm[x]
+ * (jmac_csr_build's perm; NULL: slot order, and seg_argmax holds slots).  The self-loop branch (src/jmac_model.py:50) is not
+ * exported: one edge per node and no norm, its weight is identically 1.  Only the Q half of QZ and the Rq half of RR are read.
+ * by_dst: the forward's schedule over the CSR rows (ptr = rowptr [N+1]); col / etype [E] as there.  seg_entropy [N] and
+ * seg_argmax [N] may be NULL.  Read-only on every input, fp32 logits / softmax / outputs, fixed-order reductions and no float
+ * atomics: bitwise reproducible.  Checks, in this order: null pointers, negative sizes (JMAC_EINVAL); d % 4 != 0, d > 512,
+ * ld % 4 != 0, ld < dh (JMAC_EDIM); N or E >= 2^31 - 1 (JMAC_ERANGE); ws (JMAC_EWORKSPACE).  E == 0: seg_entropy = 0,
+ * seg_argmax = -1, JMAC_OK.
+ * The _bf16 form reads bf16 tables in the padded layout of jmac_rel_attn_aggregate_fwd_bf16_padded (P rows of dh elements, Q
+ * at 0 of a [Q|Z] row, pad columns zero; dh == d: unpadded); 16-byte lane loads where dh % 8 == 0 and the rows are 16-byte
+ * aligned, 8-byte ones otherwise. */
+size_t jmac_rel_attn_edge_weights_workspace_bytes(int64_t N, int64_t E);
+
+int jmac_rel_attn_edge_weights_f32(const float* P, int64_t ldp, const float* QZ, int64_t ldqz, const float* RR, int64_t ldrr,
+                                   const float* a_att, const int32_t* col, const int32_t* etype, const int32_t* perm,
+                                   const jmac_view_t* by_dst, int64_t N, int64_t E, int64_t d, float slope,
+                                   int32_t scale_by_degree, float* alpha, float* logit, float* seg_entropy, int32_t* seg_argmax,
+                                   void* ws, size_t ws_bytes, jmac_stream_t stream);
+
+int jmac_rel_attn_edge_weights_bf16(const uint16_t* P, int64_t ldp, const uint16_t* QZ, int64_t ldqz, const uint16_t* RR,
+                                    int64_t ldrr, int64_t dh, const float* a_att, const int32_t* col, const int32_t* etype,
+                                    const int32_t* perm, const jmac_view_t* by_dst, int64_t N, int64_t E, int64_t d, float slope,
+                                    int32_t scale_by_degree, float* alpha, float* logit, float* seg_entropy,
+                                    int32_t* seg_argmax, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
 /* Merge of per-source-chunk partial aggregations: the slab-pipelined exchange of the destination-sharded layer
  * (jmac_amd/dist.py; the reference has one process and no exchange: modules/helper/message_passing.py:24,28 are the
  * per-destination softmax / sum that make the partials mergeable).  Part c = the forward above on the edges whose SOURCE is

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from torch.nn.init import xavier_normal_
 
 from . import ops, scatter as jscatter
-from ._lib import require_device
+from ._lib import check_index_range, require_device
 from .graph import DEFAULT_CHUNK, graph_cache
 
 
@@ -218,6 +218,41 @@ class RelationAwareLayer(nn.Module):
         nb = propagate(edge_index, edge_type, True)
         sl = propagate(torch.stack([loop, loop]), torch.full((n,), rel.size(0) - 1, dtype=torch.long, device=x.device), False)
         return (nb + sl) / 2
+
+    def attention(self, ent_emb, rel_emb, edge_index, edge_type, scale_by_degree=False, logits=False, stats=False):
+        """The neighbour branch's attention weights (src/jmac_model.py:71-89: scatter_softmax of the edge logits over each
+        destination), one per column of ``edge_index`` in the caller's order -> ops.EdgeAttention.  ``scale_by_degree``: times
+        sqrt(deg), what modules/helper/message_passing.py:26 multiplies the messages with; ``logits`` / ``stats``: also the
+        logits / the per-destination entropy and argmax edge.  Same tables as pre_bn, nothing of BatchNorm (alpha is pre-BN),
+        the self-loop branch (weight identically 1) is not exported.  Runs under no_grad whatever the caller's grad mode."""
+        require_device(ent_emb, rel_emb, edge_index, edge_type)
+        if ent_emb.dim() != 2 or rel_emb.dim() != 2 or ent_emb.shape[1] != self.in_channels \
+                or rel_emb.shape[1] != self.rel_transform_weight1.shape[0]:
+            raise ValueError("attention: ent_emb [N, %d] and rel_emb [nr, %d] expected, got %s and %s"
+                             % (self.in_channels, self.rel_transform_weight1.shape[0], tuple(ent_emb.shape), tuple(rel_emb.shape)))
+        slope = self.atv_mlp.negative_slope
+        kw = dict(scale_by_degree=scale_by_degree, logits=logits, stats=stats)
+        with torch.no_grad():
+            n = ent_emb.size(0)
+            rel = self.transform_relations(rel_emb)
+            if self.comp_op == "sub":
+                graph = graph_cache.get(edge_index, edge_type, n, rel.size(0), self.chunk)
+                PQZ, RR, a, _ = self._tables(ent_emb, rel)
+                return ops.rel_attn_edge_weights(*ops.pqz_views(PQZ), RR, a, graph, slope, **kw)
+            if self.comp_op == "mult":
+                # the per-edge row table of _pre_bn_mult, its Q half only: row e = (x_src(e) * r_type(e)) Wb
+                check_index_range(edge_type, rel.size(0), "edge_type")
+                check_index_range(edge_index[1], n, "edge_index[1] (message source)")
+                d_in, d = self.in_channels, self.out_channels
+                a, dp = self._padded_a()
+                graph = self._edge_row_graph(edge_index, edge_type, n)
+                wt, wb = self.w_att[:d_in], self.w_att[d_in:]
+                if dp != d:
+                    wt, wb = F.pad(wt, (0, dp - d)), F.pad(wb, (0, dp - d))
+                rows = torch.cat((ent_emb.index_select(0, edge_index[1]) * rel.index_select(0, edge_type), ent_emb * rel[-1:]), dim=0)
+                zero_rel = torch.zeros((1, dp), dtype=torch.float32, device=ent_emb.device)
+                return ops.rel_attn_edge_weights(torch.mm(ent_emb, wt), torch.mm(rows, wb), zero_rel, a, graph, slope, **kw)
+        raise NotImplementedError(self.comp_op)
 
     # -- reference signature ----------------------------------------------------------------------
     def forward(self, ent_emb, rel_emb, edge_index, edge_type):

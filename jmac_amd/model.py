@@ -290,6 +290,31 @@ class JMAC(nn.Module):
             return a.cpu(), c.cpu()
         return a.cpu().numpy(), c.cpu().numpy()
 
+    def attention(self, edge_index, edge_type, ent_bases, rel_bases, **kw):
+        """The attention weights of every GNN layer the configuration runs on this KG: {"conv1_alignment": EdgeAttention,
+        "conv1_completion": ..., "conv2_alignment": ...} (ops.EdgeAttention, one alpha per column of ``edge_index``; ``kw``:
+        RelationAwareLayer.attention's scale_by_degree / logits / stats).  Every layer is evaluated on the inputs it sees in an
+        EVAL-mode forward_base (running BatchNorm statistics, dropout off), captured by forward pre-hooks on the op-by-op
+        encoder.  The model is left as found: training flags, fused_encoder, parameters, buffers and the device RNG."""
+        names = ("conv1_alignment", "conv1_completion", "conv2_alignment")
+        was_training = [(m, m.training) for m in self.modules()]
+        fused, seen, hooks = self.fused_encoder, {}, []
+        for name in names:
+            hooks.append(getattr(self, name).register_forward_pre_hook(
+                lambda mod, inputs, name=name: seen.__setitem__(name, inputs)))
+        try:
+            self.eval()
+            self.fused_encoder = False
+            with torch.no_grad():
+                self.forward_base(edge_index, edge_type, ent_bases, rel_bases)
+                return {name: getattr(self, name).attention(*seen[name], **kw) for name in names if name in seen}
+        finally:
+            for h in hooks:
+                h.remove()
+            self.fused_encoder = fused
+            for m, t in was_training:
+                m.training = t
+
     # ---- scoring ----------------------------------------------------------------------------------
     def forward_linkpred(self, e_index, r_index, edge_index, edge_type, all_index, ent_bases, rel_bases,
                          pred_head=False, cached=None):

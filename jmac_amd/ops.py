@@ -6,7 +6,7 @@ runs in libjmac_hip.so.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -301,6 +301,53 @@ class _RelAttnAggregateSplit(torch.autograd.Function):
 def rel_attn_aggregate_split(P, QZ, RR, a, graph: RelGraph, slope: float, out_scale: float = 1.0, loop_rel: int = -1,
                              self_off: int = 0) -> torch.Tensor:
     return _RelAttnAggregateSplit.apply(P, QZ, RR, a, graph, float(slope), float(out_scale), int(loop_rel), int(self_off))
+
+
+class EdgeAttention(NamedTuple):
+    """What rel_attn_edge_weights returns; a field that was not asked for is None."""
+    alpha: torch.Tensor                      # [E] fp32, the caller's edge order
+    logit: Optional[torch.Tensor]            # [E] fp32
+    entropy: Optional[torch.Tensor]          # [N] fp32, of the unscaled alpha; 0 for a destination without in-edges
+    argmax: Optional[torch.Tensor]           # [N] int64, original edge id of the largest alpha; -1 without in-edges
+
+
+def rel_attn_edge_weights(P, QZ, RR, a, graph: RelGraph, slope: float, scale_by_degree: bool = False, logits: bool = False,
+                          stats: bool = False, dh: Optional[int] = None, slot_order: bool = False) -> EdgeAttention:
+    """jmac_rel_attn_edge_weights_*: alpha = softmax over the in-edges of every destination of s_e = a . LeakyReLU(P[i] + Q[j] -
+    Rq[t]) -- the weights the forward aggregation applies and never writes -- on the tables rel_attn_split_fwd_raw takes (P
+    [N, dh], QZ [Nsrc, >= dh] with Q in front, RR likewise; fp32, or bf16 in the padded layout with half pitch ``dh``, default
+    P.shape[1]).  ``scale_by_degree``: alpha * sqrt(deg), the factor on the layer's messages.  ``logits``: also s; ``stats``: also
+    the entropy and the argmax edge of every destination.  Outputs indexed by edge follow ``graph``'s input edge order
+    (``slot_order``: the CSR slot order instead, argmax then names slots).  No autograd: a read-out."""
+    require_device(P, QZ, RR, a)
+    if QZ.dtype != P.dtype or RR.dtype != P.dtype:
+        raise TypeError("P, QZ and RR must share a dtype")
+    _table(P), _f32c(a)
+    a = a.contiguous()
+    N, d = P.shape[0], int(a.numel())
+    dh = int(P.shape[1] if dh is None else dh)
+    bf16 = P.dtype == torch.bfloat16
+    if dh != d and not (bf16 and dh == bf16_pad(d)):
+        raise ValueError("tables of half pitch %d do not go with a_att of %d elements" % (dh, d))
+    if P.shape[1] < dh or QZ.shape[1] < dh or RR.shape[1] < dh or min(P.stride(1), QZ.stride(1), RR.stride(1)) != 1:
+        raise ValueError("table rows are shorter than the half pitch %d, or not row-major" % dh)
+    if graph.N != N or graph.num_src > QZ.shape[0] or graph.num_rel > RR.shape[0]:
+        raise ValueError("graph / table shapes disagree")
+    L = lib()
+    dev, E = P.device, graph.E
+    alpha = torch.empty(E, dtype=torch.float32, device=dev)
+    logit = torch.empty(E, dtype=torch.float32, device=dev) if logits else None
+    entropy = torch.empty(N, dtype=torch.float32, device=dev) if stats else None
+    argmax = torch.empty(N, dtype=torch.int32, device=dev) if stats else None
+    ws_bytes = int(L.jmac_rel_attn_edge_weights_workspace_bytes(N, E))
+    ws = workspace(ws_bytes, dev)
+    fn, pitch = (L.jmac_rel_attn_edge_weights_bf16, (dh,)) if bf16 else (L.jmac_rel_attn_edge_weights_f32, ())
+    args = (ptr(P), P.stride(0), ptr(QZ), QZ.stride(0), ptr(RR), RR.stride(0), *pitch, ptr(a), ptr(graph.col), ptr(graph.etype),
+            None if slot_order else ptr(graph.perm), C.pointer(graph.by_dst.view()), N, E, d, float(slope),
+            1 if scale_by_degree else 0, ptr(alpha) if E > 0 else None, ptr(logit) if E > 0 else None, ptr(entropy), ptr(argmax),
+            ptr(ws), ws_bytes, stream())
+    _launch(fn, args, "rel_attn_edge_weights_bf16" if bf16 else "rel_attn_edge_weights")
+    return EdgeAttention(alpha, logit, entropy, argmax.long() if stats else None)
 
 
 def bn_tanh_fwd_raw(x, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float, y, y2=None,
