@@ -497,6 +497,43 @@ int jmac_linkpred_topk_bf16(const jmac_link_layer_t* layers, int32_t n_layers, c
                             int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k,
                             float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
 
+/* Cross-KG ensemble link prediction: jmac_linkpred_rank_indexed_f32 and jmac_linkpred_topk_f32 on a distance that several KGs
+ * vote on through alignment links (ensemble knowledge transfer between the KGs of a jointly trained model; no counterpart in
+ * the reference).  Members g = 0 .. S, S <= 3.  Member 0 is the target KG with N candidate rows (link == NULL, n_rows == N).  A
+ * supporting member s >= 1 has its own per-layer entity and relation tables (the same n_layers and d, n_rows rows; relation
+ * ids are shared) and a link map link [N] on the device: link[n] is the row of KG s aligned with target row n, or -1.  Every
+ * member has a weight >= 0, passed by value; the weights need not sum to 1.  For query b = (h[b], r[b]) and candidate n:
+ *     d_g[b,n]       = jmac_linkpred_rank_*'s distance -- the single running fp32 sum over (layer, k) -- in member g's tables,
+ *                      query row E^g_l[hq] +/- R^g_l[r[b]], candidate row T^g_l[cn], with (hq, cn) = (h[b], n) for member 0
+ *                      and (link_s[h[b]], link_s[n]) for member s
+ *     present_s(b,n) = link_s[h[b]] >= 0 and link_s[n] >= 0
+ *     D = w_0 * d_0;  then for s = 1 .. S in that order  D = fmaf(w_s, present_s ? d_s : d_0, D)
+ * A missing link falls back to the target's own distance: the ensemble never penalises an entity for being unaligned.  With
+ * one member and w_0 = 1, D is d_0 bit for bit.  Ranks and top-k, the tie rule (smaller first, equal by lower index), pred_head
+ * (the sign applies in every member) and the padding (idx = -1, val = +inf) are the single-KG entry points', decided on D; the
+ * filter is the TARGET's known-tail index (NULL: raw).  One device function forms D wherever it is needed (gold and filter
+ * correction, tile loop, the select's recompute), so jmac_linkpred_ens_rank_f32(gold = idx[b,j]) is j + 1 for every returned
+ * entry and two calls return identical bits; no float atomics, nothing depends on the grid or the CU count.
+ * Supporting rows are read through the link map inside the kernel (no permuted copies of the tables); a link value outside
+ * [0, n_rows) counts as absent and is never dereferenced.  A 64 x 64 tile without a linked head or without a linked candidate
+ * in member s skips that member's share of the loop (no bit changes).  Cost: about (S + 1) x the single-KG call.
+ * 1 <= n_members <= 4, member 0 without and every other member with a link, finite weights >= 0 (JMAC_EINVAL); the other
+ * limits and error codes are jmac_linkpred_rank_indexed_f32's and jmac_linkpred_topk_f32's.  fp32 tables only. */
+typedef struct {
+    const jmac_link_layer_t* layers;   /* n_layers entries; table == ent (fp32) */
+    const int32_t* link;               /* [N] or NULL for member 0 */
+    int64_t n_rows;                    /* rows of this member's tables */
+    float weight;
+} jmac_link_member_t;
+size_t jmac_linkpred_ens_rank_workspace_bytes(int64_t B, int64_t d, int32_t n_layers, int32_t n_members);
+int jmac_linkpred_ens_rank_f32(const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h,
+                               const int32_t* r, int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index,
+                               int64_t B, int64_t N, int64_t d, int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream);
+size_t jmac_linkpred_ens_topk_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers, int32_t n_members, int32_t k);
+int jmac_linkpred_ens_topk_f32(const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h,
+                               const int32_t* r, int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N,
+                               int64_t d, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
 /* rank[b] = 1 + #{n : score[b,n] < score[b,gold] or (== and n < gold[b])}, where entries listed in
  * the filter CSR (filt_ptr [B+1], filt_idx) other than the gold are skipped.  descending == 0: `score` is a
  * DISTANCE (the reference's predictions = -dist, sorted descending); descending != 0: `score` is a SIMILARITY

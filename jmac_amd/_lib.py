@@ -41,6 +41,11 @@ class TailIndex(C.Structure):
     _fields_ = [("key", vp), ("n_keys", i64), ("tail_ptr", vp), ("tail_idx", vp)]
 
 
+class LinkMember(C.Structure):
+    """jmac_link_member_t"""
+    _fields_ = [("layers", C.POINTER(LinkLayer)), ("link", vp), ("n_rows", i64), ("weight", f32)]
+
+
 class AggFwdJob(C.Structure):
     """jmac_agg_fwd_job_t"""
     _fields_ = [("P", vp), ("ldp", i64), ("QZ", vp), ("ldqz", i64), ("RR", vp), ("ldrr", i64), ("a_att", vp), ("col", vp), ("etype", vp),
@@ -142,6 +147,10 @@ _SIGS = {
     "jmac_linkpred_topk_workspace_bytes": (sz, [i64, i64, i64, i32, i32]),
     "jmac_linkpred_topk_f32": (C.c_int, [vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
     "jmac_linkpred_topk_bf16": (C.c_int, [vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
+    "jmac_linkpred_ens_rank_workspace_bytes": (sz, [i64, i64, i32, i32]),
+    "jmac_linkpred_ens_rank_f32": (C.c_int, [C.POINTER(LinkMember), i32, i32, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp, sz, vp]),
+    "jmac_linkpred_ens_topk_workspace_bytes": (sz, [i64, i64, i64, i32, i32, i32]),
+    "jmac_linkpred_ens_topk_f32": (C.c_int, [C.POINTER(LinkMember), i32, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
     "jmac_sim_matrix_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, i64, vp]),
     "jmac_sim_topk_workspace_bytes": (sz, [i64, i64, i32]),
     "jmac_sim_topk_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
@@ -295,8 +304,8 @@ _CHECKED: "dict" = {}
 _CHECKED_CAP = 64
 
 
-def check_index_range(idx, n: int, what: str = "index"):
-    """Raise IndexError unless every entry of ``idx`` lies in [0, n).  Host data (lists, numpy, CPU tensors) is
+def check_index_range(idx, n: int, what: str = "index", lo: int = 0):
+    """Raise IndexError unless every entry of ``idx`` lies in [lo, n) (``lo``: 0, or -1 for maps whose -1 means "none").  Host data (lists, numpy, CPU tensors) is
     checked on the host; a device tensor is checked once per (tensor object, version) by jmac_index_check -- one host read
     the first time a tensor is seen, nothing afterwards, and nothing while a stream is being captured.  Hot loops should
     pass tensors that were checked on the host and marked before the upload (``mark_index_range``): a fresh device tensor
@@ -304,44 +313,44 @@ def check_index_range(idx, n: int, what: str = "index"):
     not bump ``_version``: re-validate such a tensor yourself (``jmac_index_check``)."""
     import numpy as np
     import torch
-    n = int(n)
+    n, lo = int(n), int(lo)
     if not isinstance(idx, torch.Tensor):
         a = np.asarray(idx)
-        if a.size and (a.min() < 0 or a.max() >= n):
-            raise IndexError("%s out of range: values in [%s, %s], valid range [0, %d)" % (what, a.min(), a.max(), n))
+        if a.size and (a.min() < lo or a.max() >= n):
+            raise IndexError("%s out of range: values in [%s, %s], valid range [%d, %d)" % (what, a.min(), a.max(), lo, n))
         return
     if idx.numel() == 0:
         return
     if not idx.is_cuda:
-        lo, hi = int(idx.min()), int(idx.max())
-        if lo < 0 or hi >= n:
-            raise IndexError("%s out of range: values in [%d, %d], valid range [0, %d)" % (what, lo, hi, n))
+        vlo, vhi = int(idx.min()), int(idx.max())
+        if vlo < lo or vhi >= n:
+            raise IndexError("%s out of range: values in [%d, %d], valid range [%d, %d)" % (what, vlo, vhi, lo, n))
         return
     if idx.dtype not in (torch.int32, torch.int64):
         raise TypeError("%s must be int32 or int64 (got %s)" % (what, idx.dtype))
     ok = getattr(idx, "_jmac_range_ok", None)             # set by a host-side check before the upload (mark_index_range)
-    if ok is not None and ok <= n:
+    if ok is not None and ok <= n and lo <= 0:
         return
     # validated tensors are remembered by IDENTITY through a weak reference (no strong reference: a [2,E] COO of a dropped
     # graph is not pinned by this cache), together with the version counter torch bumps on in-place writes
     key = id(idx)
     hit = _CHECKED.get(key)
-    if hit is not None and hit[0]() is idx and hit[1] == idx._version and hit[2] >= 0 and hit[2] <= n:
+    if hit is not None and hit[0]() is idx and hit[1] == idx._version and hit[2] >= 0 and hit[2] <= n and hit[3] >= lo:
         return
     if torch.cuda.is_current_stream_capturing():
         return                                             # cannot read back inside a capture; eager warm-up has checked
     t = idx if idx.is_contiguous() else idx.contiguous()
     bad = torch.zeros(1, dtype=torch.int32, device=idx.device)
-    check(lib().jmac_index_check(ptr(t), t.element_size(), t.numel(), 0, n, ptr(bad), stream()), "jmac_index_check")
+    check(lib().jmac_index_check(ptr(t), t.element_size(), t.numel(), lo, n, ptr(bad), stream()), "jmac_index_check")
     nbad = int(bad.item())
     if nbad:
-        raise IndexError("%s out of range: %d of %d entries outside [0, %d)" % (what, nbad, t.numel(), n))
+        raise IndexError("%s out of range: %d of %d entries outside [%d, %d)" % (what, nbad, t.numel(), lo, n))
     for k in [k for k, v in _CHECKED.items() if v[0]() is None]:
         del _CHECKED[k]                                    # tensors that have died since
     if len(_CHECKED) >= _CHECKED_CAP:
         _CHECKED.pop(next(iter(_CHECKED)))
     try:
-        _CHECKED[key] = (weakref.ref(idx), idx._version, n)
+        _CHECKED[key] = (weakref.ref(idx), idx._version, n, lo)
     except TypeError:                                      # pragma: no cover  (not weak-referenceable: do not cache)
         pass
 

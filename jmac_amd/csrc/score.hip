@@ -5,7 +5,8 @@
 //  * jmac_linkpred_rank_{,indexed_}*  forward_linkpred + that loop, ranks only; the filter from a per-batch CSR or from the
 //                            device-resident known-tail index                 src/jmac_model.py:302-313, src/validate.py:50-64
 //  * jmac_linkpred_topk_*   the k nearest tails the index does not list (the model's predictions; no counterpart)
-//  * jmac_sim_matrix_f32    torch.mm(ILL_vec, KG_vec.t())                modules/utils/util.py:52, train.py:239
+//  * jmac_linkpred_ens_*    those ranks and top-k on the cross-KG ensemble distance: supporting KGs vote through link maps (no counterpart)
+//  * jmac_sim_matrix_f32    torch.mm(ILL_vec, KG_vec.t())              modules/utils/util.py:52, train.py:239
 //  * jmac_row_topk_f32 / jmac_sim_topk_f32   sim.topk(k, dim=1)          modules/utils/util.py:53
 //  * jmac_softmax_entropy_f32, jmac_row_softmax_f32                      train.py:241-257
 //  * jmac_sim_softmax_stats_f32  the same softmax's maxima, arg-maxima, sums and entropies per row and per column from the
@@ -2597,6 +2598,543 @@ int jmac_linkpred_topk_bf16(const jmac_link_layer_t* layers, int32_t n_layers, c
                             const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k, float* val, int32_t* idx,
                             void* ws, size_t ws_bytes, jmac_stream_t stream) {
     return launch_link_topk<bf16_t>(layers, n_layers, h, r, pred_head, index, B, N, d, k, val, idx, ws, ws_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// cross-KG ensemble link prediction (jmac_linkpred_ens_*): ranks and top-k of the target KG's tails on a distance that several
+// KGs vote on through alignment links.  Members g = 0 .. S (S <= 3): member 0 is the target with N candidate rows; a supporting
+// member s >= 1 has its own layer tables (same n_layers and d, n_rows_s rows), a link map link_s [N] (the row of KG s aligned with
+// target row n, or -1) and a weight w_s >= 0; the weights need not sum to 1.  For query b = (h_b, r_b) and candidate n
+//     d_g[b, n]      jmac_linkpred_rank_*'s single running fp32 sum over (layer, k) of member g's tables, with
+//                    (query row, candidate row) = (h_b, n) for g = 0 and (link_s[h_b], link_s[n]) for g = s
+//     present_s(b,n) = link_s[h_b] >= 0 and link_s[n] >= 0     (a link outside [0, n_rows_s) is absent: never dereferenced)
+//     D = w_0 * d_0;  for s = 1 .. S in that order:  D = fmaf(w_s, present_s ? d_s : d_0, D)
+// A missing link falls back to the target's own distance: an entity is never penalised for being unaligned.  One member with
+// w_0 = 1 gives d_0 bit for bit.  Ranks, top-k, the tie rule, pred_head (the sign applies in every member) and the padding are
+// jmac_linkpred_rank_* / jmac_linkpred_topk_*'s, decided on D; the filter is the TARGET's known-tail index.  ens_fold below is
+// the ONE place D is formed -- prep kernel (gold and filter entries), tile kernel, select kernel's recompute -- so the j-th
+// prediction ranks j + 1 and two calls return identical bits; no float atomics, nothing depends on the grid or the CU count.
+// The single-KG kernels above are not touched: these are separate kernels (profiles/linkpred_ensemble_resources.txt).
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int LE_MAX = 4;                  // members
+struct LinkEnsArgs {
+    LinkRankArgs base;                     // sizes, sign, queries, gold, index and the epilogues' arguments; er = [ng][nl][B][dq]
+    const float* ent[LE_MAX][LR_MAX_LAYERS];
+    const float* rel[LE_MAX][LR_MAX_LAYERS];
+    const float* tab[LE_MAX][LR_MAX_LAYERS];
+    int64_t ld_ent[LE_MAX][LR_MAX_LAYERS], ld_rel[LE_MAX][LR_MAX_LAYERS], ld_tab[LE_MAX][LR_MAX_LAYERS];
+    const int32_t* link[LE_MAX];           // [N]; link[0] == nullptr (the identity)
+    int32_t n_rows[LE_MAX];
+    float w[LE_MAX];
+    int32_t ng;
+    int32_t* hq;                           // workspace [ng][B]: the query's head row in member g, -1 = not linked
+};
+
+// D after member g: the only place the combination is evaluated.  g = 0 is ens_fold(0, w_0, true, d_0, d_0) == w_0 * d_0.
+__device__ __forceinline__ float ens_fold(float D, float w, bool present, float dg, float d0) { return fmaf(w, present ? dg : d0, D); }
+
+// the row of member g aligned with target row n (0 <= n < N), -1 if there is none
+__device__ __forceinline__ int ens_row(const LinkEnsArgs& e, int g, int n) {
+    if (g == 0) return n;
+    const int v = e.link[g][n];
+    return (v >= 0 && v < e.n_rows[g]) ? v : -1;
+}
+
+// link_rank_prep_kernel for the ensemble.  One block per query: (1) its head row and query rows in every member (rows of an
+// unlinked head are zero) -> workspace; (2) RANK: D of the gold and of the filter entries, a.rows at a time -- the members take
+// turns in the SAME LDS (their query rows, then the candidates' rows read through the link), one lane per candidate runs the
+// tile kernel's sequential sum and folds it into its D; (3) rank[b] starts at 1 - #{filtered entries before the gold}.
+template <bool INDEXED, bool RANK>
+__global__ __launch_bounds__(kBlock) void link_ens_prep_kernel(LinkEnsArgs e) {
+    const LinkRankArgs& a = e.base;
+    extern __shared__ float le_sh[];                // RANK: [nl*dq] query rows + [rows][nl*dq + 1] candidate rows, one member at a time
+    __shared__ float gs_sh;
+    __shared__ int cand[LR_ROWS];
+    __shared__ int red[kBlock / 64];
+    __shared__ int2 rng_sh;
+    const int b = blockIdx.x, d = a.d, dq = a.dq, W = a.nl * dq, WS = W + 1;
+    const int hb = a.h[b], rb = a.r[b], g = RANK ? a.gold[b] : 0;
+    float* const er = static_cast<float*>(a.er);
+    if constexpr (INDEXED)
+        if (threadIdx.x < 64) {
+            const int2 rg = tail_range(a, hb, rb);
+            if (threadIdx.x == 0) rng_sh = rg;
+        }
+    for (int m = 0; m < e.ng; ++m) {
+        const int hq = ens_row(e, m, hb);
+        if (threadIdx.x == 0) e.hq[(int64_t)m * a.B + b] = hq;
+        for (int l = 0; l < a.nl; ++l)
+            for (int k = threadIdx.x; k < dq; k += kBlock) {
+                float v = 0.f;
+                if (hq >= 0 && k < d) v = e.ent[m][l][(int64_t)hq * e.ld_ent[m][l] + k] + a.sign * e.rel[m][l][(int64_t)rb * e.ld_rel[m][l] + k];
+                er[(((int64_t)m * a.nl + l) * a.B + b) * dq + k] = v;
+            }
+    }
+    int f0, f1;
+    if constexpr (INDEXED) {
+        __syncthreads();
+        f0 = rng_sh.x, f1 = rng_sh.y;
+    } else {
+        f0 = 0, f1 = 0;
+    }
+    if constexpr (!RANK) {
+        if (threadIdx.x == 0) a.rng[b] = make_int2(f0, f1);
+        return;
+    }
+    float* const erow = le_sh;
+    float* const crow = le_sh + W;
+    const int n_list = 1 + (f1 - f0);               // entry 0 = the gold
+    float gs = 0.f;
+    int cnt = 0;
+    for (int c0 = 0; c0 < n_list; c0 += a.rows) {
+        const int nc = min(a.rows, n_list - c0);
+        __syncthreads();                            // previous chunk consumed
+        if (threadIdx.x < nc) {
+            const int c = c0 + threadIdx.x;
+            int n = c == 0 ? g : a.filt_idx[f0 + c - 1];
+            if (c > 0 && (n == g || n < 0 || n >= a.N)) n = -1;      // skipped entries (as jmac_filtered_rank_f32)
+            cand[threadIdx.x] = n;
+        }
+        float D = 0.f, d0 = 0.f;
+        for (int m = 0; m < e.ng; ++m) {
+            const int hq = ens_row(e, m, hb);
+            __syncthreads();                        // cand complete; the previous member's rows consumed
+            for (int l = 0; l < a.nl; ++l)          // the thread that wrote an element above reads it back
+                for (int k = threadIdx.x; k < dq; k += kBlock) erow[l * dq + k] = er[(((int64_t)m * a.nl + l) * a.B + b) * dq + k];
+            for (int i = threadIdx.x; i < nc * W; i += kBlock) {
+                const int rI = i / W, q = i - rI * W, l = q / dq, k = q - l * dq;
+                const int n = cand[rI];
+                const int cn = (n >= 0 && hq >= 0) ? ens_row(e, m, n) : -1;
+                float v = 0.f;
+                if (cn >= 0 && k < d) v = e.tab[m][l][(int64_t)cn * e.ld_tab[m][l] + k];
+                crow[rI * WS + q] = v;
+            }
+            __syncthreads();
+            if (threadIdx.x < nc) {
+                const float* row = crow + threadIdx.x * WS;
+                float acc = 0.f;
+                for (int l = 0; l < a.nl; ++l)
+                    for (int k = 0; k < d; ++k) acc = add_absdiff(acc, erow[l * dq + k], row[l * dq + k]);
+                const int n = cand[threadIdx.x];
+                const bool present = hq >= 0 && n >= 0 && ens_row(e, m, n) >= 0;
+                if (m == 0) d0 = acc;
+                D = ens_fold(D, e.w[m], m == 0 || present, acc, d0);
+            }
+        }
+        __syncthreads();                            // every lane has read its rows
+        if (threadIdx.x < nc) {
+            if (c0 == 0 && threadIdx.x == 0) gs_sh = D;
+            crow[threadIdx.x * WS] = D;             // parked for the compare below
+        }
+        __syncthreads();
+        gs = gs_sh;
+        if (threadIdx.x < nc && !(c0 == 0 && threadIdx.x == 0)) {
+            const int n = cand[threadIdx.x];
+            const float sc = crow[threadIdx.x * WS];
+            if (n >= 0) cnt += (sc < gs || (sc == gs && n < g)) ? 1 : 0;
+        }
+    }
+    cnt = wave_sum_i(cnt);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
+        a.gs[b] = gs;
+        a.rank[b] = 1 - t;
+    }
+}
+
+// link_rank_tile_kernel for the ensemble: the member loop OUTSIDE the layer / slab loop.  Member 0's sums are kept (d0), every
+// member's sums are folded into the total when its slabs end, and the COUNT / STORE / FILTER epilogues run on the total.
+// A supporting member's candidate rows are read THROUGH the link map: a thread loads link_s[n0 + lrow], then its 16-byte pieces of
+// that row; an absent link reads row 0 and is zeroed when staged, and its sums are never selected.  A tile in which member s has
+// no linked head or no linked candidate skips that member's slabs (the fold takes d0 for every pair: no bit changes); the
+// decision is block-uniform (__syncthreads_or).
+template <bool VEC, int EPI>
+__global__ __launch_bounds__(kBlock) void link_ens_tile_kernel(LinkEnsArgs e) {
+    const LinkRankArgs& a = e.base;
+    __shared__ __attribute__((aligned(16))) float As[2][L1_K][L1_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[2][L1_K][L1_LD];
+    __shared__ int qbits[L1_T], cbits[L1_T];        // bit g: the row's head / the column's candidate has a row in member g
+    const int tid = threadIdx.x;
+    const int tx = tid & 15, ty = tid >> 4;
+    const int B = a.B, N = a.N, d = a.d;
+    const int b0 = blockIdx.y * L1_T, n0 = (EPI == LR_COUNT ? 0 : a.n_off) + blockIdx.x * L1_T;
+    const int lrow = tid >> 2, lk = (tid & 3) * 4;
+    const int arow = b0 + lrow, brow = n0 + lrow;
+    const bool a_ok = arow < B, b_ok = brow < N;
+    int qb = 0, cb = 0;
+    for (int g = 0; g < e.ng; ++g) {
+        qb |= (a_ok && e.hq[(int64_t)g * B + arow] >= 0) ? 1 << g : 0;
+        cb |= (b_ok && ens_row(e, g, brow) >= 0) ? 1 << g : 0;
+    }
+    if ((tid & 3) == 0) {
+        qbits[lrow] = qb;
+        cbits[lrow] = cb;
+    }
+    float acc[4][4], d0[4][4], tot[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = d0[i][j] = tot[i][j] = 0.f;
+    constexpr bool vec = VEC;
+    // row is a valid row of the table whether or not `ok` (clamped by the caller): the vector form loads unconditionally
+    auto gload = [&](const float* base, int64_t ld, int64_t row, bool ok, int k0) -> float4 {
+        const int k = k0 + lk;
+        if constexpr (vec) return ldraw(base + row * ld + (k < d ? k : d - 4));
+        float4 v = f4zero();
+        if (ok) {
+            const float* p = base + row * ld;
+            if (k + 0 < d) v.x = p[k + 0];
+            if (k + 1 < d) v.y = p[k + 1];
+            if (k + 2 < d) v.z = p[k + 2];
+            if (k + 3 < d) v.w = p[k + 3];
+        }
+        return v;
+    };
+    auto sstore = [&](float (*S)[L1_LD], float4 v, int k0, bool row_ok) {
+        if (!(row_ok && k0 + lk < d)) v = f4zero();
+        S[lk + 0][lrow] = v.x;
+        S[lk + 1][lrow] = v.y;
+        S[lk + 2][lrow] = v.z;
+        S[lk + 3][lrow] = v.w;
+    };
+    const int nk = (d + L1_K - 1) / L1_K, ns = a.nl * nk;      // slabs of one member: layer-major, k inside
+    const float* const er = static_cast<const float*>(a.er);
+    const int64_t arow_c = a_ok ? arow : B - 1;
+    for (int g = 0; g < e.ng; ++g) {
+        // block-uniform: does any pair of this tile use member g's distance?  (also the barrier that completes qbits / cbits)
+        const int any_q = __syncthreads_or((qb >> g) & 1), any_c = __syncthreads_or((cb >> g) & 1);
+        if (any_q && any_c) {
+            const int cn = b_ok ? ens_row(e, g, brow) : -1;
+            const bool c_ok = cn >= 0;
+            const int64_t crow = c_ok ? cn : 0;
+            auto slab = [&](int s, float4& ra, float4& rb) {
+                const int l = s / nk, k0 = (s - l * nk) * L1_K;
+                ra = gload(er + ((int64_t)g * a.nl + l) * B * a.dq, a.dq, arow_c, a_ok, k0);
+                rb = gload(e.tab[g][l], e.ld_tab[g][l], crow, c_ok, k0);
+            };
+            float4 ra, rb;
+            slab(0, ra, rb);
+            sstore(As[0], ra, 0, a_ok);
+            sstore(Bs[0], rb, 0, c_ok);
+            __syncthreads();
+            for (int s = 0; s < ns; ++s) {
+                const int cur = s & 1;
+                if (s + 1 < ns) slab(s + 1, ra, rb);
+#pragma unroll
+                for (int k = 0; k < L1_K; ++k) {
+                    const float4 av4 = *reinterpret_cast<const float4*>(&As[cur][k][ty * 4]);
+                    const float4 bv4 = *reinterpret_cast<const float4*>(&Bs[cur][k][tx * 4]);
+                    const float av[4] = {av4.x, av4.y, av4.z, av4.w};
+                    const float bv[4] = {bv4.x, bv4.y, bv4.z, bv4.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[i][j] = add_absdiff(acc[i][j], av[i], bv[j]);
+                }
+                if (s + 1 < ns) {
+                    const int l1 = (s + 1) / nk, k1 = (s + 1 - l1 * nk) * L1_K;
+                    sstore(As[cur ^ 1], ra, k1, a_ok);
+                    sstore(Bs[cur ^ 1], rb, k1, c_ok);
+                }
+                __syncthreads();
+            }
+        }
+        const float w = e.w[g];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool qp = (qbits[ty * 4 + i] >> g) & 1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool present = g == 0 || (qp && ((cbits[tx * 4 + j] >> g) & 1));
+                if (g == 0) d0[i][j] = acc[i][j];
+                tot[i][j] = ens_fold(tot[i][j], w, present, acc[i][j], d0[i][j]);
+                acc[i][j] = 0.f;
+            }
+        }
+    }
+    if constexpr (EPI == LR_STORE) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + ty * 4 + i;
+            if (b >= B) continue;
+            const int n = n0 + tx * 4;
+            float* o = a.S + (int64_t)b * a.ldS + (n - a.n_off);
+            if (n + 3 < N && (a.ldS % 4 == 0) && (a.n_off % 4 == 0)) st4(o, make_float4(-tot[i][0], -tot[i][1], -tot[i][2], -tot[i][3]));
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (n + j < N) o[j] = -tot[i][j];
+            }
+        }
+        return;
+    }
+    if constexpr (EPI == LR_FILTER) {                         // link_rank_tile_kernel's append, on the total
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + ty * 4 + i;
+            const bool row_ok = b < B;
+            const float nt = row_ok ? a.ntau[(int64_t)b * a.tau_stride] : INFINITY;
+            bool pass[4];
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                pass[j] = row_ok && n0 + tx * 4 + j < N && -tot[i][j] >= nt;
+                c += pass[j] ? 1 : 0;
+            }
+            if (!__any(c)) continue;
+            int inc = c;                                      // inclusive prefix over the row's 16 lanes
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+                const int t = __shfl_up(inc, o, 16);
+                if (tx >= o) inc += t;
+            }
+            const int total = __shfl(inc, 15, 16);
+            int base = 0;
+            if (tx == 0 && total) base = atomicAdd(a.cnt + b, total);
+            base = __shfl(base, 0, 16);
+            int slot = base + inc - c;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (pass[j]) {
+                    if (slot < a.cap) {
+                        a.cval[(int64_t)b * a.cap + slot] = -tot[i][j];
+                        a.cidx[(int64_t)b * a.cap + slot] = n0 + tx * 4 + j;
+                    }
+                    ++slot;
+                }
+        }
+        return;
+    }
+    if constexpr (EPI == LR_COUNT) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = b0 + ty * 4 + i;
+            const bool row_ok = b < B;
+            const float gs = row_ok ? a.gs[b] : 0.f;
+            const int g = row_ok ? a.gold[b] : 0;
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n = n0 + tx * 4 + j;
+                const float sc = tot[i][j];
+                c += (row_ok && n < N && (sc < gs || (sc == gs && n < g))) ? 1 : 0;
+            }
+            c += __shfl_xor(c, 1);
+            c += __shfl_xor(c, 2);
+            c += __shfl_xor(c, 4);
+            c += __shfl_xor(c, 8);
+            if (tx == 0 && row_ok && c) atomicAdd(a.rank + b, c);
+        }
+    }
+}
+
+// link_select_kernel for the ensemble: the same selection; an overflowing row recomputes D of its N candidates with the prep
+// kernel's sums and folds, one lane per candidate (the query rows come from the workspace: every lane reads the same address).
+__global__ __launch_bounds__(kBlock) void link_ens_select_kernel(LinkEnsArgs e, int k, const float* __restrict__ sval,
+                                                                 const int32_t* __restrict__ sidx, float* __restrict__ val,
+                                                                 int32_t* __restrict__ idx) {
+    const LinkRankArgs& a = e.base;
+    __shared__ TkShared tk;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int2 r = a.rng[b];
+    const int32_t* const tails = a.filt_idx;
+    float* const ov = val + (int64_t)b * k;
+    int32_t* const oi = idx + (int64_t)b * k;
+    auto emit = [&](int c, unsigned long long x) {
+        if (x == 0ull) {                                       // padding: fewer than k unlisted candidates
+            oi[c] = -1;
+            ov[c] = INFINITY;
+            return;
+        }
+        oi[c] = tk_unpack_index(x);
+        const float v = tk_unpack_value(x);
+        ov[c] = v == 0.f ? 0.f : -v;
+    };
+    const int C = a.cnt[b];
+    if (C + k <= a.cap) {
+        for (int c = tid; c < C; c += kBlock) {
+            const int n = a.cidx[(int64_t)b * a.cap + c];
+            tk.skey[c] = tail_listed(tails, r.x, r.y, n) ? 0ull : tk_pack(a.cval[(int64_t)b * a.cap + c], n);
+        }
+        for (int c = tid; c < k; c += kBlock) {
+            const float v = sval[(int64_t)b * k + c];
+            tk.skey[C + c] = v == -INFINITY ? 0ull : tk_pack(v, sidx[(int64_t)b * k + c]);
+        }
+        tk_sort_emit(tk.skey, C + k, k, emit);
+        return;
+    }
+    const int d = a.d, dq = a.dq;
+    const float* const er = static_cast<const float*>(a.er);
+    auto for_each_unlisted = [&](auto f) {                      // f(n, -D[b, n]) for every n in [0, N) the index does not list
+        for (int n = tid; n < a.N; n += kBlock) {
+            if (tail_listed(tails, r.x, r.y, n)) continue;
+            float D = 0.f, d0 = 0.f;
+            for (int g = 0; g < e.ng; ++g) {
+                const int cn = e.hq[(int64_t)g * a.B + b] >= 0 ? ens_row(e, g, n) : -1;
+                float acc = 0.f;
+                if (cn >= 0)
+                    for (int l = 0; l < a.nl; ++l) {
+                        const float* row = e.tab[g][l] + (int64_t)cn * e.ld_tab[g][l];
+                        const float* q = er + (((int64_t)g * a.nl + l) * a.B + b) * dq;
+                        for (int x = 0; x < d; ++x) acc = add_absdiff(acc, q[x], row[x]);
+                    }
+                if (g == 0) d0 = acc;
+                D = ens_fold(D, e.w[g], cn >= 0, acc, d0);
+            }
+            f(n, -D);
+        }
+    };
+    tk_select_recomputed(tk, k, for_each_unlisted, emit);
+}
+
+}  // namespace
+
+template <int EPI>
+static void launch_ens_tile(const LinkEnsArgs& e, bool vec, int64_t ncols, hipStream_t st) {
+    dim3 grid((unsigned)((ncols + L1_T - 1) / L1_T), (unsigned)((e.base.B + L1_T - 1) / L1_T));
+    if (vec) hipLaunchKernelGGL((link_ens_tile_kernel<true, EPI>), grid, dim3(kBlock), 0, st, e);
+    else hipLaunchKernelGGL((link_ens_tile_kernel<false, EPI>), grid, dim3(kBlock), 0, st, e);
+}
+
+// argument checks and LinkEnsArgs of both entry points (the caller has checked the sizes, B > 0 and its own pointers)
+static int ens_args(LinkEnsArgs& e, bool& vec, const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h,
+                    const int32_t* r, int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d) {
+    if (!members || !h || !r) return JMAC_EINVAL;
+    if (index && (index->n_keys < 0 || index->n_keys >= INT32_MAX || !index->key || !index->tail_ptr || !index->tail_idx)) return JMAC_EINVAL;
+    for (int g = 0; g < n_members; ++g) {
+        const jmac_link_member_t& m = members[g];
+        if (!m.layers || (g == 0) != (m.link == nullptr) || m.n_rows <= 0 || (g == 0 && m.n_rows != N)) return JMAC_EINVAL;
+        if (!(m.weight >= 0.f) || !std::isfinite(m.weight)) return JMAC_EINVAL;
+        if (m.n_rows >= INT32_MAX) return JMAC_ERANGE;
+    }
+    LinkRankArgs& a = e.base;
+    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
+    a.sign = pred_head ? -1.f : 1.f;
+    a.h = h; a.r = r;
+    if (index) {
+        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
+    }
+    e.ng = n_members;
+    vec = d % 4 == 0;
+    for (int g = 0; g < n_members; ++g) {
+        e.link[g] = members[g].link; e.n_rows[g] = (int32_t)members[g].n_rows; e.w[g] = members[g].weight;
+        for (int l = 0; l < n_layers; ++l) {
+            const jmac_link_layer_t& y = members[g].layers[l];
+            if (!y.ent || !y.rel || !y.table) return JMAC_EINVAL;
+            e.ent[g][l] = y.ent; e.rel[g][l] = y.rel; e.tab[g][l] = static_cast<const float*>(y.table);
+            e.ld_ent[g][l] = y.ld_ent; e.ld_rel[g][l] = y.ld_rel; e.ld_tab[g][l] = y.ld_table;
+            if (y.ld_table % 4 || ((uintptr_t)y.table % 16)) vec = false;
+        }
+    }
+    return JMAC_OK;
+}
+
+// the prefix of both workspaces: every member's query rows and head rows
+struct LeWs { size_t er, hq, end; };
+static LeWs le_layout(int64_t B, int64_t d, int64_t nl, int64_t ng) {
+    LeWs w{};
+    size_t off = 0;
+    w.er = off; off += align_up((size_t)ng * (size_t)nl * (size_t)B * (size_t)((d + 3) / 4 * 4) * 4);
+    w.hq = off; off += align_up((size_t)ng * (size_t)B * 4);
+    w.end = off;
+    return w;
+}
+
+extern "C" {
+
+size_t jmac_linkpred_ens_rank_workspace_bytes(int64_t B, int64_t d, int32_t n_layers, int32_t n_members) {
+    if (B < 0 || d <= 0 || n_layers <= 0 || n_members <= 0) return 0;
+    return le_layout(B, d, n_layers, n_members).end + align_up((size_t)B * 4) + 256;
+}
+
+int jmac_linkpred_ens_rank_f32(const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h, const int32_t* r,
+                               int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d,
+                               int32_t* rank, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_layers > LR_MAX_LAYERS || n_members < 1 || n_members > LE_MAX) return JMAC_EINVAL;
+    if (B == 0) return JMAC_OK;
+    if (!gold || !rank) return JMAC_EINVAL;
+    if (B >= INT32_MAX || N >= INT32_MAX || d > 512) return JMAC_ERANGE;
+    LinkEnsArgs e{};
+    bool vec;
+    if (int rc = ens_args(e, vec, members, n_members, n_layers, h, r, pred_head, index, B, N, d)) return rc;
+    if (!ws || ws_bytes < jmac_linkpred_ens_rank_workspace_bytes(B, d, n_layers, n_members)) return JMAC_EWORKSPACE;
+    LinkRankArgs& a = e.base;
+    const LeWs w = le_layout(B, d, n_layers, n_members);
+    a.gold = gold; a.rank = rank;
+    a.er = (char*)ws + w.er;
+    e.hq = (int32_t*)((char*)ws + w.hq);
+    a.gs = (float*)((char*)ws + w.end);
+    const int64_t W = (int64_t)n_layers * a.dq, words = 60 * 1024 / 4;
+    const int64_t rows = (words - W) / (W + 1);
+    if (rows < 1) return JMAC_ERANGE;                          // jmac_linkpred_rank_*'s LDS limit: the members share that LDS
+    a.rows = (int32_t)(rows < LR_ROWS ? rows : LR_ROWS);
+    const size_t shm = (size_t)(W + a.rows * (W + 1)) * sizeof(float);
+    if (index) hipLaunchKernelGGL((link_ens_prep_kernel<true, true>), dim3((unsigned)B), dim3(kBlock), shm, st, e);
+    else hipLaunchKernelGGL((link_ens_prep_kernel<false, true>), dim3((unsigned)B), dim3(kBlock), shm, st, e);
+    launch_ens_tile<LR_COUNT>(e, vec, N, st);
+    return (int)hipGetLastError();
+}
+
+size_t jmac_linkpred_ens_topk_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers, int32_t n_members, int32_t k) {
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_members <= 0 || k <= 0) return 0;
+    const LtWs t = lt_layout(B, N, d, 0, k);                   // (no query rows of its own: rng, then the driver's workspace)
+    return le_layout(B, d, n_layers, n_members).end + t.total;
+}
+
+int jmac_linkpred_ens_topk_f32(const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h, const int32_t* r,
+                               int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, int32_t k, float* val,
+                               int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_layers > LR_MAX_LAYERS || n_members < 1 || n_members > LE_MAX) return JMAC_EINVAL;
+    if (k <= 0 || k > ST_KMAX || k > N) return JMAC_EINVAL;
+    if (d > 512) return JMAC_EDIM;
+    if (B == 0) return JMAC_OK;
+    if (!val || !idx) return JMAC_EINVAL;
+    if (B >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
+    LinkEnsArgs e{};
+    bool vec;
+    if (int rc = ens_args(e, vec, members, n_members, n_layers, h, r, pred_head, index, B, N, d)) return rc;
+    if (!ws || ws_bytes < jmac_linkpred_ens_topk_workspace_bytes(B, N, d, n_layers, n_members, k)) return JMAC_EWORKSPACE;
+    LinkRankArgs& a = e.base;
+    if ((int64_t)n_layers * a.dq + 1 > 60 * 1024 / 4 - (int64_t)n_layers * a.dq) return JMAC_ERANGE;     // jmac_linkpred_rank_*'s LDS limit
+    const LeWs w = le_layout(B, d, n_layers, n_members);
+    const LtWs t = lt_layout(B, N, d, 0, k);
+    char* wb = (char*)ws;
+    a.er = wb + w.er;
+    e.hq = (int32_t*)(wb + w.hq);
+    a.rng = (int2*)(wb + w.end + t.rng);
+    if (index) hipLaunchKernelGGL((link_ens_prep_kernel<true, false>), dim3((unsigned)B), dim3(kBlock), 0, st, e);
+    else hipLaunchKernelGGL((link_ens_prep_kernel<false, false>), dim3((unsigned)B), dim3(kBlock), 0, st, e);
+    auto filter_args = [&](const SimFilter& f) {
+        LinkEnsArgs x = e;
+        x.base = link_filter_args(e.base, f);
+        return x;
+    };
+    return topk_drive(B, N, k, val, idx, wb + w.end + t.tail, t.ld_narrow, st,
+        [&](float* S, int64_t ldS, int64_t n) -> int {
+            LinkEnsArgs x = e;
+            x.base.N = (int32_t)n; x.base.S = S; x.base.ldS = ldS; x.base.n_off = 0;
+            launch_ens_tile<LR_STORE>(x, vec, n, st);
+            if (index) hipLaunchKernelGGL(link_mask_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, S, ldS, (int)n, a.rng, a.filt_idx);
+            return 0;
+        },
+        [&](const SimFilter& f) -> int {
+            launch_ens_tile<LR_FILTER>(filter_args(f), vec, N - f.n_off, st);
+            return 0;
+        },
+        [&](const SimFilter& f, const float* val0, const int32_t* idx0) {
+            hipLaunchKernelGGL(link_ens_select_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, filter_args(f), (int)k, val0, idx0, val, idx);
+        },
+        link_topk_finish_kernel);
 }
 
 size_t jmac_softmax_entropy_workspace_bytes(int64_t n1, int64_t n2) {

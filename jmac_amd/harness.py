@@ -223,6 +223,51 @@ def evaluate_completion(model: JMAC, kg: KnowledgeGraph, ei, et, args, split="va
     return float((rk <= 1).double().mean()), float((rk <= 10).double().mean()), float((1.0 / rk).mean())
 
 
+def alignment_links(kg_t: KnowledgeGraph, kg_s: KnowledgeGraph, seed_pairs, predicted=None, device=None):
+    """The link map of supporting KG ``kg_s`` for target ``kg_t`` (scoring.link_map: int32 [kg_t.num_entity], -1 = unaligned)
+    from ``seed_pairs`` [L, 2] of (target row, support row), ids local to their KG.  ``predicted``: a ``match`` vector indexed by
+    target row (scoring.stable_alignment / auction_alignment: the matched support row or -1) that fills the rows no seed
+    names -- seeds win."""
+    link = scoring.link_map(seed_pairs, kg_t.num_entity, kg_s.num_entity)
+    if predicted is not None:
+        p = torch.as_tensor(predicted).detach().cpu().to(torch.int64).reshape(-1)
+        if p.numel() != kg_t.num_entity:
+            raise ValueError("predicted must hold one entry per target entity (%d)" % kg_t.num_entity)
+        if p.numel() and (int(p.min()) < -1 or int(p.max()) >= kg_s.num_entity):
+            raise ValueError("predicted holds ids outside [-1, %d)" % kg_s.num_entity)
+        link = torch.where(link >= 0, link, p.to(torch.int32))
+    return link.to(device) if device is not None else link
+
+
+@torch.no_grad()
+def evaluate_completion_ensemble(model: JMAC, kgs: Dict[str, KnowledgeGraph], target: str, supports, graphs, links, weights, args,
+                                 split="val", filtered=True, eval_batch=None):
+    """evaluate_completion(fused=True) of KG ``target`` on the cross-KG ensemble distance (scoring.linkpred_ranks_ensemble):
+    ``supports`` names the supporting KGs, ``graphs`` = [(ei, et) of the target, then of every support], ``links`` one link map
+    per support (alignment_links), ``weights`` one per KG.  Every KG is encoded ONCE, a whole split goes through one call, the
+    filter is the target's TrueTailIndex.  Returns (hits@1, hits@10, mrr).
+    The KGs are encoded by forward_base, one call each, as evaluate_completion encodes its KG -- not as one stacked launch set
+    (forward_blocks), whose rows agree with forward_base's to rounding only: with the target's tables bit for bit the same,
+    weights (1, 0, ..) return evaluate_completion(fused=True)'s numbers exactly."""
+    model.eval()
+    kg = kgs[target]
+    data = {"val": kg.val_data, "test": kg.test_data, "train": kg.train_data}[split]
+    blocks = [(ei, et, [k.entity_id_base, k.upper_entity_base], [k.relation_id_base, k.upper_relation_base])
+              for k, (ei, et) in zip([kg] + [kgs[s] for s in supports], graphs)]
+    dev = graphs[0][0].device
+    links = [l.to(dev) for l in links]
+    cached = [model.forward_base(*b) for b in blocks]
+    index = _true_tail_index(kg, dev) if filtered else None
+    ranks = []
+    step = int(eval_batch or 16384)
+    for s in range(0, len(data), step):
+        b = data[s:s + step]
+        ranks.append(model.linkpred_ranks_ensemble(b[:, 0], b[:, 1], b[:, 2], blocks, links, weights, index=index, cached=cached))
+    rk = torch.cat(ranks).double()
+    model.train()
+    return float((rk <= 1).double().mean()), float((rk <= 10).double().mean()), float((1.0 / rk).mean())
+
+
 @torch.no_grad()
 def evaluate_alignment(model: JMAC, kg1: KnowledgeGraph, kg2: KnowledgeGraph, pairs, graphs, args, csls_k=10, top_k=(1, 5, 10),
                        matrix_free=True, screen=None):

@@ -368,6 +368,31 @@ class JMAC(nn.Module):
         return scoring.linkpred_topk([comp_layers[l] for l in layers], [comp_rel_layers[l] for l in layers], e_index, r_index,
                                      k, index, pred_head, table_dtype=getattr(self, "table_dtype", torch.float32))
 
+    def _ensemble_members(self, blocks, links, weights, cached):
+        """scoring's member list of ``blocks`` (the target's, then every support's): encoded through forward_blocks unless
+        ``cached`` holds their forward_base results."""
+        if len(links) != len(blocks) - 1 or len(weights) != len(blocks):
+            raise ValueError("one link map per supporting block and one weight per block")
+        if cached is None:
+            cached = self.forward_blocks(blocks)
+        layers = range(self.args.num_gcn_layer)
+        return [([c[1][l] for l in layers], [c[2][l] for l in layers], link, w)
+                for c, link, w in zip(cached, [None] + list(links), weights)]
+
+    def linkpred_ranks_ensemble(self, e_index, r_index, gold, blocks, links, weights, index=None, pred_head=False, cached=None):
+        """linkpred_ranks on the cross-KG ensemble distance (scoring.linkpred_ranks_ensemble): the supporting KGs score the
+        query and every candidate at their aligned rows, a missing link falls back to the target's own distance.
+        ``blocks`` = [(ei, et, ent_bases, rel_bases) of the target, then of every support], encoded through forward_blocks (one
+        launch set where it applies) unless ``cached`` = the list of their forward_base results; ``links``: one link map per
+        support (scoring.link_map, harness.alignment_links); ``weights``: one per block; ``index``: the TARGET's TrueTailIndex."""
+        return scoring.linkpred_ranks_ensemble(self._ensemble_members(blocks, links, weights, cached), e_index, r_index, gold,
+                                               index, pred_head)
+
+    def linkpred_topk_ensemble(self, e_index, r_index, k, blocks, links, weights, index=None, pred_head=False, cached=None):
+        """linkpred_topk on the ensemble distance of linkpred_ranks_ensemble (same arguments): ``(idx int64 [B, k], D fp32 [B, k])``."""
+        return scoring.linkpred_topk_ensemble(self._ensemble_members(blocks, links, weights, cached), e_index, r_index, k,
+                                              index, pred_head)
+
     @staticmethod
     def _alignment_terms(a, b, csls_k, down, sinkhorn, screen=None):
         """The rescoring terms of the two WHOLE (prepared) tables: csls_terms, or -- ``sinkhorn=dict(scale=.., iters=..)`` --

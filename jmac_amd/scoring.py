@@ -174,6 +174,112 @@ def linkpred_topk(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequence
     return idx.to(torch.int64), val
 
 
+def link_map(pairs, n_target: int, n_support: int, device=None) -> torch.Tensor:
+    """int32 [n_target] link map of a supporting KG from ``pairs`` [L, 2] of (target row, support row): entry n is the support
+    row aligned with target row n, -1 where no pair names n.  A target row listed twice keeps the SMALLEST support row.
+    Ids outside their KG raise ValueError.  (The ``match`` vectors of the alignment methods are link maps already.)"""
+    p = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    p = p.astype(np.int64).reshape(-1, 2)
+    n_target, n_support = int(n_target), int(n_support)
+    if len(p) and (p[:, 0].min() < 0 or p[:, 0].max() >= n_target or p[:, 1].min() < 0 or p[:, 1].max() >= n_support):
+        raise ValueError("link_map: pair ids outside [0, %d) x [0, %d)" % (n_target, n_support))
+    link = np.full(n_target, n_support, dtype=np.int64)
+    np.minimum.at(link, p[:, 0], p[:, 1])
+    link[link == n_support] = -1
+    return torch.from_numpy(link.astype(np.int32)).to(device) if device is not None else torch.from_numpy(link.astype(np.int32))
+
+
+def _link_members(members, who: str):
+    """(jmac_link_member_t array, tensors to keep alive, N, d, n_layers, relation rows every member has) of
+    ``[(comp_layers, comp_rel_layers, link_or_None, weight), ...]``: member 0 is the target, the others read through their link
+    maps (int32 / int64 [N] device tensors with values in [-1, rows of that member]), range-checked here before any launch."""
+    import math
+    from ._lib import LinkMember
+    if not 1 <= len(members) <= 4:
+        raise ValueError("%s: 1..4 members (the target, then up to 3 supporting KGs)" % who)
+    arr, keep = (LinkMember * len(members))(), []
+    N = d = nl = None
+    nrel = None
+    for g, (comp_layers, comp_rel_layers, link, weight) in enumerate(members):
+        lay, kp, rows, dg = _link_layers(comp_layers, comp_rel_layers, False)
+        if g == 0:
+            N, d, nl, dev = rows, dg, len(comp_layers), comp_layers[0].device
+        if dg != d or len(comp_layers) != nl or comp_layers[0].device != dev:
+            raise ValueError("%s: member %d disagrees with the target in d, layers or device" % (who, g))
+        weight = float(weight)
+        if not (math.isfinite(weight) and weight >= 0.0):
+            raise ValueError("%s: weights must be finite and >= 0 (member %d: %r)" % (who, g, weight))
+        if (g == 0) != (link is None):
+            raise ValueError("%s: the target (member 0) has no link map, every supporting member has one" % who)
+        if link is not None:
+            require_device(link)
+            if link.dim() != 1 or link.numel() != N or link.device != dev:
+                raise ValueError("%s: member %d's link map must hold one entry per target row (%d) on %s" % (who, g, N, dev))
+            if link.dtype != torch.int32:
+                if link.dtype != torch.int64:
+                    raise TypeError("%s: link maps are int32 or int64 (got %s)" % (who, link.dtype))
+                link = link.to(torch.int32)
+            link = link.contiguous()
+            check_index_range(link, rows, "member %d's link map" % g, lo=-1)
+            kp.append(link)
+        rr = min(int(x.shape[0]) for x in comp_rel_layers)
+        nrel = rr if nrel is None else min(nrel, rr)
+        keep += [lay, kp]
+        arr[g] = LinkMember(lay, ptr(link), rows, weight)
+    return arr, keep, N, d, nl, nrel
+
+
+def linkpred_ranks_ensemble(members, e_index, r_index, gold, index=None, pred_head: bool = False) -> torch.Tensor:
+    """linkpred_ranks(index=...) on the cross-KG ensemble distance.  ``members`` = ``[(comp_layers, comp_rel_layers, link, weight),
+    ...]``: member 0 is the target KG (``link`` None), a supporting member s scores query (h, r) and candidate n in its OWN
+    tables at the rows ``link_s[h]`` and ``link_s[n]`` (``link_map``; relation ids are shared).  With d_g the single-KG distance
+    of member g, D = w_0 d_0, then D = fma(w_s, d_s if both rows are linked else d_0, D) for s = 1, 2, ..: a missing link falls
+    back to the target's own distance.  The ranks are decided on D exactly as linkpred_ranks decides on d_0 (same tie rule);
+    the filter ``index`` is the TARGET's sampling.TrueTailIndex.  One member with weight 1 is linkpred_ranks bit for bit.
+    No [B, N] matrix and no permuted table copies exist: the kernel reads supporting rows through the link maps."""
+    arr, keep, N, d, nl, nrel = _link_members(members, "linkpred_ranks_ensemble")
+    dev = members[0][0][0].device
+    h = _query_column(e_index, N, "e_index", dev)
+    r = _query_column(r_index, nrel, "r_index", dev)
+    g = _query_column(gold, N, "gold", dev)
+    B = h.numel()
+    if r.numel() != B or g.numel() != B:
+        raise ValueError("e_index, r_index and gold must have one entry per query")
+    rank = torch.empty(B, dtype=torch.int32, device=dev)
+    L = lib()
+    ws_bytes = int(L.jmac_linkpred_ens_rank_workspace_bytes(B, d, nl, len(members)))
+    ws = workspace(ws_bytes, dev)
+    ix, _keep_ix = _tail_index(index, dev)
+    check(L.jmac_linkpred_ens_rank_f32(arr, len(members), nl, ptr(h), ptr(r), 1 if pred_head else 0, ptr(g), ix, B, N, d, ptr(rank),
+                                       ptr(ws), ws_bytes, stream()), "jmac_linkpred_ens_rank_f32")
+    return rank
+
+
+def linkpred_topk_ensemble(members, e_index, r_index, k: int, index=None, pred_head: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """linkpred_topk on the cross-KG ensemble distance D of linkpred_ranks_ensemble: ``(idx int64 [B, k], D fp32 [B, k])``, the
+    k nearest target rows the target's ``index`` does not list, ascending (equal: lower index first), padded with
+    ``idx = -1, D = +inf``.  ``linkpred_ranks_ensemble(members, ..., gold=idx[:, j], index=index)`` is ``j + 1``."""
+    arr, keep, N, d, nl, nrel = _link_members(members, "linkpred_topk_ensemble")
+    dev = members[0][0][0].device
+    k = int(k)
+    if not 1 <= k <= 64 or k > N:
+        raise ValueError("linkpred_topk_ensemble: k must lie in [1, min(64, N)] (got %d, N = %d)" % (k, N))
+    h = _query_column(e_index, N, "e_index", dev)
+    r = _query_column(r_index, nrel, "r_index", dev)
+    B = h.numel()
+    if r.numel() != B:
+        raise ValueError("e_index and r_index must have one entry per query")
+    idx = torch.empty((B, k), dtype=torch.int32, device=dev)
+    val = torch.empty((B, k), dtype=torch.float32, device=dev)
+    L = lib()
+    ws_bytes = int(L.jmac_linkpred_ens_topk_workspace_bytes(B, N, d, nl, len(members), k))
+    ws = workspace(ws_bytes, dev)
+    ix, _keep_ix = _tail_index(index, dev)
+    check(L.jmac_linkpred_ens_topk_f32(arr, len(members), nl, ptr(h), ptr(r), 1 if pred_head else 0, ix, B, N, d, k, ptr(val), ptr(idx),
+                                       ptr(ws), ws_bytes, stream()), "jmac_linkpred_ens_topk_f32")
+    return idx.to(torch.int64), val
+
+
 def build_filter_csr(heads, rels, true_tail: Dict, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pack er_vocab[(h, r)] lists (src/validate.py:53; knowledgegraph.py:62-86) as CSR over the batch."""
     ptr_l, idx = [0], []
