@@ -1011,6 +1011,25 @@ int jmac_sample_completion_batch(const int64_t* triples, int64_t T, const int64_
                                  const int64_t* seed, int64_t* step, int64_t* batch_h, int64_t* batch_r, int64_t* batch_t,
                                  jmac_stream_t stream);
 
+/* The same batch with HARD negatives in front (BootEA's truncated sampling: --neg_sampling truncated, generate_neg_triples* with
+ * neighbor=, modules/train/batch.py:88-165): nbr[e * ldn + j], j < M, is the j-th neighbour of entity e (int32; any content).  Row b
+ * with triple (h, r, t) and true-tail slice F of (h, r):
+ *   lane l < M holds n_l = nbr[t * ldn + l] and is ELIGIBLE if n_l is in [0, num_ent), n_l is not in F (t itself is) and no j < l has
+ *   n_j == n_l; A = eligible lanes, want1 = min(n_hard, A).
+ *   Stage 1: candidate i = word i % 4 of philox4x32_10(counter = (b, lo32(step[0]), 0x80000000 | i / 4, hi32(step[0])), same key) --
+ *   the top bit keeps the stream apart from stage 2's -- m = word * M, s = m >> 32; the candidate is invalid if lo32(m) < 2^32 mod M,
+ *   if lane s is not eligible, or if s was accepted before; neg[b, 0..want1) = n_s of the first want1 valid candidates.
+ *   Stage 2: neg[b, want1..K) by jmac_sample_completion_batch's rule on its own counters (third word i / 4 from 0), a candidate
+ *   being invalid also when it equals a value stage 1 placed.
+ * Hence n_hard == 0, or a table with no eligible lane, gives jmac_sample_completion_batch's batch bit for bit.  Stage 2 exists
+ * because A < n_hard is ordinary (neighbours that are true tails; a short or repeating list) and the loss needs K negatives.
+ * 1 <= M <= 64, ldn >= M, 0 <= n_hard <= K (JMAC_EINVAL); everything else -- layout, seed, step, perm, the other checks and
+ * preconditions -- as above. */
+int jmac_sample_completion_batch_truncated(const int64_t* triples, int64_t T, const int64_t* perm, const int32_t* key_of_triple,
+                                           const int32_t* tail_ptr, const int32_t* tail_idx, int64_t num_ent, int64_t B, int64_t K,
+                                           const int32_t* nbr, int64_t ldn, int64_t M, int64_t n_hard, const int64_t* seed,
+                                           int64_t* step, int64_t* batch_h, int64_t* batch_r, int64_t* batch_t, jmac_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * torch_scatter-compatible primitives (replace the third-party calls at src/jmac_model.py:105 and
  * modules/helper/message_passing.py:24,28) so the UNMODIFIED reference layer can run on this library.

@@ -204,6 +204,8 @@ _SIGS = {
     "jmac_margin_loss_fwd_acc_f32": (C.c_int, [vp, i64, i64, vp, vp, vp, vp]),
     "jmac_margin_loss_bwd_f32": (C.c_int, [vp, i64, i64, vp, vp, vp, vp]),
     "jmac_sample_completion_batch": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "jmac_sample_completion_batch_truncated": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp,
+                                                         vp]),
     "jmac_scatter_sum_f32": (C.c_int, [vp, vp, i64, i64, i64, vp, vp]),
     "jmac_scatter_softmax_workspace_bytes": (sz, [i64, i64]),
     "jmac_scatter_softmax_f32": (C.c_int, [vp, vp, i64, i64, i64, vp, vp, sz, vp]),

@@ -14,6 +14,12 @@
 // round); the values accepted so far live one per lane (slot s in lane s) and are read with v_readlane; repeats inside a round
 // are resolved in lane order; __ballot + mbcnt give every valid lane its slot.  At DBP-5L size (K = 25 of 11 805 entities) one
 // round serves practically every row (it would take 40 invalid candidates of 64).  ~150 B read and (K + 1) * 24 B written per row: the launch is latency-bound.
+//
+// The truncated form (jmac_sample_completion_batch_truncated; BootEA's hard negatives, modules/train/batch.py:88-165 with neighbor=)
+// is the same kernel with a first stage in front: lane l < M holds neighbour l of the gold tail (nbr[t, l]) and is ELIGIBLE if
+// that id is in range, is not a true tail of (h, r) and does not repeat a lower lane's; the first min(n_hard, eligible) slots are a
+// uniform draw without replacement from the eligible lanes over a stream of their own (third counter word 0x80000000 | i / 4: the
+// candidate is a lane number, Lemire's rejection over M), and the stage above fills the rest, skipping what stage 1 placed.
 #include "common.h"
 
 using namespace jmac;
@@ -36,12 +42,16 @@ __device__ __forceinline__ int nth_set_bit(uint64_t mask, int n) {
     return pos;
 }
 
+// kHard: stage 1 from the neighbour table in front of the uniform fill; false compiles the plain sampler, nbr .. n_hard unread
+template <bool kHard>
 __global__ __launch_bounds__(kBlock) void sample_batch_kernel(const int64_t* __restrict__ triples, int64_t T,
                                                               const int64_t* __restrict__ perm,
                                                               const int32_t* __restrict__ key_of_triple,
                                                               const int32_t* __restrict__ tail_ptr,
                                                               const int32_t* __restrict__ tail_idx, uint32_t num_ent,
                                                               uint32_t lemire_thr, int64_t B, int K,
+                                                              const int32_t* __restrict__ nbr, int64_t ldn, uint32_t M,
+                                                              uint32_t nbr_thr, int n_hard,
                                                               const int64_t* __restrict__ seed, const int64_t* __restrict__ step,
                                                               int64_t* __restrict__ batch_h, int64_t* __restrict__ batch_r,
                                                               int64_t* __restrict__ batch_t) {
@@ -69,6 +79,58 @@ __global__ __launch_bounds__(kBlock) void sample_batch_kernel(const int64_t* __r
 
     int acc = -1;                                                         // lane s: the value placed in slot s
     int placed = 0;
+    if constexpr (kHard) {
+        // eligible lanes: an id in range that is no true tail of (h, r) (the gold tail and the row's own entry of an inner-product
+        // table go here) and repeats no lower lane's.  A <= allowed, so want1 <= want; A >= want1 ends the loop below.
+        const int nl = lane < (int)M ? nbr[t * ldn + lane] : -1;
+        bool elig = lane < (int)M && (uint32_t)nl < num_ent;
+        if (elig) {
+            int a = lo, e = hi;
+            while (a < e) {
+                const int mid = (a + e) >> 1;
+                if (tail_idx[mid] < nl) a = mid + 1;
+                else e = mid;
+            }
+            elig = !(a < hi && tail_idx[a] == nl);
+        }
+        for (int j = 0; j + 1 < (int)M; ++j) {
+            const int nj = bcast_i(nl, j);
+            elig = elig && !(j < lane && nj == nl);
+        }
+        const uint64_t emask = __ballot(elig);
+        const int A = __popcll(emask);
+        const int want1 = n_hard < A ? n_hard : A;
+        uint64_t used = 0;                                                // lanes accepted so far
+        for (uint32_t round = 0; placed < want1; ++round) {
+            const uint4 w4 = philox4x32_10(make_uint4((uint32_t)b, (uint32_t)draws, 0x80000000u | (round * 16u + (uint32_t)(lane >> 2)),
+                                                      (uint32_t)(draws >> 32)), key);
+            const int q = lane & 3;
+            const uint32_t word = q == 0 ? w4.x : q == 1 ? w4.y : q == 2 ? w4.z : w4.w;
+            const uint64_t m = (uint64_t)word * (uint64_t)M;
+            const int s = (int)(m >> 32);                                 // < M
+            const int c = __shfl(nl, s, 64);
+            bool valid = (uint32_t)m >= nbr_thr && ((emask & ~used) >> s & 1ull);
+            const int se = valid ? s : -1;
+            bool taken = false;                                           // my lane number was drawn in this round
+#pragma unroll 8
+            for (int j = 0; j < 64; ++j) {                                // repeats inside the round, in lane order
+                const int sj = bcast_i(se, j);
+                valid = valid && !(j < lane && sj == s);
+                taken = taken || sj == lane;
+            }
+            used |= __ballot(taken);
+            const uint64_t mask = __ballot(valid);
+            const int before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            if (valid && placed + before < want1) neg[placed + before] = (int64_t)c;
+            const int n = __popcll(mask);
+            const int mine = lane - placed;
+            const int src = (mine >= 0 && mine < n) ? nth_set_bit(mask, mine) : lane;
+            const int got = __shfl(c, src, 64);
+            if (mine >= 0 && mine < n) acc = got;
+            placed += n;
+        }
+        placed = want1;                                                   // a last round's surplus sits in lanes >= want1: rewritten
+    }                                                                     // below before `placed` reaches them
     for (uint32_t round = 0; placed < want; ++round) {
         const uint4 w4 = philox4x32_10(make_uint4((uint32_t)b, (uint32_t)draws, round * 16u + (uint32_t)(lane >> 2), (uint32_t)(draws >> 32)), key);
         const int q = lane & 3;
@@ -125,9 +187,28 @@ int jmac_sample_completion_batch(const int64_t* triples, int64_t T, const int64_
     const uint32_t n = (uint32_t)num_ent;
     const uint32_t thr = (uint32_t)(0u - n) % n;                          // 2^32 mod num_ent
     const unsigned grid = (unsigned)((B + kBlock / 64 - 1) / (kBlock / 64));
-    hipLaunchKernelGGL(sample_batch_kernel, dim3(grid), dim3(kBlock), 0, st, triples, T, perm, key_of_triple, tail_ptr, tail_idx,
-                       n, thr, B, (int)K, seed, (const int64_t*)step, batch_h, batch_r, batch_t);
+    hipLaunchKernelGGL(sample_batch_kernel<false>, dim3(grid), dim3(kBlock), 0, st, triples, T, perm, key_of_triple, tail_ptr, tail_idx,
+                       n, thr, B, (int)K, (const int32_t*)nullptr, (int64_t)0, 0u, 0u, 0, seed, (const int64_t*)step, batch_h, batch_r,
+                       batch_t);
     // every wave above has read the step words before this runs (stream order): a captured launch advances on every replay
+    hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, st, step);
+    return (int)hipGetLastError();
+}
+
+int jmac_sample_completion_batch_truncated(const int64_t* triples, int64_t T, const int64_t* perm, const int32_t* key_of_triple,
+                                           const int32_t* tail_ptr, const int32_t* tail_idx, int64_t num_ent, int64_t B, int64_t K,
+                                           const int32_t* nbr, int64_t ldn, int64_t M, int64_t n_hard, const int64_t* seed,
+                                           int64_t* step, int64_t* batch_h, int64_t* batch_r, int64_t* batch_t, jmac_stream_t stream) {
+    if (K < 1 || K > 64 || B < 1 || T < B || num_ent < 1 || M < 1 || M > 64 || ldn < M || n_hard < 0 || n_hard > K) return JMAC_EINVAL;
+    if (num_ent >= ((int64_t)1 << 31) || B >= ((int64_t)1 << 31) || T >= ((int64_t)1 << 31)) return JMAC_ERANGE;
+    if (!triples || !perm || !key_of_triple || !tail_ptr || !tail_idx || !nbr || !seed || !step || !batch_h || !batch_r || !batch_t)
+        return JMAC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)num_ent, m = (uint32_t)M;
+    const unsigned grid = (unsigned)((B + kBlock / 64 - 1) / (kBlock / 64));
+    hipLaunchKernelGGL(sample_batch_kernel<true>, dim3(grid), dim3(kBlock), 0, st, triples, T, perm, key_of_triple, tail_ptr, tail_idx,
+                       n, (uint32_t)(0u - n) % n, B, (int)K, nbr, ldn, m, (uint32_t)(0u - m) % m, (int)n_hard, seed,
+                       (const int64_t*)step, batch_h, batch_r, batch_t);
     hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(1), 0, st, step);
     return (int)hipGetLastError();
 }

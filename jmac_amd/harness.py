@@ -19,7 +19,12 @@ Where the completion batches come from is ``args.neg_sampler``:
     "filtered"            ``sampling.CompletionSampler``: the reference's sampler (modules/load/data_loader.py:36-47: distinct
                           negatives, uniform over the entities that are not a true tail of (h, r)) as one launch per batch into
                           persistent buffers, one sampler per KG of the pair, rebuilt at every refresh.
-    ``args.capture_completion`` (with "filtered" only): after three eager steps the step zero_grad -> next_batch ->
+    "truncated"           the same sampler with BootEA's hard negatives in front (``--neg_sampling truncated``, modules/train/batch.py:
+                          88-165): at every refresh each KG of the pair gets the ``args.neg_neighbors`` (default 64) nearest entities
+                          of every entity under ``args.neg_metric`` (default "inner": ``find_neighbours``' product; ``args.sim_screen``
+                          is honoured) in a ``sampling.NeighborTable`` refreshed in place, and the first ``args.neg_hard`` (default:
+                          all ``num_negative``) negatives of a row come from its gold tail's row of that table.
+    ``args.capture_completion`` (with "filtered" / "truncated" only): after three eager steps the step zero_grad -> next_batch ->
                           completion_loss -> backward -> step is captured in a hipGraph once per (pair, side, refresh) and replayed
                           for the remaining batches of every epoch until the next refresh; the per-step losses land in a device
                           vector that is read once per epoch.  Needs an optimizer whose step captures (``jmac_amd.optim.Adam``,
@@ -34,7 +39,7 @@ import numpy as np
 import torch
 
 from . import entr, scoring
-from .sampling import CompletionSampler, TrueTailIndex
+from .sampling import CompletionSampler, NeighborTable, TrueTailIndex
 from .data import KnowledgeGraph
 from .model import JMAC
 
@@ -45,6 +50,7 @@ def make_args(dim=300, batch_size=1000, num_negative=25, device="cuda", entr_mat
              pair_sample_weight=0.2, lr=1e-3,                     # train.py:57-102 defaults for the fields used here
              eval_metric="cosine", eval_norm=False,              # the alignment evaluator's sim() (train.py:95-96, :112)
              neg_sampler="uniform", capture_completion=False,    # this harness' own: where the completion batches come from
+             neg_neighbors=64, neg_hard=None, neg_metric="inner",  # "truncated": table width, hard negatives per row, metric
              entr_matrix_free=entr_matrix_free)                   # EnTr refresh from scoring.alignment_stats (no N1 x N2 matrix)
     a.update(kw)
     return types.SimpleNamespace(**a)
@@ -78,15 +84,23 @@ def train_completion_component(model: JMAC, opt, ei1, et1, ei2, et2, feeddict, t
                                state: dict = None):
     """One completion epoch on a KG pair (train.py:328-364): every full batch of KG 1, then of KG 2.  ``state`` (optional): a
     dict that lives as long as the triple lists and graphs do (train_epoch: until the next refresh); the "filtered" mode keeps
-    its samplers and captured steps there and leaves the epoch's per-step losses (device, [steps]) under "step_losses"."""
+    its samplers and captured steps there and leaves the epoch's per-step losses (device, [steps]) under "step_losses".  The
+    "truncated" mode reads ``state["neighbors"]``, one ``NeighborTable`` per KG, or builds them from ``state["embeddings"]``, the
+    two KGs' entity embeddings ``[n1, d]`` / ``[n2, d]`` on the device (``neighbor_tables``)."""
     mode = getattr(args, "neg_sampler", "uniform")
-    if mode == "filtered":
-        return _train_completion_filtered(model, opt, ei1, et1, ei2, et2, feeddict, triples1, triples2, n1, n2, args, generator,
-                                          {} if state is None else state)
+    if mode in ("filtered", "truncated"):
+        state = {} if state is None else state
+        if mode == "truncated" and "neighbors" not in state:
+            if state.get("embeddings") is None:
+                raise ValueError("args.neg_sampler == 'truncated' needs the neighbour tables: pass state={'neighbors': (NeighborTable of "
+                                 "KG 1, NeighborTable of KG 2)} or state={'embeddings': (emb1 [n1, d], emb2 [n2, d])} (device tensors)")
+            state["neighbors"] = neighbor_tables(state["embeddings"], (n1, n2), args)
+        return _train_completion_filtered(model, opt, ei1, et1, ei2, et2, feeddict, triples1, triples2, n1, n2, args, generator, state)
     if mode != "uniform":
-        raise ValueError("args.neg_sampler must be 'uniform' or 'filtered' (got %r)" % (mode,))
+        raise ValueError("args.neg_sampler must be 'uniform', 'filtered' or 'truncated' (got %r)" % (mode,))
     if getattr(args, "capture_completion", False):
-        raise ValueError("args.capture_completion needs args.neg_sampler == 'filtered' (the uniform batches are new tensors every step)")
+        raise ValueError("args.capture_completion needs args.neg_sampler == 'filtered' or 'truncated' (the uniform batches are new "
+                         "tensors every step)")
     losses = []
     for triples, n_ent, source in ((triples1, n1, True), (triples2, n2, False)):
         for tr, neg in completion_batches(triples, n_ent, args.batch_size, args.num_negative, ei1.device, generator):
@@ -101,6 +115,16 @@ def train_completion_component(model: JMAC, opt, ei1, et1, ei2, et2, feeddict, t
     return float(torch.stack(losses).mean()) if losses else float("nan")
 
 
+def neighbor_tables(embeddings, num_ents, args, tables=None):
+    """One ``NeighborTable`` per KG for the "truncated" sampler, filled from the KG's entity embeddings (``generate_neighbours``);
+    ``tables``: an earlier call's result, refreshed in place (their buffers keep their addresses)."""
+    if tables is None:
+        tables = tuple(NeighborTable(n, getattr(args, "neg_neighbors", 64), e.device) for e, n in zip(embeddings, num_ents))
+    for t, e in zip(tables, embeddings):
+        t.refresh(e, getattr(args, "neg_metric", "inner"), getattr(args, "sim_screen", None))
+    return tables
+
+
 _CAPTURE_WARMUP = 3      # eager steps in front of a capture (bench.py:try_capture): real training steps of the epoch
 
 
@@ -109,9 +133,12 @@ def _train_completion_filtered(model, opt, ei1, et1, ei2, et2, feeddict, triples
     capture = bool(getattr(args, "capture_completion", False))
     sides = state.get("completion_sides")
     if sides is None:                                      # once per (pair, refresh): the CSR of the true tails, the batch buffers
+        hard = [{}, {}]
+        if getattr(args, "neg_sampler", "uniform") == "truncated":
+            hard = [{"neighbors": t, "n_hard": getattr(args, "neg_hard", None)} for t in state["neighbors"]]
         sides = state["completion_sides"] = [
-            {"sampler": CompletionSampler(tr, n, args.batch_size, args.num_negative, dev), "source": src, "graph": None}
-            for tr, n, src in ((triples1, n1, True), (triples2, n2, False)) if len(tr) >= args.batch_size]
+            {"sampler": CompletionSampler(tr, n, args.batch_size, args.num_negative, dev, **kw), "source": src, "graph": None}
+            for tr, n, src, kw in ((triples1, n1, True, hard[0]), (triples2, n2, False, hard[1])) if len(tr) >= args.batch_size]
     links = feeddict["links"]
     if len(links) and not (isinstance(links, torch.Tensor) and links.device == dev):
         # host seed links (train.py:190-193 hands out numpy arrays) would be uploaded by every step, which a stream capture
@@ -395,7 +422,7 @@ def train_epoch(model: JMAC, kgs: Dict[str, KnowledgeGraph], seeds_train: Dict[T
         if refresh or "feeddict" not in st:
             model.eval()
             with torch.no_grad():                      # train.py:450-451: get_emb once per KG of the pair -- one encoder pass here
-                (a1, _), (a2, _) = model.get_emb_blocks([(ei1, et1, eb1, rb1), (ei2, et2, eb2, rb2)])
+                (a1, c1), (a2, c2) = model.get_emb_blocks([(ei1, et1, eb1, rb1), (ei2, et2, eb2, rb2)])
                 o1, o2 = torch.from_numpy(a1).to(dev), torch.from_numpy(a2).to(dev)
             model.train()
             test_pairs = seeds_test.get((l1, l2), links)
@@ -409,7 +436,11 @@ def train_epoch(model: JMAC, kgs: Dict[str, KnowledgeGraph], seeds_train: Dict[T
             st["g1"] = entr.align_data_processing(new1, dev)           # train-mode graph: head <- tail, one direction
             st["g2"] = entr.align_data_processing(new2, dev)
             st["tr"] = (new1, new2)
+            tables = st.get("completion", {}).get("neighbors")
             st["completion"] = {}                                      # "filtered": samplers and captured steps of this refresh
+            if getattr(args, "neg_sampler", "uniform") == "truncated":  # the tables outlive it: refreshed in place, from the
+                comp = (torch.from_numpy(c1).to(dev), torch.from_numpy(c2).to(dev))      # normalised completion embeddings
+                st["completion"]["neighbors"] = neighbor_tables(comp, (kg1.num_entity, kg2.num_entity), args, tables)
         (ei1, et1), (ei2, et2) = st["g1"], st["g2"]
         closs = train_completion_component(model, opt_c, ei1, et1, ei2, et2, st["feeddict"], st["tr"][0], st["tr"][1],
                                            kg1.num_entity, kg2.num_entity, args, generator, state=st["completion"])

@@ -8,6 +8,10 @@ worker processes) and the ``repeat`` / ``cat`` of train.py:347-352:
     CompletionSampler   persistent batch buffers + ``jmac_sample_completion_batch`` (csrc/sample.hip): ``next_batch()`` is one
                         launch, no host read, and returns THE SAME tensors every time -- a step that starts with it captures
                         in a hipGraph and every replay trains on the next batch of the epoch
+    NeighborTable       ``generate_neighbours`` / ``find_neighbours`` (modules/train/batch.py:121-164): every entity's ``m`` nearest
+                        entities in one persistent int32 buffer, refreshed in place by the fused top-k; a sampler that is given
+                        one draws its first ``n_hard`` negatives from the gold tail's row (``--neg_sampling truncated``:
+                        ``jmac_sample_completion_batch_truncated``)
 
 The draw is the reference's distribution (uniform, without replacement, from the entities that are not a true tail of the
 row's ``(h, r)``) over a Philox stream of its own -- include/jmac_hip.h states it; tests/sampler_ref.py restates it in numpy.
@@ -17,7 +21,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._lib import check, lib, mark_index_range, ptr, require_device, stream
+from ._lib import check, check_index_range, lib, mark_index_range, ptr, require_device, stream, workspace
 
 
 class TrueTailIndex:
@@ -79,15 +83,85 @@ class TrueTailIndex:
         return int((p[1:] - p[:-1]).max())
 
 
+class NeighborTable:
+    """``idx`` int32 ``[num_ent, m]`` on the device: row e lists the ``m`` entities nearest to entity e, best first -- the
+    dictionary of ``generate_neighbours`` (modules/train/batch.py:121-164) as one buffer whose address never changes, so a
+    captured step that samples from it stays valid across refreshes.  Like the reference's list, a row computed by ``refresh``
+    contains the entity itself (its own nearest neighbour); the sampler never draws it for a gold tail t because t is a true
+    tail of the row's (h, r).  ``1 <= m <= min(64, num_ent)`` (the fused top-k's bound)."""
+
+    def __init__(self, num_ent: int, m: int, device):
+        self.num_ent, self.m = int(num_ent), int(m)
+        if not 1 <= self.num_ent < 1 << 31:
+            raise ValueError("NeighborTable: num_ent must lie in [1, 2^31)")
+        if not 1 <= self.m <= min(64, self.num_ent):
+            raise ValueError("NeighborTable: m must lie in [1, min(64, num_ent)] (got %d, num_ent = %d)" % (self.m, self.num_ent))
+        self.idx = torch.zeros((self.num_ent, self.m), dtype=torch.int32, device=torch.device(device))
+        self._val = None                                                   # 'manhattan': the L1 entry insists on a value output
+
+    @classmethod
+    def from_indices(cls, idx, device=None) -> "NeighborTable":
+        """A table from a caller's ``[num_ent, m]`` int32 / int64 array or tensor (entries in ``[0, num_ent)``: IndexError
+        otherwise).  Repeats inside a row are allowed: the kernel counts an entity once."""
+        if not isinstance(idx, torch.Tensor):
+            idx = torch.from_numpy(np.ascontiguousarray(np.asarray(idx)))
+        if idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError("NeighborTable.from_indices: an int32 / int64 [num_ent, m] array is expected (got %s %s)"
+                             % (idx.dtype, tuple(idx.shape)))
+        table = cls(idx.shape[0], idx.shape[1], idx.device if device is None else device)
+        check_index_range(idx, table.num_ent, "NeighborTable.from_indices")
+        table.idx.copy_(idx)
+        return table
+
+    def refresh(self, emb: torch.Tensor, metric: str = "inner", screen=None) -> "NeighborTable":
+        """Fill the table in place with the ``m`` nearest rows of ``emb`` ``[num_ent, d]`` (fp32, device) for every row of ``emb``.
+        ``"inner"``: largest inner product first, ``find_neighbours``' ``np.matmul`` (``jmac_sim_topk_f32``; ``screen="bf16"``: its
+        screened form, the same bits); ``"manhattan"``: smallest L1 distance first (``jmac_l1_csls_topk_f32`` without CSLS terms).
+        Ties -> lower index first.  The kernels write the int32 table itself: no host read, no copy."""
+        from .scoring import _check_screen, _rows16
+        if metric not in ("inner", "manhattan"):
+            raise ValueError("NeighborTable.refresh: metric must be 'inner' or 'manhattan' (got %r)" % (metric,))
+        _check_screen("NeighborTable.refresh", screen, metric)
+        if emb.dim() != 2 or emb.shape[0] != self.num_ent:
+            raise ValueError("NeighborTable.refresh: emb must be [%d, d] (got %s)" % (self.num_ent, tuple(emb.shape)))
+        require_device(emb, self.idx)
+        a = _rows16(emb.detach())
+        n, d = a.shape
+        L = lib()
+        if metric == "manhattan":
+            if self._val is None:
+                self._val = torch.empty((n, self.m), dtype=torch.float32, device=a.device)
+            ws_bytes = int(L.jmac_l1_csls_topk_workspace_bytes(n, n, d, self.m))
+            ws = workspace(ws_bytes, a.device)
+            check(L.jmac_l1_csls_topk_f32(ptr(a), d, ptr(a), d, n, n, d, None, None, self.m, ptr(self._val), ptr(self.idx), ptr(ws),
+                                          ws_bytes, stream()), "jmac_l1_csls_topk_f32")
+        elif screen is None:
+            ws_bytes = int(L.jmac_sim_topk_workspace_bytes(n, n, self.m))
+            ws = workspace(ws_bytes, a.device)
+            check(L.jmac_sim_topk_f32(ptr(a), d, ptr(a), d, n, n, d, self.m, None, ptr(self.idx), ptr(ws), ws_bytes, stream()),
+                  "jmac_sim_topk_f32")
+        else:
+            ws_bytes = int(L.jmac_sim_topk_screened_workspace_bytes(n, n, d, self.m))
+            ws = workspace(ws_bytes, a.device)
+            check(L.jmac_sim_topk_screened_f32(ptr(a), d, ptr(a), d, n, n, d, self.m, None, ptr(self.idx), None, ptr(ws), ws_bytes,
+                                               stream()), "jmac_sim_topk_screened_f32")
+        return self
+
+
 class CompletionSampler:
     """The batches of one KG's completion epochs (train.py:338-352), on the device.
 
     ``new_epoch(generator)`` draws the epoch's order; ``len(sampler)`` full batches follow (the ragged last batch is skipped:
     train.py:342-346); ``next_batch()`` returns ``{"batch_h", "batch_r", "batch_t"}`` for ``JMAC.completion_loss``, each
     int64 ``[B (K + 1)]``; ``neg`` is the ``[B, K]`` view of the negatives.  ``seed``: two int64 words (or one int: the second
-    word is 0) that key the Philox stream; None draws them from torch's generator of the device."""
+    word is 0) that key the Philox stream; None draws them from torch's generator of the device.
 
-    def __init__(self, triples, num_ent: int, batch_size: int, num_negative: int, device, seed=None):
+    ``neighbors`` (a ``NeighborTable`` of the same ``num_ent``): the first ``n_hard`` (default: all ``K``) negatives of a row
+    come from the gold tail's neighbours that are not a true tail, the rest from the uniform draw (include/jmac_hip.h,
+    jmac_sample_completion_batch_truncated; tests/trunc_sampler_ref.py).  The table is read at every launch: refresh it in place."""
+
+    def __init__(self, triples, num_ent: int, batch_size: int, num_negative: int, device, seed=None, neighbors: NeighborTable = None,
+                 n_hard: int = None):
         device = torch.device(device)
         tr = np.ascontiguousarray(np.asarray(triples.cpu() if isinstance(triples, torch.Tensor) else triples, dtype=np.int64).reshape(-1, 3))
         self.num_ent, self.B, self.K, self.T = int(num_ent), int(batch_size), int(num_negative), len(tr)
@@ -97,6 +171,14 @@ class CompletionSampler:
             raise ValueError("CompletionSampler: need 1 <= batch_size <= len(triples) (got %d, %d)" % (self.B, self.T))
         if not 1 <= self.num_ent < 1 << 31:
             raise ValueError("CompletionSampler: num_ent must lie in [1, 2^31)")
+        if neighbors is None and n_hard is not None:
+            raise ValueError("CompletionSampler: n_hard needs a NeighborTable (neighbors=)")
+        self.neighbors, self.n_hard = neighbors, self.K if n_hard is None else int(n_hard)
+        if neighbors is not None:
+            if neighbors.num_ent != self.num_ent:
+                raise ValueError("CompletionSampler: the NeighborTable covers %d entities, the sampler %d" % (neighbors.num_ent, self.num_ent))
+            if not 0 <= self.n_hard <= self.K:
+                raise ValueError("CompletionSampler: n_hard must lie in [0, num_negative] (got %d)" % self.n_hard)
         if tr[:, [0, 2]].min() < 0 or tr[:, [0, 2]].max() >= self.num_ent or tr[:, 1].min() < 0:   # the reference: IndexError
             raise IndexError("CompletionSampler: triple ids out of range: entities in [%d, %d], valid range [0, %d); relations >= %d"
                              % (tr[:, [0, 2]].min(), tr[:, [0, 2]].max(), self.num_ent, tr[:, 1].min()))
@@ -106,6 +188,8 @@ class CompletionSampler:
             raise ValueError("CompletionSampler: a (head, relation) with %d true tails leaves fewer than num_negative = %d of the "
                              "%d entities" % (self.index.longest(), self.K, self.num_ent))
         require_device(self.triples)                            # the batches are built by a kernel: there is no CPU path
+        if neighbors is not None and neighbors.idx.device != self.triples.device:
+            raise ValueError("CompletionSampler: the NeighborTable lives on %s, the sampler on %s" % (neighbors.idx.device, self.triples.device))
         n = self.B * (self.K + 1)
         # The kernel rewrites these three in place on every launch WITHOUT bumping their _version.  Nothing on the completion path
         # caches on their identity or version: losses._PAIR_INDEX keys on the link columns only, model._link_columns on the links
@@ -152,6 +236,13 @@ class CompletionSampler:
                 raise StopIteration
             self._served += 1
         ix = self.index
+        if self.neighbors is not None:
+            nb = self.neighbors
+            check(lib().jmac_sample_completion_batch_truncated(
+                ptr(self.triples), self.T, ptr(self.perm), ptr(ix.key_of_triple), ptr(ix.tail_ptr), ptr(ix.tail_idx), self.num_ent,
+                self.B, self.K, ptr(nb.idx), nb.idx.stride(0), nb.m, self.n_hard, ptr(self.seed), ptr(self.step), ptr(self.batch_h),
+                ptr(self.batch_r), ptr(self.batch_t), stream()), "jmac_sample_completion_batch_truncated")
+            return self._batch
         check(lib().jmac_sample_completion_batch(ptr(self.triples), self.T, ptr(self.perm), ptr(ix.key_of_triple), ptr(ix.tail_ptr),
                                                  ptr(ix.tail_idx), self.num_ent, self.B, self.K, ptr(self.seed), ptr(self.step),
                                                  ptr(self.batch_h), ptr(self.batch_r), ptr(self.batch_t), stream()),
