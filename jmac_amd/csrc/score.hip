@@ -31,7 +31,14 @@ constexpr int kBlock = 256;
 static_assert(TK_THREADS == kBlock, "the selection routines stride by the block size");
 
 // ------------------------------------------------------------------------------------------------
-// L1 score: 64x64 output tile per block, 4x4 per thread, K staged 16 at a time (transposed in LDS)
+// The L1 (Manhattan) tile family: 64x64 output tile per block, 4x4 per thread, K staged 16 at a time (transposed in LDS).
+// Three kernels -- l1_score_kernel (one table), link_rank_tile_kernel (the layers of one KG) and link_ens_tile_kernel (members x
+// layers, candidate rows read through link maps) -- are assembled from ONE set of pieces, so a pair (b, n) gets the same bits
+// wherever it is evaluated:
+//   l1_load, l1_stage, l1_step   a thread's operand quad from global memory, its transposed copy in LDS, one 16-deep slab
+//   l1_slab_loop                 the double-buffered loop; a kernel passes in where slab s's operands come from
+//   l1_epi_store / l1_epi_append / l1_epi_count   the epilogues, on the 4x4 values a thread decides on
+//   l1_seq_sum                   the same sum for ONE pair: the one-lane-per-candidate sites (prep, select, gold kernels)
 // ------------------------------------------------------------------------------------------------
 constexpr int L1_T = 64, L1_K = 16, L1_LD = L1_T + 4;
 
@@ -51,95 +58,161 @@ __device__ __forceinline__ float add_absdiff(float acc, float a, float b) {
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return __uint_as_float((uint32_t)(*p) << 16); }
 
-// TT = float or bf16_t (raw bits): bf16 operands are widened when they are staged into LDS, the |a-b| accumulation
-// is fp32 either way (the kernel is VALU-bound, so the narrower tables change the bytes, not the time)
+// where a thread stands in its block's tile: it owns outputs (b0 + ty * 4 + i, n0 + tx * 4 + j) and loads one quad (4 consecutive
+// k from lk) of row lrow of either operand
+struct L1Pos {
+    int b0, n0, tx, ty, lrow, lk;
+};
+__device__ __forceinline__ L1Pos l1_pos(int b0, int n0, int tid = threadIdx.x) {
+    return L1Pos{b0, n0, tid & 15, tid >> 4, tid >> 2, (tid & 3) * 4};
+}
+// threadIdx.x, opaque to the compiler (an empty asm, no instruction): what is derived from it is computed where it is used.
+// Without this the compiler forms a later phase's lane-dependent values ahead of a loop and holds them in VGPRs across it.
+// This steers one compiler's register allocation, nothing else: the figures next to its uses are hipcc 7.2 (AMD clang 22) for
+// gfx950, profiles/l1_tile_refactor_resources.txt is the table to regenerate under another compiler, and the code is correct
+// with or without it.  link_ens_tile_kernel does not need it: its 96-100 VGPRs are what it took written out in full.
+__device__ __forceinline__ int tid_again() {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    return tid;
+}
+// the same position for the epilogue: its indices are then formed after the slab loop (2-3 VGPRs in the append forms)
+__device__ __forceinline__ L1Pos l1_pos_again(const L1Pos& p) { return l1_pos(p.b0, p.n0, tid_again()); }
+
+// Elements k .. k + 3 of a row (k = slab offset + lk).  TT = float or bf16_t (raw bits): bf16 operands are widened here, the
+// |a - b| accumulation is fp32 either way (the kernels are VALU-bound, so the narrower tables change the bytes, not the time).
+// Every global load is UNCONDITIONAL at a clamped address: a load behind an exec-mask branch gets its s_waitcnt inside the branch
+// (hipcc), i.e. the next slab's prefetch would be waited for before the current slab's arithmetic instead of after it.  So `row`
+// is always a row of the table -- a row past the end is clamped by the caller to one that exists, ok = false, and only feeds
+// outputs that are never stored -- and a k quad past d re-reads the last quad; l1_stage zeroes both.
+// VEC = false (d % 4 != 0, or a base or leading dimension that rules 4-element loads out): the scalar form, zeros where VEC pads.
+template <typename TT, bool VEC>
+__device__ __forceinline__ float4 l1_load(const TT* base, int64_t ld, int64_t row, bool ok, int k, int d) {
+    if constexpr (VEC) return cvt4(ldraw(base + row * ld + (k < d ? k : d - 4)));
+    float4 v = f4zero();
+    if (ok) {
+        const TT* p = base + row * ld;
+        if (k + 0 < d) v.x = ld1(p + k + 0);
+        if (k + 1 < d) v.y = ld1(p + k + 1);
+        if (k + 2 < d) v.z = ld1(p + k + 2);
+        if (k + 3 < d) v.w = ld1(p + k + 3);
+    }
+    return v;
+}
+// ... into one LDS buffer, transposed; keep = the row exists and the quad lies inside d
+template <bool VEC>
+__device__ __forceinline__ void l1_stage(float (*S)[L1_LD], float4 v, const L1Pos& p, bool keep) {
+    if (VEC && !keep) v = f4zero();                              // the clamped loads' padding: |0 - 0| adds nothing
+    S[p.lk + 0][p.lrow] = v.x;
+    S[p.lk + 1][p.lrow] = v.y;
+    S[p.lk + 2][p.lrow] = v.z;
+    S[p.lk + 3][p.lrow] = v.w;
+}
+// acc[i][j] += sum over the slab's 16 k, in order, of |A[k][ty * 4 + i] - B[k][tx * 4 + j]|
+__device__ __forceinline__ void l1_step(float (&acc)[4][4], const float (*As)[L1_LD], const float (*Bs)[L1_LD], const L1Pos& p) {
+#pragma unroll
+    for (int k = 0; k < L1_K; ++k) {
+        const float4 a = *reinterpret_cast<const float4*>(&As[k][p.ty * 4]);
+        const float4 b = *reinterpret_cast<const float4*>(&Bs[k][p.tx * 4]);
+        const float av[4] = {a.x, a.y, a.z, a.w};
+        const float bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = add_absdiff(acc[i][j], av[i], bv[j]);
+    }
+}
+// acc += slabs 0 .. ns-1, double-buffered: slab s + 1 is loaded before slab s's arithmetic and staged after it.
+// src(s, ra, rb) loads the thread's two quads of slab s and returns the slab's k offset.
+template <bool VEC, class Src>
+__device__ __forceinline__ void l1_slab_loop(float (&acc)[4][4], float (&As)[2][L1_K][L1_LD], float (&Bs)[2][L1_K][L1_LD],
+                                             const L1Pos& p, int ns, int d, bool a_ok, bool b_ok, Src src) {
+    float4 ra, rb;
+    src(0, ra, rb);
+    l1_stage<VEC>(As[0], ra, p, a_ok && p.lk < d);
+    l1_stage<VEC>(Bs[0], rb, p, b_ok && p.lk < d);
+    __syncthreads();
+    for (int s = 0; s < ns; ++s) {
+        const int cur = s & 1;
+        int k0 = 0;
+        if (s + 1 < ns) k0 = src(s + 1, ra, rb);
+        l1_step(acc, As[cur], Bs[cur], p);
+        if (s + 1 < ns) {
+            l1_stage<VEC>(As[cur ^ 1], ra, p, a_ok && k0 + p.lk < d);
+            l1_stage<VEC>(Bs[cur ^ 1], rb, p, b_ok && k0 + p.lk < d);
+        }
+        __syncthreads();
+    }
+}
+
+// acc + |a[0] - b[0]| + ... + |a[d-1] - b[d-1]|, one add after the other.  This IS a tile kernel's order of additions for one
+// output element (its zero padding adds exact zeros; a caller with layers carries acc from one layer into the next), so every
+// one-lane-per-pair site has the tile's bits.  QUAD (the prep kernels, whose B lanes each run the whole chain out of LDS): four
+// pairs are loaded at a time -- the loads are independent, the adds are not -- which takes 2 more VGPRs than the plain loop.
+template <bool QUAD = false, typename TA, typename TB>
+__device__ __forceinline__ float l1_seq_sum(float acc, const TA* a, const TB* b, int d) {
+    int k = 0;
+    if constexpr (QUAD)
+        for (; k + 4 <= d; k += 4) {
+            const float a0 = ld1(a + k), a1 = ld1(a + k + 1), a2 = ld1(a + k + 2), a3 = ld1(a + k + 3);
+            const float b0 = ld1(b + k), b1 = ld1(b + k + 1), b2 = ld1(b + k + 2), b3 = ld1(b + k + 3);
+            acc = add_absdiff(acc, a0, b0);
+            acc = add_absdiff(acc, a1, b1);
+            acc = add_absdiff(acc, a2, b2);
+            acc = add_absdiff(acc, a3, b3);
+        }
+    for (; k < d; ++k) acc = add_absdiff(acc, ld1(a + k), ld1(b + k));
+    return acc;
+}
+
+// store epilogue: out[b * ld + n - n_off] = v, 16 bytes at a time where the quad is whole and aligned; row(i, v) fills v[0..3] with
+// the values of the thread's output row i
+template <class Row>
+__device__ __forceinline__ void l1_epi_store(Row row, const L1Pos& p, int B, int N, float* out, int64_t ld, int n_off) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int b = p.b0 + p.ty * 4 + i;
+        if (b >= B) continue;
+        const int n = p.n0 + p.tx * 4;
+        float* o = out + (int64_t)b * ld + (n - n_off);
+        float v[4];
+        row(i, v);
+        if (n + 3 < N && (ld % 4 == 0) && (n_off % 4 == 0)) st4(o, make_float4(v[0], v[1], v[2], v[3]));
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (n + j < N) o[j] = v[j];
+        }
+    }
+}
+
 template <typename TT, bool VEC>
 __global__ __launch_bounds__(kBlock) void l1_score_kernel(const TT* __restrict__ er, int64_t lder,
                                                           const TT* __restrict__ tab, int64_t ldt, int B, int N, int d,
                                                           float* __restrict__ out, int64_t ldout, int accumulate) {
     __shared__ __attribute__((aligned(16))) float As[2][L1_K][L1_LD];
     __shared__ __attribute__((aligned(16))) float Bs[2][L1_K][L1_LD];
-    const int tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-    const int b0 = blockIdx.y * L1_T, n0 = blockIdx.x * L1_T;
-    // loader mapping: one float4 (4 consecutive k) of one row per thread and per operand
-    const int lrow = tid >> 2, lk = (tid & 3) * 4;
-    const int64_t arow = b0 + lrow, brow = n0 + lrow;
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-    // Every global load is UNCONDITIONAL at a clamped address: a load behind an exec-mask branch gets its s_waitcnt
-    // inside the branch (hipcc), i.e. the next slab's prefetch would be waited for before the current slab's arithmetic
-    // instead of after it.  Rows past the end re-read the last row (they only feed outputs that are never stored); k
-    // quads past d re-read the last quad and are zeroed when they are written to LDS.  (d % 4 != 0: scalar tail form.)
-    constexpr bool vec = VEC;                    // d % 4 == 0 (the launcher picks the instantiation)
-    auto gload = [&](const TT* base, int64_t ld, int64_t row, int64_t nrows, int k0) -> float4 {
-        const int k = k0 + lk;
-        if constexpr (vec) {
-            const int64_t r = row < nrows ? row : nrows - 1;
-            return cvt4(ldraw(base + r * ld + (k < d ? k : d - 4)));
-        }
-        float4 v = f4zero();
-        if (row < nrows) {
-            if (k + 3 < d) v = cvt4(ldraw(base + row * ld + k));
-            else {
-                const TT* p = base + row * ld;
-                if (k + 0 < d) v.x = ld1(p + k + 0);
-                if (k + 1 < d) v.y = ld1(p + k + 1);
-                if (k + 2 < d) v.z = ld1(p + k + 2);
-            }
-        }
-        return v;
-    };
-    auto sstore = [&](float (*S)[L1_LD], float4 v, int k0, bool row_ok) {
-        if (vec && !(row_ok && k0 + lk < d)) v = f4zero();          // the clamped loads' padding: |0 - 0| adds nothing
-        S[lk + 0][lrow] = v.x;
-        S[lk + 1][lrow] = v.y;
-        S[lk + 2][lrow] = v.z;
-        S[lk + 3][lrow] = v.w;
-    };
-    const int nk = (d + L1_K - 1) / L1_K;
-    float4 ra = gload(er, lder, arow, B, 0), rb = gload(tab, ldt, brow, N, 0);
-    sstore(As[0], ra, 0, arow < B);
-    sstore(Bs[0], rb, 0, brow < N);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < nk) {
-            ra = gload(er, lder, arow, B, (kt + 1) * L1_K);
-            rb = gload(tab, ldt, brow, N, (kt + 1) * L1_K);
-        }
-#pragma unroll
-        for (int k = 0; k < L1_K; ++k) {
-            const float4 a = *reinterpret_cast<const float4*>(&As[cur][k][ty * 4]);
-            const float4 b = *reinterpret_cast<const float4*>(&Bs[cur][k][tx * 4]);
-            const float av[4] = {a.x, a.y, a.z, a.w};
-            const float bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = add_absdiff(acc[i][j], av[i], bv[j]);
-        }
-        if (kt + 1 < nk) {
-            sstore(As[cur ^ 1], ra, (kt + 1) * L1_K, arow < B);
-            sstore(Bs[cur ^ 1], rb, (kt + 1) * L1_K, brow < N);
-        }
-        __syncthreads();
-    }
+    const L1Pos p = l1_pos(blockIdx.y * L1_T, blockIdx.x * L1_T);
+    const bool a_ok = p.b0 + p.lrow < B, b_ok = p.n0 + p.lrow < N;
+    const int64_t arow = a_ok ? p.b0 + p.lrow : B - 1, brow = b_ok ? p.n0 + p.lrow : N - 1;
+    float acc[4][4] = {};
+    l1_slab_loop<VEC>(acc, As, Bs, p, (d + L1_K - 1) / L1_K, d, a_ok, b_ok, [&](int s, float4& ra, float4& rb) {
+        ra = l1_load<TT, VEC>(er, lder, arow, a_ok, s * L1_K + p.lk, d);
+        rb = l1_load<TT, VEC>(tab, ldt, brow, b_ok, s * L1_K + p.lk, d);
+        return s * L1_K;
+    });
+    // the store epilogue in its accumulate form, this kernel's alone: through l1_epi_store the bf16 vector form takes 56 VGPRs, not 54
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int64_t b = b0 + ty * 4 + i;
+        const int64_t b = p.b0 + p.ty * 4 + i;
         if (b >= B) continue;
-        const int64_t n = n0 + tx * 4;
+        const int64_t n = p.n0 + p.tx * 4;
         float* o = out + b * ldout + n;
         if (n + 3 < N && (ldout % 4 == 0)) {
             float4 v = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
             if (accumulate) {
-                const float4 p = ld4(o);
-                v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
+                const float4 q = ld4(o);
+                v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
             }
             st4(o, v);
         } else {
@@ -189,8 +262,8 @@ __global__ __launch_bounds__(kBlock) void filtered_rank_kernel(const float* __re
 //   dist[b, n] = sum over layers l, then k, of |(E_l[h_b] +/- R_l[r_b])[k] - T_l[n, k]|   (ONE running fp32 sum, in that order)
 //   rank[b]    = 1 + #{n : dist[b, n] before dist[b, gold_b]} - #{filtered n != gold : ... before ...}
 // "before" = smaller, or equal with the lower index (jmac_filtered_rank_f32).  Two launches: the prep kernel builds the
-// query rows, the gold distances and the filter correction; the tile kernel is the L1 score kernel with a layer loop around
-// its slab loop and a compare-and-count epilogue (integer atomics: order-independent) instead of the [B, N] store.
+// query rows, the gold distances and the filter correction; the tile kernel is the L1 tile body over layer-major slabs with
+// a compare-and-count epilogue (integer atomics: order-independent) instead of the [B, N] store.
 // ------------------------------------------------------------------------------------------------
 constexpr int LR_MAX_LAYERS = 4;
 struct LinkRankArgs {
@@ -256,19 +329,128 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float x) {
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16_t* p, float v) { *p = f32_to_bf16_rne(v); }
 
-// one block per query: (1) its rows er_l = E_l[h] +/- R_l[r] (rounded to TT) -> workspace and LDS; (2) the listed candidates
-// (the gold first, then the filter entries), LR_ROWS at a time: their table rows are staged into LDS with coalesced loads, then
-// one lane per candidate runs the SAME sequential sum the tile kernel runs (bit-identical distances: exact ties resolve by
-// index as in the materialised path); (3) rank[b] starts at 1 - #{filtered entries before the gold}
-// INDEXED: the filter range comes from the known-tail index -- wave 0 searches (h_b, r_b), the block reads the range from LDS.
-// RANK = false (top-k): only (1) and the lookup, whose range goes to a.rng[b].
+// The epilogues below decide on 4x4 values that a tile kernel hands over one row at a time: row(i, v) fills v[0..3] with the values
+// of output row i (computing them inside the row loop keeps 4, not 16, of them live beside the accumulators).
+// append epilogue: (v, n) goes to row b's candidate list where v >= ntau[b] and extra(i, j, v) holds.  The 16 lanes of a row claim
+// their slots with ONE integer atomic (list order varies from run to run; the select kernel sorts, so the results do not).
+template <class Row, class Extra>
+__device__ __forceinline__ void l1_epi_append(Row row, const L1Pos& p, const LinkRankArgs& a, Extra extra) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int b = p.b0 + p.ty * 4 + i;
+        const bool row_ok = b < a.B;
+        const float nt = row_ok ? a.ntau[(int64_t)b * a.tau_stride] : INFINITY;
+        bool pass[4];
+        float v[4];
+        row(i, v);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            pass[j] = row_ok && p.n0 + p.tx * 4 + j < a.N && v[j] >= nt;
+            pass[j] = pass[j] && extra(i, j, v[j]);
+            c += pass[j] ? 1 : 0;
+        }
+        if (!__any(c)) continue;                              // wave-uniform: most tiles append nothing
+        int inc = c;                                          // inclusive prefix over the row's 16 lanes
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            const int t = __shfl_up(inc, o, 16);
+            if (p.tx >= o) inc += t;
+        }
+        const int tot = __shfl(inc, 15, 16);
+        int base = 0;
+        if (p.tx == 0 && tot) base = atomicAdd(a.cnt + b, tot);
+        base = __shfl(base, 0, 16);
+        int slot = base + inc - c;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (pass[j]) {
+                if (slot < a.cap) {
+                    a.cval[(int64_t)b * a.cap + slot] = v[j];
+                    a.cidx[(int64_t)b * a.cap + slot] = p.n0 + p.tx * 4 + j;
+                }
+                ++slot;
+            }
+    }
+}
+
+// count epilogue: rank[b] += #{n : v(b, n) before gs[b]}, "before" = smaller (LARGER: larger), or equal with an index below gold_b.
+// 4 rows x 4 columns per thread; the 16 threads of a row (tx = 0..15: consecutive lanes) are summed with DPP; integer atomics.
+template <bool LARGER, class Row>
+__device__ __forceinline__ void l1_epi_count(Row row, const L1Pos& p, const LinkRankArgs& a) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int b = p.b0 + p.ty * 4 + i;
+        const bool row_ok = b < a.B;
+        const float gs = row_ok ? a.gs[b] : 0.f;
+        const int g = row_ok ? a.gold[b] : 0;
+        float v[4];
+        row(i, v);
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = p.n0 + p.tx * 4 + j;
+            const float sc = v[j];
+            c += (row_ok && n < a.N && ((LARGER ? sc > gs : sc < gs) || (sc == gs && n < g))) ? 1 : 0;
+        }
+        c += __shfl_xor(c, 1);
+        c += __shfl_xor(c, 2);
+        c += __shfl_xor(c, 4);
+        c += __shfl_xor(c, 8);
+        if (p.tx == 0 && row_ok && c) atomicAdd(a.rank + b, c);
+    }
+}
+
+// The prep kernels' walk over query b's listed candidates -- entry 0 the gold g, then the filter entries [f0, f1) -- a.rows at a
+// time: rank[b] starts at 1 - #{filtered entries before the gold}, gs[b] = the gold's value.  value(nc, cand) is called by the whole
+// block once cand[0, nc) is visible and may use barriers; lane t < nc returns the value of candidate cand[t] (-1: a skipped entry,
+// any value will do) with the tile kernel's bits, so exact ties resolve by index as in the materialised path.
 constexpr int LR_ROWS = 16;                        // at most; fewer when nl * d is large (60 KB of LDS)
-template <typename TT, bool INDEXED, bool RANK = true>
-__global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) {
-    extern __shared__ float lr_sh[];                // [nl*dq] query rows (widened) + [LR_ROWS][nl*dq + 1] candidate rows
+template <class Value>
+__device__ __forceinline__ void link_prep_walk(const LinkRankArgs& a, int b, int g, int f0, int f1, Value value) {
     __shared__ float gs_sh;
     __shared__ int cand[LR_ROWS];
     __shared__ int red[kBlock / 64];
+    const int n_list = 1 + (f1 - f0);               // entry 0 = the gold
+    float gs = 0.f;
+    int cnt = 0;
+    for (int c0 = 0; c0 < n_list; c0 += a.rows) {
+        const int nc = min(a.rows, n_list - c0);
+        __syncthreads();                            // previous chunk consumed; the caller's own LDS rows complete
+        if (threadIdx.x < nc) {
+            const int c = c0 + threadIdx.x;
+            int n = c == 0 ? g : a.filt_idx[f0 + c - 1];
+            if (c > 0 && (n == g || n < 0 || n >= a.N)) n = -1;      // skipped entries (as jmac_filtered_rank_f32)
+            cand[threadIdx.x] = n;
+        }
+        __syncthreads();
+        const float sc = value(nc, cand);
+        if (c0 == 0 && threadIdx.x == 0) gs_sh = sc;
+        __syncthreads();
+        gs = gs_sh;
+        if (threadIdx.x < nc && !(c0 == 0 && threadIdx.x == 0)) {
+            const int n = cand[threadIdx.x];
+            if (n >= 0) cnt += (sc < gs || (sc == gs && n < g)) ? 1 : 0;
+        }
+    }
+    cnt = wave_sum_i(cnt);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
+        a.gs[b] = gs;
+        a.rank[b] = 1 - t;
+    }
+}
+
+// one block per query: (1) its rows er_l = E_l[h] +/- R_l[r] (rounded to TT) -> workspace and LDS; (2) link_prep_walk over the
+// listed candidates: their table rows are staged into LDS with coalesced loads, then one lane per candidate runs l1_seq_sum.
+// INDEXED: the filter range comes from the known-tail index -- wave 0 searches (h_b, r_b), the block reads the range from LDS.
+// RANK = false (top-k): only (1) and the lookup, whose range goes to a.rng[b].
+template <typename TT, bool INDEXED, bool RANK = true>
+__global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) {
+    extern __shared__ float lr_sh[];                // [nl*dq] query rows (widened) + [LR_ROWS][nl*dq + 1] candidate rows
     __shared__ int2 rng_sh;
     const int b = blockIdx.x, d = a.d, dq = a.dq, W = a.nl * dq, WS = W + 1;
     float* const erow = lr_sh;
@@ -299,19 +481,7 @@ __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) 
         if (threadIdx.x == 0) a.rng[b] = make_int2(f0, f1);
         return;
     }
-    const int n_list = 1 + (f1 - f0);               // entry 0 = the gold
-    float gs = 0.f;
-    int cnt = 0;
-    for (int c0 = 0; c0 < n_list; c0 += a.rows) {
-        const int nc = min(a.rows, n_list - c0);
-        __syncthreads();                            // previous chunk consumed; erow complete
-        if (threadIdx.x < nc) {
-            const int c = c0 + threadIdx.x;
-            int n = c == 0 ? g : a.filt_idx[f0 + c - 1];
-            if (c > 0 && (n == g || n < 0 || n >= a.N)) n = -1;      // skipped entries (as jmac_filtered_rank_f32)
-            cand[threadIdx.x] = n;
-        }
-        __syncthreads();
+    link_prep_walk(a, b, g, f0, f1, [&](int nc, const int* cand) -> float {
         for (int i = threadIdx.x; i < nc * W; i += kBlock) {
             const int rI = i / W, q = i - rI * W, l = q / dq, k = q - l * dq;
             const int n = cand[rI];
@@ -320,269 +490,77 @@ __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) 
             crow[rI * WS + q] = v;
         }
         __syncthreads();
-        if (threadIdx.x < nc) {
-            const float* row = crow + threadIdx.x * WS;
-            float acc = 0.f;
-            for (int l = 0; l < a.nl; ++l) {
-                int k = 0;
-                for (; k + 4 <= d; k += 4) {
-                    const float e0 = erow[l * dq + k], e1 = erow[l * dq + k + 1], e2 = erow[l * dq + k + 2], e3 = erow[l * dq + k + 3];
-                    const float t0 = row[l * dq + k], t1 = row[l * dq + k + 1], t2 = row[l * dq + k + 2], t3 = row[l * dq + k + 3];
-                    acc = add_absdiff(acc, e0, t0);
-                    acc = add_absdiff(acc, e1, t1);
-                    acc = add_absdiff(acc, e2, t2);
-                    acc = add_absdiff(acc, e3, t3);
-                }
-                for (; k < d; ++k) acc = add_absdiff(acc, erow[l * dq + k], row[l * dq + k]);
-            }
-            if (c0 == 0 && threadIdx.x == 0) gs_sh = acc;
-            crow[threadIdx.x * WS] = acc;           // parked for the compare below (row data no longer needed)
-        }
-        __syncthreads();
-        gs = gs_sh;
-        if (threadIdx.x < nc && !(c0 == 0 && threadIdx.x == 0)) {
-            const int n = cand[threadIdx.x];
-            const float sc = crow[threadIdx.x * WS];
-            if (n >= 0) cnt += (sc < gs || (sc == gs && n < g)) ? 1 : 0;
-        }
-    }
-    cnt = wave_sum_i(cnt);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
-        a.gs[b] = gs;
-        a.rank[b] = 1 - t;
-    }
+        float acc = 0.f;
+        const int t = tid_again();                  // (the lane's row address is formed here, not held across the chunk loop)
+        if (t < nc)
+            for (int l = 0; l < a.nl; ++l) acc = l1_seq_sum<true>(acc, erow + l * dq, crow + t * WS + l * dq, d);
+        return acc;
+    });
 }
 
-// the L1 score tile kernel over the concatenated (layer, k) axis.  One slab loop, three epilogues:
+// the tile body over one KG's concatenated (layer, k) axis, with these epilogues:
 //   LR_COUNT   count the entries that rank before the gold                                   (jmac_linkpred_rank_*)
 //   LR_STORE   S[b, n - n_off] = -dist[b, n]: the column sample (or the whole narrow matrix)  (jmac_linkpred_topk_*)
-//   LR_FILTER  append (-dist, n) where dist <= tau_b to row b's candidate list; the 16 lanes of a row claim their slots with
-//              ONE integer atomic (list order varies from run to run; the select kernel sorts, so the results do not)
+//   LR_FILTER  append (-dist, n) where dist <= tau_b to row b's candidate list
 // STORE and FILTER cover columns [n_off, N).
-// The same epilogues on the Manhattan alignment value c = csls_value(1 - dist, r1, r2), larger first (jmac_l1_csls_*; what
-// sim_gemm_kernel's SG_CSLS_* epilogues are to the cosine similarity):
+// The same epilogues on the Manhattan alignment value c = csls_value(1 - dist, r1, r2), or s = 1 - dist when r1 == NULL, larger
+// first (jmac_l1_csls_*; what sim_gemm_kernel's SG_CSLS_* epilogues are to the cosine similarity):
 //   LR_CSLS_COUNT   count the columns whose c beats gs[b] = c(b, gold_b): larger, or equal with an index below gold_b
 //   LR_CSLS_FILTER  append (c, n) where c >= tau_b
 //   LR_CSLS_VIABLE  ... and tk_pack(c, row_id[b]) > best[n]: the suitor would displace what reviewer n holds
 enum { LR_COUNT = 0, LR_STORE = 1, LR_FILTER = 2, LR_CSLS_COUNT = 3, LR_CSLS_FILTER = 4, LR_CSLS_VIABLE = 5 };
-template <typename TT, bool VEC, int EPI = LR_COUNT>
-__global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) {
-    __shared__ __attribute__((aligned(16))) float As[2][L1_K][L1_LD];
-    __shared__ __attribute__((aligned(16))) float Bs[2][L1_K][L1_LD];
-    const int tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-    const int B = a.B, N = a.N, d = a.d;
-    const int b0 = blockIdx.y * L1_T, n0 = (EPI == LR_COUNT ? 0 : a.n_off) + blockIdx.x * L1_T;
-    const int lrow = tid >> 2, lk = (tid & 3) * 4;
-    const int64_t arow = b0 + lrow, brow = n0 + lrow;
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-    constexpr bool vec = VEC;
-    // unconditional clamped loads, zeroed when staged (see l1_score_kernel)
-    auto gload = [&](const TT* base, int64_t ld, int64_t row, int64_t nrows, int k0) -> float4 {
-        const int k = k0 + lk;
-        if constexpr (vec) {
-            const int64_t r = row < nrows ? row : nrows - 1;
-            return cvt4(ldraw(base + r * ld + (k < d ? k : d - 4)));
-        }
-        float4 v = f4zero();
-        if (row < nrows) {
-            const TT* p = base + row * ld;
-            if (k + 0 < d) v.x = ld1(p + k + 0);
-            if (k + 1 < d) v.y = ld1(p + k + 1);
-            if (k + 2 < d) v.z = ld1(p + k + 2);
-            if (k + 3 < d) v.w = ld1(p + k + 3);
-        }
-        return v;
-    };
-    auto sstore = [&](float (*S)[L1_LD], float4 v, int k0, bool row_ok) {
-        if (vec && !(row_ok && k0 + lk < d)) v = f4zero();
-        S[lk + 0][lrow] = v.x;
-        S[lk + 1][lrow] = v.y;
-        S[lk + 2][lrow] = v.z;
-        S[lk + 3][lrow] = v.w;
-    };
-    const int nk = (d + L1_K - 1) / L1_K, ns = a.nl * nk;      // slabs: layer-major, k inside
-    const TT* const er = static_cast<const TT*>(a.er);
-    auto slab = [&](int s, float4& ra, float4& rb) {
-        const int l = s / nk, k0 = (s - l * nk) * L1_K;
-        ra = gload(er + (int64_t)l * B * a.dq, a.dq, arow, B, k0);
-        rb = gload(static_cast<const TT*>(a.tab[l]), a.ld_tab[l], brow, N, k0);
-    };
-    float4 ra, rb;
-    slab(0, ra, rb);
-    sstore(As[0], ra, 0, arow < B);
-    sstore(Bs[0], rb, 0, brow < N);
-    __syncthreads();
-    for (int s = 0; s < ns; ++s) {
-        const int cur = s & 1;
-        if (s + 1 < ns) slab(s + 1, ra, rb);
-#pragma unroll
-        for (int k = 0; k < L1_K; ++k) {
-            const float4 av4 = *reinterpret_cast<const float4*>(&As[cur][k][ty * 4]);
-            const float4 bv4 = *reinterpret_cast<const float4*>(&Bs[cur][k][tx * 4]);
-            const float av[4] = {av4.x, av4.y, av4.z, av4.w};
-            const float bv[4] = {bv4.x, bv4.y, bv4.z, bv4.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = add_absdiff(acc[i][j], av[i], bv[j]);
-        }
-        if (s + 1 < ns) {
-            const int l1 = (s + 1) / nk, k1 = (s + 1 - l1 * nk) * L1_K;
-            sstore(As[cur ^ 1], ra, k1, arow < B);
-            sstore(Bs[cur ^ 1], rb, k1, brow < N);
-        }
-        __syncthreads();
-    }
-    if constexpr (EPI == LR_STORE) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + ty * 4 + i;
-            if (b >= B) continue;
-            const int n = n0 + tx * 4;
-            float* o = a.S + (int64_t)b * a.ldS + (n - a.n_off);
-            if (n + 3 < N && (a.ldS % 4 == 0) && (a.n_off % 4 == 0)) st4(o, make_float4(-acc[i][0], -acc[i][1], -acc[i][2], -acc[i][3]));
-            else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (n + j < N) o[j] = -acc[i][j];
-            }
-        }
-        return;
-    }
-    if constexpr (EPI == LR_FILTER) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + ty * 4 + i;
-            const bool row_ok = b < B;
-            const float nt = row_ok ? a.ntau[(int64_t)b * a.tau_stride] : INFINITY;
-            bool pass[4];
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pass[j] = row_ok && n0 + tx * 4 + j < N && -acc[i][j] >= nt;
-                c += pass[j] ? 1 : 0;
-            }
-            if (!__any(c)) continue;                          // wave-uniform: most tiles append nothing
-            int inc = c;                                      // inclusive prefix over the row's 16 lanes
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const int t = __shfl_up(inc, o, 16);
-                if (tx >= o) inc += t;
-            }
-            const int tot = __shfl(inc, 15, 16);
-            int base = 0;
-            if (tx == 0 && tot) base = atomicAdd(a.cnt + b, tot);
-            base = __shfl(base, 0, 16);
-            int slot = base + inc - c;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (pass[j]) {
-                    if (slot < a.cap) {
-                        a.cval[(int64_t)b * a.cap + slot] = -acc[i][j];
-                        a.cidx[(int64_t)b * a.cap + slot] = n0 + tx * 4 + j;
-                    }
-                    ++slot;
-                }
-        }
-        return;
-    }
+
+// the epilogue EPI on a tile's distances: it decides on dist (COUNT), -dist (STORE, FILTER) or the alignment value (LR_CSLS_*)
+template <int EPI>
+__device__ __forceinline__ void l1_epilogue(const float (&dist)[4][4], const L1Pos& p, const LinkRankArgs& a) {
     constexpr bool CSLS = EPI >= LR_CSLS_COUNT;
-    // alignment: the decided value of acc[i][j] is c, or s when there are no terms (cs is block-uniform)
-    const bool cs = CSLS && a.r1 != nullptr;
+    const bool cs = CSLS && a.r1 != nullptr;                   // block-uniform
     float r2v[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (CSLS)
         if (cs) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) r2v[j] = a.r2[min(n0 + tx * 4 + j, N - 1)];
+            for (int j = 0; j < 4; ++j) r2v[j] = a.r2[min(p.n0 + p.tx * 4 + j, a.N - 1)];
         }
-    auto decided = [&](float dist, float r1b, int j) -> float {
-        const float s = 1.f - dist;
-        return cs ? csls_value(s, r1b, r2v[j]) : s;
-    };
-    if constexpr (EPI == LR_CSLS_FILTER || EPI == LR_CSLS_VIABLE) {
-        unsigned long long bw[4] = {0ull, 0ull, 0ull, 0ull};
-        if constexpr (EPI == LR_CSLS_VIABLE) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bw[j] = a.best[min(n0 + tx * 4 + j, N - 1)];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + ty * 4 + i;
-            const bool row_ok = b < B;
-            const float nt = row_ok ? a.ntau[(int64_t)b * a.tau_stride] : INFINITY;
-            const float r1b = (cs && row_ok) ? a.r1[b] : 0.f;
-            int rid = 0;
-            if constexpr (EPI == LR_CSLS_VIABLE) rid = row_ok ? a.row_id[b] : 0;
-            bool pass[4];
-            float v[4];
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[j] = decided(acc[i][j], r1b, j);
-                pass[j] = row_ok && n0 + tx * 4 + j < N && v[j] >= nt;
-                if constexpr (EPI == LR_CSLS_VIABLE) pass[j] = pass[j] && tk_pack(v[j], rid) > bw[j];
-                c += pass[j] ? 1 : 0;
-            }
-            if (!__any(c)) continue;                          // the LR_FILTER append, with c for -dist
-            int inc = c;                                      // inclusive prefix over the row's 16 lanes
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const int t = __shfl_up(inc, o, 16);
-                if (tx >= o) inc += t;
-            }
-            const int tot = __shfl(inc, 15, 16);
-            int base = 0;
-            if (tx == 0 && tot) base = atomicAdd(a.cnt + b, tot);
-            base = __shfl(base, 0, 16);
-            int slot = base + inc - c;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (pass[j]) {
-                    if (slot < a.cap) {
-                        a.cval[(int64_t)b * a.cap + slot] = v[j];
-                        a.cidx[(int64_t)b * a.cap + slot] = n0 + tx * 4 + j;
-                    }
-                    ++slot;
-                }
-        }
-        return;
-    }
-    // count: 4 rows x 4 columns per thread; the 16 threads of a row (tx = 0..15: consecutive lanes) are summed with DPP
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int b = b0 + ty * 4 + i;
-        const bool row_ok = b < B;
-        const float gs = row_ok ? a.gs[b] : 0.f;
-        const int g = row_ok ? a.gold[b] : 0;
-        const float r1b = (cs && row_ok) ? a.r1[b] : 0.f;
-        int c = 0;
+    auto row = [&](int i, float (&v)[4]) {
+        float r1b = 0.f;
+        if constexpr (CSLS) r1b = (cs && p.b0 + p.ty * 4 + i < a.B) ? a.r1[p.b0 + p.ty * 4 + i] : 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int n = n0 + tx * 4 + j;
-            if constexpr (CSLS) {
-                const float sc = decided(acc[i][j], r1b, j);
-                c += (row_ok && n < N && (sc > gs || (sc == gs && n < g))) ? 1 : 0;
-            } else {
-                const float sc = acc[i][j];
-                c += (row_ok && n < N && (sc < gs || (sc == gs && n < g))) ? 1 : 0;
-            }
+            if constexpr (CSLS) v[j] = cs ? csls_value(1.f - dist[i][j], r1b, r2v[j]) : 1.f - dist[i][j];
+            else v[j] = EPI == LR_COUNT ? dist[i][j] : -dist[i][j];
         }
-        c += __shfl_xor(c, 1);
-        c += __shfl_xor(c, 2);
-        c += __shfl_xor(c, 4);
-        c += __shfl_xor(c, 8);
-        if (tx == 0 && row_ok && c) atomicAdd(a.rank + b, c);
-    }
+    };
+    if constexpr (EPI == LR_STORE) l1_epi_store(row, p, a.B, a.N, a.S, a.ldS, a.n_off);
+    else if constexpr (EPI == LR_FILTER || EPI == LR_CSLS_FILTER) l1_epi_append(row, p, a, [](int, int, float) { return true; });
+    else if constexpr (EPI == LR_CSLS_VIABLE) {
+        unsigned long long bw[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bw[j] = a.best[min(p.n0 + p.tx * 4 + j, a.N - 1)];
+        l1_epi_append(row, p, a, [&](int i, int j, float c) {
+            const int b = p.b0 + p.ty * 4 + i;
+            return tk_pack(c, b < a.B ? a.row_id[b] : 0) > bw[j];
+        });
+    } else l1_epi_count<CSLS>(row, p, a);
+}
+
+template <typename TT, bool VEC, int EPI = LR_COUNT>
+__global__ __launch_bounds__(kBlock) void link_rank_tile_kernel(LinkRankArgs a) {
+    __shared__ __attribute__((aligned(16))) float As[2][L1_K][L1_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[2][L1_K][L1_LD];
+    const int B = a.B, N = a.N, d = a.d;
+    const L1Pos p = l1_pos(blockIdx.y * L1_T, (EPI == LR_COUNT ? 0 : a.n_off) + blockIdx.x * L1_T);
+    const bool a_ok = p.b0 + p.lrow < B, b_ok = p.n0 + p.lrow < N;
+    const int64_t arow = a_ok ? p.b0 + p.lrow : B - 1, brow = b_ok ? p.n0 + p.lrow : N - 1;
+    const int nk = (d + L1_K - 1) / L1_K;                      // slabs: layer-major, k inside
+    const TT* const er = static_cast<const TT*>(a.er);
+    float acc[4][4] = {};
+    l1_slab_loop<VEC>(acc, As, Bs, p, a.nl * nk, d, a_ok, b_ok, [&](int s, float4& ra, float4& rb) {
+        const int l = s / nk, k0 = (s - l * nk) * L1_K;
+        ra = l1_load<TT, VEC>(er + (int64_t)l * B * a.dq, a.dq, arow, a_ok, k0 + p.lk, d);
+        rb = l1_load<TT, VEC>(static_cast<const TT*>(a.tab[l]), a.ld_tab[l], brow, b_ok, k0 + p.lk, d);
+        return k0;
+    });
+    l1_epilogue<EPI>(acc, l1_pos_again(p), a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1480,12 +1458,9 @@ __global__ __launch_bounds__(kBlock) void row_topk_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------
 // (sim_tile_32x32 and for_each_row_score, the recomputation itself: sim_rescore.h -- screen.hip rescores with them too)
 
-// s(m, n) = 1 - dist(m, n) of ONE pair of rows with link_rank_tile_kernel's sum: the single running fp32 sum over k = 0 .. d-1 of
-// |a[k] - b[k]| (the tile's zero padding adds exact zeros), so the bits are the tile's.  One lane per pair.
+// s(m, n) = 1 - dist(m, n) of ONE pair of rows (l1_seq_sum).  One lane per pair.
 __device__ __forceinline__ float l1_row_sim(const float* __restrict__ arow, const float* __restrict__ brow, int d) {
-    float acc = 0.f;
-    for (int q = 0; q < d; ++q) acc = add_absdiff(acc, arow[q], brow[q]);
-    return 1.f - acc;
+    return 1.f - l1_seq_sum(0.f, arow, brow, d);
 }
 template <class F>
 __device__ __forceinline__ void for_each_row_l1(const float* __restrict__ arow, const float* __restrict__ Bm, int64_t ldb, int N,
@@ -1498,8 +1473,7 @@ __device__ __forceinline__ void for_each_row_l1(const float* __restrict__ arow, 
 // VIABLE (jmac_sim_csls_topk_viable_f32): the lists hold viable columns only; the sample's k best may end in masked (-inf)
 // entries and a recomputed row skips the columns whose word best[n] the row's own word tk_pack(c, row_id[b]) does not beat;
 // what is missing of the k comes out as (idx -1, val -inf).  CS is then decided at run time (r1 != NULL).
-// L1 (jmac_l1_csls_topk_*): the Manhattan form -- a recomputed score is s = 1 - dist from the L1 tile kernel's sequential sum
-// (l1_row_sim), CS decided at run time
+// L1 (jmac_l1_csls_topk_*): the Manhattan form -- a recomputed score is s = 1 - dist (l1_row_sim), CS decided at run time
 template <bool CS, bool VIABLE, bool L1 = false>
 __device__ __forceinline__ void cand_select_body(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                  int64_t ldb, int N, int d, int k, const int* __restrict__ cnt,
@@ -1616,8 +1590,8 @@ __global__ __launch_bounds__(kBlock) void viable_topk_finish_kernel(const float*
 }
 
 // ---- Manhattan alignment (jmac_l1_csls_*): csls_gold_kernel / csls_inplace_kernel / viable_inplace_kernel for s = 1 - dist ----
-// gval[m] = c(m, gold[m]) from l1_row_sim (the tile kernel's bits: the count's "equal, lower index first" is exact at the gold
-// column itself); rank[m] = 1.  One lane per row.
+// gval[m] = c(m, gold[m]) from l1_row_sim (the count's "equal, lower index first" is exact at the gold column itself);
+// rank[m] = 1.  One lane per row.
 __global__ __launch_bounds__(kBlock) void l1_csls_gold_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
                                                               int64_t ldb, int M, int d, const float* __restrict__ r1,
                                                               const float* __restrict__ r2, const int32_t* __restrict__ gold,
@@ -1683,25 +1657,17 @@ __device__ __forceinline__ bool tail_listed(const int32_t* __restrict__ tail_idx
     return false;
 }
 
-// one block per query: the k best of (candidate list + the sample's k best), listed candidates dropped (the sample's were
-// masked before its selection).  Every unlisted n with dist <= tau_b is in that set and at least k of them exist (tau_b is
-// the k-th smallest unlisted SAMPLE distance), so its k best are the row's; a sample entry tied with tau_b outside the
-// sample's k best has k entries before it already.
+// The select kernels (one block per query), single-KG and ensemble: the k best of (candidate list + the sample's k best), listed
+// candidates dropped (the sample's were masked before its selection).  Every unlisted n with dist <= tau_b is in that set and at
+// least k of them exist (tau_b is the k-th smallest unlisted SAMPLE distance), so its k best are the row's; a sample entry tied
+// with tau_b outside the sample's k best has k entries before it already.
 // A row whose list overflowed (a constant table, a huge tie, or fewer than k unlisted sample entries: tau_b = +inf) recomputes
-// its N distances with the prep kernel's sequential sum -- the tile kernel's bits -- one lane per candidate, once per pass of
-// the two-pass selection and once per arg-max round if the top bin overflows too.  Slow by design, exact.
-template <typename TT>
-__global__ __launch_bounds__(kBlock) void link_select_kernel(LinkRankArgs a, int k, const float* __restrict__ sval,
-                                                             const int32_t* __restrict__ sidx, float* __restrict__ val,
-                                                             int32_t* __restrict__ idx) {
-    extern __shared__ float ls_sh[];                           // [nl * dq] the query's rows (overflow path)
-    __shared__ TkShared tk;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int2 r = a.rng[b];
-    const int32_t* const tails = a.filt_idx;
-    float* const ov = val + (int64_t)b * k;
-    int32_t* const oi = idx + (int64_t)b * k;
-    auto emit = [&](int c, unsigned long long e) {
+// its N distances (l1_seq_sum), one lane per candidate, once per pass of the two-pass selection and once per arg-max round if the
+// top bin overflows too.  Slow by design, exact.  The kernels differ in that recomputation only.
+struct LinkEmit {                                              // rank c of row b: (-dist, n) -> (dist, n)
+    float* ov;
+    int32_t* oi;
+    __device__ __forceinline__ void operator()(int c, unsigned long long e) const {
         if (e == 0ull) {                                       // padding: fewer than k unlisted candidates
             oi[c] = -1;
             ov[c] = INFINITY;
@@ -1710,21 +1676,36 @@ __global__ __launch_bounds__(kBlock) void link_select_kernel(LinkRankArgs a, int
         oi[c] = tk_unpack_index(e);
         const float v = tk_unpack_value(e);
         ov[c] = v == 0.f ? 0.f : -v;
-    };
-    const int C = a.cnt[b];
-    if (C + k <= a.cap) {                                      // the normal case (cap <= TK_CAP)
-        for (int c = tid; c < C; c += kBlock) {
-            const int n = a.cidx[(int64_t)b * a.cap + c];
-            tk.skey[c] = tail_listed(tails, r.x, r.y, n) ? 0ull : tk_pack(a.cval[(int64_t)b * a.cap + c], n);
-        }
-        for (int c = tid; c < k; c += kBlock) {
-            const float v = sval[(int64_t)b * k + c];
-            tk.skey[C + c] = v == -INFINITY ? 0ull : tk_pack(v, sidx[(int64_t)b * k + c]);
-        }
-        tk_sort_emit(tk.skey, C + k, k, emit);
-        return;
     }
-    // ---- overflow: the selection over recomputed distances
+};
+// the normal case (cap <= TK_CAP); false: the list overflowed and nothing was emitted
+__device__ __forceinline__ bool link_select_listed(const LinkRankArgs& a, int b, int2 r, int k, const float* __restrict__ sval,
+                                                   const int32_t* __restrict__ sidx, TkShared& tk, const LinkEmit& emit) {
+    const int tid = threadIdx.x;
+    const int C = a.cnt[b];
+    if (C + k > a.cap) return false;
+    for (int c = tid; c < C; c += kBlock) {
+        const int n = a.cidx[(int64_t)b * a.cap + c];
+        tk.skey[c] = tail_listed(a.filt_idx, r.x, r.y, n) ? 0ull : tk_pack(a.cval[(int64_t)b * a.cap + c], n);
+    }
+    for (int c = tid; c < k; c += kBlock) {
+        const float v = sval[(int64_t)b * k + c];
+        tk.skey[C + c] = v == -INFINITY ? 0ull : tk_pack(v, sidx[(int64_t)b * k + c]);
+    }
+    tk_sort_emit(tk.skey, C + k, k, emit);
+    return true;
+}
+
+template <typename TT>
+__global__ __launch_bounds__(kBlock) void link_select_kernel(LinkRankArgs a, int k, const float* __restrict__ sval,
+                                                             const int32_t* __restrict__ sidx, float* __restrict__ val,
+                                                             int32_t* __restrict__ idx) {
+    extern __shared__ float ls_sh[];                           // [nl * dq] the query's rows (overflow path)
+    __shared__ TkShared tk;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int2 r = a.rng[b];                                   // the query's listed tails
+    const LinkEmit emit{val + (int64_t)b * k, idx + (int64_t)b * k};
+    if (link_select_listed(a, b, r, k, sval, sidx, tk, emit)) return;
     const int d = a.d, dq = a.dq, W = a.nl * dq;
     for (int i = tid; i < W; i += kBlock) {
         const int l = i / dq, q = i - l * dq;
@@ -1732,13 +1713,10 @@ __global__ __launch_bounds__(kBlock) void link_select_kernel(LinkRankArgs a, int
     }
     auto for_each_unlisted = [&](auto f) {                      // f(n, -dist[b, n]) for every n in [0, N) the index does not list
         for (int n = tid; n < a.N; n += kBlock) {
-            if (tail_listed(tails, r.x, r.y, n)) continue;
+            if (tail_listed(a.filt_idx, r.x, r.y, n)) continue;
             float acc = 0.f;
-            for (int l = 0; l < a.nl; ++l) {
-                const TT* row = static_cast<const TT*>(a.tab[l]) + (int64_t)n * a.ld_tab[l];
-                const float* e = ls_sh + l * dq;
-                for (int q = 0; q < d; ++q) acc = add_absdiff(acc, e[q], ld1(row + q));
-            }
+            for (int l = 0; l < a.nl; ++l)
+                acc = l1_seq_sum(acc, ls_sh + l * dq, static_cast<const TT*>(a.tab[l]) + (int64_t)n * a.ld_tab[l], d);
             f(n, -acc);
         }
     };
@@ -2245,24 +2223,45 @@ static void launch_link_tile(const LinkRankArgs& a, bool vec, int64_t ncols, hip
     else hipLaunchKernelGGL((link_rank_tile_kernel<TT, false, EPI>), grid, dim3(kBlock), 0, st, a);
 }
 
-// what jmac_linkpred_rank_* and jmac_linkpred_topk_* fill of LinkRankArgs alike: sizes, layer tables, sign, queries and the known-tail
-// index.  vec: whether the tile kernel may take its vector form, which issues 4-element loads (16 B fp32, 8 B bf16) -- every table's
-// leading dimension AND base pointer must allow it
+// a jmac_tail_index_t an entry point may read
+static bool tail_index_ok(const jmac_tail_index_t* index) {
+    return index->n_keys >= 0 && index->n_keys < INT32_MAX && index->key && index->tail_ptr && index->tail_idx;
+}
+
+// what every link-prediction entry point, single-KG or ensemble, fills of LinkRankArgs alike: sizes, sign, queries and the index
+static void link_base_args(LinkRankArgs& a, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
+                           const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d) {
+    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
+    a.sign = pred_head ? -1.f : 1.f;
+    a.h = h; a.r = r;
+    if (index) {
+        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
+    }
+}
+
+// The prep kernels' LDS: the query's nl * dq words and a.rows candidate rows of one word more, within 60 KB.  false: not even one
+// candidate row fits (JMAC_ERANGE at every entry point; the top-k prep kernels stage nothing, but their select kernels do)
+static bool prep_lds(LinkRankArgs& a, size_t& shm) {
+    const int64_t W = (int64_t)a.nl * a.dq, words = 60 * 1024 / 4;
+    const int64_t rows = (words - W) / (W + 1);
+    if (rows < 1) return false;
+    a.rows = (int32_t)(rows < LR_ROWS ? rows : LR_ROWS);
+    shm = (size_t)(W + a.rows * (W + 1)) * sizeof(float);
+    return true;
+}
+
+// ... and of the single-KG ones: the layer tables.  vec: whether the tile kernel may take its vector form, which issues
+// 4-element loads (16 B fp32, 8 B bf16) -- every table's leading dimension AND base pointer must allow it
 template <typename TT>
 static int link_args(LinkRankArgs& a, bool& vec, const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
                      int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d) {
-    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
+    link_base_args(a, n_layers, h, r, pred_head, index, B, N, d);
     vec = d % 4 == 0;
     for (int l = 0; l < n_layers; ++l) {
         if (!layers[l].ent || !layers[l].rel || !layers[l].table) return JMAC_EINVAL;
         a.ent[l] = layers[l].ent; a.rel[l] = layers[l].rel; a.tab[l] = layers[l].table;
         a.ld_ent[l] = layers[l].ld_ent; a.ld_rel[l] = layers[l].ld_rel; a.ld_tab[l] = layers[l].ld_table;
         if (a.ld_tab[l] % 4 || ((uintptr_t)a.tab[l] % (4 * sizeof(TT)))) vec = false;
-    }
-    a.sign = pred_head ? -1.f : 1.f;
-    a.h = h; a.r = r;
-    if (index) {
-        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
     }
     return JMAC_OK;
 }
@@ -2274,7 +2273,7 @@ static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, c
     if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_layers > LR_MAX_LAYERS) return JMAC_EINVAL;
     if (B == 0) return JMAC_OK;
     if (!layers || !h || !r || !gold || !rank || (filt_ptr && !filt_idx)) return JMAC_EINVAL;
-    if (index && (index->n_keys < 0 || index->n_keys >= INT32_MAX || !index->key || !index->tail_ptr || !index->tail_idx)) return JMAC_EINVAL;
+    if (index && !tail_index_ok(index)) return JMAC_EINVAL;
     if (B >= INT32_MAX || N >= INT32_MAX || d > 512) return JMAC_ERANGE;
     if (!ws || ws_bytes < jmac_linkpred_rank_workspace_bytes(B, d, n_layers)) return JMAC_EWORKSPACE;
     LinkRankArgs a{};
@@ -2284,11 +2283,8 @@ static int launch_link_rank(const jmac_link_layer_t* layers, int32_t n_layers, c
     a.gs = (float*)ws;
     a.er = (char*)ws + align_up((size_t)B * 4);
     a.rank = rank;
-    const int64_t W = (int64_t)n_layers * a.dq, words = 60 * 1024 / 4;
-    int64_t rows = (words - W) / (W + 1);
-    if (rows < 1) return JMAC_ERANGE;
-    a.rows = (int32_t)(rows < LR_ROWS ? rows : LR_ROWS);
-    const size_t shm = (size_t)(W + a.rows * (W + 1)) * sizeof(float);
+    size_t shm;
+    if (!prep_lds(a, shm)) return JMAC_ERANGE;
     if (index) hipLaunchKernelGGL((link_rank_prep_kernel<TT, true>), dim3((unsigned)B), dim3(kBlock), shm, st, a);
     else hipLaunchKernelGGL((link_rank_prep_kernel<TT, false>), dim3((unsigned)B), dim3(kBlock), shm, st, a);
     launch_link_tile<TT, LR_COUNT>(a, vec, N, st);
@@ -2549,14 +2545,15 @@ static int launch_link_topk(const jmac_link_layer_t* layers, int32_t n_layers, c
     if (d > 512) return JMAC_EDIM;
     if (B == 0) return JMAC_OK;
     if (!layers || !h || !r || !val || !idx) return JMAC_EINVAL;
-    if (index && (index->n_keys < 0 || index->n_keys >= INT32_MAX || !index->key || !index->tail_ptr || !index->tail_idx)) return JMAC_EINVAL;
+    if (index && !tail_index_ok(index)) return JMAC_EINVAL;
     if (B >= INT32_MAX || N >= INT32_MAX) return JMAC_ERANGE;
     if (!ws || ws_bytes < jmac_linkpred_topk_workspace_bytes(B, N, d, n_layers, k)) return JMAC_EWORKSPACE;
     LinkRankArgs a{};
     bool vec;
     if (int rc = link_args<TT>(a, vec, layers, n_layers, h, r, pred_head, index, B, N, d)) return rc;
     const int64_t W = (int64_t)n_layers * a.dq;
-    if (W + 1 > 60 * 1024 / 4 - W) return JMAC_ERANGE;         // jmac_linkpred_rank_*'s LDS limit
+    size_t shm;                                                // unused: RANK = false stages only the W query words
+    if (!prep_lds(a, shm)) return JMAC_ERANGE;                 // jmac_linkpred_rank_*'s LDS limit
     const LtWs w = lt_layout(B, N, d, n_layers, k);
     char* wb = (char*)ws;
     a.er = wb + w.er;
@@ -2616,7 +2613,9 @@ int jmac_linkpred_topk_bf16(const jmac_link_layer_t* layers, int32_t n_layers, c
 // jmac_linkpred_rank_* / jmac_linkpred_topk_*'s, decided on D; the filter is the TARGET's known-tail index.  ens_fold below is
 // the ONE place D is formed -- prep kernel (gold and filter entries), tile kernel, select kernel's recompute -- so the j-th
 // prediction ranks j + 1 and two calls return identical bits; no float atomics, nothing depends on the grid or the CU count.
-// The single-KG kernels above are not touched: these are separate kernels (profiles/linkpred_ensemble_resources.txt).
+// These are kernels of their own (three accumulator sets: 96-102 VGPRs against the single-KG tile kernel's 56,
+// profiles/linkpred_ensemble_resources.txt) that share the single-KG kernels' body: slab loop, epilogues, sequential sum, prep walk
+// and select merge are the L1 tile family's pieces, called here with the members' sources.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -2645,16 +2644,12 @@ __device__ __forceinline__ int ens_row(const LinkEnsArgs& e, int g, int n) {
 }
 
 // link_rank_prep_kernel for the ensemble.  One block per query: (1) its head row and query rows in every member (rows of an
-// unlinked head are zero) -> workspace; (2) RANK: D of the gold and of the filter entries, a.rows at a time -- the members take
-// turns in the SAME LDS (their query rows, then the candidates' rows read through the link), one lane per candidate runs the
-// tile kernel's sequential sum and folds it into its D; (3) rank[b] starts at 1 - #{filtered entries before the gold}.
+// unlinked head are zero) -> workspace; (2) RANK: link_prep_walk on D -- the members take turns in the SAME LDS (their query
+// rows, then the candidates' rows read through the link), one lane per candidate runs l1_seq_sum and folds it into its D.
 template <bool INDEXED, bool RANK>
 __global__ __launch_bounds__(kBlock) void link_ens_prep_kernel(LinkEnsArgs e) {
     const LinkRankArgs& a = e.base;
     extern __shared__ float le_sh[];                // RANK: [nl*dq] query rows + [rows][nl*dq + 1] candidate rows, one member at a time
-    __shared__ float gs_sh;
-    __shared__ int cand[LR_ROWS];
-    __shared__ int red[kBlock / 64];
     __shared__ int2 rng_sh;
     const int b = blockIdx.x, d = a.d, dq = a.dq, W = a.nl * dq, WS = W + 1;
     const int hb = a.h[b], rb = a.r[b], g = RANK ? a.gold[b] : 0;
@@ -2687,22 +2682,11 @@ __global__ __launch_bounds__(kBlock) void link_ens_prep_kernel(LinkEnsArgs e) {
     }
     float* const erow = le_sh;
     float* const crow = le_sh + W;
-    const int n_list = 1 + (f1 - f0);               // entry 0 = the gold
-    float gs = 0.f;
-    int cnt = 0;
-    for (int c0 = 0; c0 < n_list; c0 += a.rows) {
-        const int nc = min(a.rows, n_list - c0);
-        __syncthreads();                            // previous chunk consumed
-        if (threadIdx.x < nc) {
-            const int c = c0 + threadIdx.x;
-            int n = c == 0 ? g : a.filt_idx[f0 + c - 1];
-            if (c > 0 && (n == g || n < 0 || n >= a.N)) n = -1;      // skipped entries (as jmac_filtered_rank_f32)
-            cand[threadIdx.x] = n;
-        }
+    link_prep_walk(a, b, g, f0, f1, [&](int nc, const int* cand) -> float {
         float D = 0.f, d0 = 0.f;
         for (int m = 0; m < e.ng; ++m) {
             const int hq = ens_row(e, m, hb);
-            __syncthreads();                        // cand complete; the previous member's rows consumed
+            if (m > 0) __syncthreads();             // the previous member's rows consumed
             for (int l = 0; l < a.nl; ++l)          // the thread that wrote an element above reads it back
                 for (int k = threadIdx.x; k < dq; k += kBlock) erow[l * dq + k] = er[(((int64_t)m * a.nl + l) * a.B + b) * dq + k];
             for (int i = threadIdx.x; i < nc * W; i += kBlock) {
@@ -2715,97 +2699,49 @@ __global__ __launch_bounds__(kBlock) void link_ens_prep_kernel(LinkEnsArgs e) {
             }
             __syncthreads();
             if (threadIdx.x < nc) {
-                const float* row = crow + threadIdx.x * WS;
                 float acc = 0.f;
-                for (int l = 0; l < a.nl; ++l)
-                    for (int k = 0; k < d; ++k) acc = add_absdiff(acc, erow[l * dq + k], row[l * dq + k]);
+                for (int l = 0; l < a.nl; ++l) acc = l1_seq_sum<true>(acc, erow + l * dq, crow + threadIdx.x * WS + l * dq, d);
                 const int n = cand[threadIdx.x];
                 const bool present = hq >= 0 && n >= 0 && ens_row(e, m, n) >= 0;
                 if (m == 0) d0 = acc;
                 D = ens_fold(D, e.w[m], m == 0 || present, acc, d0);
             }
         }
-        __syncthreads();                            // every lane has read its rows
-        if (threadIdx.x < nc) {
-            if (c0 == 0 && threadIdx.x == 0) gs_sh = D;
-            crow[threadIdx.x * WS] = D;             // parked for the compare below
-        }
-        __syncthreads();
-        gs = gs_sh;
-        if (threadIdx.x < nc && !(c0 == 0 && threadIdx.x == 0)) {
-            const int n = cand[threadIdx.x];
-            const float sc = crow[threadIdx.x * WS];
-            if (n >= 0) cnt += (sc < gs || (sc == gs && n < g)) ? 1 : 0;
-        }
-    }
-    cnt = wave_sum_i(cnt);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
-        a.gs[b] = gs;
-        a.rank[b] = 1 - t;
-    }
+        return D;
+    });
 }
 
-// link_rank_tile_kernel for the ensemble: the member loop OUTSIDE the layer / slab loop.  Member 0's sums are kept (d0), every
-// member's sums are folded into the total when its slabs end, and the COUNT / STORE / FILTER epilogues run on the total.
-// A supporting member's candidate rows are read THROUGH the link map: a thread loads link_s[n0 + lrow], then its 16-byte pieces of
-// that row; an absent link reads row 0 and is zeroed when staged, and its sums are never selected.  A tile in which member s has
-// no linked head or no linked candidate skips that member's slabs (the fold takes d0 for every pair: no bit changes); the
-// decision is block-uniform (__syncthreads_or).
+// link_rank_tile_kernel for the ensemble: the same body with the member loop OUTSIDE the layer / slab loop.  Member 0's sums are
+// kept (d0), every member's sums are folded into the total when its slabs end, and the COUNT / STORE / FILTER epilogues run on
+// the total.  A supporting member's candidate rows are read THROUGH the link map: a thread loads link_s[n0 + lrow], then its
+// 16-byte pieces of that row; an absent link reads row 0 and is zeroed when staged, and its sums are never selected.  A tile in
+// which member s has no linked head or no linked candidate skips that member's slabs (the fold takes d0 for every pair: no bit
+// changes); the decision is block-uniform (__syncthreads_or).
 template <bool VEC, int EPI>
 __global__ __launch_bounds__(kBlock) void link_ens_tile_kernel(LinkEnsArgs e) {
     const LinkRankArgs& a = e.base;
     __shared__ __attribute__((aligned(16))) float As[2][L1_K][L1_LD];
     __shared__ __attribute__((aligned(16))) float Bs[2][L1_K][L1_LD];
     __shared__ int qbits[L1_T], cbits[L1_T];        // bit g: the row's head / the column's candidate has a row in member g
-    const int tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
     const int B = a.B, N = a.N, d = a.d;
-    const int b0 = blockIdx.y * L1_T, n0 = (EPI == LR_COUNT ? 0 : a.n_off) + blockIdx.x * L1_T;
-    const int lrow = tid >> 2, lk = (tid & 3) * 4;
-    const int arow = b0 + lrow, brow = n0 + lrow;
+    const L1Pos p = l1_pos(blockIdx.y * L1_T, (EPI == LR_COUNT ? 0 : a.n_off) + blockIdx.x * L1_T);
+    const int arow = p.b0 + p.lrow, brow = p.n0 + p.lrow;
     const bool a_ok = arow < B, b_ok = brow < N;
     int qb = 0, cb = 0;
     for (int g = 0; g < e.ng; ++g) {
         qb |= (a_ok && e.hq[(int64_t)g * B + arow] >= 0) ? 1 << g : 0;
         cb |= (b_ok && ens_row(e, g, brow) >= 0) ? 1 << g : 0;
     }
-    if ((tid & 3) == 0) {
-        qbits[lrow] = qb;
-        cbits[lrow] = cb;
+    if (p.lk == 0) {
+        qbits[p.lrow] = qb;
+        cbits[p.lrow] = cb;
     }
     float acc[4][4], d0[4][4], tot[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = d0[i][j] = tot[i][j] = 0.f;
-    constexpr bool vec = VEC;
-    // row is a valid row of the table whether or not `ok` (clamped by the caller): the vector form loads unconditionally
-    auto gload = [&](const float* base, int64_t ld, int64_t row, bool ok, int k0) -> float4 {
-        const int k = k0 + lk;
-        if constexpr (vec) return ldraw(base + row * ld + (k < d ? k : d - 4));
-        float4 v = f4zero();
-        if (ok) {
-            const float* p = base + row * ld;
-            if (k + 0 < d) v.x = p[k + 0];
-            if (k + 1 < d) v.y = p[k + 1];
-            if (k + 2 < d) v.z = p[k + 2];
-            if (k + 3 < d) v.w = p[k + 3];
-        }
-        return v;
-    };
-    auto sstore = [&](float (*S)[L1_LD], float4 v, int k0, bool row_ok) {
-        if (!(row_ok && k0 + lk < d)) v = f4zero();
-        S[lk + 0][lrow] = v.x;
-        S[lk + 1][lrow] = v.y;
-        S[lk + 2][lrow] = v.z;
-        S[lk + 3][lrow] = v.w;
-    };
-    const int nk = (d + L1_K - 1) / L1_K, ns = a.nl * nk;      // slabs of one member: layer-major, k inside
+    const int nk = (d + L1_K - 1) / L1_K;                      // slabs of one member: layer-major, k inside
     const float* const er = static_cast<const float*>(a.er);
     const int64_t arow_c = a_ok ? arow : B - 1;
     for (int g = 0; g < e.ng; ++g) {
@@ -2815,177 +2751,53 @@ __global__ __launch_bounds__(kBlock) void link_ens_tile_kernel(LinkEnsArgs e) {
             const int cn = b_ok ? ens_row(e, g, brow) : -1;
             const bool c_ok = cn >= 0;
             const int64_t crow = c_ok ? cn : 0;
-            auto slab = [&](int s, float4& ra, float4& rb) {
+            l1_slab_loop<VEC>(acc, As, Bs, p, a.nl * nk, d, a_ok, c_ok, [&](int s, float4& ra, float4& rb) {
                 const int l = s / nk, k0 = (s - l * nk) * L1_K;
-                ra = gload(er + ((int64_t)g * a.nl + l) * B * a.dq, a.dq, arow_c, a_ok, k0);
-                rb = gload(e.tab[g][l], e.ld_tab[g][l], crow, c_ok, k0);
-            };
-            float4 ra, rb;
-            slab(0, ra, rb);
-            sstore(As[0], ra, 0, a_ok);
-            sstore(Bs[0], rb, 0, c_ok);
-            __syncthreads();
-            for (int s = 0; s < ns; ++s) {
-                const int cur = s & 1;
-                if (s + 1 < ns) slab(s + 1, ra, rb);
-#pragma unroll
-                for (int k = 0; k < L1_K; ++k) {
-                    const float4 av4 = *reinterpret_cast<const float4*>(&As[cur][k][ty * 4]);
-                    const float4 bv4 = *reinterpret_cast<const float4*>(&Bs[cur][k][tx * 4]);
-                    const float av[4] = {av4.x, av4.y, av4.z, av4.w};
-                    const float bv[4] = {bv4.x, bv4.y, bv4.z, bv4.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = add_absdiff(acc[i][j], av[i], bv[j]);
-                }
-                if (s + 1 < ns) {
-                    const int l1 = (s + 1) / nk, k1 = (s + 1 - l1 * nk) * L1_K;
-                    sstore(As[cur ^ 1], ra, k1, a_ok);
-                    sstore(Bs[cur ^ 1], rb, k1, c_ok);
-                }
-                __syncthreads();
-            }
+                ra = l1_load<float, VEC>(er + ((int64_t)g * a.nl + l) * B * a.dq, a.dq, arow_c, a_ok, k0 + p.lk, d);
+                rb = l1_load<float, VEC>(e.tab[g][l], e.ld_tab[g][l], crow, c_ok, k0 + p.lk, d);
+                return k0;
+            });
         }
         const float w = e.w[g];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const bool qp = (qbits[ty * 4 + i] >> g) & 1;
+            const bool qp = (qbits[p.ty * 4 + i] >> g) & 1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool present = g == 0 || (qp && ((cbits[tx * 4 + j] >> g) & 1));
+                const bool present = g == 0 || (qp && ((cbits[p.tx * 4 + j] >> g) & 1));
                 if (g == 0) d0[i][j] = acc[i][j];
                 tot[i][j] = ens_fold(tot[i][j], w, present, acc[i][j], d0[i][j]);
                 acc[i][j] = 0.f;
             }
         }
     }
-    if constexpr (EPI == LR_STORE) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + ty * 4 + i;
-            if (b >= B) continue;
-            const int n = n0 + tx * 4;
-            float* o = a.S + (int64_t)b * a.ldS + (n - a.n_off);
-            if (n + 3 < N && (a.ldS % 4 == 0) && (a.n_off % 4 == 0)) st4(o, make_float4(-tot[i][0], -tot[i][1], -tot[i][2], -tot[i][3]));
-            else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (n + j < N) o[j] = -tot[i][j];
-            }
-        }
-        return;
-    }
-    if constexpr (EPI == LR_FILTER) {                         // link_rank_tile_kernel's append, on the total
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + ty * 4 + i;
-            const bool row_ok = b < B;
-            const float nt = row_ok ? a.ntau[(int64_t)b * a.tau_stride] : INFINITY;
-            bool pass[4];
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pass[j] = row_ok && n0 + tx * 4 + j < N && -tot[i][j] >= nt;
-                c += pass[j] ? 1 : 0;
-            }
-            if (!__any(c)) continue;
-            int inc = c;                                      // inclusive prefix over the row's 16 lanes
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const int t = __shfl_up(inc, o, 16);
-                if (tx >= o) inc += t;
-            }
-            const int total = __shfl(inc, 15, 16);
-            int base = 0;
-            if (tx == 0 && total) base = atomicAdd(a.cnt + b, total);
-            base = __shfl(base, 0, 16);
-            int slot = base + inc - c;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (pass[j]) {
-                    if (slot < a.cap) {
-                        a.cval[(int64_t)b * a.cap + slot] = -tot[i][j];
-                        a.cidx[(int64_t)b * a.cap + slot] = n0 + tx * 4 + j;
-                    }
-                    ++slot;
-                }
-        }
-        return;
-    }
-    if constexpr (EPI == LR_COUNT) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b = b0 + ty * 4 + i;
-            const bool row_ok = b < B;
-            const float gs = row_ok ? a.gs[b] : 0.f;
-            const int g = row_ok ? a.gold[b] : 0;
-            int c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = n0 + tx * 4 + j;
-                const float sc = tot[i][j];
-                c += (row_ok && n < N && (sc < gs || (sc == gs && n < g))) ? 1 : 0;
-            }
-            c += __shfl_xor(c, 1);
-            c += __shfl_xor(c, 2);
-            c += __shfl_xor(c, 4);
-            c += __shfl_xor(c, 8);
-            if (tx == 0 && row_ok && c) atomicAdd(a.rank + b, c);
-        }
-    }
+    static_assert(EPI == LR_COUNT || EPI == LR_STORE || EPI == LR_FILTER, "the ensemble has no alignment epilogues");
+    l1_epilogue<EPI>(tot, p, a);
 }
 
-// link_select_kernel for the ensemble: the same selection; an overflowing row recomputes D of its N candidates with the prep
-// kernel's sums and folds, one lane per candidate (the query rows come from the workspace: every lane reads the same address).
+// link_select_kernel for the ensemble: an overflowing row recomputes D of its N candidates with the prep kernel's sums and folds,
+// one lane per candidate (the query rows come from the workspace: every lane reads the same address).
 __global__ __launch_bounds__(kBlock) void link_ens_select_kernel(LinkEnsArgs e, int k, const float* __restrict__ sval,
                                                                  const int32_t* __restrict__ sidx, float* __restrict__ val,
                                                                  int32_t* __restrict__ idx) {
     const LinkRankArgs& a = e.base;
     __shared__ TkShared tk;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int2 r = a.rng[b];
-    const int32_t* const tails = a.filt_idx;
-    float* const ov = val + (int64_t)b * k;
-    int32_t* const oi = idx + (int64_t)b * k;
-    auto emit = [&](int c, unsigned long long x) {
-        if (x == 0ull) {                                       // padding: fewer than k unlisted candidates
-            oi[c] = -1;
-            ov[c] = INFINITY;
-            return;
-        }
-        oi[c] = tk_unpack_index(x);
-        const float v = tk_unpack_value(x);
-        ov[c] = v == 0.f ? 0.f : -v;
-    };
-    const int C = a.cnt[b];
-    if (C + k <= a.cap) {
-        for (int c = tid; c < C; c += kBlock) {
-            const int n = a.cidx[(int64_t)b * a.cap + c];
-            tk.skey[c] = tail_listed(tails, r.x, r.y, n) ? 0ull : tk_pack(a.cval[(int64_t)b * a.cap + c], n);
-        }
-        for (int c = tid; c < k; c += kBlock) {
-            const float v = sval[(int64_t)b * k + c];
-            tk.skey[C + c] = v == -INFINITY ? 0ull : tk_pack(v, sidx[(int64_t)b * k + c]);
-        }
-        tk_sort_emit(tk.skey, C + k, k, emit);
-        return;
-    }
+    const int2 r = a.rng[b];                                   // the query's listed tails
+    const LinkEmit emit{val + (int64_t)b * k, idx + (int64_t)b * k};
+    if (link_select_listed(a, b, r, k, sval, sidx, tk, emit)) return;
     const int d = a.d, dq = a.dq;
     const float* const er = static_cast<const float*>(a.er);
     auto for_each_unlisted = [&](auto f) {                      // f(n, -D[b, n]) for every n in [0, N) the index does not list
         for (int n = tid; n < a.N; n += kBlock) {
-            if (tail_listed(tails, r.x, r.y, n)) continue;
+            if (tail_listed(a.filt_idx, r.x, r.y, n)) continue;
             float D = 0.f, d0 = 0.f;
             for (int g = 0; g < e.ng; ++g) {
                 const int cn = e.hq[(int64_t)g * a.B + b] >= 0 ? ens_row(e, g, n) : -1;
                 float acc = 0.f;
                 if (cn >= 0)
-                    for (int l = 0; l < a.nl; ++l) {
-                        const float* row = e.tab[g][l] + (int64_t)cn * e.ld_tab[g][l];
-                        const float* q = er + (((int64_t)g * a.nl + l) * a.B + b) * dq;
-                        for (int x = 0; x < d; ++x) acc = add_absdiff(acc, q[x], row[x]);
-                    }
+                    for (int l = 0; l < a.nl; ++l)
+                        acc = l1_seq_sum(acc, er + (((int64_t)g * a.nl + l) * a.B + b) * dq, e.tab[g][l] + (int64_t)cn * e.ld_tab[g][l], d);
                 if (g == 0) d0 = acc;
                 D = ens_fold(D, e.w[g], cn >= 0, acc, d0);
             }
@@ -3008,20 +2820,14 @@ static void launch_ens_tile(const LinkEnsArgs& e, bool vec, int64_t ncols, hipSt
 static int ens_args(LinkEnsArgs& e, bool& vec, const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h,
                     const int32_t* r, int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d) {
     if (!members || !h || !r) return JMAC_EINVAL;
-    if (index && (index->n_keys < 0 || index->n_keys >= INT32_MAX || !index->key || !index->tail_ptr || !index->tail_idx)) return JMAC_EINVAL;
+    if (index && !tail_index_ok(index)) return JMAC_EINVAL;
     for (int g = 0; g < n_members; ++g) {
         const jmac_link_member_t& m = members[g];
         if (!m.layers || (g == 0) != (m.link == nullptr) || m.n_rows <= 0 || (g == 0 && m.n_rows != N)) return JMAC_EINVAL;
         if (!(m.weight >= 0.f) || !std::isfinite(m.weight)) return JMAC_EINVAL;
         if (m.n_rows >= INT32_MAX) return JMAC_ERANGE;
     }
-    LinkRankArgs& a = e.base;
-    a.nl = n_layers; a.B = (int32_t)B; a.N = (int32_t)N; a.d = (int32_t)d; a.dq = (int32_t)((d + 3) / 4 * 4);
-    a.sign = pred_head ? -1.f : 1.f;
-    a.h = h; a.r = r;
-    if (index) {
-        a.key = index->key; a.n_keys = index->n_keys; a.filt_ptr = index->tail_ptr; a.filt_idx = index->tail_idx;
-    }
+    link_base_args(e.base, n_layers, h, r, pred_head, index, B, N, d);
     e.ng = n_members;
     vec = d % 4 == 0;
     for (int g = 0; g < n_members; ++g) {
@@ -3073,11 +2879,8 @@ int jmac_linkpred_ens_rank_f32(const jmac_link_member_t* members, int32_t n_memb
     a.er = (char*)ws + w.er;
     e.hq = (int32_t*)((char*)ws + w.hq);
     a.gs = (float*)((char*)ws + w.end);
-    const int64_t W = (int64_t)n_layers * a.dq, words = 60 * 1024 / 4;
-    const int64_t rows = (words - W) / (W + 1);
-    if (rows < 1) return JMAC_ERANGE;                          // jmac_linkpred_rank_*'s LDS limit: the members share that LDS
-    a.rows = (int32_t)(rows < LR_ROWS ? rows : LR_ROWS);
-    const size_t shm = (size_t)(W + a.rows * (W + 1)) * sizeof(float);
+    size_t shm;
+    if (!prep_lds(a, shm)) return JMAC_ERANGE;                 // jmac_linkpred_rank_*'s LDS limit: the members share that LDS
     if (index) hipLaunchKernelGGL((link_ens_prep_kernel<true, true>), dim3((unsigned)B), dim3(kBlock), shm, st, e);
     else hipLaunchKernelGGL((link_ens_prep_kernel<false, true>), dim3((unsigned)B), dim3(kBlock), shm, st, e);
     launch_ens_tile<LR_COUNT>(e, vec, N, st);
@@ -3105,7 +2908,8 @@ int jmac_linkpred_ens_topk_f32(const jmac_link_member_t* members, int32_t n_memb
     if (int rc = ens_args(e, vec, members, n_members, n_layers, h, r, pred_head, index, B, N, d)) return rc;
     if (!ws || ws_bytes < jmac_linkpred_ens_topk_workspace_bytes(B, N, d, n_layers, n_members, k)) return JMAC_EWORKSPACE;
     LinkRankArgs& a = e.base;
-    if ((int64_t)n_layers * a.dq + 1 > 60 * 1024 / 4 - (int64_t)n_layers * a.dq) return JMAC_ERANGE;     // jmac_linkpred_rank_*'s LDS limit
+    size_t shm;                                                // unused: RANK = false stages nothing
+    if (!prep_lds(a, shm)) return JMAC_ERANGE;                 // jmac_linkpred_rank_*'s LDS limit
     const LeWs w = le_layout(B, d, n_layers, n_members);
     const LtWs t = lt_layout(B, N, d, 0, k);
     char* wb = (char*)ws;
