@@ -534,7 +534,48 @@ int jmac_linkpred_ens_topk_f32(const jmac_link_member_t* members, int32_t n_memb
                                const int32_t* r, int32_t pred_head, const jmac_tail_index_t* index, int64_t B, int64_t N,
                                int64_t d, int32_t k, float* val, int32_t* idx, void* ws, size_t ws_bytes, jmac_stream_t stream);
 
-/* rank[b] = 1 + #{n : score[b,n] < score[b,gold] or (== and n < gold[b])}, where entries listed in
+/* Link-prediction confidence: the softmax over tails of every query, without the [B,N] matrix (no counterpart in the reference;
+ * what a caller otherwise gets from softmax(-scale * forward_linkpred(...)) ).  THE DEFINITION -- every other place refers here:
+ *   dist[b,n]   jmac_linkpred_rank_*'s distance of query b = (h[b], r[b]) to candidate n, bit for bit: one running fp32 sum over
+ *               (layer, k); pred_head and the bf16 rounding of query and table as there.  Ensemble form: the folded D above.
+ *   z[b,n]      = -scale * dist[b,n], scale > 0 and finite (a temperature; JMAC_EINVAL otherwise)
+ *   C_b         the candidate set.  gold == NULL (prediction mode, as jmac_linkpred_topk_*): every n in [0,N) the index does not
+ *               list for (h[b], r[b]); index NULL or an absent key: all of [0,N).  gold != NULL (evaluation mode, as the ranks):
+ *               the same set plus gold[b], even where the index lists it.
+ *   near[b]     the n in C_b of smallest dist, the lowest index on ties        dmin[b]  that distance, jmac_linkpred_topk_*'s bits
+ *   sum[b]      = sum over C_b of exp(z[b,n] - zmax_b) >= 1, zmax_b = -scale * dmin[b]: 1 / sum is the top-1 probability
+ *   ent[b]      = log(l) - t / l with l = sum[b], t = sum over C_b of e^u u, u = z - zmax_b: the entropy of softmax over C_b of z,
+ *               in jmac_sim_softmax_stats_f32's form
+ *   logp_gold[b] = scale * (dmin[b] - dist[b,gold[b]]) - log(sum[b]), the gold's log-probability; it needs gold (JMAC_EINVAL with
+ *               gold == NULL).  dist[b,gold[b]] is the prep kernel's gold distance, which has the tile kernel's bits, so
+ *               near[b] == gold[b] implies logp_gold[b] == -logf(sum[b]) exactly, logf being the correctly rounded one here
+ *               ((float)log((double)sum[b])), so a caller can reproduce the bits.
+ * Every output pointer may be NULL, at least one must be given (JMAC_EINVAL).  An empty C_b (prediction mode, everything listed):
+ * near = -1, dmin = +inf, sum = 0, ent = 0.
+ * An excluded candidate contributes NOTHING: it is masked to -inf before any reduction, never subtracted afterwards (the known
+ * tails are the nearest candidates by training; subtracting them would cancel the whole sum).  The tile kernel's epilogue takes
+ * the maximum of every 64-column part before any exponential and plain-stores one partial per (part, query); the partials are
+ * merged in ascending part order (jmac_sim_softmax_stats_f32's merge).  No float atomics: results are bitwise reproducible and do
+ * not depend on the grid, the CU count or on which other queries share the call.
+ * Limits and error codes are jmac_linkpred_rank_indexed_*'s (n_layers <= 4, the LDS limit, d <= 512: JMAC_ERANGE); the ensemble
+ * form's are jmac_linkpred_ens_rank_f32's.  Workspace: the rank call's, a few [B] vectors and the partials [ceil(N/64)][B] of
+ * 16 bytes -- never B x N. */
+size_t jmac_linkpred_stats_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers);
+int jmac_linkpred_stats_f32(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                            int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d,
+                            float scale, int32_t* near, float* dmin, float* sum, float* ent, float* logp_gold, void* ws,
+                            size_t ws_bytes, jmac_stream_t stream);
+int jmac_linkpred_stats_bf16(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r,
+                             int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d,
+                             float scale, int32_t* near, float* dmin, float* sum, float* ent, float* logp_gold, void* ws,
+                             size_t ws_bytes, jmac_stream_t stream);
+size_t jmac_linkpred_ens_stats_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers, int32_t n_members);
+int jmac_linkpred_ens_stats_f32(const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h,
+                                const int32_t* r, int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index,
+                                int64_t B, int64_t N, int64_t d, float scale, int32_t* near, float* dmin, float* sum, float* ent,
+                                float* logp_gold, void* ws, size_t ws_bytes, jmac_stream_t stream);
+
+/* rank[b] = 1 +#{n : score[b,n] < score[b,gold] or (== and n < gold[b])}, where entries listed in
  * the filter CSR (filt_ptr [B+1], filt_idx) other than the gold are skipped.  descending == 0: `score` is a
  * DISTANCE (the reference's predictions = -dist, sorted descending); descending != 0: `score` is a SIMILARITY
  * and `<` reads `>` (alignment ranks, modules/finding/alignment.py:87-112).  filt_ptr may be NULL (raw ranking). */

@@ -151,6 +151,12 @@ _SIGS = {
     "jmac_linkpred_ens_rank_f32": (C.c_int, [C.POINTER(LinkMember), i32, i32, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp, sz, vp]),
     "jmac_linkpred_ens_topk_workspace_bytes": (sz, [i64, i64, i64, i32, i32, i32]),
     "jmac_linkpred_ens_topk_f32": (C.c_int, [C.POINTER(LinkMember), i32, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp, vp, vp, sz, vp]),
+    "jmac_linkpred_stats_workspace_bytes": (sz, [i64, i64, i64, i32]),
+    "jmac_linkpred_stats_f32": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "jmac_linkpred_stats_bf16": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "jmac_linkpred_ens_stats_workspace_bytes": (sz, [i64, i64, i64, i32, i32]),
+    "jmac_linkpred_ens_stats_f32": (C.c_int, [C.POINTER(LinkMember), i32, i32, vp, vp, i32, vp, vp, i64, i64, i64, f32, vp, vp, vp, vp, vp,
+                                              vp, sz, vp]),
     "jmac_sim_matrix_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, i64, vp]),
     "jmac_sim_topk_workspace_bytes": (sz, [i64, i64, i32]),
     "jmac_sim_topk_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, i32, vp, vp, vp, sz, vp]),

@@ -121,6 +121,6 @@ const char* jmac_strerror(int rc) {
 // 121: jmac_softmax_parts_merge_f32 added;  122-124: round 5 additions;  125: superseded entry points removed;
 // 126: jmac_sample_completion_batch added;  127: jmac_triple_l1_margin_fwd_counts_f32, jmac_margin_counts_scale_clear_f32 added;
 // 128: jmac_linkpred_rank_indexed_*, jmac_linkpred_topk_* added (jmac_tail_index_t)
-int jmac_version(void) { return 139; }
+int jmac_version(void) { return 140; }
 
 }  // extern "C"

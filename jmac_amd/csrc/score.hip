@@ -5,6 +5,8 @@
 //  * jmac_linkpred_rank_{,indexed_}*  forward_linkpred + that loop, ranks only; the filter from a per-batch CSR or from the
 //                            device-resident known-tail index                 src/jmac_model.py:302-313, src/validate.py:50-64
 //  * jmac_linkpred_topk_*   the k nearest tails the index does not list (the model's predictions; no counterpart)
+//  * jmac_linkpred_stats_*, jmac_linkpred_ens_stats_f32   the softmax over tails of every query -- nearest candidate, normaliser,
+//                            entropy, the gold's log-probability -- from the L1 tile kernel's epilogue (no counterpart)
 //  * jmac_linkpred_ens_*    those ranks and top-k on the cross-KG ensemble distance: supporting KGs vote through link maps (no counterpart)
 //  * jmac_sim_matrix_f32    torch.mm(ILL_vec, KG_vec.t())              modules/utils/util.py:52, train.py:239
 //  * jmac_row_topk_f32 / jmac_sim_topk_f32   sim.topk(k, dim=1)          modules/utils/util.py:53
@@ -274,6 +276,7 @@ struct LinkRankArgs {
     int32_t nl, B, N, d, dq;              // dq = d rounded up to 4: row stride of the query workspace
     int32_t rows;                         // candidate rows the prep kernel stages per pass (LDS budget)
     float sign;                           // +1: E[h] + R[r] (tail prediction), -1: E[h] - R[r]
+    float scale;                          // STATS: the temperature, logit = -scale * dist
     const int32_t *h, *r, *gold, *filt_ptr, *filt_idx;
     void* er;                             // workspace [nl][B][dq] of TT
     float* gs;                            // workspace [B]
@@ -286,7 +289,7 @@ struct LinkRankArgs {
     int2* rng;                            // workspace [B]: every query's [begin, end) in filt_idx (the prep kernel's lookup)
     int32_t n_off;
     float* S;                             // STORE: S[b * ldS + n - n_off] = -dist[b, n]
-    int64_t ldS;
+    int64_t ldS;                          // STATS: S = the partials, float4 [ceil(N / 64)][B] (max -dist, sum e, sum e u, arg)
     const float* ntau;                    // FILTER: ntau[b * tau_stride] = -tau_b; (dist, n) with -dist >= -tau_b are appended
     int32_t tau_stride, cap;
     int32_t* cnt;                         // [B] entries appended (may exceed cap: that row overflowed)
@@ -320,6 +323,18 @@ __device__ __forceinline__ int2 tail_range(const LinkRankArgs& a, int h, int r) 
     return make_int2(0, 0);
 }
 
+// whether n is among the (ascending) tails tail_idx[f0, f1) of a query
+__device__ __forceinline__ bool tail_listed(const int32_t* __restrict__ tail_idx, int f0, int f1, int n) {
+    while (f0 < f1) {
+        const int mid = (f0 + f1) >> 1;
+        const int t = tail_idx[mid];
+        if (t == n) return true;
+        if (t < n) f0 = mid + 1;
+        else f1 = mid;
+    }
+    return false;
+}
+
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float x) {
     uint32_t u = __float_as_uint(x);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);     // NaN stays NaN
@@ -328,6 +343,16 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float x) {
 }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16_t* p, float v) { *p = f32_to_bf16_rne(v); }
+
+// (the softmax-statistics epilogues of both tile families, sim_gemm_kernel's SG_STATS and LR_STATS below)
+// e^x and e^x x of one logit difference x = scale (s - max) <= 0; an excluded element (s = -inf, or the whole part excluded:
+// NaN) is clamped to -1e30, where e^x is 0 and the product -0
+__device__ __forceinline__ void sg_exp_term(float s, float mx, float scale, float& l, float& t) {
+    const float x = fmaxf(scale * (s - mx), -1e30f);
+    const float e = fast_exp(x);
+    l += e;
+    t = fmaf(e, x, t);
+}
 
 // The epilogues below decide on 4x4 values that a tile kernel hands over one row at a time: row(i, v) fills v[0..3] with the values
 // of output row i (computing them inside the row loop keeps 4, not 16, of them live beside the accumulators).
@@ -401,6 +426,57 @@ __device__ __forceinline__ void l1_epi_count(Row row, const L1Pos& p, const Link
     }
 }
 
+// stats epilogue: the softmax statistics of row b's logits scale * v(b, n), v = -dist, over THIS tile's 64 columns, the candidates
+// outside C_b (include/jmac_hip.h: listed by the index and not the row's gold) masked to -inf BEFORE anything is reduced.  The 16
+// lanes of a row agree on (max v, lowest n that attains it), then sum e^u and e^u u with u = scale (v - max) <= 0, and lane 0
+// plain-stores ONE float4 (max v, sum e, sum e u, arg) at part[tile column][b]: no atomics, every (part, b) written exactly once
+// by a fixed lane in a fixed order of additions, so the bits do not depend on the grid or on which rows share the tile.  A part
+// with nothing left stores sum = 0 (SsState skips it).  This is sim_gemm_kernel's SG_STATS row side on -dist.
+template <class Row>
+__device__ __forceinline__ void l1_epi_stats(Row row, const L1Pos& p, const LinkRankArgs& a) {
+    float4* const part = reinterpret_cast<float4*>(a.S) + (int64_t)(p.n0 / L1_T) * a.B;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int b = p.b0 + p.ty * 4 + i;
+        const bool row_ok = b < a.B;                              // the same for the row's 16 lanes
+        const int2 rg = row_ok ? a.rng[b] : make_int2(0, 0);
+        const int g = (row_ok && a.gold != nullptr) ? a.gold[b] : -1;
+        float v[4];
+        row(i, v);
+        float best = -INFINITY;
+        int arg = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = p.n0 + p.tx * 4 + j;
+            bool in = row_ok && n < a.N;
+            if (in && rg.x < rg.y && n != g) in = !tail_listed(a.filt_idx, rg.x, rg.y, n);
+            v[j] = in ? v[j] : -INFINITY;
+            if (v[j] > best) {                                    // strict: the lowest index keeps a tie
+                best = v[j];
+                arg = n;
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            const float ob = __shfl_xor(best, o);
+            const int oa = __shfl_xor(arg, o);
+            if (ob > best || (ob == best && oa < arg)) {
+                best = ob;
+                arg = oa;
+            }
+        }
+        float z = 0.f, y = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sg_exp_term(v[j], best, a.scale, z, y);
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            z += __shfl_xor(z, o);
+            y += __shfl_xor(y, o);
+        }
+        if (p.tx == 0 && row_ok) part[b] = make_float4(best, z, y, __int_as_float(arg));
+    }
+}
+
 // The prep kernels' walk over query b's listed candidates -- entry 0 the gold g, then the filter entries [f0, f1) -- a.rows at a
 // time: rank[b] starts at 1 - #{filtered entries before the gold}, gs[b] = the gold's value.  value(nc, cand) is called by the whole
 // block once cand[0, nc) is visible and may use barriers; lane t < nc returns the value of candidate cand[t] (-1: a skipped entry,
@@ -447,8 +523,9 @@ __device__ __forceinline__ void link_prep_walk(const LinkRankArgs& a, int b, int
 // one block per query: (1) its rows er_l = E_l[h] +/- R_l[r] (rounded to TT) -> workspace and LDS; (2) link_prep_walk over the
 // listed candidates: their table rows are staged into LDS with coalesced loads, then one lane per candidate runs l1_seq_sum.
 // INDEXED: the filter range comes from the known-tail index -- wave 0 searches (h_b, r_b), the block reads the range from LDS.
-// RANK = false (top-k): only (1) and the lookup, whose range goes to a.rng[b].
-template <typename TT, bool INDEXED, bool RANK = true>
+// RANK = false (top-k, statistics without gold): only (1) and the lookup, whose range goes to a.rng[b].  RNG: the range is written
+// (always without RANK; with it for the statistics in evaluation mode, which need gs AND the range).
+template <typename TT, bool INDEXED, bool RANK = true, bool RNG = !RANK>
 __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) {
     extern __shared__ float lr_sh[];                // [nl*dq] query rows (widened) + [LR_ROWS][nl*dq + 1] candidate rows
     __shared__ int2 rng_sh;
@@ -477,10 +554,9 @@ __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) 
     } else {
         f0 = a.filt_ptr ? a.filt_ptr[b] : 0, f1 = a.filt_ptr ? a.filt_ptr[b + 1] : 0;
     }
-    if constexpr (!RANK) {
+    if constexpr (RNG)
         if (threadIdx.x == 0) a.rng[b] = make_int2(f0, f1);
-        return;
-    }
+    if constexpr (!RANK) return;
     link_prep_walk(a, b, g, f0, f1, [&](int nc, const int* cand) -> float {
         for (int i = threadIdx.x; i < nc * W; i += kBlock) {
             const int rI = i / W, q = i - rI * W, l = q / dq, k = q - l * dq;
@@ -502,18 +578,20 @@ __global__ __launch_bounds__(kBlock) void link_rank_prep_kernel(LinkRankArgs a) 
 //   LR_COUNT   count the entries that rank before the gold                                   (jmac_linkpred_rank_*)
 //   LR_STORE   S[b, n - n_off] = -dist[b, n]: the column sample (or the whole narrow matrix)  (jmac_linkpred_topk_*)
 //   LR_FILTER  append (-dist, n) where dist <= tau_b to row b's candidate list
-// STORE and FILTER cover columns [n_off, N).
+// STORE, FILTER and STATS cover columns [n_off, N) (STATS: n_off = 0).
 // The same epilogues on the Manhattan alignment value c = csls_value(1 - dist, r1, r2), or s = 1 - dist when r1 == NULL, larger
 // first (jmac_l1_csls_*; what sim_gemm_kernel's SG_CSLS_* epilogues are to the cosine similarity):
 //   LR_CSLS_COUNT   count the columns whose c beats gs[b] = c(b, gold_b): larger, or equal with an index below gold_b
 //   LR_CSLS_FILTER  append (c, n) where c >= tau_b
 //   LR_CSLS_VIABLE  ... and tk_pack(c, row_id[b]) > best[n]: the suitor would displace what reviewer n holds
-enum { LR_COUNT = 0, LR_STORE = 1, LR_FILTER = 2, LR_CSLS_COUNT = 3, LR_CSLS_FILTER = 4, LR_CSLS_VIABLE = 5 };
+// and, on -dist again:
+//   LR_STATS   per 64-column part, the softmax statistics of -scale * dist over the query's candidate set (jmac_linkpred_stats_*)
+enum { LR_COUNT = 0, LR_STORE = 1, LR_FILTER = 2, LR_CSLS_COUNT = 3, LR_CSLS_FILTER = 4, LR_CSLS_VIABLE = 5, LR_STATS = 6 };
 
 // the epilogue EPI on a tile's distances: it decides on dist (COUNT), -dist (STORE, FILTER) or the alignment value (LR_CSLS_*)
 template <int EPI>
 __device__ __forceinline__ void l1_epilogue(const float (&dist)[4][4], const L1Pos& p, const LinkRankArgs& a) {
-    constexpr bool CSLS = EPI >= LR_CSLS_COUNT;
+    constexpr bool CSLS = EPI >= LR_CSLS_COUNT && EPI <= LR_CSLS_VIABLE;
     const bool cs = CSLS && a.r1 != nullptr;                   // block-uniform
     float r2v[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (CSLS)
@@ -540,7 +618,8 @@ __device__ __forceinline__ void l1_epilogue(const float (&dist)[4][4], const L1P
             const int b = p.b0 + p.ty * 4 + i;
             return tk_pack(c, b < a.B ? a.row_id[b] : 0) > bw[j];
         });
-    } else l1_epi_count<CSLS>(row, p, a);
+    } else if constexpr (EPI == LR_STATS) l1_epi_stats(row, p, a);
+    else l1_epi_count<CSLS>(row, p, a);
 }
 
 template <typename TT, bool VEC, int EPI = LR_COUNT>
@@ -727,14 +806,6 @@ __device__ __forceinline__ void sg_halves(float x, float& lo, float& hi) {
     lo = x;
     hi = x;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(lo), "+v"(hi));
-}
-// e^x and e^x x of one logit difference x = scale (s - max) <= 0; an excluded element (s = -inf, or the whole part excluded:
-// NaN) is clamped to -1e30, where e^x is 0 and the product -0
-__device__ __forceinline__ void sg_exp_term(float s, float mx, float scale, float& l, float& t) {
-    const float x = fmaxf(scale * (s - mx), -1e30f);
-    const float e = fast_exp(x);
-    l += e;
-    t = fmaf(e, x, t);
 }
 
 // e^(z - max z) of one logit of the log-sum-exp epilogue; an excluded element (z = -inf, or the whole part excluded: NaN) gives 0
@@ -1644,17 +1715,6 @@ __global__ __launch_bounds__(kBlock) void link_topk_finish_kernel(float* __restr
     } else {
         val[i] = v == 0.f ? 0.f : -v;
     }
-}
-
-__device__ __forceinline__ bool tail_listed(const int32_t* __restrict__ tail_idx, int f0, int f1, int n) {
-    while (f0 < f1) {
-        const int mid = (f0 + f1) >> 1;
-        const int t = tail_idx[mid];
-        if (t == n) return true;
-        if (t < n) f0 = mid + 1;
-        else f1 = mid;
-    }
-    return false;
 }
 
 // The select kernels (one block per query), single-KG and ensemble: the k best of (candidate list + the sample's k best), listed
@@ -2599,6 +2659,136 @@ int jmac_linkpred_topk_bf16(const jmac_link_layer_t* layers, int32_t n_layers, c
 
 }  // extern "C"
 
+// ---- link-prediction confidence (jmac_linkpred_stats_*, jmac_linkpred_ens_stats_f32): the LR_STATS epilogue, merged -------------
+// The definition is include/jmac_hip.h's.  After the prep kernel (query rows, every query's range in the index, and with gold the
+// gold distance gs) the tile kernel's LR_STATS epilogue leaves one float4 per (64-column part, query); sim_stats_merge_kernel's row
+// side folds a query's parts in ascending order with SsState -- the merge jmac_sim_softmax_stats_f32 runs, on max = -dist_min --
+// and link_stats_finish_kernel turns (max, arg, sum, entropy) into the outputs: the empty set's values, dmin = -max, logp_gold.
+namespace {
+
+__global__ __launch_bounds__(kBlock) void link_stats_finish_kernel(int B, float scale, const float* __restrict__ mbest,
+                                                                   const int32_t* __restrict__ marg, const float* __restrict__ msum,
+                                                                   const float* __restrict__ ment, const float* __restrict__ gs,
+                                                                   int32_t* __restrict__ near, float* __restrict__ dmin,
+                                                                   float* __restrict__ sum, float* __restrict__ ent,
+                                                                   float* __restrict__ logp_gold) {
+    const int b = blockIdx.x * kBlock + threadIdx.x;
+    if (b >= B) return;
+    const float best = mbest[b], l = msum[b];
+    const bool some = l > 0.f;                                 // false: every candidate is listed (prediction mode only)
+    if (near) near[b] = some ? marg[b] : -1;
+    if (dmin) dmin[b] = some ? (best == 0.f ? 0.f : -best) : INFINITY;       // jmac_linkpred_topk_*'s bits of the distance
+    if (sum) sum[b] = some ? l : 0.f;
+    if (ent) ent[b] = some ? ment[b] : 0.f;
+    // the gold is in the set: l >= 1.  best = -dmin, so -(gs + best) = dmin - gs <= 0, and where the gold is the nearest it is -0
+    // exactly: that row is -log(sum) bit for bit, the sign of -log(1) included.  The logarithm is taken in double precision and
+    // rounded once -- the correctly rounded fp32 value, which a caller can reproduce; logf's last bit varies between libraries
+    if (logp_gold) logp_gold[b] = scale * -(gs[b] + best) - (float)log((double)l);
+}
+
+// what both statistics calls append to their rank workspace: rng, the merge's four vectors and the partials
+struct LsWs { size_t rank, rng, mbest, marg, msum, ment, part, total; };
+LsWs ls_layout(size_t off, int64_t B, int64_t N) {
+    LsWs w{};
+    const size_t vec = align_up((size_t)B * 4);
+    w.rank = off;  off += vec;                                 // the prep walk's filter correction: written, not read
+    w.rng = off;   off += align_up((size_t)B * 8);
+    w.mbest = off; off += vec;
+    w.marg = off;  off += vec;
+    w.msum = off;  off += vec;
+    w.ment = off;  off += vec;
+    w.part = off;  off += align_up((size_t)((N + L1_T - 1) / L1_T) * (size_t)B * 16);
+    w.total = off + 256;
+    return w;
+}
+
+// the argument checks both calls share beyond the rank entry points' (the caller has checked the sizes and B > 0)
+int link_stats_check(const int32_t* gold, const int32_t* near, const float* dmin, const float* sum, const float* ent,
+                     const float* logp_gold) {
+    if (!(near || dmin || sum || ent || logp_gold) || (logp_gold && !gold)) return JMAC_EINVAL;
+    return JMAC_OK;
+}
+
+// merge + finish over the partials the tile kernel has left in a.S
+int link_stats_finish(const LinkRankArgs& a, const LsWs& w, char* wb, int32_t* near, float* dmin, float* sum, float* ent,
+                      float* logp_gold, hipStream_t st) {
+    float* const mbest = (float*)(wb + w.mbest);
+    int32_t* const marg = (int32_t*)(wb + w.marg);
+    float* const msum = (float*)(wb + w.msum);
+    float* const ment = (float*)(wb + w.ment);
+    const int rb = (a.B + 63) / 64;
+    hipLaunchKernelGGL(sim_stats_merge_kernel, dim3((unsigned)rb), dim3(kBlock), 0, st, (const float4*)a.S, nullptr, nullptr, a.B, a.N,
+                       a.scale, rb, mbest, marg, msum, ment, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(link_stats_finish_kernel, dim3((unsigned)((a.B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a.B, a.scale, mbest,
+                       marg, msum, ment, a.gs, near, dmin, sum, ent, logp_gold);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+template <typename TT>
+static int launch_link_stats(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
+                             const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, float scale,
+                             int32_t* near, float* dmin, float* sum, float* ent, float* logp_gold, void* ws, size_t ws_bytes,
+                             hipStream_t st) {
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_layers > LR_MAX_LAYERS) return JMAC_EINVAL;
+    if (!(scale > 0.f) || !std::isfinite(scale)) return JMAC_EINVAL;
+    if (int rc = link_stats_check(gold, near, dmin, sum, ent, logp_gold)) return rc;
+    if (B == 0) return JMAC_OK;
+    if (!layers || !h || !r) return JMAC_EINVAL;
+    if (index && !tail_index_ok(index)) return JMAC_EINVAL;
+    if (B >= INT32_MAX || N >= INT32_MAX || d > 512) return JMAC_ERANGE;
+    if (!ws || ws_bytes < jmac_linkpred_stats_workspace_bytes(B, N, d, n_layers)) return JMAC_EWORKSPACE;
+    LinkRankArgs a{};
+    bool vec;
+    a.gold = gold;
+    if (int rc = link_args<TT>(a, vec, layers, n_layers, h, r, pred_head, index, B, N, d)) return rc;
+    const size_t rank_ws = jmac_linkpred_rank_workspace_bytes(B, d, n_layers) - 256;
+    const LsWs w = ls_layout(rank_ws, B, N);
+    char* wb = (char*)ws;
+    a.gs = (float*)wb;                                         // (jmac_linkpred_rank_*'s layout: gs, then the query rows)
+    a.er = wb + align_up((size_t)B * 4);
+    a.rank = (int32_t*)(wb + w.rank);
+    a.rng = (int2*)(wb + w.rng);
+    a.S = (float*)(wb + w.part);
+    a.scale = scale;
+    size_t shm;
+    if (!prep_lds(a, shm)) return JMAC_ERANGE;
+    const size_t shq = (size_t)n_layers * a.dq * 4;            // without gold the prep kernel stages the query rows only
+    const dim3 grid((unsigned)B), block(kBlock);
+    if (gold && index) hipLaunchKernelGGL((link_rank_prep_kernel<TT, true, true, true>), grid, block, shm, st, a);
+    else if (gold) hipLaunchKernelGGL((link_rank_prep_kernel<TT, false, true, true>), grid, block, shm, st, a);
+    else if (index) hipLaunchKernelGGL((link_rank_prep_kernel<TT, true, false>), grid, block, shq, st, a);
+    else hipLaunchKernelGGL((link_rank_prep_kernel<TT, false, false>), grid, block, shq, st, a);
+    launch_link_tile<TT, LR_STATS>(a, vec, N, st);
+    return link_stats_finish(a, w, wb, near, dmin, sum, ent, logp_gold, st);
+}
+
+extern "C" {
+
+size_t jmac_linkpred_stats_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers) {
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0) return 0;
+    return ls_layout(jmac_linkpred_rank_workspace_bytes(B, d, n_layers) - 256, B, N).total;
+}
+
+int jmac_linkpred_stats_f32(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
+                            const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, float scale,
+                            int32_t* near, float* dmin, float* sum, float* ent, float* logp_gold, void* ws, size_t ws_bytes,
+                            jmac_stream_t stream) {
+    return launch_link_stats<float>(layers, n_layers, h, r, pred_head, gold, index, B, N, d, scale, near, dmin, sum, ent, logp_gold, ws,
+                                    ws_bytes, (hipStream_t)stream);
+}
+
+int jmac_linkpred_stats_bf16(const jmac_link_layer_t* layers, int32_t n_layers, const int32_t* h, const int32_t* r, int32_t pred_head,
+                             const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d, float scale,
+                             int32_t* near, float* dmin, float* sum, float* ent, float* logp_gold, void* ws, size_t ws_bytes,
+                             jmac_stream_t stream) {
+    return launch_link_stats<bf16_t>(layers, n_layers, h, r, pred_head, gold, index, B, N, d, scale, near, dmin, sum, ent, logp_gold, ws,
+                                     ws_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------------------------------------------
 // cross-KG ensemble link prediction (jmac_linkpred_ens_*): ranks and top-k of the target KG's tails on a distance that several
 // KGs vote on through alignment links.  Members g = 0 .. S (S <= 3): member 0 is the target with N candidate rows; a supporting
@@ -2646,7 +2836,7 @@ __device__ __forceinline__ int ens_row(const LinkEnsArgs& e, int g, int n) {
 // link_rank_prep_kernel for the ensemble.  One block per query: (1) its head row and query rows in every member (rows of an
 // unlinked head are zero) -> workspace; (2) RANK: link_prep_walk on D -- the members take turns in the SAME LDS (their query
 // rows, then the candidates' rows read through the link), one lane per candidate runs l1_seq_sum and folds it into its D.
-template <bool INDEXED, bool RANK>
+template <bool INDEXED, bool RANK, bool RNG = !RANK>
 __global__ __launch_bounds__(kBlock) void link_ens_prep_kernel(LinkEnsArgs e) {
     const LinkRankArgs& a = e.base;
     extern __shared__ float le_sh[];                // RANK: [nl*dq] query rows + [rows][nl*dq + 1] candidate rows, one member at a time
@@ -2676,10 +2866,9 @@ __global__ __launch_bounds__(kBlock) void link_ens_prep_kernel(LinkEnsArgs e) {
     } else {
         f0 = 0, f1 = 0;
     }
-    if constexpr (!RANK) {
+    if constexpr (RNG)
         if (threadIdx.x == 0) a.rng[b] = make_int2(f0, f1);
-        return;
-    }
+    if constexpr (!RANK) return;
     float* const erow = le_sh;
     float* const crow = le_sh + W;
     link_prep_walk(a, b, g, f0, f1, [&](int nc, const int* cand) -> float {
@@ -2771,7 +2960,7 @@ __global__ __launch_bounds__(kBlock) void link_ens_tile_kernel(LinkEnsArgs e) {
             }
         }
     }
-    static_assert(EPI == LR_COUNT || EPI == LR_STORE || EPI == LR_FILTER, "the ensemble has no alignment epilogues");
+    static_assert(EPI == LR_COUNT || EPI == LR_STORE || EPI == LR_FILTER || EPI == LR_STATS, "the ensemble has no alignment epilogues");
     l1_epilogue<EPI>(tot, p, a);
 }
 
@@ -2939,6 +3128,49 @@ int jmac_linkpred_ens_topk_f32(const jmac_link_member_t* members, int32_t n_memb
             hipLaunchKernelGGL(link_ens_select_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, filter_args(f), (int)k, val0, idx0, val, idx);
         },
         link_topk_finish_kernel);
+}
+
+size_t jmac_linkpred_ens_stats_workspace_bytes(int64_t B, int64_t N, int64_t d, int32_t n_layers, int32_t n_members) {
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_members <= 0) return 0;
+    return ls_layout(jmac_linkpred_ens_rank_workspace_bytes(B, d, n_layers, n_members) - 256, B, N).total;
+}
+
+// jmac_linkpred_stats_f32 on the folded D: the ensemble's prep and tile kernels, the same epilogue, merge and finish
+int jmac_linkpred_ens_stats_f32(const jmac_link_member_t* members, int32_t n_members, int32_t n_layers, const int32_t* h, const int32_t* r,
+                                int32_t pred_head, const int32_t* gold, const jmac_tail_index_t* index, int64_t B, int64_t N, int64_t d,
+                                float scale, int32_t* near, float* dmin, float* sum, float* ent, float* logp_gold, void* ws,
+                                size_t ws_bytes, jmac_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (B < 0 || N <= 0 || d <= 0 || n_layers <= 0 || n_layers > LR_MAX_LAYERS || n_members < 1 || n_members > LE_MAX) return JMAC_EINVAL;
+    if (!(scale > 0.f) || !std::isfinite(scale)) return JMAC_EINVAL;
+    if (int rc = link_stats_check(gold, near, dmin, sum, ent, logp_gold)) return rc;
+    if (B == 0) return JMAC_OK;
+    if (B >= INT32_MAX || N >= INT32_MAX || d > 512) return JMAC_ERANGE;
+    LinkEnsArgs e{};
+    bool vec;
+    if (int rc = ens_args(e, vec, members, n_members, n_layers, h, r, pred_head, index, B, N, d)) return rc;
+    if (!ws || ws_bytes < jmac_linkpred_ens_stats_workspace_bytes(B, N, d, n_layers, n_members)) return JMAC_EWORKSPACE;
+    LinkRankArgs& a = e.base;
+    const LeWs lw = le_layout(B, d, n_layers, n_members);
+    const LsWs w = ls_layout(jmac_linkpred_ens_rank_workspace_bytes(B, d, n_layers, n_members) - 256, B, N);
+    char* wb = (char*)ws;
+    a.gold = gold;
+    a.er = wb + lw.er;
+    e.hq = (int32_t*)(wb + lw.hq);
+    a.gs = (float*)(wb + lw.end);                              // (jmac_linkpred_ens_rank_f32's layout)
+    a.rank = (int32_t*)(wb + w.rank);
+    a.rng = (int2*)(wb + w.rng);
+    a.S = (float*)(wb + w.part);
+    a.scale = scale;
+    size_t shm;
+    if (!prep_lds(a, shm)) return JMAC_ERANGE;
+    const dim3 grid((unsigned)B), block(kBlock);
+    if (gold && index) hipLaunchKernelGGL((link_ens_prep_kernel<true, true, true>), grid, block, shm, st, e);
+    else if (gold) hipLaunchKernelGGL((link_ens_prep_kernel<false, true, true>), grid, block, shm, st, e);
+    else if (index) hipLaunchKernelGGL((link_ens_prep_kernel<true, false>), grid, block, 0, st, e);
+    else hipLaunchKernelGGL((link_ens_prep_kernel<false, false>), grid, block, 0, st, e);
+    launch_ens_tile<LR_STATS>(e, vec, N, st);
+    return link_stats_finish(a, w, wb, near, dmin, sum, ent, logp_gold, st);
 }
 
 size_t jmac_softmax_entropy_workspace_bytes(int64_t n1, int64_t n2) {

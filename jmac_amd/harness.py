@@ -250,6 +250,72 @@ def evaluate_completion(model: JMAC, kg: KnowledgeGraph, ei, et, args, split="va
     return float((rk <= 1).double().mean()), float((rk <= 10).double().mean()), float((1.0 / rk).mean())
 
 
+def calibration_error(confidence: torch.Tensor, correct: torch.Tensor, bins: int = 10) -> torch.Tensor:
+    """Expected calibration error of top-1 predictions: over ``bins`` equal-width confidence bins [j / bins, (j + 1) / bins)
+    (the last one closed), sum of (share of the queries in the bin) * |accuracy in the bin - mean confidence in the bin|.
+    A 0-d float64 tensor on the inputs' device (no host read)."""
+    conf = confidence.double().reshape(-1)
+    hit = correct.double().reshape(-1)
+    which = (conf * bins).long().clamp_(0, bins - 1)
+    zero = torch.zeros(bins, dtype=torch.float64, device=conf.device)
+    n = zero.index_add(0, which, torch.ones_like(conf))
+    gap = (zero.index_add(0, which, hit) - zero.index_add(0, which, conf)).abs()      # n_j |acc_j - conf_j|
+    return gap.sum() / n.sum().clamp_min(1.0)
+
+
+def _completion_stats(model: JMAC, kg: KnowledgeGraph, ei, et, split, eval_batch):
+    """(triples of the split, call(scale) -> scoring.LinkStats of the whole split in evaluation mode, filtered): the encoder runs
+    once, every call scores on its cached tables."""
+    data = {"val": kg.val_data, "test": kg.test_data, "train": kg.train_data}[split]
+    eb, rb = [kg.entity_id_base, kg.upper_entity_base], [kg.relation_id_base, kg.upper_relation_base]
+    cached = model.forward_base(ei, et, eb, rb)
+    index = _true_tail_index(kg, ei.device)
+    step = int(eval_batch or 16384)
+
+    def call(scale):
+        parts = [model.linkpred_stats(data[s:s + step, 0], data[s:s + step, 1], scale, ei, et, eb, rb, gold=data[s:s + step, 2],
+                                      index=index, cached=cached) for s in range(0, len(data), step)]
+        if len(parts) == 1:
+            return parts[0]
+        return scoring.LinkStats(*[torch.cat([getattr(p, f) for p in parts]) for f in scoring.LinkStats._fields[:-1]], parts[0].scale)
+
+    return data, call
+
+
+@torch.no_grad()
+def evaluate_completion_confidence(model: JMAC, kg: KnowledgeGraph, ei, et, args, scale, split="val", eval_batch=None):
+    """How well calibrated the completion model is on a split, under ``softmax(-scale * dist)`` over the filtered candidates
+    (scoring.linkpred_stats in evaluation mode): ``{"nll": mean -log p(gold), "entropy": mean entropy in nats, "confidence": mean
+    top-1 probability, "hits1": share of queries whose nearest candidate is the gold, "ece": calibration_error of the top-1
+    prediction over ten bins}``.  The encoder runs once, the whole split goes through one call (``eval_batch`` as in
+    evaluate_completion's fused path), the reductions run on the device and ONE host read ends it."""
+    model.eval()
+    data, call = _completion_stats(model, kg, ei, et, split, eval_batch)
+    st = call(scale)
+    gold = torch.as_tensor(np.ascontiguousarray(data[:, 2]), dtype=torch.int64, device=st.nearest.device)
+    hit = st.nearest == gold
+    conf = st.confidence
+    out = torch.stack([-st.logp_gold.double().mean(), st.entropy.double().mean(), conf.double().mean(), hit.double().mean(),
+                       calibration_error(conf, hit)]).tolist()
+    model.train()
+    return dict(zip(("nll", "entropy", "confidence", "hits1", "ece"), out))
+
+
+@torch.no_grad()
+def calibrate_link_scale(model: JMAC, kg: KnowledgeGraph, ei, et, args, scales, split="val"):
+    """Temperature scaling by grid: ``(best_scale, {scale: nll})``, the ``scale`` of ``scales`` with the smallest mean negative
+    log-likelihood of the split's gold tails (the first on ties).  One encoder pass, one statistics call per scale, one host read."""
+    scales = [float(s) for s in scales]
+    if not scales:
+        raise ValueError("calibrate_link_scale: no scales given")
+    model.eval()
+    _, call = _completion_stats(model, kg, ei, et, split, None)
+    nll = torch.stack([-call(s).logp_gold.double().mean() for s in scales]).tolist()
+    model.train()
+    table = dict(zip(scales, nll))
+    return min(scales, key=lambda s: table[s]), table
+
+
 def alignment_links(kg_t: KnowledgeGraph, kg_s: KnowledgeGraph, seed_pairs, predicted=None, device=None):
     """The link map of supporting KG ``kg_s`` for target ``kg_t`` (scoring.link_map: int32 [kg_t.num_entity], -1 = unaligned)
     from ``seed_pairs`` [L, 2] of (target row, support row), ids local to their KG.  ``predicted``: a ``match`` vector indexed by

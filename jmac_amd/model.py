@@ -393,6 +393,41 @@ class JMAC(nn.Module):
         return scoring.linkpred_topk_ensemble(self._ensemble_members(blocks, links, weights, cached), e_index, r_index, k,
                                               index, pred_head)
 
+    def _link_tables(self, edge_index, edge_type, ent_bases, rel_bases, cached):
+        """The completion layers' (entity tables, relation tables) the fused link-prediction calls score on."""
+        if cached is None:
+            cached = self.forward_base(edge_index, edge_type, ent_bases, rel_bases)
+        _, comp_layers, comp_rel_layers = cached
+        layers = range(self.args.num_gcn_layer)
+        return [comp_layers[l] for l in layers], [comp_rel_layers[l] for l in layers]
+
+    def linkpred_stats(self, e_index, r_index, scale, edge_index, edge_type, ent_bases, rel_bases, gold=None, index=None,
+                       pred_head=False, cached=None):
+        """How sure the model is about every ``(h, r)``: scoring.LinkStats of ``softmax(-scale * dist)`` over the candidate tails
+        under forward_linkpred's distance (:295-313) -- nearest candidate, its distance, normaliser, entropy and, with ``gold``,
+        the gold's log-probability -- without the [B, N] matrix (scoring.linkpred_stats).  Honours ``table_dtype``."""
+        ent, rel = self._link_tables(edge_index, edge_type, ent_bases, rel_bases, cached)
+        return scoring.linkpred_stats(ent, rel, e_index, r_index, scale, gold=gold, index=index, pred_head=pred_head,
+                                      table_dtype=getattr(self, "table_dtype", torch.float32))
+
+    def linkpred_topk_prob(self, e_index, r_index, k, scale, edge_index, edge_type, ent_bases, rel_bases, index=None, pred_head=False,
+                           cached=None):
+        """linkpred_topk with the predictions' probabilities: ``(idx, dist, prob)`` (scoring.linkpred_topk_prob)."""
+        ent, rel = self._link_tables(edge_index, edge_type, ent_bases, rel_bases, cached)
+        return scoring.linkpred_topk_prob(ent, rel, e_index, r_index, k, scale, index=index, pred_head=pred_head,
+                                          table_dtype=getattr(self, "table_dtype", torch.float32))
+
+    def linkpred_stats_ensemble(self, e_index, r_index, scale, blocks, links, weights, gold=None, index=None, pred_head=False,
+                                cached=None):
+        """linkpred_stats on the ensemble distance of linkpred_ranks_ensemble (``blocks``, ``links``, ``weights``, ``cached`` as there)."""
+        return scoring.linkpred_stats_ensemble(self._ensemble_members(blocks, links, weights, cached), e_index, r_index, scale,
+                                               gold=gold, index=index, pred_head=pred_head)
+
+    def linkpred_topk_prob_ensemble(self, e_index, r_index, k, scale, blocks, links, weights, index=None, pred_head=False, cached=None):
+        """linkpred_topk_prob on the ensemble distance: ``(idx, D, prob)``."""
+        return scoring.linkpred_topk_prob_ensemble(self._ensemble_members(blocks, links, weights, cached), e_index, r_index, k, scale,
+                                                   index=index, pred_head=pred_head)
+
     @staticmethod
     def _alignment_terms(a, b, csls_k, down, sinkhorn, screen=None):
         """The rescoring terms of the two WHOLE (prepared) tables: csls_terms, or -- ``sinkhorn=dict(scale=.., iters=..)`` --

@@ -280,6 +280,106 @@ def linkpred_topk_ensemble(members, e_index, r_index, k: int, index=None, pred_h
     return idx.to(torch.int64), val
 
 
+class LinkStats(namedtuple("LinkStats", "nearest dist_min sum entropy logp_gold scale")):
+    """Per-query statistics of ``softmax_n(-scale * dist[b, n])`` over the query's candidate set (include/jmac_hip.h,
+    jmac_linkpred_stats_*): ``nearest`` int64 [B] (-1: empty set), ``dist_min`` (+inf), ``sum`` = sum of exp(z - zmax) (0),
+    ``entropy`` in nats (0), ``logp_gold`` (None without gold) and the ``scale`` they were taken at."""
+    __slots__ = ()
+
+    @property
+    def confidence(self) -> torch.Tensor:
+        """The top-1 probability 1 / sum; 0 where the candidate set is empty."""
+        return torch.where(self.sum > 0, 1.0 / self.sum.clamp_min(1.0), torch.zeros_like(self.sum))
+
+    @property
+    def lse(self) -> torch.Tensor:
+        """log sum_n exp(-scale * dist[b, n]) = -scale * dist_min + log(sum); -inf where the candidate set is empty."""
+        return torch.where(self.sum > 0, -self.scale * self.dist_min + torch.log(self.sum), torch.full_like(self.sum, float("-inf")))
+
+
+def _check_scale(who: str, scale) -> float:
+    import math
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError("%s: scale must be finite and > 0 (got %r)" % (who, scale))
+    return scale
+
+
+def _link_stats_call(who: str, name: str, ws_name: str, head_args, ws_args, N: int, nrel: int, dev, e_index, r_index, scale, gold,
+                     index, pred_head: bool) -> LinkStats:
+    """The statistics entry point ``name`` on prepared tables (``head_args``: the arguments before h; ``ws_args``: those of the
+    workspace query after B, N, d)."""
+    scale = _check_scale(who, scale)
+    h = _query_column(e_index, N, "e_index", dev)
+    r = _query_column(r_index, nrel, "r_index", dev)
+    B = h.numel()
+    g = None if gold is None else _query_column(gold, N, "gold", dev)
+    if r.numel() != B or (g is not None and g.numel() != B):
+        raise ValueError("%s: e_index, r_index and gold must have one entry per query" % who)
+    near = torch.empty(B, dtype=torch.int32, device=dev)
+    dmin, lsum, ent = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
+    logp = torch.empty(B, dtype=torch.float32, device=dev) if g is not None else None
+    L = lib()
+    d = ws_args[0]
+    ws_bytes = int(getattr(L, ws_name)(B, N, *ws_args))
+    ws = workspace(ws_bytes, dev)
+    ix, _keep_ix = _tail_index(index, dev)
+    check(getattr(L, name)(*head_args, ptr(h), ptr(r), 1 if pred_head else 0, ptr(g), ix, B, N, d, scale, ptr(near), ptr(dmin),
+                           ptr(lsum), ptr(ent), ptr(logp), ptr(ws), ws_bytes, stream()), name)
+    return LinkStats(near.to(torch.int64), dmin, lsum, ent, logp, scale)
+
+
+def linkpred_stats(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequence[torch.Tensor], e_index, r_index, scale: float,
+                   gold=None, index=None, pred_head: bool = False, table_dtype=torch.float32) -> LinkStats:
+    """How sure the model is: the statistics of ``softmax(-scale * dist)`` over the tails of every ``(h, r)``, dist being
+    linkpred_ranks' / linkpred_topk's distance bit for bit, without the [B, N] matrix.  Without ``gold`` the candidates are
+    those ``index`` (a sampling.TrueTailIndex) does not list -- linkpred_topk's set; with ``gold`` the gold tail joins them even
+    where listed -- the filtered ranks' set -- and ``logp_gold`` is its log-probability.  Listed tails are masked before the
+    sums, never subtracted.  ``scale`` > 0 is the temperature (``harness.calibrate_link_scale`` fits it)."""
+    _check_scale("linkpred_stats", scale)
+    bf16 = table_dtype == torch.bfloat16
+    arr, keep, N, d = _link_layers(comp_layers, comp_rel_layers, bf16)
+    nl = len(comp_layers)
+    return _link_stats_call("linkpred_stats", "jmac_linkpred_stats_bf16" if bf16 else "jmac_linkpred_stats_f32",
+                            "jmac_linkpred_stats_workspace_bytes", (arr, nl), (d, nl), N, comp_rel_layers[0].shape[0],
+                            comp_layers[0].device, e_index, r_index, scale, gold, index, pred_head)
+
+
+def linkpred_stats_ensemble(members, e_index, r_index, scale: float, gold=None, index=None, pred_head: bool = False) -> LinkStats:
+    """linkpred_stats on the cross-KG ensemble distance D of linkpred_ranks_ensemble (``members`` as there; ``index`` is the
+    TARGET's).  One member with weight 1 gives linkpred_stats' bits."""
+    _check_scale("linkpred_stats_ensemble", scale)
+    arr, keep, N, d, nl, nrel = _link_members(members, "linkpred_stats_ensemble")
+    return _link_stats_call("linkpred_stats_ensemble", "jmac_linkpred_ens_stats_f32", "jmac_linkpred_ens_stats_workspace_bytes",
+                            (arr, len(members), nl), (d, nl, len(members)), N, nrel, members[0][0][0].device, e_index, r_index, scale,
+                            gold, index, pred_head)
+
+
+def _topk_prob(idx: torch.Tensor, dist: torch.Tensor, st: LinkStats) -> torch.Tensor:
+    """prob[b, j] = exp(-scale (dist[b, j] - dist_min[b])) / sum[b]; padded entries (idx = -1) get 0."""
+    pad = idx < 0
+    u = -st.scale * (dist.masked_fill(pad, 0.0) - st.dist_min.masked_fill(st.sum <= 0, 0.0)[:, None])
+    return (torch.exp(u) / st.sum.clamp_min(1.0)[:, None]).masked_fill(pad, 0.0)
+
+
+def linkpred_topk_prob(comp_layers: Sequence[torch.Tensor], comp_rel_layers: Sequence[torch.Tensor], e_index, r_index, k: int,
+                       scale: float, index=None, pred_head: bool = False, table_dtype=torch.float32):
+    """``(idx, dist, prob)``: linkpred_topk's predictions with their probabilities under ``softmax(-scale * dist)`` over ALL
+    unlisted candidates (one top-k call and one linkpred_stats call in prediction mode); padded entries have ``prob = 0``."""
+    _check_scale("linkpred_topk_prob", scale)
+    idx, dist = linkpred_topk(comp_layers, comp_rel_layers, e_index, r_index, k, index=index, pred_head=pred_head, table_dtype=table_dtype)
+    st = linkpred_stats(comp_layers, comp_rel_layers, e_index, r_index, scale, index=index, pred_head=pred_head, table_dtype=table_dtype)
+    return idx, dist, _topk_prob(idx, dist, st)
+
+
+def linkpred_topk_prob_ensemble(members, e_index, r_index, k: int, scale: float, index=None, pred_head: bool = False):
+    """linkpred_topk_prob on the cross-KG ensemble distance."""
+    _check_scale("linkpred_topk_prob_ensemble", scale)
+    idx, dist = linkpred_topk_ensemble(members, e_index, r_index, k, index=index, pred_head=pred_head)
+    st = linkpred_stats_ensemble(members, e_index, r_index, scale, index=index, pred_head=pred_head)
+    return idx, dist, _topk_prob(idx, dist, st)
+
+
 def build_filter_csr(heads, rels, true_tail: Dict, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pack er_vocab[(h, r)] lists (src/validate.py:53; knowledgegraph.py:62-86) as CSR over the batch."""
     ptr_l, idx = [0], []
